@@ -6,13 +6,19 @@ a batch of 4096 synthetic 21x21 two-aperture patch pairs (8192 CNN patches) per 
   LocalStage CNN (fp32-MFMA implicit GEMM)  ->  wedge renderer pass A (colours, ridge solve)  ->  DfD depth solve
 with the input already resident in HBM.  Prints ONE JSON line (rank 0).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          N > 1: this process only spawns the N ranks (children of the same
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                               N > 1: this process only spawns the N ranks (children of the same
                                                                script, started before any GPU call) and relays their exit codes
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W      (the same ranks under a launcher)
 The line's `launch` object says who ran: launcher, backend, rccl_ranks (world size under backend nccl), RCCL version, every rank's
 device / pid / own clock, and value / world.
 
-`value` is that configuration and nothing else.  The same line also carries (outside the timed region of `value`):
+A plain run sets up, runs W warm-up steps, times K steps (`value`, `ms_per_step`), writes the outputs of the last timed step if
+--dump-outputs DIR is given (rank 0: DIR/logits.npy [8192,10], DIR/colors.npy [8192,3,3], DIR/depth.npy [4096,2], float32; the
+inputs and weights are seeded, so two builds can be compared output for output) and prints the line.  Everything below runs only
+with --full (--layers implies it); without it those keys are null.
+
+`value` is that configuration and nothing else.  With --full the same line also carries (outside the timed region of `value`):
   roofline       the dominant kernel of the step, measured live with hipEvents on the launch stream (SURVEY 8d);
                  `frac` = the FLOPs of the algorithm that runs (Winograd tiles on layers 1-3: what the matrix pipe issues)
                  / duration / peak, a utilisation <= 1; `direct_conv_equivalent_frac` = the same time priced in the reference's
@@ -223,6 +229,13 @@ def build_info():
         return json.load(open(os.path.join(ROOT, "blurry-edges_amd", "lib", "BUILD_INFO.json")))
     except Exception:
         return {}
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: what the timed path handed its caller in its last step, one float32 .npy per array (0.6 MB in all)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def leg_local_training(dev, native, peak, steps=60):
@@ -668,10 +681,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)      # 1.4 s of timed region: long enough for an outside observer to see the load
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the soak, roofline, extra_configs, dp and "
+                                                         "cpu_baseline legs (the options below refine those legs)")
     ap.add_argument("--soak-seconds", type=float, default=float(os.environ.get("BE_BENCH_SOAK", "3")),
-                    help="after the timed region, keep running the step for this long (untimed; 0 = off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs / dp legs (profiling runs)")
+                    help="with --full: after the timed region, keep running the step for this long (untimed; 0 = off)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs / dp legs (profiling runs)")
     ap.add_argument("--chunk", type=int, default=0, help="LocalStage sub-batch (patches); 0 = library default")
     ap.add_argument("--streams", type=int, default=0, help="LocalStage eval schedule: 2 = two half-batches on two side streams "
                                                            "(default), 1 = one stream (what profiles/ are taken with)")
@@ -679,9 +696,14 @@ def main():
                     help="gradient exchange of the dp leg: one all_reduce per bucket, or reduce_scatter + all_gather (be_hip.dp.GradSync)")
     ap.add_argument("--dp-buckets", type=int, default=int(os.environ.get("BE_DP_BUCKETS", "4")), choices=(2, 4, 5),
                     help="gradient buckets of the dp leg (be_hip.dp.GROUPS_BY_COUNT): 4 (default), 2 or 5")
-    ap.add_argument("--only-dp", action="store_true", help="run the dp leg alone (A/B runs of the exchange): no extra_configs, no cpu baseline")
-    ap.add_argument("--layers", action="store_true", help="print the per-launch conv timing table to stderr")
+    ap.add_argument("--only-dp", action="store_true", help="with --full: run the dp leg alone (A/B runs of the exchange): no extra_configs, "
+                                                            "no cpu baseline")
+    ap.add_argument("--layers", action="store_true", help="print the per-launch conv timing table of the roofline leg to stderr "
+                                                           "(implies --full)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    args.full = args.full or args.layers
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -767,10 +789,60 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     pairs_per_s = world * PAIRS * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before any later leg runs the step again and overwrites colors / depth
+        dump_outputs(args.dump_outputs, logits=est, colors=colors, depth=depth)
+
+    # ---- what lets a reader verify the run (VERDICT r4 #1): who ran, on which device, over which library
+    prop = torch.cuda.get_device_properties(dev)
+    me = dict(rank=rank, local_rank=local_rank, device=f"cuda:{local_rank}", name=prop.name, pid=os.getpid(),
+              pci_bus_id=getattr(prop, "pci_bus_id", None), visible=os.environ.get("HIP_VISIBLE_DEVICES", os.environ.get("CUDA_VISIBLE_DEVICES")),
+              ms_per_step=round(own_elapsed / args.steps * 1e3, 3))
+    ranks_info = [me]
+    if dist is not None:
+        ranks_info = [None] * world
+        dist.all_gather_object(ranks_info, me)
+    backend = dist.get_backend() if dist is not None else None
+    try:
+        rccl_version = ".".join(str(v) for v in torch.cuda.nccl.version())
+    except Exception:
+        rccl_version = None
+    launch = dict(launcher=os.environ.get("BE_BENCH_LAUNCHER", "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "none"),
+                  backend=backend, rccl_ranks=(dist.get_world_size() if backend == "nccl" else 0), rccl_version=rccl_version,
+                  ranks=ranks_info, value_per_gpu=round(pairs_per_s / world, 1))
+
+    # ---- the legs of --full fill these, each on its own clock (never part of `value`)
+    soak, roof, extra, dp_leg = None, None, None, None
+    head = git_head()
+
+    def headline(dp_result, cpu=None, more=None):
+        """the one JSON line, from whatever has been measured so far"""
+        out = {
+            "metric": "patch-pairs/s (local CNN + render + depth) on 21x21 synth",
+            "value": round(pairs_per_s, 1), "unit": "patch-pairs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
+            "config": {"workload": "configs[1]: batch of 4096 synthetic 21x21 two-aperture patch pairs per GPU "
+                                   "(8192 CNN patches): LocalStage inference + pass-A colour solve + depth solve",
+                       "pairs_per_gpu": PAIRS, "streams": model.streams, "weights": "portable-generator random init (no checkpoint offline)",
+                       "sharding": "independent pairs per rank, no data-path collective"},
+            "roofline": roof, "cpu_baseline": cpu, "soak": soak, "launch": launch, "extra_configs": extra, "dp": dp_result, "git_head": head,
+        }
+        out.update(more or {})
+        return out
+
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            emit(json.dumps(headline(None)))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # ---- untimed soak (NOT part of `value`): the same step for a few seconds, so that an outside observer sampling the GPU sees
     #      the load (K = 20 steps are 0.24 s of a 40 s run) and so that the line carries a second, longer-window rate to hold
     #      `value` against
-    soak = None
     if args.soak_seconds > 0:
         barrier()
         t1 = time.perf_counter()
@@ -788,7 +860,6 @@ def main():
     # ---- roofline leg: the same K steps again with a hipEvent pair around every matrix-kernel launch (on the launch
     #      stream = torch's current stream); dominant kernel = whichever kernel id takes the most time in the step
     peak = PEAK_FP32_MFMA_TFLOPS
-    roof = None
     if rank == 0:
         # per-kernel durations mean something only when nothing else shares the chip: this pass runs the ONE-stream schedule
         # (the timed region above used model.streams, two half-batches on two side streams by default)
@@ -855,44 +926,7 @@ def main():
             except Exception:
                 roof["traffic_recorded"] = None
 
-    # ---- what lets a reader verify the run (VERDICT r4 #1): who ran, on which device, over which library
-    prop = torch.cuda.get_device_properties(dev)
-    me = dict(rank=rank, local_rank=local_rank, device=f"cuda:{local_rank}", name=prop.name, pid=os.getpid(),
-              pci_bus_id=getattr(prop, "pci_bus_id", None), visible=os.environ.get("HIP_VISIBLE_DEVICES", os.environ.get("CUDA_VISIBLE_DEVICES")),
-              ms_per_step=round(own_elapsed / args.steps * 1e3, 3))
-    ranks_info = [me]
-    if dist is not None:
-        ranks_info = [None] * world
-        dist.all_gather_object(ranks_info, me)
-    backend = dist.get_backend() if dist is not None else None
-    try:
-        rccl_version = ".".join(str(v) for v in torch.cuda.nccl.version())
-    except Exception:
-        rccl_version = None
-    launch = dict(launcher=os.environ.get("BE_BENCH_LAUNCHER", "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "none"),
-                  backend=backend, rccl_ranks=(dist.get_world_size() if backend == "nccl" else 0), rccl_version=rccl_version,
-                  ranks=ranks_info, value_per_gpu=round(pairs_per_s / world, 1))
-
     # ---- the other configurations, each on its own clock (never part of `value`)
-    extra, dp_leg = None, None
-    head = git_head()
-
-    def headline(dp_result, cpu=None, more=None):
-        """the one JSON line, from whatever has been measured so far"""
-        out = {
-            "metric": "patch-pairs/s (local CNN + render + depth) on 21x21 synth",
-            "value": round(pairs_per_s, 1), "unit": "patch-pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "configs[1]: batch of 4096 synthetic 21x21 two-aperture patch pairs per GPU "
-                                   "(8192 CNN patches): LocalStage inference + pass-A colour solve + depth solve",
-                       "pairs_per_gpu": PAIRS, "streams": model.streams, "weights": "portable-generator random init (no checkpoint offline)",
-                       "sharding": "independent pairs per rank, no data-path collective"},
-            "roofline": roof, "cpu_baseline": cpu, "soak": soak, "launch": launch, "extra_configs": extra, "dp": dp_result, "git_head": head,
-        }
-        out.update(more or {})
-        return out
-
     if not args.no_extra:
         if rank == 0 and not args.only_dp:
             extra = []

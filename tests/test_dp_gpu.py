@@ -231,7 +231,7 @@ def test_workflow_local_and_global_training_data_parallel_two_ranks(tmp_path):
 
 @pytest.mark.parametrize("launcher", ["plain", "torchrun"])
 def test_bench_two_rank_rehearsal_on_one_gpu(tmp_path, launcher):
-    """`python bench.py --gpus 2` - the PLAIN command, as the driver's N = 1 record is launched: bench.py spawns its two ranks itself
+    """`python bench.py --gpus 2 --full` - the PLAIN command, as the driver's N = 1 record is launched: bench.py spawns its two ranks itself
     as child processes before any GPU call - rehearsed on ONE GPU over gloo (BE_DIST_BACKEND=gloo BE_LOCAL_DEVICE=0): the N > 1
     branch - barriers, MAX over ranks, rank-0-only legs, the dp leg with the real gradient exchange and the segmented-graph step,
     the watchdog plumbing - must produce ONE well-formed JSON line that says who ran where.  "torchrun": the same through
@@ -243,7 +243,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu(tmp_path, launcher):
     env = dict(os.environ, BE_DIST_BACKEND="gloo", BE_LOCAL_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     if launcher == "plain":
         cmd = [sys.executable] + tail
     else:
@@ -282,3 +282,47 @@ def test_bench_two_rank_rehearsal_on_one_gpu(tmp_path, launcher):
     assert dp["ab_best"]["segmented_graph_step_ms"] == min(e["segmented_graph_step_ms"] for e in ab) and "BE_BENCH_CAPTURED_DP" in dp["ab_note"]
     assert len(d["extra_configs"]) == 4 and all("error" not in e for e in d["extra_configs"])
     assert d["extra_configs"][3]["images_per_s"] > 0                       # the global-stage training step
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_timed_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the headline keys with `value` and
+    `ms_per_step` from the K timed steps, none of the --full legs, and what the timed path returned in its last step as float32 .npy
+    files.  Inputs and weights are seeded, so a second run dumps the same bits; the dumped logits are the oracle's on the same pairs."""
+    if not torch.cuda.is_available():
+        pytest.fail("gpu-marked test run without a GPU")
+    import json
+    import subprocess
+    for p in (ROOT, PKG):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    from be_hip import synth
+    from oracle import local_stage as ols
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    shapes = {"logits": (8192, 10), "colors": (8192, 3, 3), "depth": (4096, 2)}
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["full"] is False and d["n_gpus"] == 1
+        assert d["unit"] == "patch-pairs/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["metric"]
+        assert d["value"] == pytest.approx(4096 * 4 / (d["ms_per_step"] * 4e-3), rel=1e-3)
+        for k in ("roofline", "cpu_baseline", "soak", "extra_configs", "dp"):
+            assert d[k] is None, k
+        got = {n: np.load(out / f"{n}.npy") for n in shapes}
+        assert {n: (a.shape, a.dtype) for n, a in got.items()} == {n: (s, np.float32) for n, s in shapes.items()}
+        assert all(np.isfinite(a).all() for a in got.values())
+        dumps.append(got)
+    for n in shapes:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+    # the first 16 pairs (both apertures) through the oracle: the dump is the hot path's answer for bench.py's own inputs
+    x_np, _ = synth.synthetic_patch_pairs(4096)
+    xb = torch.from_numpy(np.concatenate([x_np[:16], x_np[4096:4112]]))
+    with torch.no_grad():
+        est_o = ols.local_stage_forward(ols.to_torch_sd(synth.local_stage_state_dict()), xb).numpy()
+    est = np.concatenate([dumps[0]["logits"][:16], dumps[0]["logits"][4096:4112]])
+    assert np.abs(est - est_o).max() / np.abs(est_o).max() <= 1e-5
