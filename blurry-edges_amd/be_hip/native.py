@@ -119,6 +119,8 @@ _SIGNATURES = {
     "be_datagen_noise_f64": (C.c_int, [_P, _P, C.c_double, C.c_uint32, C.c_int64, C.c_int64, _P, _P, _P]),
     "be_datagen_candidates_f64": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "be_datagen_crop_f64": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64] + [C.c_int] * 4 + [_P, _P]),
+    "be_datagen_test_psf_doubles": (C.c_size_t, [C.c_int] * 3),
+    "be_datagen_test_render_f64": (C.c_int, [_P] * 8 + [C.c_size_t] + [C.c_int] * 6 + [_P, _P, _P]),
     "be_attention_train_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "be_attention_train_fwd_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint32, _P]),
     "be_attention_bwd_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

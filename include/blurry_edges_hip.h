@@ -628,6 +628,23 @@ int be_datagen_crop_f64(const double* const* in6, const double* bloc, const doub
                         int64_t n_patch, int n, int H, int W, int R, double* const* out9, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Textured test set (test_data_generator.py:87-121, render_layer + render_image): the layered defocus render, float64, both
+ * apertures.  L = n_interval + 1 depth layers per layer set (set 0 background, set 1 foreground object + mask); keys [N,2,L] =
+ * np.linspace(max, min, L) of each set's depth plane (:116-117; the foreground's over its mask); layer weights are the hat functions
+ * of :95-102 evaluated in the reference's operation order; each layer is a scipy.ndimage.convolve(mode='reflect') with its PSF
+ * (taps in row-major order, |w| <= DBL_EPSILON skipped, no contraction).  bkgd, frgd [N,H,W,3] (BGR, 0..255), mask [N,H,W] (0/1),
+ * depth_bg, depth_fg [N,H,W].  psf: per (image, set, aperture, layer) one (2*kmax+1)^2 slot holding the layer's (2k+1)^2 kernel
+ * (utils/data_generator.py:19-23) centred in it, k = psf_k [N,2,2,L] (clamped to kmax on the device); psf_len (doubles) must be at
+ * least be_datagen_test_psf_doubles(N, n_interval, kmax).  Outputs img_clean [N,2,H,W,3] = bg * (1 - m) + fg, mask_blur [N,2,H,W]
+ * = m (clipped to [0, 1]).  all_layers = 1 adds every layer's term (the reference's full sum; checking only).  N <= 32767, kmax <= 64;
+ * N = 0 launches nothing. */
+size_t be_datagen_test_psf_doubles(int n, int n_interval, int kmax);
+int be_datagen_test_render_f64(const double* bkgd, const double* frgd, const double* mask, const double* depth_bg,
+                               const double* depth_fg, const double* keys, const double* psf, const int* psf_k, size_t psf_len,
+                               int kmax, int n, int H, int W, int n_interval, int all_layers, double* img_clean, double* mask_blur,
+                               void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py's roofline leg): opt-in hipEvent pair around every matrix-kernel launch and around the
  * HBM-bound kernels of the LocalStage / pass-A step, recorded on
  * the launch stream.  be_profile_enable(0) turns it off and frees the events.  Not thread-safe.
