@@ -768,7 +768,7 @@ def local_stage_forward_view(packed, view, patches_per_image: int, n: int, devic
 KERNEL_NAMES = {0: "k_conv_igemm<2,2,2,2,TAPS> (128x128)", 1: "k_conv_igemm<4,1,1,3,TAPS> (128x96)",
                 2: "k_conv_igemm<4,1,1,2,TAPS> (128x64)", 3: "k_conv_igemm<4,1,1,1,TAPS> (128x32)",
                 4: "k_conv_igemm<4,1,1,2,ROW8> (conv1)", 5: "k_conv_igemm small-M tiles (64x64 / 128x32)",
-                6: "k_wino_gemm_ws / k_wino_gemm (128x128 tiles, the Winograd transform-domain GEMMs of a layer - one per position: 40 for the 8x5 tiles - per launch; weight-stationary form for K = 96 / 256 / 384 and full tiles)",
+                6: "k_wino_gemm<0, 1> (128x128 tiles, the Winograd transform-domain GEMMs of a layer - one per position: 40 for the 8x5 tiles - per launch, in split-bf16 arithmetic: six v_mfma_f32_32x32x16_bf16 per product, FLOPs counted as fp32 products; BE_WINO_F32=1: the fp32 k_wino_gemm_ws / k_wino_gemm / batched k_conv_igemm)",
                 7: "k_wino_gemm as a row GEMM (1x1 convolutions / linears of large batches)",
                 8: "k_wino_in / k_wino_out_in / k_wino_out / k_wino_out_pool2 (Winograd transforms)", 9: "k_maxpool_nhwc",
                 10: "k_render_colors (pass A)", 11: "conv1 input staging",

@@ -4,7 +4,9 @@
 //     Y = A^T [ (G g G^T) o (B^T d B) ] A      summed over the input channels
 // turns the convolution into NPOS = 40 independent GEMMs [2N tiles x Cin] x [Cin x Cout] (one per position of the 8x5 transform
 // domain): 80 multiplies per (cin, cout) pair and map instead of the 324 of the direct form - 4.05x less work for the matrix
-// pipe, in exact fp32 products.  Interpolation points: rows 0, +-1, +-2, +-1/2, inf; columns 0, +-1, 2, inf.
+// pipe.  The products are split-bf16 (bf16x6: each fp32 operand split exactly into three bf16 pieces, six bf16 MFMAs per product,
+// fp32 accumulation - k_wino_gemm<0, 1>); BE_WINO_F32=1 restores exact fp32 products (the kernels below marked fp32).
+// Interpolation points: rows 0, +-1, +-2, +-1/2, inf; columns 0, +-1, 2, inf.
 // -DBE_WINO_TH=3 builds rounds 1-3's F(3x3,3x3): four 5x5 tiles per map, 25 GEMMs, 100 multiplies (an A/B target, `make wino3`).
 // Accuracy on the whole network against the fp64 oracle: logits 0.9-4.9e-6 over random, trained and stressed weights (5x5 tiles:
 // 1.8-3.0e-6; direct fp32 convolutions 1.1-3.3e-6), tolerance 1e-5 - DESIGN.md 3.1 / 4.
@@ -12,11 +14,15 @@
 //   k_wino_pack    weights [Cout,Cin,3,3] (+ folded BatchNorm) -> U [NPOS][Cout_pad][Cin] in the 1x1 layout of k_conv_igemm
 //   k_wino_in      x [N,6,6,C] NHWC -> V: tile-major [TPI N][NPOS][C] for large batches, plane-major [NPOS][TPI N][C] for small ones
 //                  (HBM-bound: reads 36, writes TPI * NPOS = 80 values per channel)
-//   k_wino_gemm    M[xi] = V[xi] U[xi]^T for the NPOS positions xi: one workgroup per 128x128 tile walks all of them (large
-//                  batches; small ones go through be_conv_nhwc_batched_f32 on k_conv_igemm, same arithmetic per output element)
-//   k_wino_gemm_ws the same GEMMs weight-stationary (B tile in registers, A streamed through LDS by DMA): batches of >= 4096 maps
+//   k_wino_gemm    M[xi] = V[xi] U[xi]^T for the NPOS positions xi: one workgroup per 128x128 tile walks a group of them.
+//                  <0, 1>: split-bf16, every batch size (tile-major buffers for large batches, plane-major for small ones).
+//                  fp32 (BE_WINO_F32=1): <0, 0> for large batches, all positions per workgroup; small ones go through
+//                  be_conv_nhwc_batched_f32 on k_conv_igemm, same arithmetic per output element
+//   k_wino_gemm_ws the fp32 GEMMs weight-stationary (B tile in registers, A streamed through LDS by DMA): batches of >= 4096 maps
 //   k_wino_out     M -> y [N,6,6,Cout] + bias (+ residual) (+ Smish)
 //   k_wino_out_in  conv1 -> conv2 of a residual block: output transform + Smish + input transform, the map stays in registers
+#include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include "be_common.h"
 #include "be_device_math.h"
@@ -315,9 +321,49 @@ struct GemmArgs {
     const float* bias;    // EPI = 1: y = act(acc + bias[col] (+ res[row][col]))
     const float* res;     //          same row stride as y
     int act;
+    int zgroups;          // BF6: problem groups (one workgroup per M tile x N tile x group)
+    int npad;             // BF6: rows of w that exist (Npad; B rows past it load row 0 of the tile and are never stored)
 };
 
-template <int EPI>
+// ---- split-bf16 operands (BF6 = 1) --------------------------------------------------------------------------------------------
+// x = hi + mid + lo exactly, each a bf16 rounded to nearest-even from what is left: |mid| <= 2^-8 |x|, |lo| <= 2^-16 |x| (finite x
+// whose lo stays a bf16 normal, |x| >= ~2^-110; below that lo loses bits to the bf16 subnormal grid, an absolute error < 2^-133).
+// A product of two split operands is the six bf16 MFMAs of all pieces but mid.lo, lo.mid, lo.lo (<= 3 x 2^-24 relative), in fp32
+// accumulation.  Inf / NaN: hi keeps them, x - hi is NaN, so the products stay non-finite.  The residuals are formed with plain
+// v_sub_f32: hipcc's SLP pass otherwise packs them into v_pk_add_f32, which beside MFMAs costs more issue than two scalar ops.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
+__device__ __forceinline__ float sub_f32(float x, float y) {
+    float r;
+    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+    return r;
+}
+// the 8 values of two fp32 quads -> the hi / mid / lo fragments of one 32x32x16 bf16 MFMA operand
+__device__ __forceinline__ void split8(f32x4 a, f32x4 b, bf16x8& h, bf16x8& m, bf16x8& l) {
+    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        const bf16x2 hb = __builtin_convertvector((f32x2){x[e], x[e + 1]}, bf16x2);          // v_cvt_pk_bf16_f32: RNE
+        const unsigned hu = __builtin_bit_cast(unsigned, hb);
+        const float r0 = sub_f32(x[e], bf_lo(hu)), r1 = sub_f32(x[e + 1], bf_hi(hu));        // exact
+        const bf16x2 mb = __builtin_convertvector((f32x2){r0, r1}, bf16x2);
+        const unsigned mu = __builtin_bit_cast(unsigned, mb);
+        const bf16x2 lb = __builtin_convertvector((f32x2){sub_f32(r0, bf_lo(mu)), sub_f32(r1, bf_hi(mu))}, bf16x2);   // exact
+        h[e] = hb[0]; h[e + 1] = hb[1];
+        m[e] = mb[0]; m[e + 1] = mb[1];
+        l[e] = lb[0]; l[e + 1] = lb[1];
+    }
+}
+
+// EPI: 0 = raw Winograd problems, 1 = row GEMM with bias / residual / activation (fp32 only).
+// BF6 = 1: the split-bf16 arithmetic of the Winograd GEMMs (v_mfma_f32_32x32x16_bf16, six products per 16-deep K chunk, in the
+// fixed order lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi), fp32 operands in memory and LDS, split after the fragment read.
+// The workgroup walks a group of problems rather than all of them (a.zgroups groups: the 40 problems of a 4096-patch layer are
+// only 64 x 2-3 tiles otherwise); every output element still sees the same K loop, so the group count changes no bit.
+template <int EPI, int BF6 = 0>
 __global__ __launch_bounds__(256, 3)
 void k_wino_gemm(GemmArgs a) {
     constexpr int BM = 128, BN = 128, BKT = 16;
@@ -326,7 +372,16 @@ void k_wino_gemm(GemmArgs a) {
     const int bid = blockIdx.x;
     const int xcd = bid & 7, slot = bid >> 3;          // all N tiles of an M tile on one XCD
     const int n_tile = slot % a.n_tiles;
-    const int m_tile = (slot / a.n_tiles) * 8 + xcd;
+    int m_tile = (slot / a.n_tiles) * 8 + xcd;
+    if constexpr (BF6) {                               // unit -> (M tile, problem group): the groups of an M tile on one XCD too
+        const int zg = m_tile % a.zgroups, zper = (a.nb + a.zgroups - 1) / a.zgroups;
+        m_tile /= a.zgroups;
+        if (m_tile >= a.m_tiles || zg * zper >= a.nb) return;
+        a.x += (int64_t)zg * zper * a.xb;
+        a.w += (int64_t)zg * zper * a.wb;
+        a.y += (int64_t)zg * zper * a.yb;
+        a.nb = min(zper, a.nb - zg * zper);
+    }
     if (m_tile >= a.m_tiles) return;
     const int n0 = n_tile * BN, row_base = m_tile * a.mrows;
     const int tid = threadIdx.x;
@@ -343,16 +398,19 @@ void k_wino_gemm(GemmArgs a) {
         // (walked tiles, zrows > 0, are launched only when every tile is full: M % (128 nb) == 0)
         a_off[p] = (unsigned)((row_base + r < a.M ? r : 0) * a.lda + 4 * sq) * 4u;
         b_off[p] = (unsigned)(r * a.K + 4 * sq) * 4u;  // rows up to Npad exist (zero rows past N)
+        if (BF6 && n0 + r >= a.npad) b_off[p] = (unsigned)(4 * sq) * 4u;   // (small layers: Npad need not be a multiple of 128)
     }
     const float* xt = a.x + (int64_t)row_base * a.lda; // uniform
     const float* wt = a.w + (int64_t)n0 * a.K;
     const int kchunks = a.K / BKT, total = kchunks * a.nb;
     // fragment reads: row = 64 wm + 32 i + li, quad (lh + 2 g) ^ ((li >> 2) & 3)
+    // (BF6: k = 8 lh .. 8 lh + 7, the quads 2 lh and 2 lh + 1 - the bf16 operand map; conflict-free for the same reason)
     const int fsw = (li >> 2) & 3;
-    const int a_fr0 = (wm * 64 + li) * BKT + 4 * (lh ^ fsw);
-    const int a_fr1 = (wm * 64 + li) * BKT + 4 * ((lh + 2) ^ fsw);
-    const int b_fr0 = BM * BKT + (wn * 64 + li) * BKT + 4 * (lh ^ fsw);
-    const int b_fr1 = BM * BKT + (wn * 64 + li) * BKT + 4 * ((lh + 2) ^ fsw);
+    const int q0 = BF6 ? 2 * lh : lh, q1 = BF6 ? 2 * lh + 1 : lh + 2;
+    const int a_fr0 = (wm * 64 + li) * BKT + 4 * (q0 ^ fsw);
+    const int a_fr1 = (wm * 64 + li) * BKT + 4 * (q1 ^ fsw);
+    const int b_fr0 = BM * BKT + (wn * 64 + li) * BKT + 4 * (q0 ^ fsw);
+    const int b_fr1 = BM * BKT + (wn * 64 + li) * BKT + 4 * (q1 ^ fsw);
     f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -401,6 +459,22 @@ void k_wino_gemm(GemmArgs a) {
                 af[1][i] = *reinterpret_cast<const f32x4*>(sb + a_fr1 + i * 32 * BKT);
                 bf[1][i] = *reinterpret_cast<const f32x4*>(sb + b_fr1 + i * 32 * BKT);
             }
+            if constexpr (BF6) {
+                bf16x8 ap[3][2], bp[3][2];             // [hi, mid, lo][i or j]
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    split8(af[0][i], af[1][i], ap[0][i], ap[1][i], ap[2][i]);
+                    split8(bf[0][i], bf[1][i], bp[0][i], bp[1][i], bp[2][i]);
+                }
+                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi
+#pragma unroll
+                for (int p = 0; p < 6; ++p)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[PA[p]][i], bp[PB[p]][j], acc[i][j], 0, 0, 0);
+            } else {
 #pragma unroll
             for (int g = 0; g < 2; ++g)
 #pragma unroll
@@ -412,6 +486,7 @@ void k_wino_gemm(GemmArgs a) {
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g][i].z, bf[g][j].z, acc[i][j], 0, 0, 0);
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g][i].w, bf[g][j].w, acc[i][j], 0, 0, 0);
                     }
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
@@ -693,7 +768,51 @@ bool wino_large(int64_t n, int cout) {
     return ((cout + 31) / 32 * 32) % 128 == 0 && n >= 1024 && !no_persist && (int64_t)NPOS * TPI * n * (int64_t)cout < ((int64_t)1 << 31);
 }
 
+// The split-bf16 GEMMs (k_wino_gemm<0, 1>) for every batch size: tile-major buffers for large batches, plane-major for small ones
+// (only the strides differ), so one patch gets the same bits in any batch.
+int wino_gemms_bf6(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s) {
+    constexpr size_t lds = (size_t)2 * (128 + 128) * 16 * sizeof(float);
+    static be::DeviceFlags attr_set{};                          // dynamic-LDS cap raised once per device (thread-safe)
+    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm<0, 1>), lds, attr_set)) return rc_;
+    const int cp = (cout + 31) / 32 * 32;
+    const int64_t rows = (int64_t)TPI * n;
+    const bool tm = wino_large(n, cout);
+    const int m_tiles = (int)((rows + 127) / 128), n_tiles = (cp + 127) / 128, kchunks = cin / 16;
+    // problem groups: the fewest that give every CU >= 2 workgroups of the least work per CU (a workgroup costs its problems x K
+    // chunks + ~2 chunks of prologue and turnover; 3 fit on a CU, and a CU with fewer runs no faster than with 2 - one wave per SIMD)
+    static const int zg_env = getenv("BE_WINO_ZGROUPS") ? atoi(getenv("BE_WINO_ZGROUPS")) : 0;   // A/B knob
+    const int cus = be::device_cu_count();
+    int zgroups = 1;
+    if (zg_env > 0 && zg_env <= NPOS) {
+        zgroups = zg_env;
+    } else {
+        int64_t best = INT64_MAX;
+        for (int zg = 1; zg <= NPOS; ++zg) {
+            if (NPOS % zg) continue;
+            const int64_t wgs = (int64_t)m_tiles * zg * n_tiles, per_cu = std::max<int64_t>(2, (wgs + cus - 1) / cus);
+            const int64_t cost = per_cu * ((NPOS / zg) * kchunks + 2);
+            if (cost < best) { best = cost; zgroups = zg; }
+        }
+    }
+    GemmArgs g{V, packed_w, M, (int)rows, cin, cout, tm ? NPOS * cout : cout, NPOS, m_tiles, n_tiles,
+               tm ? (int64_t)cin : rows * cin, (int64_t)cp * cin, tm ? (int64_t)cout : rows * cout, tm ? NPOS * cin : cin, 128, 0,
+               nullptr, nullptr, 0, zgroups, cp};
+    const unsigned grid = (unsigned)(8 * ((m_tiles * zgroups + 7) / 8) * n_tiles);
+    {
+        // (FLOPs in fp32-equivalent products: what the layer computes, not the six bf16 products the matrix pipe issues)
+        be::ProfileScope prof(s, BE_KERNEL_WINO_GEMM, (double)NPOS * 2.0 * rows * cin * cout,
+                              (double)NPOS * 4.0 * ((double)rows * cin + (double)cin * cout + (double)rows * cout),
+                              (double)NPOS * 2.0 * m_tiles * n_tiles * 128.0 * 128.0 * cin);
+        hipLaunchKernelGGL((k_wino_gemm<0, 1>), dim3(grid), dim3(256), lds, s, g);
+    }
+    return be::check_launch("be_wino_conv3x3_6x6_f32(gemm, split bf16)");
+}
+
 int wino_gemms(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s, void* stream) {
+    // A/B knob: BE_WINO_F32=1 restores the fp32-MFMA GEMMs of all three batch regimes (weight-stationary, walked 128x128, and
+    // the batched k_conv_igemm of small batches)
+    static const bool f32 = getenv("BE_WINO_F32") != nullptr && atoi(getenv("BE_WINO_F32")) != 0;
+    if (!f32) return wino_gemms_bf6(V, packed_w, M, n, cin, cout, s);
     const int cp = (cout + 31) / 32 * 32;
     if (wino_large(n, cout)) {
         // large batches: one workgroup per (M tile, N tile) walks the 25 problems back to back

@@ -330,8 +330,10 @@ int be_conv_nhwc_fused2_f32(const be_conv_desc* desc_host, const float* x, const
 int be_conv_nhwc_batched_f32(const be_conv_desc* d, const float* x, const float* packed_w, const float* packed_bias, float* y,
                              int ldy, int nbatch, int64_t x_stride, int64_t w_stride, int64_t y_stride, void* stream);
 
-/* Winograd form of the 3x3 'same' convolutions on 6x6 maps (LocalStage layers 1-3): exact fp32 products and accumulation with
- * fewer multiplies than the direct form.  Tile shape (compile-time, be_wino_tile_rows()): 6 = F(6,3) along the rows x F(3,3) along
+/* Winograd form of the 3x3 'same' convolutions on 6x6 maps (LocalStage layers 1-3): fewer multiplies than the direct form, the
+ * transforms in fp32, the transform-domain products in split-bf16 (each fp32 operand split exactly into three bf16 pieces, six bf16
+ * MFMAs per product, fp32 accumulation; per-GEMM error at or below the fp32 products'; the same bits at every batch size).
+ * Environment BE_WINO_F32=1 (read once per process) restores exact fp32 products and accumulation.  Tile shape (compile-time, be_wino_tile_rows()): 6 = F(6,3) along the rows x F(3,3) along
  * the columns - two 8x5 tiles per map, 40 transform positions, 80 multiplies per map and channel pair instead of 324 (the default
  * since round 4); 3 = F(3,3) x F(3,3) - four 5x5 tiles, 25 positions, 100 multiplies (rounds 1-3).  be_wino_pack_f32 folds an
  * optional eval BatchNorm like be_conv_pack_f32 and writes U [positions][cout_pad32][cin] + bias [cout_pad32];
@@ -655,7 +657,7 @@ int be_datagen_test_render_f64(const double* bkgd, const double* frgd, const dou
 #define BE_KERNEL_CONV_128x32       3   /* fc.4                                                                */
 #define BE_KERNEL_CONV_ROW8_128x64  4   /* conv1 (7x7 row-gather)                                              */
 #define BE_KERNEL_CONV_SMALL        5   /* 64x64 / 128x32 tiles for small M (training batches)                 */
-#define BE_KERNEL_WINO_GEMM         6   /* k_wino_gemm_ws / k_wino_gemm: the transform-domain GEMMs (one per position) of a Winograd layer */
+#define BE_KERNEL_WINO_GEMM         6   /* k_wino_gemm<0, 1> (split bf16; fp32: k_wino_gemm_ws / k_wino_gemm): the transform-domain GEMMs (one per position) of a Winograd layer; FLOPs as fp32 products */
 #define BE_KERNEL_GEMM_ROWS         7   /* k_wino_gemm as a row GEMM: 1x1 convolutions / linears, large batches */
 /* HBM-bound kernels: `bytes` = the algorithmic bytes the launch has to move, `flops` = 0 */
 #define BE_KERNEL_WINO_TRANSFORM    8   /* k_wino_in / k_wino_out / k_wino_out_in / k_wino_out_pool2 */
