@@ -5,17 +5,20 @@
 // turns the convolution into NPOS = 40 independent GEMMs [2N tiles x Cin] x [Cin x Cout] (one per position of the 8x5 transform
 // domain): 80 multiplies per (cin, cout) pair and map instead of the 324 of the direct form - 4.05x less work for the matrix
 // pipe.  The products are split-bf16 (bf16x6: each fp32 operand split exactly into three bf16 pieces, six bf16 MFMAs per product,
-// fp32 accumulation - k_wino_gemm<0, 1>); BE_WINO_F32=1 restores exact fp32 products (the kernels below marked fp32).
+// fp32 accumulation - k_wino_gemm_ps); BE_WINO_F32=1 restores exact fp32 products (the kernels below marked fp32).
 // Interpolation points: rows 0, +-1, +-2, +-1/2, inf; columns 0, +-1, 2, inf.
 // -DBE_WINO_TH=3 builds rounds 1-3's F(3x3,3x3): four 5x5 tiles per map, 25 GEMMs, 100 multiplies (an A/B target, `make wino3`).
 // Accuracy on the whole network against the fp64 oracle: logits 0.9-4.9e-6 over random, trained and stressed weights (5x5 tiles:
 // 1.8-3.0e-6; direct fp32 convolutions 1.1-3.3e-6), tolerance 1e-5 - DESIGN.md 3.1 / 4.
 //
 //   k_wino_pack    weights [Cout,Cin,3,3] (+ folded BatchNorm) -> U [NPOS][Cout_pad][Cin] in the 1x1 layout of k_conv_igemm
+//   k_wino_pack_split  U -> its hi / mid / lo bf16 planes behind it, in k_wino_gemm_ps's LDS image (round 8)
 //   k_wino_in      x [N,6,6,C] NHWC -> V: tile-major [TPI N][NPOS][C] for large batches, plane-major [NPOS][TPI N][C] for small ones
 //                  (HBM-bound: reads 36, writes TPI * NPOS = 80 values per channel)
 //   k_wino_gemm    M[xi] = V[xi] U[xi]^T for the NPOS positions xi: one workgroup per 128x128 tile walks a group of them.
-//                  <0, 1>: split-bf16, every batch size (tile-major buffers for large batches, plane-major for small ones).
+//                  <0, 1>: split-bf16, every batch size (tile-major buffers for large batches, plane-major for small ones), both
+//                  operands split in the loop (round 7; BE_WINO_BF6_R7=1)
+//   k_wino_gemm_ps the same GEMMs and bits with B's pieces read ready from the planes, a 3-stage ring, counted waits (the default)
 //                  fp32 (BE_WINO_F32=1): <0, 0> for large batches, all positions per workgroup; small ones go through
 //                  be_conv_nhwc_batched_f32 on k_conv_igemm, same arithmetic per output element
 //   k_wino_gemm_ws the fp32 GEMMs weight-stationary (B tile in registers, A streamed through LDS by DMA): batches of >= 4096 maps
@@ -358,6 +361,39 @@ __device__ __forceinline__ void split8(f32x4 a, f32x4 b, bf16x8& h, bf16x8& m, b
     }
 }
 
+// ---- the weights pre-split (round 8) -------------------------------------------------------------------------------------------
+// k_wino_pack_split writes the hi / mid / lo pieces of U behind it, formed by split8 - the very pieces k_wino_gemm<0, 1> forms in
+// registers - in the image k_wino_gemm_ps's LDS stage holds: per (position, 128-row N tile, 16-deep K chunk) one contiguous 12-KB
+// block [plane hi, mid, lo][128 rows][2 x 16 B], the 16-B half h of a row (k = 8 h .. 8 h + 7) at slot h ^ ((row >> 3) & 1).  With
+// the swap a ds_read_b128 of one half for 32 rows puts each 16-lane group (rows 0-3, 12-15, 20-27 / 4-11, 16-19, 28-31) on 16
+// distinct 16-B slots of the 256-B bank row: conflict-free.  Rows from cout_pad up to the 128-row tile are zero.
+constexpr int PS_BLOCK = 3 * 128 * 16;                 // bf16 values per block (12 KB)
+constexpr int PS_STAGES = 4;                           // k_wino_gemm_ps's LDS ring: 4 x 20 KB, two workgroups per CU (160 KB)
+__device__ __forceinline__ int ps_slot(int row, int half) { return half ^ ((row >> 3) & 1); }
+
+__global__ void k_wino_pack_split(const float* __restrict__ U, int cout_pad, int cin, int n_tiles, __bf16* __restrict__ P) {
+    const int kg = cin / 8, rows = 128 * n_tiles;      // one thread = one (position, row, 8-deep K group)
+    const int64_t total = (int64_t)NPOS * rows * kg;
+    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
+        const int g = (int)(idx % kg), row = (int)((idx / kg) % rows), z = (int)(idx / ((int64_t)kg * rows));
+        f32x4 lo4 = {0.f, 0.f, 0.f, 0.f}, hi4 = lo4;
+        if (row < cout_pad) {
+            const f32x4* src = reinterpret_cast<const f32x4*>(U + ((size_t)z * cout_pad + row) * cin + 8 * g);
+            lo4 = src[0];
+            hi4 = src[1];
+        }
+        bf16x8 h, m, l;
+        split8(lo4, hi4, h, m, l);
+        const int r = row & 127;
+        bf16x8* dst = reinterpret_cast<bf16x8*>(P + ((size_t)(z * n_tiles + (row >> 7)) * (cin / 16) + (g >> 1)) * PS_BLOCK) + 2 * r +
+                      ps_slot(r, g & 1);
+        dst[0] = h;
+        dst[256] = m;                                  // (planes 128 rows x 2 halves of 16 B apart)
+        dst[512] = l;
+    }
+}
+
 // EPI: 0 = raw Winograd problems, 1 = row GEMM with bias / residual / activation (fp32 only).
 // BF6 = 1: the split-bf16 arithmetic of the Winograd GEMMs (v_mfma_f32_32x32x16_bf16, six products per 16-deep K chunk, in the
 // fixed order lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi), fp32 operands in memory and LDS, split after the fragment read.
@@ -540,6 +576,163 @@ void k_wino_gemm(GemmArgs a) {
         }
     }
 #undef WG_LOAD
+}
+
+// ---- split-bf16 GEMMs on the pre-split weights (round 8, the default) ---------------------------------------------------------------
+// k_wino_gemm<0, 1>'s arithmetic - the same pieces (split8, for B at pack time), the same v_mfma_f32_32x32x16_bf16 with the same lane ->
+// k map (k = 8 lh .. 8 lh + 7), the same six products per chunk in the same order, K ascending from a zero accumulator per problem:
+// bit-identical - with B's pieces read ready from LDS (k_wino_pack_split's blocks), so that only A (fp32 in HBM and LDS, as before)
+// is split in the loop: half the split instructions.  The stage grows to 8 KB A + 12 KB B; the K loop runs over a ring of four
+// stages (80 KB: two workgroups per CU) with the DMA three chunks ahead, explicit counted vmcnt waits and one raw s_barrier per chunk
+// (the idiom of k_wino_gemm_ws: no full drain of the DMA in front of every barrier), and the next chunk's fragments are read and
+// split right behind the current chunk's MFMAs (the read -> split chain no longer sits in front of every chunk's MFMAs).
+// vmcnt: every wave issues 5 DMA pieces per chunk (2 A + 3 B), so "vmcnt(5)" = all but the newest chunk's have landed.  At the end of
+// a problem the wait for the chunk after next sits IN FRONT of the stores (after them no count would be right without knowing how many
+// store instructions the compiler emitted); the last one drains everything, so no DMA into LDS outlives the workgroup.
+__global__ __launch_bounds__(256, 2)
+void k_wino_gemm_ps(GemmArgs a) {
+    constexpr int BM = 128, BKT = 16;
+    constexpr int ABYTES = BM * BKT * 4, BBYTES = PS_BLOCK * 2, STAGE = ABYTES + BBYTES;   // 8 KB + 12 KB
+    constexpr int NS = PS_STAGES;
+    extern __shared__ __attribute__((aligned(16))) float smem_w[];
+    char* const lds = reinterpret_cast<char*>(smem_w);
+    const int bid = blockIdx.x;
+    const int xcd = bid & 7, slot = bid >> 3;          // all N tiles and problem groups of an M tile on one XCD
+    const int n_tile = slot % a.n_tiles;
+    int m_tile = (slot / a.n_tiles) * 8 + xcd;
+    const int zg = m_tile % a.zgroups, zper = (a.nb + a.zgroups - 1) / a.zgroups;
+    m_tile /= a.zgroups;
+    if (m_tile >= a.m_tiles || zg * zper >= a.nb) return;
+    const int nb = min(zper, a.nb - zg * zper), kchunks = a.K / BKT, total = kchunks * nb;
+    const int n0 = n_tile * 128, row_base = m_tile * BM;
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int li = lane & 31, lh = lane >> 5;
+    // A staging as in k_wino_gemm: wave w fills pieces 2w, 2w+1 of the A tile, lane -> (row lane >> 2, swizzled quad)
+    const int srow = lane >> 2, sq = (lane & 3) ^ ((lane >> 4) & 3);
+    unsigned a_off[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int r = (2 * wave + p) * 16 + srow;
+        a_off[p] = (unsigned)((row_base + r < a.M ? r : 0) * a.lda + 4 * sq) * 4u;     // rows past M load a valid row, never stored
+    }
+    const char* xt = reinterpret_cast<const char*>(a.x + (int64_t)zg * zper * a.xb + (int64_t)row_base * a.lda);
+    // B: pieces 3w .. 3w+2 of the chunk's 12-KB block, which is already the LDS image (lane-linear: this lane's 16 B)
+    const char* wt = reinterpret_cast<const char*>(a.w + (int64_t)zg * zper * a.wb) + (int64_t)n_tile * kchunks * BBYTES + lane * 16;
+    float* const yg = a.y + (int64_t)zg * zper * a.yb;
+    // fragment reads: A row 64 wm + 32 i + li, quads 2 lh, 2 lh + 1 (swizzled as stored); B plane p, row 64 wn + 32 j + li, half lh
+    const int fsw = (li >> 2) & 3;
+    const int a_fr0 = ((wm * 64 + li) * BKT + 4 * ((2 * lh) ^ fsw)) * 4;
+    const int a_fr1 = ((wm * 64 + li) * BKT + 4 * ((2 * lh + 1) ^ fsw)) * 4;
+    const int b_fr = ABYTES + (wn * 64 + li) * 32 + ps_slot(li, lh) * 16;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    int lz = 0, lk = 0, l_buf = 0;                     // (problem, chunk) of the next DMA and its ring slot
+#define PS_DMA()                                                                                                \
+    do {                                                                                                        \
+        const char* xs_ = xt + ((int64_t)lz * a.xb + lk * BKT) * 4;                                             \
+        const char* ws_ = wt + (int64_t)lz * a.wb * 4 + lk * BBYTES;                                            \
+        char* st_ = lds + l_buf * STAGE;                                                                        \
+        _Pragma("unroll") for (int p_ = 0; p_ < 2; ++p_)                                                        \
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(xs_ + a_off[p_]), (lds_ptr_t)(st_ + (2 * wave + p_) * 1024), 16, 0, 0); \
+        _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                        \
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(ws_ + (3 * wave + p_) * 1024),                         \
+                                             (lds_ptr_t)(st_ + ABYTES + (3 * wave + p_) * 1024), 16, 0, 0);     \
+        if (lk + 1 < kchunks) ++lk; else if (lz + 1 < nb) { lk = 0; ++lz; }   /* past the end: the last chunk again */ \
+        l_buf = (l_buf + 1) % NS;                                                                               \
+    } while (0)
+    const unsigned y_off = (unsigned)((wm * 64 + 4 * lh) * a.ldy + wn * 64 + li) * 4u;
+    // the pieces of the chunk being multiplied: read from LDS and split (A) while the chunk before is still on the matrix pipe
+    bf16x8 ap[3][2], bp[3][2];                         // [hi, mid, lo][i or j]
+    int r_buf = 0;                                     // ring slot whose fragments are read next
+#define PS_FRAGS()                                                                                              \
+    do {                                                                                                        \
+        const char* sb_ = lds + r_buf * STAGE;                                                                  \
+        f32x4 af_[2][2];                                                                                        \
+        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                      \
+            af_[0][i_] = *reinterpret_cast<const f32x4*>(sb_ + a_fr0 + i_ * 32 * BKT * 4);                      \
+            af_[1][i_] = *reinterpret_cast<const f32x4*>(sb_ + a_fr1 + i_ * 32 * BKT * 4);                      \
+        }                                                                                                       \
+        _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                        \
+            _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                                    \
+                bp[p_][j_] = *reinterpret_cast<const bf16x8*>(sb_ + b_fr + p_ * 4096 + j_ * 32 * 32);           \
+        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) split8(af_[0][i_], af_[1][i_], ap[0][i_], ap[1][i_], ap[2][i_]); \
+        r_buf = (r_buf + 1) % NS;                                                                               \
+    } while (0)
+    PS_DMA();                                          // chunk 0
+    PS_DMA();                                          // chunk 1
+    PS_DMA();                                          // chunk 2
+    __builtin_amdgcn_s_waitcnt(0x0F75);                // vmcnt(5): chunks 0 and 1 have landed
+    __builtin_amdgcn_s_barrier();                      // ... every wave's
+    PS_FRAGS();                                        // chunk 0's pieces
+    int cz = 0, ck = 0;
+    bool landed = true;                                // the NEXT chunk's DMA is known to be in LDS
+    for (int kc = 0; kc < total; ++kc) {
+        if (!landed) __builtin_amdgcn_s_waitcnt(0x0F75);                               // vmcnt(5): chunk + 1 has landed
+        landed = false;
+        __builtin_amdgcn_s_barrier();                  // ... every wave's; everyone has read the slot of chunk - 1 (a chunk ago)
+        PS_DMA();                                      // chunk + 3, into that slot
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi
+#pragma unroll
+            for (int p = 0; p < 6; ++p)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[PA[p]][i], bp[PB[p]][j], acc[i][j], 0, 0, 0);
+            PS_FRAGS();                                // chunk + 1's pieces, under this chunk's MFMAs
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (++ck == kchunks) {                          // problem cz is complete: store, clear
+            if (kc + 1 < total) __builtin_amdgcn_s_waitcnt(0x0F75);                    // chunk + 2 has landed
+            else __builtin_amdgcn_s_waitcnt(0x0F70);                                   // nothing left in flight
+            landed = true;
+            __builtin_amdgcn_sched_barrier(0);
+            const int zrow = row_base;
+            char* yt = reinterpret_cast<char*>(yg + (int64_t)cz * a.yb + (int64_t)row_base * a.ldy + n0);             // uniform
+            if (zrow + BM <= a.M && n0 + 128 <= a.N) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
+                        float* yr = reinterpret_cast<float*>(yt + (size_t)ro * a.ldy * 4 + y_off);
+                        yr[0] = acc[i][0][r];
+                        yr[32] = acc[i][1][r];
+                    }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const bool c_ok = n0 + wn * 64 + j * 32 + li < a.N;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
+                            if (c_ok && zrow + wm * 64 + 4 * lh + ro < a.M)
+                                reinterpret_cast<float*>(yt + (size_t)ro * a.ldy * 4 + y_off)[j * 32] = acc[i][j][r];
+                        }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+            ck = 0; ++cz;
+        }
+    }
+#undef PS_DMA
+#undef PS_FRAGS
 }
 
 // ---- weight-stationary form of the same GEMMs (large batches, K = 96 / 256 / 384) ------------------------------------------
@@ -737,9 +930,12 @@ int launch_ws(const GemmArgs& g, hipStream_t s, int64_t n, int cin, int cout, in
 
 extern "C" int be_wino_tile_rows(void) { return TH; }
 
+// U [NPOS][cout_pad32][cin] fp32, then its pre-split bf16 planes: NPOS x (cout padded to 128) x cin x 3 bf16 (k_wino_pack_split)
+static size_t wino_u_floats(int cout, int cin) { return (size_t)NPOS * ((cout + 31) / 32 * 32) * cin; }
+
 extern "C" size_t be_wino_packed_floats(int cout, int cin) {
     if (cout <= 0 || cin <= 0 || cin % 32) return 0;
-    return (size_t)NPOS * ((cout + 31) / 32 * 32) * cin;
+    return wino_u_floats(cout, cin) + (size_t)NPOS * ((cout + 127) / 128 * 128) * cin * 3 / 2;
 }
 
 extern "C" int be_wino_pack_f32(const float* w, const float* b, const float* gamma, const float* beta, const float* mean,
@@ -752,7 +948,12 @@ extern "C" int be_wino_pack_f32(const float* w, const float* b, const float* gam
     const int cp = (cout + 31) / 32 * 32;
     hipLaunchKernelGGL(k_wino_pack, dim3(grid_cap((int64_t)cp * cin, 256, 4096)), dim3(256), 0, be::as_stream(stream), w, b, gamma,
                        beta, mean, var, eps, cout, cin, cp, packed_w, packed_bias);
-    return be::check_launch("be_wino_pack_f32");
+    if (int rc = be::check_launch("be_wino_pack_f32")) return rc;
+    const int n_tiles = (cout + 127) / 128;
+    hipLaunchKernelGGL(k_wino_pack_split, dim3(grid_cap((int64_t)NPOS * 128 * n_tiles * (cin / 8), 256, 4096)), dim3(256), 0,
+                       be::as_stream(stream), packed_w, cp, cin, n_tiles,
+                       reinterpret_cast<__bf16*>(packed_w + wino_u_floats(cout, cin)));
+    return be::check_launch("be_wino_pack_f32(split)");
 }
 
 extern "C" size_t be_wino_workspace_floats(int64_t n, int cin, int cout) {
@@ -808,11 +1009,52 @@ int wino_gemms_bf6(const float* V, const float* packed_w, float* M, int64_t n, i
     return be::check_launch("be_wino_conv3x3_6x6_f32(gemm, split bf16)");
 }
 
+// The same GEMMs on k_wino_gemm_ps: A (V) split in the loop, B from the pre-split planes behind U.  Bit-identical to wino_gemms_bf6.
+int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s) {
+    constexpr size_t lds = (size_t)PS_STAGES * (128 * 16 * 4 + PS_BLOCK * 2);    // stages of 8 KB A + 12 KB B
+    static be::DeviceFlags attr_set{};                          // dynamic-LDS cap raised once per device (thread-safe)
+    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm_ps), lds, attr_set)) return rc_;
+    const int64_t rows = (int64_t)TPI * n;
+    const bool tm = wino_large(n, cout);
+    const int m_tiles = (int)((rows + 127) / 128), n_tiles = (cout + 127) / 128, kchunks = cin / 16;
+    // problem groups: two workgroups fit on a CU, and a CU with one runs no faster than with two, so a launch costs rounds of two
+    // workgroups per CU times a workgroup's problems x K chunks + ~2 chunks of prologue and turnover; the fewest groups of least cost
+    static const int zg_env = getenv("BE_WINO_ZGROUPS") ? atoi(getenv("BE_WINO_ZGROUPS")) : 0;   // A/B knob
+    const int cus = be::device_cu_count();
+    int zgroups = 1;
+    if (zg_env > 0 && zg_env <= NPOS) {
+        zgroups = zg_env;
+    } else {
+        int64_t best = INT64_MAX;
+        for (int zg = 1; zg <= NPOS; ++zg) {
+            if (NPOS % zg) continue;
+            const int64_t wgs = (int64_t)m_tiles * zg * n_tiles, rounds = ((wgs + cus - 1) / cus + 1) / 2;
+            const int64_t cost = rounds * ((NPOS / zg) * kchunks + 2);
+            if (cost < best) { best = cost; zgroups = zg; }
+        }
+    }
+    // (w: the planes; wb = floats per position of them)
+    GemmArgs g{V, packed_w + wino_u_floats(cout, cin), M, (int)rows, cin, cout, tm ? NPOS * cout : cout, NPOS, m_tiles, n_tiles,
+               tm ? (int64_t)cin : rows * cin, (int64_t)n_tiles * kchunks * (PS_BLOCK / 2), tm ? (int64_t)cout : rows * cout,
+               tm ? NPOS * cin : cin, 128, 0, nullptr, nullptr, 0, zgroups, n_tiles * 128};
+    const unsigned grid = (unsigned)(8 * ((m_tiles * zgroups + 7) / 8) * n_tiles);
+    {
+        // (FLOPs in fp32-equivalent products, as wino_gemms_bf6)
+        be::ProfileScope prof(s, BE_KERNEL_WINO_GEMM, (double)NPOS * 2.0 * rows * cin * cout,
+                              (double)NPOS * 4.0 * ((double)rows * cin + (double)rows * cout) + (double)NPOS * 6.0 * cin * n_tiles * 128,
+                              (double)NPOS * 2.0 * m_tiles * n_tiles * 128.0 * 128.0 * cin);
+        hipLaunchKernelGGL(k_wino_gemm_ps, dim3(grid), dim3(256), lds, s, g);
+    }
+    return be::check_launch("be_wino_conv3x3_6x6_f32(gemm, split bf16, pre-split weights)");
+}
+
 int wino_gemms(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s, void* stream) {
-    // A/B knob: BE_WINO_F32=1 restores the fp32-MFMA GEMMs of all three batch regimes (weight-stationary, walked 128x128, and
-    // the batched k_conv_igemm of small batches)
+    // A/B knobs: BE_WINO_F32=1 restores the fp32-MFMA GEMMs of all three batch regimes (weight-stationary, walked 128x128, and
+    // the batched k_conv_igemm of small batches); BE_WINO_BF6_R7=1 the split-bf16 GEMMs that split B in the loop too (round 7:
+    // the same bits as the default)
     static const bool f32 = getenv("BE_WINO_F32") != nullptr && atoi(getenv("BE_WINO_F32")) != 0;
-    if (!f32) return wino_gemms_bf6(V, packed_w, M, n, cin, cout, s);
+    static const bool r7 = getenv("BE_WINO_BF6_R7") != nullptr && atoi(getenv("BE_WINO_BF6_R7")) != 0;
+    if (!f32) return r7 ? wino_gemms_bf6(V, packed_w, M, n, cin, cout, s) : wino_gemms_ps(V, packed_w, M, n, cin, cout, s);
     const int cp = (cout + 31) / 32 * 32;
     if (wino_large(n, cout)) {
         // large batches: one workgroup per (M tile, N tile) walks the 25 problems back to back

@@ -333,10 +333,13 @@ int be_conv_nhwc_batched_f32(const be_conv_desc* d, const float* x, const float*
 /* Winograd form of the 3x3 'same' convolutions on 6x6 maps (LocalStage layers 1-3): fewer multiplies than the direct form, the
  * transforms in fp32, the transform-domain products in split-bf16 (each fp32 operand split exactly into three bf16 pieces, six bf16
  * MFMAs per product, fp32 accumulation; per-GEMM error at or below the fp32 products'; the same bits at every batch size).
- * Environment BE_WINO_F32=1 (read once per process) restores exact fp32 products and accumulation.  Tile shape (compile-time, be_wino_tile_rows()): 6 = F(6,3) along the rows x F(3,3) along
+ * Environment BE_WINO_F32=1 (read once per process) restores exact fp32 products and accumulation; BE_WINO_BF6_R7=1 the round-7 split-bf16
+ * GEMMs that split the fp32 U in the loop (same bits as the default).  Tile shape (compile-time, be_wino_tile_rows()): 6 = F(6,3) along the rows x F(3,3) along
  * the columns - two 8x5 tiles per map, 40 transform positions, 80 multiplies per map and channel pair instead of 324 (the default
  * since round 4); 3 = F(3,3) x F(3,3) - four 5x5 tiles, 25 positions, 100 multiplies (rounds 1-3).  be_wino_pack_f32 folds an
- * optional eval BatchNorm like be_conv_pack_f32 and writes U [positions][cout_pad32][cin] + bias [cout_pad32];
+ * optional eval BatchNorm like be_conv_pack_f32 and writes U [positions][cout_pad32][cin] + bias [cout_pad32]; behind U in the same buffer
+ * the hi / mid / lo bf16 pieces of U that the split-bf16 GEMMs read (positions x cout padded to 128 x cin x 3 bf16: packed size =
+ * U + 1.5 x positions x cout_pad128 x cin floats, be_wino_packed_floats);
  * be_wino_conv3x3_6x6_f32 runs input transform, `positions` batched GEMMs and output transform (+ bias, residual, activation).
  * workspace: be_wino_workspace_floats(n, cin, cout) floats.  cin %% 32 == 0, cout %% 4 == 0. */
 int be_wino_tile_rows(void);      /* 6 or 3: output rows per Winograd tile; positions = 5 (rows + 2), tiles per map = 12 / rows */
