@@ -99,6 +99,9 @@ _SIGNATURES = {
     "be_wino_pack_f32": (C.c_int, [_P] * 6 + [C.c_float, C.c_int, C.c_int, _P, _P, _P]),
     "be_wino_workspace_floats": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "be_wino_conv3x3_6x6_f32": (C.c_int, [_P] * 5 + [C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "be_gemm_rows_bf6_packed_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "be_gemm_rows_bf6_pack_f32": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "be_gemm_rows_bf6_f32": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P]),
     "be_wino_pair_workspace_floats": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "be_wino_conv3x3_pair_6x6_f32": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P,
                                                C.c_size_t, _P]),
@@ -723,6 +726,25 @@ def wino_pack(weight, bias, bn=None, eps=1e-5):
     return pw, pb
 
 
+def gemm_rows_bf6_pack(pw, cout, cin):
+    """pw: a packed fp32 matrix [cout_pad32][cin] (conv_pack of a 1x1 convolution / linear) -> its hi / mid / lo bf16 planes (as float32 storage)."""
+    nfl = lib().be_gemm_rows_bf6_packed_floats(cout, cin)
+    if nfl == 0:
+        raise RuntimeError(f"gemm_rows_bf6_pack: unsupported shape cout={cout} cin={cin}")
+    planes = torch.empty(nfl, dtype=torch.float32, device=pw.device)
+    check(lib().be_gemm_rows_bf6_pack_f32(dptr(pw, "pw"), cout, cin, dptr(planes), stream_ptr(pw.device)), "be_gemm_rows_bf6_pack_f32")
+    return planes
+
+
+def gemm_rows_bf6(x, planes, n, bias=None, residual=None, act=0, out=None):
+    """x [M,K] -> act(x w^T + bias (+ residual)) [M,n] in split-bf16 arithmetic; out = an [M,ld] tensor whose first n columns receive it."""
+    m, k = x.shape
+    y = torch.empty(m, n, dtype=torch.float32, device=x.device) if out is None else out
+    check(lib().be_gemm_rows_bf6_f32(dptr(x, "x"), m, k, dptr(planes), n, dptr(bias), dptr(residual), int(act), dptr(y), y.shape[-1],
+                                     stream_ptr(x.device)), "be_gemm_rows_bf6_f32")
+    return y
+
+
 def wino_conv3x3(x, pw, pb, cout, act=0, residual=None, workspace=None):
     """x [N,6,6,Cin] NHWC -> [N,6,6,cout] by Winograd F(3x3,3x3)."""
     n, h, w, cin = x.shape
@@ -769,7 +791,7 @@ KERNEL_NAMES = {0: "k_conv_igemm<2,2,2,2,TAPS> (128x128)", 1: "k_conv_igemm<4,1,
                 2: "k_conv_igemm<4,1,1,2,TAPS> (128x64)", 3: "k_conv_igemm<4,1,1,1,TAPS> (128x32)",
                 4: "k_conv_igemm<4,1,1,2,ROW8> (conv1)", 5: "k_conv_igemm small-M tiles (64x64 / 128x32)",
                 6: "k_wino_gemm<0, 1> (128x128 tiles, the Winograd transform-domain GEMMs of a layer - one per position: 40 for the 8x5 tiles - per launch, in split-bf16 arithmetic: six v_mfma_f32_32x32x16_bf16 per product, FLOPs counted as fp32 products; BE_WINO_F32=1: the fp32 k_wino_gemm_ws / k_wino_gemm / batched k_conv_igemm)",
-                7: "k_wino_gemm as a row GEMM (1x1 convolutions / linears of large batches)",
+                7: "row GEMMs: k_wino_gemm_ps<EPI> on pre-split weights (split-bf16 arithmetic, FLOPs counted as fp32 products: LocalStage's 1x1 downsamples and fc.1; BE_ROWS_F32=1 / BE_WINO_F32=1: fp32) and the fp32 k_wino_gemm<1> / k_wino_gemm_ws<.., 1> (1x1 convolutions / linears of large batches)",
                 8: "k_wino_in / k_wino_out_in / k_wino_out / k_wino_out_pool2 (Winograd transforms)", 9: "k_maxpool_nhwc",
                 10: "k_render_colors (pass A)", 11: "conv1 input staging",
                 12: "k_unit_gemms / k_unit_gemms_sk (training units: weight-gradient GEMMs + data-gradient convolutions of one or two units in one launch; a residual block's two forward convolutions)",

@@ -74,6 +74,11 @@ int gemm_rows(const float* x, int64_t M, int K, const float* packed_w, int N, co
 // be_wino.hip: y[M][ldy] = x[M][K] w[Npad][K]^T, RAW accumulators (no bias, no activation) on the weight-stationary GEMM kernel;
 // returns 1 when the shape is not one it takes (K in {96, 256, 384}, M % 128 == 0, >= 128 row tiles, N % 128 == 0)
 int gemm_rows_ws(const float* x, int64_t M, int K, const float* packed_w, int N, float* y, int ldy, void* stream);
+// be_wino.hip: the split-bf16 (bf16x6) row GEMM on the pre-split planes of w (be_gemm_rows_bf6_pack_f32), any M >= 1: the body of
+// be_gemm_rows_bf6_f32.  rows_bf6_enabled(): false under BE_ROWS_F32=1 or BE_WINO_F32=1 (read once per process)
+int gemm_rows_bf6(const float* x, int64_t M, int K, const float* planes, int N, const float* bias, const float* res, int act,
+                  float* y, int ldy, void* stream);
+bool rows_bf6_enabled();
 // be_api.hip: a[i] += b[i], i < n (pack-time helper)
 int vec_add_inplace(float* a, const float* b, int n, void* stream);
 

@@ -7,10 +7,13 @@
 // (input transform, 40 GEMMs, output+input transform, 40 GEMMs, output transform - layer3's with the 2x2 max-pool in it;
 // be_wino.hip), fc.1, fc.4.  Sub-batches of 512 patches and more take the LDS-DMA kernels (be_conv_pm.hip for conv1 on a
 // row-padded staging and for layer0, the row GEMM of be_wino.hip for the 1x1s and fc.1); smaller ones k_conv_igemm - same
-// results bit for bit.  No allocation, no synchronisation, no process-wide state: graph-capturable, re-entrant.  opts->winograd = 0
-// runs layers 1-3 as direct launches like layer0.
+// results bit for bit.  On the Winograd path the 1x1 downsamples of layers 1-3 and fc.1 run in split-bf16 arithmetic on ONE kernel for
+// every sub-batch size (be::gemm_rows_bf6; BE_ROWS_F32=1 / BE_WINO_F32=1: the fp32 kernels just named).  No allocation, no
+// synchronisation, no process-wide state: graph-capturable, re-entrant.  opts->winograd = 0 runs layers 1-3 as direct launches
+// like layer0, all in fp32.
 #include "be_common.h"
 #include <cstdlib>
+#include <initializer_list>
 
 namespace {
 
@@ -55,9 +58,14 @@ struct PackedLayout {
             }
         }
         zero_off = o; o += 384;            // a zero "bias" for the Winograd blocks' downsample convolutions (their bias lives in conv2's)
+        for (int i = 0; i < 15; ++i) sw_off[i] = 0;
+        for (int i : {6, 9, 12, 13}) {     // hi / mid / lo bf16 planes of the downsamples' and fc.1's packed matrices (split-bf16 row GEMMs)
+            sw_off[i] = o; o += be_gemm_rows_bf6_packed_floats(kLayers[i].cout, kLayers[i].cin);
+        }
         total = o;
     }
     size_t zero_off;
+    size_t sw_off[15];
 };
 const PackedLayout& layout() { static PackedLayout l; return l; }
 
@@ -122,8 +130,15 @@ extern "C" int be_local_stage_pack_f32(const float* const* t, float bn_eps, floa
     int rc = be_conv_pack_f32(f[0], f[1], f[2], f[3], f[4], f[5], bn_eps, 1024, 2304, 1, 9,
                               packed + L.w_off[13], packed + L.b_off[13], stream);
     if (rc) return rc;
-    return be_conv_pack_f32(f[6], f[7], nullptr, nullptr, nullptr, nullptr, bn_eps, 10, 1024, 1, 0,
-                            packed + L.w_off[14], packed + L.b_off[14], stream);
+    if ((rc = be_conv_pack_f32(f[6], f[7], nullptr, nullptr, nullptr, nullptr, bn_eps, 10, 1024, 1, 0,
+                               packed + L.w_off[14], packed + L.b_off[14], stream))) return rc;
+    // the planes of the four matrices the split-bf16 row GEMMs read, from the packed fp32 matrices (BatchNorm folded, fc.1's columns
+    // permuted), which stay for the fp32 arms
+    for (int i : {6, 9, 12, 13}) {
+        const float* src = packed + (i == 13 ? L.w_off[13] : L.dw_off[i]);
+        if ((rc = be_gemm_rows_bf6_pack_f32(src, kLayers[i].cout, kLayers[i].cin, packed + L.sw_off[i], stream))) return rc;
+    }
+    return BE_OK;
 }
 
 namespace {
@@ -156,9 +171,13 @@ int block_wino(const float* packed, int l0, const float* x, float* t, float* o, 
     const PackedLayout& L = layout();
     const int c = kLayers[l0].cout;
     (void)t;                                          // conv1's 6x6 result only ever exists in registers (k_wino_out_in)
-    // the 1x1 downsample, bias-free (its bias sits in conv2's, see be_local_stage_pack_f32): large sub-batches on the
-    // weight-stationary GEMM (raw accumulators; 128 TFLOP/s where the row GEMM does 92-119), others on the general kernel with a zero bias
-    {
+    // the 1x1 downsample, bias-free (its bias sits in conv2's, see be_local_stage_pack_f32), raw accumulators: the split-bf16 row
+    // GEMM at every batch size.  fp32 arm (BE_ROWS_F32=1 / BE_WINO_F32=1): large sub-batches on the weight-stationary GEMM
+    // (128 TFLOP/s where the row GEMM does 92-119), others on the general kernel with a zero bias
+    if (be::rows_bf6_enabled()) {
+        if (int rc = be::gemm_rows_bf6(x, (int64_t)n * 36, kLayers[l0 + 2].cin, packed + L.sw_off[l0 + 2], c, nullptr, nullptr, 0, r, c,
+                                       stream)) return rc;
+    } else {
         int rc = be::gemm_rows_ws(x, (int64_t)n * 36, kLayers[l0 + 2].cin, packed + L.dw_off[l0 + 2], c, r, c, stream);
         if (rc < 0) return rc;
         if (rc > 0) {
@@ -248,7 +267,12 @@ int forward_impl(const float* packed, const float* x, const be_patch_view* view,
             if ((rc = be_maxpool_nhwc_f32(rc_, p3, nb, 6, 6, 256, 2, 2, 0, stream))) return rc;
         }
         float* f1 = ra;                                   // nb*1024
-        if ((rc = conv(packed, 13, p3, nullptr, f1, nb, 1, 1, 1024, stream))) return rc;
+        // fc.1 (+ BN1d + Smish): where the Winograd path runs, the split-bf16 row GEMM at every batch size
+        if (wino && be::rows_bf6_enabled()) {
+            const PackedLayout& L = layout();
+            if ((rc = be::gemm_rows_bf6(p3, nb, 2304, packed + L.sw_off[13], 1024, packed + L.b_off[13], nullptr, 1, f1, 1024, stream)))
+                return rc;
+        } else if ((rc = conv(packed, 13, p3, nullptr, f1, nb, 1, 1, 1024, stream))) return rc;
         if ((rc = conv(packed, 14, f1, nullptr, out + first * BE_LOCAL_OUT, nb, 1, 0, BE_LOCAL_OUT, stream))) return rc;
     }
     return BE_OK;

@@ -19,6 +19,8 @@
 //                  <0, 1>: split-bf16, every batch size (tile-major buffers for large batches, plane-major for small ones), both
 //                  operands split in the loop (round 7; BE_WINO_BF6_R7=1)
 //   k_wino_gemm_ps the same GEMMs and bits with B's pieces read ready from the planes, a 3-stage ring, counted waits (the default)
+//                  <EPI, 1> (round 9): the same loop as a plain row GEMM on pre-split planes of a packed matrix - LocalStage's 1x1
+//                  downsamples (raw accumulators) and fc.1 (bias + Smish), every batch size; BE_ROWS_F32=1: the fp32 kernels
 //                  fp32 (BE_WINO_F32=1): <0, 0> for large batches, all positions per workgroup; small ones go through
 //                  be_conv_nhwc_batched_f32 on k_conv_igemm, same arithmetic per output element
 //   k_wino_gemm_ws the fp32 GEMMs weight-stationary (B tile in registers, A streamed through LDS by DMA): batches of >= 4096 maps
@@ -371,9 +373,9 @@ constexpr int PS_BLOCK = 3 * 128 * 16;                 // bf16 values per block 
 constexpr int PS_STAGES = 4;                           // k_wino_gemm_ps's LDS ring: 4 x 20 KB, two workgroups per CU (160 KB)
 __device__ __forceinline__ int ps_slot(int row, int half) { return half ^ ((row >> 3) & 1); }
 
-__global__ void k_wino_pack_split(const float* __restrict__ U, int cout_pad, int cin, int n_tiles, __bf16* __restrict__ P) {
-    const int kg = cin / 8, rows = 128 * n_tiles;      // one thread = one (position, row, 8-deep K group)
-    const int64_t total = (int64_t)NPOS * rows * kg;
+__global__ void k_wino_pack_split(const float* __restrict__ U, int npos, int cout_pad, int cin, int n_tiles, __bf16* __restrict__ P) {
+    const int kg = cin / 8, rows = 128 * n_tiles;      // one thread = one (position, row, 8-deep K group); a plain matrix is npos = 1
+    const int64_t total = (int64_t)npos * rows * kg;
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
         const int g = (int)(idx % kg), row = (int)((idx / kg) % rows), z = (int)(idx / ((int64_t)kg * rows));
@@ -589,6 +591,11 @@ void k_wino_gemm(GemmArgs a) {
 // vmcnt: every wave issues 5 DMA pieces per chunk (2 A + 3 B), so "vmcnt(5)" = all but the newest chunk's have landed.  At the end of
 // a problem the wait for the chunk after next sits IN FRONT of the stores (after them no count would be right without knowing how many
 // store instructions the compiler emitted); the last one drains everything, so no DMA into LDS outlives the workgroup.
+// Round 9, the same loop as a plain row GEMM.  EPI = 1: k_wino_gemm<1>'s epilogue, y = act(acc + bias[col] (+ res)).  ROWS = 1: the
+// "problems" may be GemmArgs' walked row tiles (nb consecutive 128-row tiles of one matrix per workgroup: mrows = 128 nb, zrows = 128,
+// xb = 128 lda, yb = 128 ldy, wb = 0; only when every walked tile is full), so that a short K loop keeps one continuous pipeline.
+// <0, 0> is the Winograd kernel of round 8, instruction for instruction.
+template <int EPI, int ROWS = 0>
 __global__ __launch_bounds__(256, 2)
 void k_wino_gemm_ps(GemmArgs a) {
     constexpr int BM = 128, BKT = 16;
@@ -604,7 +611,7 @@ void k_wino_gemm_ps(GemmArgs a) {
     m_tile /= a.zgroups;
     if (m_tile >= a.m_tiles || zg * zper >= a.nb) return;
     const int nb = min(zper, a.nb - zg * zper), kchunks = a.K / BKT, total = kchunks * nb;
-    const int n0 = n_tile * 128, row_base = m_tile * BM;
+    const int n0 = n_tile * 128, row_base = m_tile * (ROWS ? a.mrows : BM);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int wm = wave >> 1, wn = wave & 1;
@@ -648,6 +655,14 @@ void k_wino_gemm_ps(GemmArgs a) {
         l_buf = (l_buf + 1) % NS;                                                                               \
     } while (0)
     const unsigned y_off = (unsigned)((wm * 64 + 4 * lh) * a.ldy + wn * 64 + li) * 4u;
+    float bias_v[2] = {0.f, 0.f};
+    if (EPI) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int c = n0 + wn * 64 + j * 32 + li;
+            bias_v[j] = (a.bias && c < a.N) ? a.bias[c] : 0.0f;
+        }
+    }
     // the pieces of the chunk being multiplied: read from LDS and split (A) while the chunk before is still on the matrix pipe
     bf16x8 ap[3][2], bp[3][2];                         // [hi, mid, lo][i or j]
     int r_buf = 0;                                     // ring slot whose fragments are read next
@@ -696,8 +711,16 @@ void k_wino_gemm_ps(GemmArgs a) {
             else __builtin_amdgcn_s_waitcnt(0x0F70);                                   // nothing left in flight
             landed = true;
             __builtin_amdgcn_sched_barrier(0);
-            const int zrow = row_base;
+            const int zrow = ROWS ? row_base + cz * a.zrows : row_base;
             char* yt = reinterpret_cast<char*>(yg + (int64_t)cz * a.yb + (int64_t)row_base * a.ldy + n0);             // uniform
+            const char* rt = EPI && a.res ? reinterpret_cast<const char*>(a.res) + (yt - reinterpret_cast<char*>(a.y)) : nullptr;
+#define PS_VALUE(J)                                                                                             \
+            float v_ = acc[i][J][r];                                                                            \
+            if (EPI) {                                                                                          \
+                v_ += bias_v[J];                                                                                \
+                if (rt) v_ += reinterpret_cast<const float*>(rt + (size_t)ro * a.ldy * 4 + y_off)[(J) * 32];    \
+                if (a.act == 1) v_ = be::smish(v_); else if (a.act == 2) v_ = fmaxf(v_, 0.0f);                  \
+            }
             if (zrow + BM <= a.M && n0 + 128 <= a.N) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
@@ -705,8 +728,8 @@ void k_wino_gemm_ps(GemmArgs a) {
                     for (int r = 0; r < 16; ++r) {
                         const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
                         float* yr = reinterpret_cast<float*>(yt + (size_t)ro * a.ldy * 4 + y_off);
-                        yr[0] = acc[i][0][r];
-                        yr[32] = acc[i][1][r];
+                        { PS_VALUE(0) yr[0] = v_; }
+                        { PS_VALUE(1) yr[32] = v_; }
                     }
             } else {
 #pragma unroll
@@ -717,11 +740,14 @@ void k_wino_gemm_ps(GemmArgs a) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
-                            if (c_ok && zrow + wm * 64 + 4 * lh + ro < a.M)
-                                reinterpret_cast<float*>(yt + (size_t)ro * a.ldy * 4 + y_off)[j * 32] = acc[i][j][r];
+                            if (c_ok && zrow + wm * 64 + 4 * lh + ro < a.M) {
+                                PS_VALUE(j)
+                                reinterpret_cast<float*>(yt + (size_t)ro * a.ldy * 4 + y_off)[j * 32] = v_;
+                            }
                         }
                 }
             }
+#undef PS_VALUE
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -951,7 +977,7 @@ extern "C" int be_wino_pack_f32(const float* w, const float* b, const float* gam
     if (int rc = be::check_launch("be_wino_pack_f32")) return rc;
     const int n_tiles = (cout + 127) / 128;
     hipLaunchKernelGGL(k_wino_pack_split, dim3(grid_cap((int64_t)NPOS * 128 * n_tiles * (cin / 8), 256, 4096)), dim3(256), 0,
-                       be::as_stream(stream), packed_w, cp, cin, n_tiles,
+                       be::as_stream(stream), packed_w, NPOS, cp, cin, n_tiles,
                        reinterpret_cast<__bf16*>(packed_w + wino_u_floats(cout, cin)));
     return be::check_launch("be_wino_pack_f32(split)");
 }
@@ -1013,7 +1039,7 @@ int wino_gemms_bf6(const float* V, const float* packed_w, float* M, int64_t n, i
 int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s) {
     constexpr size_t lds = (size_t)PS_STAGES * (128 * 16 * 4 + PS_BLOCK * 2);    // stages of 8 KB A + 12 KB B
     static be::DeviceFlags attr_set{};                          // dynamic-LDS cap raised once per device (thread-safe)
-    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm_ps), lds, attr_set)) return rc_;
+    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm_ps<0, 0>), lds, attr_set)) return rc_;
     const int64_t rows = (int64_t)TPI * n;
     const bool tm = wino_large(n, cout);
     const int m_tiles = (int)((rows + 127) / 128), n_tiles = (cout + 127) / 128, kchunks = cin / 16;
@@ -1043,7 +1069,7 @@ int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, in
         be::ProfileScope prof(s, BE_KERNEL_WINO_GEMM, (double)NPOS * 2.0 * rows * cin * cout,
                               (double)NPOS * 4.0 * ((double)rows * cin + (double)rows * cout) + (double)NPOS * 6.0 * cin * n_tiles * 128,
                               (double)NPOS * 2.0 * m_tiles * n_tiles * 128.0 * 128.0 * cin);
-        hipLaunchKernelGGL(k_wino_gemm_ps, dim3(grid), dim3(256), lds, s, g);
+        hipLaunchKernelGGL((k_wino_gemm_ps<0, 0>), dim3(grid), dim3(256), lds, s, g);
     }
     return be::check_launch("be_wino_conv3x3_6x6_f32(gemm, split bf16, pre-split weights)");
 }
@@ -1136,6 +1162,91 @@ int be::gemm_rows_ws(const float* x, int64_t M, int K, const float* packed_w, in
     if (K == 96) return launch_ws<6, 1>(g, s, M, K, N, BE_KERNEL_GEMM_ROWS);
     if (K == 256) return launch_ws<16, 1>(g, s, M, K, N, BE_KERNEL_GEMM_ROWS);
     return launch_ws<24, 1>(g, s, M, K, N, BE_KERNEL_GEMM_ROWS);
+}
+
+// ---- split-bf16 row GEMMs (round 9): LocalStage's 1x1 downsamples and fc.1 on k_wino_gemm_ps ---------------------------------------
+// y[M][ldy] = act(x[M][K] w^T + bias (+ res)) with w's hi / mid / lo planes in k_wino_pack_split's block layout (one "position").
+// ONE body for every M: a row's bits depend on neither the batch nor the walk (every output element sees the same K loop from a zero
+// accumulator).  Without bias, residual and activation the raw-store instantiation runs (the downsamples).
+extern "C" size_t be_gemm_rows_bf6_packed_floats(int cout, int cin) {
+    if (cout <= 0 || cin <= 0 || cin % 16) return 0;
+    return (size_t)((cout + 127) / 128 * 128) * cin * 3 / 2;
+}
+
+extern "C" int be_gemm_rows_bf6_pack_f32(const float* packed_w, int cout, int cin, float* planes, void* stream) {
+    BE_REQUIRE(packed_w && planes, "be_gemm_rows_bf6_pack_f32: null pointer");
+    BE_REQUIRE(cout > 0 && cin > 0 && cin % 16 == 0, "be_gemm_rows_bf6_pack_f32: cin must be a multiple of 16 (got %d)", cin);
+    BE_REQUIRE(be::aligned16(packed_w) && be::aligned16(planes), "be_gemm_rows_bf6_pack_f32: packed_w / planes must be 16-byte aligned");
+    const int cp = (cout + 31) / 32 * 32, n_tiles = (cout + 127) / 128;     // the fp32 matrix: [cout_pad32][cin], zero rows past cout
+    hipLaunchKernelGGL(k_wino_pack_split, dim3(grid_cap((int64_t)128 * n_tiles * (cin / 8), 256, 4096)), dim3(256), 0,
+                       be::as_stream(stream), packed_w, 1, cp, cin, n_tiles, reinterpret_cast<__bf16*>(planes));
+    return be::check_launch("be_gemm_rows_bf6_pack_f32");
+}
+
+bool be::rows_bf6_enabled() {
+    // A/B knobs: BE_ROWS_F32=1 sends only these row GEMMs back to the fp32 kernels; BE_WINO_F32=1 restores fp32 everywhere
+    static const bool f32 = (getenv("BE_ROWS_F32") != nullptr && atoi(getenv("BE_ROWS_F32")) != 0) ||
+                            (getenv("BE_WINO_F32") != nullptr && atoi(getenv("BE_WINO_F32")) != 0);
+    return !f32;
+}
+
+namespace {
+
+template <int EPI>
+int launch_rows_ps(const GemmArgs& g, hipStream_t s, unsigned grid) {
+    constexpr size_t lds = (size_t)PS_STAGES * (128 * 16 * 4 + PS_BLOCK * 2);
+    static be::DeviceFlags attr_set{};                          // dynamic-LDS cap raised once per device (thread-safe)
+    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm_ps<EPI, 1>), lds, attr_set)) return rc_;
+    hipLaunchKernelGGL((k_wino_gemm_ps<EPI, 1>), dim3(grid), dim3(256), lds, s, g);
+    return BE_OK;
+}
+
+}  // namespace
+
+int be::gemm_rows_bf6(const float* x, int64_t M, int K, const float* planes, int N, const float* bias, const float* res, int act,
+                      float* y, int ldy, void* stream) {
+    BE_REQUIRE(x && planes && y, "be_gemm_rows_bf6_f32: null pointer");
+    BE_REQUIRE(M > 0 && M < ((int64_t)1 << 31) - 128 && K > 0 && K % 16 == 0 && N > 0 && ldy >= N && (unsigned)act <= 2u,
+               "be_gemm_rows_bf6_f32: bad shape (M %lld, K %d, N %d, ldy %d, act %d; K %% 16 == 0)", (long long)M, K, N, ldy, act);
+    BE_REQUIRE((int64_t)128 * std::max(K, ldy) * 4 < ((int64_t)1 << 31), "be_gemm_rows_bf6_f32: rows too long");
+    BE_REQUIRE(be::aligned16(x) && be::aligned16(planes), "be_gemm_rows_bf6_f32: x / planes must be 16-byte aligned");
+    hipStream_t s = be::as_stream(stream);
+    const int n_tiles = (N + 127) / 128, kchunks = K / 16;
+    const int64_t tiles = (M + 127) / 128;
+    // short K loops: one workgroup walks nb consecutive row tiles (only when all of them are full).  Cost as for the Winograd problem
+    // groups: rounds of two workgroups per CU times a workgroup's tiles x K chunks + ~2 chunks of prologue and turnover; a walk is worth
+    // it only while a tile's loop is short (<= 16 chunks)
+    static const int nb_env = getenv("BE_ROWS_WALK") ? atoi(getenv("BE_ROWS_WALK")) : 0;         // A/B knob: tiles per workgroup
+    int nb = 1;
+    if (nb_env > 0) {
+        if (M % 128 == 0 && tiles % nb_env == 0) nb = nb_env;
+    } else if (M % 128 == 0 && kchunks <= 16) {
+        const int cus = be::device_cu_count();
+        int64_t best = INT64_MAX;
+        for (int c = 1; c <= 16; ++c) {
+            if (tiles % c) continue;
+            const int64_t wgs = (tiles / c) * n_tiles, rounds = ((wgs + cus - 1) / cus + 1) / 2;
+            const int64_t cost = rounds * ((int64_t)c * kchunks + 2);
+            if (cost <= best) { best = cost; nb = c; }
+        }
+    }
+    const int m_tiles = (int)(tiles / nb);
+    GemmArgs g{x, planes, y, (int)M, K, N, ldy, nb, m_tiles, n_tiles, (int64_t)128 * K, 0, (int64_t)128 * ldy,
+               K, 128 * nb, nb > 1 ? 128 : 0, bias, res, act, 1, n_tiles * 128};
+    const unsigned grid = (unsigned)(8 * ((m_tiles + 7) / 8) * n_tiles);
+    {
+        // (FLOPs in fp32-equivalent products, as the Winograd GEMMs)
+        be::ProfileScope prof(s, BE_KERNEL_GEMM_ROWS, 2.0 * M * K * N, 4.0 * ((double)M * K + (double)M * N) + 6.0 * K * n_tiles * 128,
+                              2.0 * tiles * n_tiles * 128.0 * 128.0 * K);
+        const int rc = (bias || res || act) ? launch_rows_ps<1>(g, s, grid) : launch_rows_ps<0>(g, s, grid);
+        if (rc) return rc;
+    }
+    return be::check_launch("be_gemm_rows_bf6_f32");
+}
+
+extern "C" int be_gemm_rows_bf6_f32(const float* x, int64_t m, int k, const float* planes, int n, const float* bias,
+                                    const float* residual, int act, float* y, int ldy, void* stream) {
+    return be::gemm_rows_bf6(x, m, k, planes, n, bias, residual, act, y, ldy, stream);
 }
 
 // The transform kernels read every byte once: non-temporal loads (default) move 5.42-5.46 TB/s where plain loads move 5.24-5.28

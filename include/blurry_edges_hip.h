@@ -357,6 +357,17 @@ int be_wino_conv3x3_pair_6x6_f32(const float* x, const float* packed_w1, const f
                                  const float* packed_w2, const float* packed_bias2, const float* residual, int act2, float* y,
                                  int64_t n, int cin, int cmid, int cout, float* workspace, size_t workspace_floats, void* stream);
 
+/* Row GEMM in the same split-bf16 arithmetic (bf16x6): y[m][ldy] = act(x[m][k] w^T + bias (+ residual)), act 0 none / 1 Smish / 2 ReLU,
+ * residual with y's row stride; bias and residual may be NULL.  LocalStage's 1x1 downsamples of layers 1-3 and fc.1 run on it wherever
+ * the Winograd path runs; environment BE_ROWS_F32=1 (read once per process) sends those four back to the fp32 kernels (BE_WINO_F32=1 does
+ * too).  One kernel body for every m >= 1: a row's bits do not depend on the batch it is computed in.  be_gemm_rows_bf6_pack_f32 reads
+ * a packed fp32 matrix [cout_pad32][cin] (be_conv_pack_f32 of a 1x1 convolution or linear) and writes its hi / mid / lo bf16 planes:
+ * be_gemm_rows_bf6_packed_floats = 1.5 x cout_pad128 x cin floats (0 unless cin %% 16 == 0).  x, packed_w and planes 16-byte aligned. */
+size_t be_gemm_rows_bf6_packed_floats(int cout, int cin);
+int be_gemm_rows_bf6_pack_f32(const float* packed_w, int cout, int cin, float* planes, void* stream);
+int be_gemm_rows_bf6_f32(const float* x, int64_t m, int k, const float* planes, int n, const float* bias, const float* residual,
+                         int act, float* y, int ldy, void* stream);
+
 /* nn.MaxPool2d(k, stride, pad) on NHWC (models/local_stage.py:42-43). */
 int be_maxpool_nhwc_f32(const float* x, float* y, int n, int h, int w, int c, int k, int stride, int pad,
                         void* stream);
@@ -661,7 +672,7 @@ int be_datagen_test_render_f64(const double* bkgd, const double* frgd, const dou
 #define BE_KERNEL_CONV_ROW8_128x64  4   /* conv1 (7x7 row-gather)                                              */
 #define BE_KERNEL_CONV_SMALL        5   /* 64x64 / 128x32 tiles for small M (training batches)                 */
 #define BE_KERNEL_WINO_GEMM         6   /* k_wino_gemm<0, 1> (split bf16; fp32: k_wino_gemm_ws / k_wino_gemm): the transform-domain GEMMs (one per position) of a Winograd layer; FLOPs as fp32 products */
-#define BE_KERNEL_GEMM_ROWS         7   /* k_wino_gemm as a row GEMM: 1x1 convolutions / linears, large batches */
+#define BE_KERNEL_GEMM_ROWS         7   /* row GEMMs: k_wino_gemm_ps<EPI> on pre-split weights (split bf16: LocalStage's 1x1 downsamples and fc.1; FLOPs as fp32 products); fp32: k_wino_gemm<1> / k_wino_gemm_ws<.., 1> (1x1 convolutions / linears, large batches) */
 /* HBM-bound kernels: `bytes` = the algorithmic bytes the launch has to move, `flops` = 0 */
 #define BE_KERNEL_WINO_TRANSFORM    8   /* k_wino_in / k_wino_out / k_wino_out_in / k_wino_out_pool2 */
 #define BE_KERNEL_MAXPOOL           9   /* k_maxpool_nhwc */
