@@ -146,6 +146,9 @@ _SIGNATURES = {
                                      C.POINTER(PatchView), _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "be_fold_records_f32": (C.c_int, [C.POINTER(RenderOpts), _P] + [C.c_int] * 6 + [_P] * 6 + [_P]),
     "be_fold_records_batch_f32": (C.c_int, [C.POINTER(RenderOpts), _P] + [C.c_int] * 7 + [_P] * 6 + [_P]),
+    "be_render_full_grid_f32": (C.c_int, [C.POINTER(RenderOpts), C.POINTER(DepthConsts), C.c_float, C.c_int, _P, _P, C.c_int, C.c_int,
+                                          _P, _P, C.c_int, C.c_int, _P, _P]),
+    "be_fold_records_grid_f32": (C.c_int, [C.POINTER(RenderOpts), _P] + [C.c_int] * 4 + [_P, _P, C.c_int] + [_P] * 6 + [_P]),
     "be_unfold_patches_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "be_local_features_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "be_global_denorm_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
@@ -918,6 +921,69 @@ def fold_records_batch(opts, records, hp, wp, H, W, stride=2, densify_w=False, w
     check(lib().be_fold_records_batch_f32(C.byref(opts), dptr(records, "records"), B, hp, wp, H, W, stride, int(bool(densify_w)),
                                           g("image"), g("shpd"), g("refoc"), g("bndry"), g("depth"), g("conf"),
                                           stream_ptr(dev)), "be_fold_records_batch_f32")
+    return out
+
+
+def origin_table(lines, size: int, device, name: str = "origins", cover: bool = False) -> torch.Tensor:
+    """One axis of a patch grid given by origins -> the device int32 table the *_grid entry points take.  `lines`: a sequence of
+    ints or an integer tensor; checked HERE, on the host, because the kernels trust it: strictly increasing, inside
+    [0, size - 21]; cover=True (the fold, which divides by the number of covering patches) also wants every pixel of [0, size)
+    under a patch: first origin 0, last size - 21, no gap above 21."""
+    vals = [int(v) for v in (lines.tolist() if isinstance(lines, torch.Tensor) else lines)]
+    if not vals:
+        raise ValueError(f"{name}: empty origin table")
+    if any(b <= a for a, b in zip(vals, vals[1:])):
+        raise ValueError(f"{name}: patch origins must be strictly increasing")
+    if vals[0] < 0 or vals[-1] + BE_R > size:
+        raise ValueError(f"{name}: origins {vals[0]}..{vals[-1]} leave [0, {size} - {BE_R}]")
+    if cover and (vals[0] != 0 or vals[-1] != size - BE_R or any(b - a > BE_R for a, b in zip(vals, vals[1:]))):
+        raise ValueError(f"{name}: the patches do not cover every pixel of [0, {size}) (first origin 0, last {size - BE_R}, gaps <= {BE_R})")
+    if isinstance(lines, torch.Tensor) and lines.is_cuda and lines.dtype == torch.int32 and lines.is_contiguous():
+        return lines
+    return torch.tensor(vals, dtype=torch.int32, device=device)
+
+
+def render_full_grid(opts, consts, rho_prime, densify_w, params12, img, ys, xs):
+    """params12 [HP*WP,12] + img [2,3,H,W] -> records [HP*WP,32] with patch (i, j) at pixel (ys[i], xs[j]): render_full over a
+    grid given by origin tables (tiling.patch_grid), one launch.  ys / xs: int sequences or device int32 tensors."""
+    if img.dim() != 4 or img.shape[0] != 2 or img.shape[1] != 3:
+        raise RuntimeError(f"render_full_grid: expected img [2,3,H,W], got {tuple(img.shape)}")
+    dptr(img, "img", (torch.float32,))
+    dev, (_, _, H, W) = img.device, img.shape
+    ys, xs = origin_table(ys, H, dev, "render_full_grid(ys)"), origin_table(xs, W, dev, "render_full_grid(xs)")
+    HP, WP = ys.numel(), xs.numel()
+    if tuple(params12.shape) != (HP * WP, 12):
+        raise RuntimeError(f"render_full_grid: params12 must be [{HP * WP},12], got {tuple(params12.shape)}")
+    o = ops()
+    if o is not None:
+        return o.render_full_grid(struct_tensor(opts), struct_tensor(consts), float(rho_prime), bool(densify_w), params12.contiguous(),
+                                  img, ys, xs)
+    rec = torch.empty(HP * WP, RECORD_FLOATS, dtype=torch.float32, device=dev)
+    check(lib().be_render_full_grid_f32(C.byref(opts), C.byref(consts), float(rho_prime), int(bool(densify_w)),
+                                        dptr(params12, "params12", (torch.float32,)), dptr(img), H, W, dptr(ys), dptr(xs), HP, WP,
+                                        dptr(rec), stream_ptr(dev)), "be_render_full_grid_f32")
+    return rec
+
+
+def fold_records_grid(opts, records, H, W, ys, xs, densify_w=False, want=FOLD_MAPS):
+    """records [HP*WP,32] of a grid given by origin tables -> the maps of fold_records on an H x W image; each pixel is divided
+    by the number of patches that cover it.  The tables must cover every pixel (checked here)."""
+    dev = records.device
+    ys, xs = origin_table(ys, H, dev, "fold_records_grid(ys)", cover=True), origin_table(xs, W, dev, "fold_records_grid(xs)", cover=True)
+    HP, WP = ys.numel(), xs.numel()
+    if tuple(records.shape) != (HP * WP, RECORD_FLOATS):
+        raise RuntimeError(f"fold_records_grid: records must be [{HP * WP},{RECORD_FLOATS}], got {tuple(records.shape)}")
+    o = ops()
+    if o is not None:
+        mask = sum(1 << i for i, k in enumerate(FOLD_MAPS) if k in want)
+        r = o.fold_records_grid(struct_tensor(opts), records.contiguous(), ys, xs, H, W, bool(densify_w), mask)
+        return dict(zip([k for k in FOLD_MAPS if k in want], r))
+    shapes = dict(image=(2, 3, H, W), shpd=(3, H, W), refoc=(3, H, W), bndry=(H, W), depth=(H, W), conf=(H, W))
+    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in want}
+    g = lambda k: dptr(out.get(k))
+    check(lib().be_fold_records_grid_f32(C.byref(opts), dptr(records, "records", (torch.float32,)), HP, WP, H, W, dptr(ys), dptr(xs),
+                                         int(bool(densify_w)), g("image"), g("shpd"), g("refoc"), g("bndry"), g("depth"), g("conf"),
+                                         stream_ptr(dev)), "be_fold_records_grid_f32")
     return out
 
 

@@ -5,6 +5,8 @@ image pair [2,3,H,W]  ->  unfold  ->  LocalStage (HIP)  ->  pass-A colours (HIP)
   ->  GlobalStage (HIP)  ->  de-normalisation (HIP)  ->  pass-B records (HIP)
   ->  owner-computes fold (HIP)  ->  six maps + thresholded depth (or, with densify='pp', the DepthCompletion U-Net
   on the folded depth map, blurry_edges_test.py:141-142).
+DepthPipeline.__call__ is the reference's one 147x147 pair, run_big its big-image tiler (sizes 59 + 88 k), run_any the same
+pipeline for a pair of any size >= one block (flush-edge patch grid, be_hip/tiling.py).
 Nothing here computes on the CPU; tensors stay on the GPU until the caller asks for them.
 """
 from __future__ import annotations
@@ -13,7 +15,7 @@ import math
 
 import torch
 
-from . import native
+from . import native, tiling
 
 
 def params_src_layout(pm):
@@ -150,4 +152,79 @@ class DepthPipeline:
             maps["depth_map"] = self.pp(maps["depth"][None, None])[0, 0]
         else:                                                                       # blurry_edges_test_big.py:189
             maps["depth_map"] = torch.where(maps["conf"] > 0.05, maps["depth"], torch.zeros_like(maps["depth"]))
+        return maps
+
+    # ---- any size >= one block: flush-edge patch grid + pulled-back last block (be_hip/tiling.py) -----------------------
+    def local_grid(self, img):
+        """pm of every patch of the flush-edge grid, [HP, WP, 38], each distinct window through LocalStage once: the uniform part
+        of the grid in one local pass over the image, the flush row / column / corner (where the size asks for them) in one
+        local pass each over the 21-pixel strip that holds them."""
+        _, _, H, W = img.shape
+        s, R = self.stride, native.BE_R
+        hu, wu = (H - R) // s + 1, (W - R) // s + 1
+        fv, fh = (H - R) % s != 0, (W - R) % s != 0
+        core = self.local_pass(img)[3].view(hu, wu, 38)
+        if not (fv or fh):
+            return core
+        grid = torch.empty(hu + fv, wu + fh, 38, dtype=torch.float32, device=img.device)
+        grid[:hu, :wu] = core
+        if fv:
+            grid[hu, :wu] = self.local_pass(img, (H - R, 0, R, W))[3]
+        if fh:
+            grid[:hu, wu] = self.local_pass(img, (0, W - R, H, R))[3]
+        if fv and fh:
+            grid[hu, wu] = self.local_pass(img, (H - R, W - R, R, R))[3][0]
+        return grid
+
+    @torch.no_grad()
+    def run_any(self, img, block=147, n_margin=10):
+        """img [2,3,H,W] with H, W >= block, ANY such size -> the dict of run_big (image, shpd, refoc, bndry, depth, conf,
+        depth_map; plus est12 [HP*WP,12] and records [HP*WP,32] of the whole grid).
+
+        Patch grid: tiling.patch_grid per axis - origins 0, s, 2s, .. and one more flush with the edge at H - 21 when the
+        uniform grid stops short of it, so every pixel is covered (the uniform fold leaves 0/0 in the last row / column
+        otherwise).  Blocks: tiling.block_schedule - 64 consecutive grid lines each, 44 apart, the last pulled back to end on
+        the grid's last line; a grid line is kept by one block and never closer than n_margin to an inner block edge.  For the
+        sizes the reference defines (59 + 88 k) grid and schedule ARE run_big's and the maps are equal bit for bit (147x147:
+        equal to __call__).  GlobalStage always sees 64 x 64 tokens in the layout it was trained on; in the last block of an
+        axis with a flush line the final gap between two lines is smaller than the stride - the one place the input geometry
+        differs from training.
+
+        LocalStage runs once per distinct window (as run_big(dedup=True)); the blocks go through GlobalStage in groups of 12 in
+        row-major order (run_big's grouping); the kept est12 rows are gathered into ONE [HP,WP,12] grid, rendered by one
+        render_full_grid launch and folded by one fold_records_grid launch.  Single process only: sharding over ranks
+        (run_big's rank / world) is not offered here."""
+        img = img.contiguous()
+        if img.dim() != 4 or img.shape[0] != 2 or img.shape[1] != 3:
+            raise ValueError(f"run_any: expected img [2,3,H,W], got {tuple(img.shape)}")
+        _, _, H, W = img.shape
+        if H < block or W < block:
+            raise ValueError(f"run_any: a {H}x{W} pair is smaller than one {block}x{block} block; DepthPipeline.__call__ takes "
+                             f"a pair whose whole patch grid fits one GlobalStage input")
+        s, R = self.stride, native.BE_R
+        hp = (block - R) // s + 1
+        ys, xs, blocks = tiling.any_windows(H, W, block, n_margin, s, R)
+        tiling.check_grid(ys, H, s, R)
+        tiling.check_grid(xs, W, s, R)
+        HP, WP = len(ys), len(xs)
+        grid = self.local_grid(img)
+        assert tuple(grid.shape) == (HP, WP, 38)
+        feats = [grid[sv:sv + hp, sh:sh + hp].reshape(hp * hp, 38) for (sv, sh), _, _ in blocks]
+        est = torch.empty(HP, WP, 12, dtype=torch.float32, device=img.device)
+        for g0 in range(0, len(blocks), 12):
+            y = self.globl(torch.stack(feats[g0:g0 + 12]))                          # [g,4096,12]
+            for i in range(y.shape[0]):
+                _, (vs, ve, hs, he), (Vs, Hs) = blocks[g0 + i]
+                est[Vs:Vs + ve - vs, Hs:Hs + he - hs] = native.global_denorm(y[i]).view(hp, hp, 12)[vs:ve, hs:he]
+        est = est.view(HP * WP, 12)
+        dev_ys = native.origin_table(ys, H, img.device, "run_any(ys)", cover=True)
+        dev_xs = native.origin_table(xs, W, img.device, "run_any(xs)", cover=True)
+        rec = native.render_full_grid(self.helper.render_opts(False), self.dcal.consts, self.rho_prime, self.densify == "w", est, img,
+                                      dev_ys, dev_xs)
+        maps = native.fold_records_grid(self.helper.render_opts(False), rec, H, W, dev_ys, dev_xs, self.densify == "w")
+        if self.densify == "pp":
+            maps["depth_map"] = self.pp(maps["depth"][None, None])[0, 0]
+        else:                                                                       # as run_big (blurry_edges_test_big.py:189)
+            maps["depth_map"] = torch.where(maps["conf"] > 0.05, maps["depth"], torch.zeros_like(maps["depth"]))
+        maps.update(est12=est, records=rec)
         return maps

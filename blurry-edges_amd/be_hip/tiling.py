@@ -1,0 +1,79 @@
+"""Patch grid and block schedule for image pairs of ANY size (host, pure Python).
+
+The reference's tiler (blurry_edges_test_big.py:116-119, DepthPipeline.big_windows) is defined only for H = 59 + 88 k: its
+uniform patch grid must end exactly on the last pixel and its block count must divide the grid.  The two functions here drop
+both conditions and reduce to the reference's grid and schedule wherever those are defined:
+
+  patch_grid      per axis, origins 0, s, 2s, .. plus - when that grid stops short of the edge - ONE more origin flush with the
+                  edge at size - R, so every pixel is under a patch.  The 2-D grid stays separable: a row table and a column table.
+  block_schedule  per axis, hp (64) consecutive grid lines per block, blocks `hp - 2 n_margin` (44) lines apart, the last one pulled
+                  back to end on the grid's last line; every grid line is KEPT by exactly one block and no kept line sits closer
+                  than n_margin to a block edge that is not a grid edge.
+
+A block is always hp x hp consecutive grid lines, i.e. the 4096 tokens in the row-major layout GlobalStage was trained on.  The
+one place its input geometry differs from training: in the last block of an axis with a flush line the final gap between two
+lines is smaller than `s` pixels.
+"""
+from __future__ import annotations
+
+R = 21          # patch side (BE_R)
+
+
+def patch_grid(size: int, stride: int = 2, r: int = R) -> list:
+    """Origins of the patches along one axis of `size` pixels: range(0, size - r + 1, stride), and size - r appended if it is not
+    already the last.  Strictly increasing, first 0, last size - r, every gap <= stride."""
+    if stride < 1:
+        raise ValueError(f"patch_grid: stride must be >= 1, got {stride}")
+    if size < r:
+        raise ValueError(f"patch_grid: {size} pixels do not hold one {r}-pixel patch")
+    lines = list(range(0, size - r + 1, stride))
+    if lines[-1] != size - r:
+        lines.append(size - r)
+    return lines
+
+
+def check_grid(lines, size: int, stride: int, r: int = R) -> None:
+    """The conditions render / fold over an origin table rest on (the kernels do not check them)."""
+    lines = list(lines)
+    if not lines or lines[0] != 0 or lines[-1] != size - r:
+        raise ValueError(f"patch grid must start at 0 and end at {size - r}")
+    for a, b in zip(lines, lines[1:]):
+        if not 0 < b - a <= stride:
+            raise ValueError(f"patch grid must be strictly increasing with gaps <= {stride}: {a} -> {b}")
+
+
+def block_schedule(n: int, hp: int = 64, n_margin: int = 10) -> list:
+    """Blocks along one axis of a grid of n lines -> [(start, ks, ke)]: the block holds grid lines start .. start + hp - 1 and
+    KEEPS its local lines ks .. ke - 1 (global start + ks .. start + ke - 1).  Starts 0, step, 2 step, .. while start + hp < n,
+    then a last block at n - hp; the first block keeps [0, hp - n_margin) (everything if it is alone), a middle block
+    [n_margin, hp - n_margin), the last block everything from where its predecessor's kept range ended."""
+    step = hp - 2 * n_margin
+    if n_margin < 0 or step < 1:
+        raise ValueError(f"block_schedule: n_margin {n_margin} leaves no kept lines in a block of {hp}")
+    if n < hp:
+        raise ValueError(f"block_schedule: {n} grid lines do not fill one block of {hp}")
+    starts = []
+    while len(starts) * step + hp < n:
+        starts.append(len(starts) * step)
+    starts.append(n - hp)
+    out, kept_to = [], 0                                  # kept_to: first grid line no block has kept yet
+    for k, st in enumerate(starts):
+        ks = kept_to - st
+        ke = hp if k == len(starts) - 1 else hp - n_margin
+        out.append((st, ks, ke))
+        kept_to = st + ke
+    return out
+
+
+def any_windows(H: int, W: int, block: int = 147, n_margin: int = 10, stride: int = 2, r: int = R):
+    """-> (ys, xs, blocks): the two origin tables and the row-major block list
+    [((sv, sh) first grid row / column of the block, (vs, ve, hs, he) kept local rows / columns, (Vs, Hs) where the kept window
+    starts in the grid)] - big_windows with the pixel window replaced by the block's position in the grid (its pixel window is
+    (ys[sv], xs[sh], block, block) whenever the block holds no flush line)."""
+    if H < block or W < block:
+        raise ValueError(f"an {H}x{W} image is smaller than one {block}x{block} block")
+    hp = (block - r) // stride + 1
+    ys, xs = patch_grid(H, stride, r), patch_grid(W, stride, r)
+    blocks = [((sv, sh), (vs, ve, hs, he), (sv + vs, sh + hs))
+              for sv, vs, ve in block_schedule(len(ys), hp, n_margin) for sh, hs, he in block_schedule(len(xs), hp, n_margin)]
+    return ys, xs, blocks

@@ -6,6 +6,7 @@ formats (argument names and defaults = utils/args.py of the reference):
     python -m be_hip.workflow global_pre       global_data_pre_cal.py:52-69 (local stage over images -> params_src_*.npy)
     python -m be_hip.workflow global_train     global_training.py:168-224   (ShapeDataset 'global' -> best_run_exp_global_stage.pth)
     python -m be_hip.workflow eval [--big]     blurry_edges_test.py:102-176 / blurry_edges_test_big.py (TestDataset -> metrics)
+    python -m be_hip.workflow eval --any       the same for image pairs of any size >= 147 x 147 (DepthPipeline.run_any)
 
 Data parallel (BASELINE configs[4]): the two training commands run under torchrun, one process per GPU -
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m be_hip.workflow local_train ...
@@ -289,8 +290,9 @@ def global_train(args, quiet=False):
 
 # ------------------------------------------------------------------------- blurry_edges_test.py / blurry_edges_test_big.py
 @torch.no_grad()
-def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weights=None, quiet=False):
-    """-> dict(delta1, delta2, delta3, RMSE, AbsRel, seconds_per_pair), averaged over the test set as the scripts do."""
+def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weights=None, quiet=False, any_size=False):
+    """-> dict(delta1, delta2, delta3, RMSE, AbsRel, seconds_per_pair), averaged over the test set as the scripts do.
+    any_size: pairs of any size >= 147 x 147 through DepthPipeline.run_any (checkpoint names and arguments as big)."""
     import data, models, utils
     from .pipeline import DepthPipeline
     dev = _device(args)
@@ -298,7 +300,7 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     local = load(models.LocalStage().to(dev), local_weights or f'{args.model_path}/pretrained_local_stage.pth')
     # blurry_edges_test.py:187-190 loads pretrained_global_stage_w.pth for `--densify w`; the big-image script
     # (blurry_edges_test_big.py) always loads the plain name
-    gname = 'pretrained_global_stage_w.pth' if (args.densify == 'w' and not big) else 'pretrained_global_stage.pth'
+    gname = 'pretrained_global_stage_w.pth' if (args.densify == 'w' and not (big or any_size)) else 'pretrained_global_stage.pth'
     globl = load(models.GlobalStage(in_parameter_size=38, out_parameter_size=12, device=dev).to(dev),
                  global_weights or f'{args.model_path}/{gname}')
     pp = None
@@ -314,7 +316,10 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
         img = img_ny.permute(0, 3, 1, 2).contiguous()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        maps = pipe.run_big(img, n_margin=args.n_margin_patch) if big else pipe(img)
+        if any_size:
+            maps = pipe.run_any(img, n_margin=args.n_margin_patch)
+        else:
+            maps = pipe.run_big(img, n_margin=args.n_margin_patch) if big else pipe(img)
         torch.cuda.synchronize()
         secs += time.perf_counter() - t0
         depth = maps["depth_map"][None]
@@ -335,12 +340,15 @@ def main(argv=None):
     import utils
     argv = list(sys.argv[1:] if argv is None else argv)
     if not argv or argv[0] not in ("local_train", "global_pre", "global_train", "eval"):
-        raise SystemExit("usage: python -m be_hip.workflow {local_train|global_pre|global_train|eval} [--big] [reference arguments]")
+        raise SystemExit("usage: python -m be_hip.workflow {local_train|global_pre|global_train|eval} [--big | --any] [reference arguments]")
     cmd, rest = argv[0], argv[1:]
-    big = "--big" in rest
-    rest = [a for a in rest if a != "--big"]
+    big, any_size = "--big" in rest, "--any" in rest
+    rest = [a for a in rest if a not in ("--big", "--any")]
     if cmd == "eval":
-        evaluate(utils.get_args('eval', big=big, argv=rest), big=big)
+        if big and any_size:
+            raise SystemExit("eval: --big (the reference's tiler, sizes 59 + 88 k) and --any (any size >= 147 x 147) exclude each other")
+        # --any takes the big-image arguments (--n_margin_patch, default --data_path ./data/data_test_big)
+        return evaluate(utils.get_args('eval', big=big or any_size, argv=rest), big=big, any_size=any_size)
     elif cmd == "local_train":
         local_train(utils.get_args('local_train', argv=rest))
     elif cmd == "global_pre":

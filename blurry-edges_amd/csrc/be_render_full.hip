@@ -14,6 +14,11 @@
 //                      blur sets (aperture 1, aperture 2, sharpened, refocused) and accumulates the six maps.
 //                      Deterministic (no atomics), divides by the analytic overlap count.
 //
+// Both kernels are templated on how a patch's origin is obtained: UNIFORM (origin = stride * index, the grid of
+// nn.Unfold) or ORIGIN TABLES ys[HP] / xs[WP] (a separable grid whose last line may sit flush with the image edge, so an
+// image of any size is covered; the fold then divides by the number of patches it visited).  The uniform instantiation
+// is the code path every existing entry point takes.
+//
 // The reference materialises 26.5 KB per patch pair and folds it six times; here the per-patch state is
 // 128 B and every output byte is written once.
 #include "be_common.h"
@@ -44,6 +49,9 @@ struct FullArgs {
     float rho_prime;
     int densify_w;
     int64_t n;
+    const int32_t* ys;       // [HP] / [WP] patch origins (pixels), k_render_records<true> only
+    const int32_t* xs;
+    int y_max, x_max;        // H - R, W - R: an origin outside [0, max] is clamped (no read leaves the image)
 };
 
 __device__ __forceinline__ void composite3(const float* col, float u0, float u1, float u2, float* out, int pix) {
@@ -53,6 +61,7 @@ __device__ __forceinline__ void composite3(const float* col, float u0, float u1,
     out[2 * NPIX + pix] = u0 * col[6] + u1 * col[7] + u2 * col[8];
 }
 
+template <bool TABLES>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK)
 void k_render_records(be_render_opts o, be_depth_consts dc, FullArgs a) {
     __shared__ float lin[R];
@@ -72,7 +81,13 @@ void k_render_records(be_render_opts o, be_depth_consts dc, FullArgs a) {
         rad[k] = be::kRoot2 * eta[k];
     }
     const int pi = (int)(patch / a.v.wp), pj = (int)(patch % a.v.wp);
-    const float* img1 = a.v.base + pi * a.v.s_pi + pj * a.v.s_pj;
+    const float* img1;
+    if constexpr (TABLES) {
+        const int oy = min(max(a.ys[pi], 0), a.y_max), ox = min(max(a.xs[pj], 0), a.x_max);
+        img1 = a.v.base + oy * a.v.s_row + ox * a.v.s_col;
+    } else {
+        img1 = a.v.base + pi * a.v.s_pi + pj * a.v.s_pj;
+    }
     const float* img2 = img1 + a.v.s_aperture;
 
     float d1s[PASSES], d2s[PASSES];
@@ -174,15 +189,40 @@ struct FoldArgs {
     float* depth;            // [H,W] or null
     float* conf;             // [H,W] or null
     int64_t rec_stride;      // batched form (grid.z = image): floats between the records / maps of consecutive images
+    const int32_t* ys;       // [hp] / [wp] patch origins, strictly increasing (k_fold_records<true> only)
+    const int32_t* xs;
 };
 
+constexpr int FOLD_TILE = 16;                       // output pixels per workgroup and axis
+constexpr int FOLD_LINES = FOLD_TILE + R - 1;       // strictly increasing integer origins: at most one grid line per pixel
+                                                    // of [tile_first - (R-1), tile_last] can cover a pixel of the tile
+constexpr int LINE_NONE = 0x7fffffff;
+
+// first index in t[0..n) with t[i] >= v (t increasing)
+__device__ __forceinline__ int lower_bound(const int32_t* __restrict__ t, int n, int v) {
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (t[mid] < v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+template <bool TABLES>
 __global__ __launch_bounds__(256)
 void k_fold_records(be_render_opts o, FoldArgs a) {
     __shared__ float lin[R];
+    __shared__ int sy[TABLES ? FOLD_LINES : 1], sx[TABLES ? FOLD_LINES : 1];
     if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
+    int i0 = 0, j0 = 0;                                         // grid line held by sy[0] / sx[0]
+    if constexpr (TABLES) {
+        // the grid lines that can cover this tile, staged once per workgroup; absent slots hold LINE_NONE
+        i0 = lower_bound(a.ys, a.hp, (int)blockIdx.y * FOLD_TILE - (R - 1));
+        j0 = lower_bound(a.xs, a.wp, (int)blockIdx.x * FOLD_TILE - (R - 1));
+        const int t = threadIdx.x;
+        if (t < FOLD_LINES) sy[t] = i0 + t < a.hp ? a.ys[i0 + t] : LINE_NONE;
+        else if (t >= 64 && t < 64 + FOLD_LINES) sx[t - 64] = j0 + t - 64 < a.wp ? a.xs[j0 + t - 64] : LINE_NONE;
+    }
     __syncthreads();
-    const int x = blockIdx.x * 16 + (threadIdx.x & 15);
-    const int y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    const int x = blockIdx.x * FOLD_TILE + (threadIdx.x & 15);
+    const int y = blockIdx.y * FOLD_TILE + (threadIdx.x >> 4);
     if (x >= a.W || y >= a.H) return;
     if (blockIdx.z) {                                           // image blockIdx.z of a batch
         const size_t b = blockIdx.z, hw = (size_t)a.H * a.W;
@@ -194,21 +234,29 @@ void k_fold_records(be_render_opts o, FoldArgs a) {
         if (a.depth) a.depth += b * hw;
         if (a.conf) a.conf += b * hw;
     }
-    // patches covering (y,x): stride*i <= y <= stride*i + 20
+    // patches covering (y,x): origin(i) <= y <= origin(i) + 20, a contiguous run of grid lines on either axis
     const int s = a.stride;
-    int i_lo = (y - (R - 1) + s - 1) / s; if (y - (R - 1) < 0) i_lo = 0;
-    int j_lo = (x - (R - 1) + s - 1) / s; if (x - (R - 1) < 0) j_lo = 0;
-    int i_hi = y / s; if (i_hi > a.hp - 1) i_hi = a.hp - 1;
-    int j_hi = x / s; if (j_hi > a.wp - 1) j_hi = a.wp - 1;
+    int i_lo, j_lo, i_hi, j_hi;
+    if constexpr (TABLES) {
+        i_lo = 0; while (i_lo < FOLD_LINES && sy[i_lo] < y - (R - 1)) ++i_lo;
+        j_lo = 0; while (j_lo < FOLD_LINES && sx[j_lo] < x - (R - 1)) ++j_lo;
+        i_hi = i_lo - 1; while (i_hi + 1 < FOLD_LINES && sy[i_hi + 1] <= y) ++i_hi;
+        j_hi = j_lo - 1; while (j_hi + 1 < FOLD_LINES && sx[j_hi + 1] <= x) ++j_hi;
+    } else {
+        i_lo = (y - (R - 1) + s - 1) / s; if (y - (R - 1) < 0) i_lo = 0;
+        j_lo = (x - (R - 1) + s - 1) / s; if (x - (R - 1) < 0) j_lo = 0;
+        i_hi = y / s; if (i_hi > a.hp - 1) i_hi = a.hp - 1;
+        j_hi = x / s; if (j_hi > a.wp - 1) j_hi = a.wp - 1;
+    }
     float acc1[3] = {0, 0, 0}, acc2[3] = {0, 0, 0}, accs[3] = {0, 0, 0}, accf[3] = {0, 0, 0};
     float accb = 0.f, accz = 0.f;
     int cnt = 0, cntz = 0;
     const float rs = be::kRoot2 * 1e-4f;
     for (int i = i_lo; i <= i_hi; ++i) {
-        const float py = lin[y - s * i];
+        const float py = lin[y - (TABLES ? sy[i] : s * i)];
         for (int j = j_lo; j <= j_hi; ++j) {
-            const float px = lin[x - s * j];
-            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)(i * a.wp + j) * REC);
+            const float px = lin[x - (TABLES ? sx[j] : s * j)];
+            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)((i0 + i) * a.wp + (j0 + j)) * REC);
             float r[REC];
 #pragma unroll
             for (int k = 0; k < REC / 4; ++k) { const float4 t = rp[k]; r[4 * k] = t.x; r[4 * k + 1] = t.y; r[4 * k + 2] = t.z; r[4 * k + 3] = t.w; }
@@ -251,7 +299,7 @@ void k_fold_records(be_render_opts o, FoldArgs a) {
         }
     }
     const size_t hw = (size_t)a.H * a.W, at = (size_t)y * a.W + x;
-    const float n = (float)cnt;                         // = nn.Fold(ones) at this pixel (>= 1)
+    const float n = (float)cnt;                         // = nn.Fold(ones) at this pixel (>= 1): the patches visited
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         if (a.image) { a.image[c * hw + at] = acc1[c] / n; a.image[(3 + c) * hw + at] = acc2[c] / n; }
@@ -322,10 +370,11 @@ extern "C" int be_render_full_f32(const be_render_opts* o, const be_depth_consts
     BE_REQUIRE(o && dc && params12 && view && view->base && records, "be_render_full_f32: null pointer");
     BE_REQUIRE(view->wp > 0, "be_render_full_f32: view.wp must be > 0");
     BE_REQUIRE(be::aligned16(records), "be_render_full_f32: records must be 16-byte aligned");
-    FullArgs a{params12, *view, records, patches, shpd, refoc, boundary, depth_map, depth_mask, rho_prime, densify_w, n};
+    FullArgs a{params12, *view, records, patches, shpd, refoc, boundary, depth_map, depth_mask, rho_prime, densify_w, n,
+               nullptr, nullptr, 0, 0};
     const int64_t blocks = (n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     BE_REQUIRE(blocks <= 0x7fffffff, "be_render_full_f32: n too large");
-    hipLaunchKernelGGL(k_render_records, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, be::as_stream(stream),
+    hipLaunchKernelGGL(k_render_records<false>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, be::as_stream(stream),
                        *o, *dc, a);
     return be::check_launch("be_render_full_f32");
 }
@@ -337,8 +386,8 @@ extern "C" int be_fold_records_f32(const be_render_opts* o, const float* records
     BE_REQUIRE(hp > 0 && wp > 0 && H > 0 && W > 0 && stride > 0, "be_fold_records_f32: bad sizes");
     BE_REQUIRE(stride * (hp - 1) + R <= H && stride * (wp - 1) + R <= W, "be_fold_records_f32: patch grid exceeds the image");
     BE_REQUIRE(be::aligned16(records), "be_fold_records_f32: records must be 16-byte aligned");
-    FoldArgs a{records, hp, wp, H, W, stride, densify_w, image, shpd, refoc, bndry, depth, conf, 0};
-    hipLaunchKernelGGL(k_fold_records, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, be::as_stream(stream), *o, a);
+    FoldArgs a{records, hp, wp, H, W, stride, densify_w, image, shpd, refoc, bndry, depth, conf, 0, nullptr, nullptr};
+    hipLaunchKernelGGL(k_fold_records<false>, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, be::as_stream(stream), *o, a);
     return be::check_launch("be_fold_records_f32");
 }
 
@@ -349,9 +398,43 @@ extern "C" int be_fold_records_batch_f32(const be_render_opts* o, const float* r
     BE_REQUIRE(B > 0 && B <= 65535 && hp > 0 && wp > 0 && H > 0 && W > 0 && stride > 0, "be_fold_records_batch_f32: bad sizes");
     BE_REQUIRE(stride * (hp - 1) + R <= H && stride * (wp - 1) + R <= W, "be_fold_records_batch_f32: patch grid exceeds the image");
     BE_REQUIRE(be::aligned16(records), "be_fold_records_batch_f32: records must be 16-byte aligned");
-    FoldArgs a{records, hp, wp, H, W, stride, densify_w, image, shpd, refoc, bndry, depth, conf, (int64_t)hp * wp * REC};
-    hipLaunchKernelGGL(k_fold_records, dim3((W + 15) / 16, (H + 15) / 16, B), dim3(256), 0, be::as_stream(stream), *o, a);
+    FoldArgs a{records, hp, wp, H, W, stride, densify_w, image, shpd, refoc, bndry, depth, conf, (int64_t)hp * wp * REC, nullptr, nullptr};
+    hipLaunchKernelGGL(k_fold_records<false>, dim3((W + 15) / 16, (H + 15) / 16, B), dim3(256), 0, be::as_stream(stream), *o, a);
     return be::check_launch("be_fold_records_batch_f32");
+}
+
+extern "C" int be_render_full_grid_f32(const be_render_opts* o, const be_depth_consts* dc, float rho_prime, int densify_w,
+                                       const float* params12, const float* img, int H, int W, const int32_t* ys,
+                                       const int32_t* xs, int HP, int WP, float* records, void* stream) {
+    BE_REQUIRE(o && dc && params12 && img && ys && xs && records, "be_render_full_grid_f32: null pointer");
+    BE_REQUIRE(H >= R && W >= R, "be_render_full_grid_f32: the image is smaller than one patch");
+    BE_REQUIRE(HP > 0 && WP > 0 && HP <= H - R + 1 && WP <= W - R + 1,
+               "be_render_full_grid_f32: HP / WP must be in [1, H-20] / [1, W-20] (origins are distinct pixels)");
+    BE_REQUIRE(be::aligned16(records), "be_render_full_grid_f32: records must be 16-byte aligned");
+    const int64_t n = (int64_t)HP * WP, hw = (int64_t)H * W;
+    const be_patch_view v{img, 3 * hw, hw, W, 1, 0, 0, WP};
+    FullArgs a{params12, v, records, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rho_prime, densify_w, n,
+               ys, xs, H - R, W - R};
+    const int64_t blocks = (n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    BE_REQUIRE(blocks <= 0x7fffffff, "be_render_full_grid_f32: grid too large");
+    hipLaunchKernelGGL(k_render_records<true>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, be::as_stream(stream),
+                       *o, *dc, a);
+    return be::check_launch("be_render_full_grid_f32");
+}
+
+extern "C" int be_fold_records_grid_f32(const be_render_opts* o, const float* records, int HP, int WP, int H, int W,
+                                        const int32_t* ys, const int32_t* xs, int densify_w, float* image, float* shpd,
+                                        float* refoc, float* bndry, float* depth, float* conf, void* stream) {
+    BE_REQUIRE(o && records && ys && xs, "be_fold_records_grid_f32: null pointer");
+    BE_REQUIRE(H >= R && W >= R, "be_fold_records_grid_f32: the image is smaller than one patch");
+    BE_REQUIRE(HP > 0 && WP > 0 && HP <= H - R + 1 && WP <= W - R + 1,
+               "be_fold_records_grid_f32: HP / WP must be in [1, H-20] / [1, W-20] (origins are distinct pixels)");
+    BE_REQUIRE((H + FOLD_TILE - 1) / FOLD_TILE <= 65535 && (int64_t)HP * WP <= 0x7fffffff, "be_fold_records_grid_f32: image too large");
+    BE_REQUIRE(be::aligned16(records), "be_fold_records_grid_f32: records must be 16-byte aligned");
+    FoldArgs a{records, HP, WP, H, W, 0, densify_w, image, shpd, refoc, bndry, depth, conf, 0, ys, xs};
+    hipLaunchKernelGGL(k_fold_records<true>, dim3((W + FOLD_TILE - 1) / FOLD_TILE, (H + FOLD_TILE - 1) / FOLD_TILE), dim3(256), 0,
+                       be::as_stream(stream), *o, a);
+    return be::check_launch("be_fold_records_grid_f32");
 }
 
 extern "C" int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream) {

@@ -423,6 +423,48 @@ std::vector<Tensor> fold_records(const Tensor& opts, const Tensor& records, int6
     return r;
 }
 
+// the two passes over a patch grid given by origin tables (ys [HP], xs [WP]: int32 on the GPU) instead of one stride
+static const int32_t* origin_table(const Tensor& t, const char* what) {
+    TORCH_CHECK(t.is_cuda(), what, ": expected the origin table on the GPU; the HIP path has no CPU fallback");
+    TORCH_CHECK(t.dim() == 1 && t.numel() > 0 && t.scalar_type() == at::kInt && t.is_contiguous(), what, ": a contiguous int32 vector");
+    return t.data_ptr<int32_t>();
+}
+Tensor render_full_grid(const Tensor& opts, const Tensor& consts, double rho_prime, bool densify_w, const Tensor& params12,
+                        const Tensor& img, const Tensor& ys, const Tensor& xs) {
+    TORCH_CHECK(img.dim() == 4 && img.size(0) == 2 && img.size(1) == 3, "render_full_grid: img [2,3,H,W]");
+    const int64_t HP = ys.numel(), WP = xs.numel();
+    TORCH_CHECK(params12.dim() == 2 && params12.size(0) == HP * WP && params12.size(1) == 12, "render_full_grid: params12 [HP*WP,12]");
+    Tensor rec = at::empty({HP * WP, BE_RECORD_FLOATS}, params12.options());
+    check(be_render_full_grid_f32(host_struct<be_render_opts>(opts, "render_full_grid(opts)"),
+                                  host_struct<be_depth_consts>(consts, "render_full_grid(consts)"), (float)rho_prime, densify_w ? 1 : 0,
+                                  fp(params12, "params12"), fp(img, "img"), (int)img.size(2), (int)img.size(3),
+                                  origin_table(ys, "render_full_grid(ys)"), origin_table(xs, "render_full_grid(xs)"), (int)HP, (int)WP,
+                                  rec.data_ptr<float>(), stream_of(params12)), "be_render_full_grid_f32");
+    return rec;
+}
+std::vector<Tensor> fold_records_grid(const Tensor& opts, const Tensor& records, const Tensor& ys, const Tensor& xs, int64_t H, int64_t W,
+                                      bool densify_w, int64_t want) {
+    const int64_t HP = ys.numel(), WP = xs.numel();
+    TORCH_CHECK(records.dim() == 2 && records.size(0) == HP * WP && records.size(1) == BE_RECORD_FLOATS,
+                "fold_records_grid: records [HP*WP,32]");
+    fp(records, "records");
+    auto o = records.options();
+    Tensor t[6];
+    if (want & 1) t[0] = at::empty({2, 3, H, W}, o);
+    if (want & 2) t[1] = at::empty({3, H, W}, o);
+    if (want & 4) t[2] = at::empty({3, H, W}, o);
+    if (want & 8) t[3] = at::empty({H, W}, o);
+    if (want & 16) t[4] = at::empty({H, W}, o);
+    if (want & 32) t[5] = at::empty({H, W}, o);
+    auto f = [&](int i) { return t[i].defined() ? t[i].data_ptr<float>() : nullptr; };
+    check(be_fold_records_grid_f32(host_struct<be_render_opts>(opts, "fold_records_grid(opts)"), records.data_ptr<float>(), (int)HP, (int)WP,
+                                   (int)H, (int)W, origin_table(ys, "fold_records_grid(ys)"), origin_table(xs, "fold_records_grid(xs)"),
+                                   densify_w ? 1 : 0, f(0), f(1), f(2), f(3), f(4), f(5), stream_of(records)), "be_fold_records_grid_f32");
+    std::vector<Tensor> r;
+    for (int i = 0; i < 6; ++i) if (t[i].defined()) r.push_back(t[i]);
+    return r;
+}
+
 // LocalLoss forward + analytic backward in one launch -> (partial [B,3], grad_est [B,10] or an empty tensor)
 std::tuple<Tensor, Tensor> local_loss(const Tensor& opts, const Tensor& est, const Tensor& img_fit, const Tensor& gt, const Tensor& bdist,
                                       const Tensor& deri, double beta_b, double beta_s, bool want_grad) {
@@ -539,6 +581,8 @@ TORCH_LIBRARY(be, m) {
     m.def("wrap_angles_(Tensor(a!) est, int col0, int col1) -> ()");
     m.def("render_full(Tensor opts, Tensor consts, float rho_prime, bool densify_w, Tensor params12, Tensor view, Tensor pixels, int want) -> Tensor[]");
     m.def("fold_records(Tensor opts, Tensor records, int hp, int wp, int H, int W, int stride, bool densify_w, int want) -> Tensor[]");
+    m.def("render_full_grid(Tensor opts, Tensor consts, float rho_prime, bool densify_w, Tensor params12, Tensor img, Tensor ys, Tensor xs) -> Tensor");
+    m.def("fold_records_grid(Tensor opts, Tensor records, Tensor ys, Tensor xs, int H, int W, bool densify_w, int want) -> Tensor[]");
     m.def("local_loss(Tensor opts, Tensor est, Tensor img_fit, Tensor gt, Tensor bdist, Tensor deri, float beta_b, float beta_s, bool want_grad) -> (Tensor, Tensor)");
     m.def("local_loss_finish(Tensor partial, float beta_b, float beta_s) -> Tensor");
     m.def("global_loss(Tensor opts, Tensor consts, Tensor est, Tensor img_fit, Tensor img_gt, Tensor G, Tensor Gd, Tensor Gb, Tensor bdist, Tensor deri, "
@@ -589,6 +633,8 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("wrap_angles_", wrap_angles_);
     m.impl("render_full", render_full);
     m.impl("fold_records", fold_records);
+    m.impl("render_full_grid", render_full_grid);
+    m.impl("fold_records_grid", fold_records_grid);
     m.impl("local_loss", local_loss);
     m.impl("local_loss_finish", local_loss_finish);
     m.impl("global_loss", global_loss);

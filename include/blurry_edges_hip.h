@@ -148,6 +148,26 @@ int be_fold_records_batch_f32(const be_render_opts* o, const float* records, int
                               int densify_w, float* image, float* shpd, float* refoc, float* bndry, float* depth, float* conf,
                               void* stream);
 
+/* The same two passes over a SEPARABLE PATCH GRID GIVEN BY ORIGIN TABLES instead of one uniform stride: patch (i, j) of the
+ * HP x WP grid has its 21 x 21 window at pixel (ys[i], xs[j]) of img [2,3,H,W].  ys [HP] / xs [WP] are DEVICE int32 arrays,
+ * strictly increasing, inside [0, H-21] / [0, W-21].  This generalises nn.Unfold(21, stride) (blurry_edges_test.py:120-121,
+ * blurry_edges_test_big.py:116-117, defined only while (H - 21) % stride == 0) to a grid whose last line sits flush with the
+ * image edge at H - 21, so every pixel of an image of any size is covered (be_hip/tiling.py builds the tables and checks
+ * them; the library checks pointers and sizes, and the render clamps an origin that would leave the image).
+ * Render: params12 [HP*WP,12] -> records [HP*WP,32], one launch for the whole grid, the arithmetic of the uniform entry point
+ * above (with tables 0, s, 2s, .. the records are bit-identical to it). */
+int be_render_full_grid_f32(const be_render_opts* opts_host, const be_depth_consts* consts_host, float rho_prime,
+                            int densify_w, const float* params12, const float* img, int H, int W, const int32_t* ys,
+                            const int32_t* xs, int HP, int WP, float* records, void* stream);
+/* Fold (utils/postprocessing_loss.py:151-173 with nn.Fold's uniform stride replaced by the tables): pixel (y, x) visits
+ * the grid lines with ys[i] <= y <= ys[i] + 20 in ascending i, then ascending j (the order of the uniform fold), and
+ * divides by the number of patches it visited - the generalisation of nn.Fold(ones).  The tables must cover every pixel
+ * (first origin 0, last H-21 / W-21, gaps <= 21) or the uncovered pixels are 0/0.  Owner-computes: no atomics, every
+ * output written once, bit-reproducible; with tables 0, s, 2s, .. bit-identical to the uniform fold above.  Outputs as there. */
+int be_fold_records_grid_f32(const be_render_opts* opts_host, const float* records, int HP, int WP, int H, int W,
+                             const int32_t* ys, const int32_t* xs, int densify_w, float* image, float* shpd, float* refoc,
+                             float* bndry, float* depth, float* conf, void* stream);
+
 /* nn.Unfold(21, stride) in the order blurry_edges_test.py:120-121 consumes it:
  * img [B,C,H,W] -> out [B, Hp*Wp, C, 21, 21], patch (i,j) = rows stride*i.., cols stride*j.., index i*Wp+j. */
 int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream);
