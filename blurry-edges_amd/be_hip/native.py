@@ -149,6 +149,8 @@ _SIGNATURES = {
     "be_render_full_grid_f32": (C.c_int, [C.POINTER(RenderOpts), C.POINTER(DepthConsts), C.c_float, C.c_int, _P, _P, C.c_int, C.c_int,
                                           _P, _P, C.c_int, C.c_int, _P, _P]),
     "be_fold_records_grid_f32": (C.c_int, [C.POINTER(RenderOpts), _P] + [C.c_int] * 4 + [_P, _P, C.c_int] + [_P] * 6 + [_P]),
+    "be_refocus_stack_chunk": (C.c_int, []),
+    "be_fold_refocus_stack_f32": (C.c_int, [C.POINTER(RenderOpts), C.POINTER(DepthConsts), _P] + [C.c_int] * 5 + [_P, _P, _P, C.c_int, _P, _P]),
     "be_unfold_patches_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "be_local_features_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "be_global_denorm_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
@@ -984,6 +986,62 @@ def fold_records_grid(opts, records, H, W, ys, xs, densify_w=False, want=FOLD_MA
     check(lib().be_fold_records_grid_f32(C.byref(opts), dptr(records, "records", (torch.float32,)), HP, WP, H, W, dptr(ys), dptr(xs),
                                          int(bool(densify_w)), g("image"), g("shpd"), g("refoc"), g("bndry"), g("depth"), g("conf"),
                                          stream_ptr(dev)), "be_fold_records_grid_f32")
+    return out
+
+
+REFOCUS_STACK_KC = 8          # BE_REFOCUS_STACK_KC of the header: the planes one workgroup of the stack kernel accumulates
+
+
+def rho_prime_list(rho_primes, name: str = "rho_primes"):
+    """A sequence of floats or a tensor of optical powers -> a list of python floats, checked on the host (before any native
+    code is touched): one dimension, non-empty, finite."""
+    if isinstance(rho_primes, torch.Tensor):
+        if rho_primes.dim() != 1:
+            raise ValueError(f"{name}: expected a 1-d tensor of optical powers, got shape {tuple(rho_primes.shape)}")
+        vals = rho_primes.detach().double().cpu().tolist()
+    else:
+        vals = [float(v) for v in rho_primes]
+    if not vals:
+        raise ValueError(f"{name}: empty - a focal stack needs at least one optical power")
+    if not all(v == v and abs(v) != float("inf") for v in vals):
+        raise ValueError(f"{name}: optical powers must be finite, got {vals}")
+    return vals
+
+
+def fold_refocus_stack(opts, consts, records, rho_primes, H, W, hp=None, wp=None, stride=2, ys=None, xs=None):
+    """records [hp*wp,32] (render_full / render_full_grid at ANY rho_prime) + K optical powers -> [K,3,H,W]: plane k is the
+    `refoc` map of render_full*(rho_prime=rho_primes[k]) + fold_records*, bit for bit, from one launch that shares the record
+    fetch and the wedge distances between the planes.  ys / xs (both): origin tables as fold_records_grid takes them (hp / wp
+    then come from the tables); neither: the uniform grid hp x wp of `stride`.  rho_primes: floats or a float32 tensor."""
+    vals = rho_prime_list(rho_primes, "fold_refocus_stack(rho_primes)")
+    if (ys is None) != (xs is None):
+        raise ValueError("fold_refocus_stack: ys and xs must both be given (origin tables) or both be None (uniform grid)")
+    if not isinstance(records, torch.Tensor) or records.dim() != 2:
+        raise RuntimeError(f"fold_refocus_stack: records must be a [P,{RECORD_FLOATS}] tensor")
+    dev = records.device
+    if ys is not None:
+        ys = origin_table(ys, H, dev, "fold_refocus_stack(ys)", cover=True)
+        xs = origin_table(xs, W, dev, "fold_refocus_stack(xs)", cover=True)
+        if (hp is not None and hp != ys.numel()) or (wp is not None and wp != xs.numel()):
+            raise RuntimeError(f"fold_refocus_stack: hp / wp ({hp}, {wp}) do not match the tables ({ys.numel()}, {xs.numel()})")
+        hp, wp = ys.numel(), xs.numel()
+    elif hp is None or wp is None:
+        raise RuntimeError("fold_refocus_stack: the uniform grid needs hp and wp")
+    if tuple(records.shape) != (hp * wp, RECORD_FLOATS):
+        raise RuntimeError(f"fold_refocus_stack: records must be [{hp * wp},{RECORD_FLOATS}], got {tuple(records.shape)}")
+    records = records.contiguous()
+    dptr(records, "records", (torch.float32,))
+    if isinstance(rho_primes, torch.Tensor) and rho_primes.device == dev and rho_primes.dtype == torch.float32 and rho_primes.is_contiguous():
+        rho = rho_primes
+    else:
+        rho = torch.tensor(vals, dtype=torch.float32, device=dev)
+    o = ops()
+    if o is not None:
+        return o.fold_refocus_stack(struct_tensor(opts), struct_tensor(consts), records, rho, ys, xs, hp, wp, H, W, stride)
+    out = torch.empty(len(vals), 3, H, W, dtype=torch.float32, device=dev)
+    check(lib().be_fold_refocus_stack_f32(C.byref(opts), C.byref(consts), dptr(records, "records", (torch.float32,)), hp, wp, H, W,
+                                          stride, dptr(ys), dptr(xs), dptr(rho), len(vals), dptr(out), stream_ptr(dev)),
+          "be_fold_refocus_stack_f32")
     return out
 
 

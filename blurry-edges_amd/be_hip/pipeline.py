@@ -7,6 +7,8 @@ image pair [2,3,H,W]  ->  unfold  ->  LocalStage (HIP)  ->  pass-A colours (HIP)
   on the folded depth map, blurry_edges_test.py:141-142).
 DepthPipeline.__call__ is the reference's one 147x147 pair, run_big its big-image tiler (sizes 59 + 88 k), run_any the same
 pipeline for a pair of any size >= one block (flush-edge patch grid, be_hip/tiling.py).
+All three return `records` (the [HP*WP,32] grid they fold) and `grid` (its geometry); DepthPipeline.refocus_stack turns those into a
+focal stack - the pair refocused at K optical powers - with one more launch and no second pass B.
 Nothing here computes on the CPU; tensors stay on the GPU until the caller asks for them.
 """
 from __future__ import annotations
@@ -74,7 +76,8 @@ class DepthPipeline:
             maps["depth_map"] = self.pp(maps["depth"][None, None])[0, 0]
         else:
             maps["depth_map"] = torch.where(maps["conf"] > self.depth_thres, maps["depth"], torch.zeros_like(maps["depth"]))
-        maps.update(est10=est10, colors_a=colors, est12=est12, records=rec)
+        maps.update(est10=est10, colors_a=colors, est12=est12, records=rec,
+                    grid=dict(H=H, W=W, hp=hp, wp=wp, stride=self.stride, ys=None, xs=None))
         return maps
 
     # ---- big image: 147x147 blocks with margin patches dropped (blurry_edges_test_big.py:116-189) -----
@@ -152,6 +155,7 @@ class DepthPipeline:
             maps["depth_map"] = self.pp(maps["depth"][None, None])[0, 0]
         else:                                                                       # blurry_edges_test_big.py:189
             maps["depth_map"] = torch.where(maps["conf"] > 0.05, maps["depth"], torch.zeros_like(maps["depth"]))
+        maps.update(records=big.view(HP * WP, -1), grid=dict(H=H, W=W, hp=HP, wp=WP, stride=s, ys=None, xs=None))
         return maps
 
     # ---- any size >= one block: flush-edge patch grid + pulled-back last block (be_hip/tiling.py) -----------------------
@@ -179,7 +183,7 @@ class DepthPipeline:
     @torch.no_grad()
     def run_any(self, img, block=147, n_margin=10):
         """img [2,3,H,W] with H, W >= block, ANY such size -> the dict of run_big (image, shpd, refoc, bndry, depth, conf,
-        depth_map; plus est12 [HP*WP,12] and records [HP*WP,32] of the whole grid).
+        depth_map, records [HP*WP,32], grid; plus est12 [HP*WP,12] of the whole grid; grid holds the device origin tables).
 
         Patch grid: tiling.patch_grid per axis - origins 0, s, 2s, .. and one more flush with the edge at H - 21 when the
         uniform grid stops short of it, so every pixel is covered (the uniform fold leaves 0/0 in the last row / column
@@ -226,5 +230,30 @@ class DepthPipeline:
             maps["depth_map"] = self.pp(maps["depth"][None, None])[0, 0]
         else:                                                                       # as run_big (blurry_edges_test_big.py:189)
             maps["depth_map"] = torch.where(maps["conf"] > 0.05, maps["depth"], torch.zeros_like(maps["depth"]))
-        maps.update(est12=est, records=rec)
+        maps.update(est12=est, records=rec, grid=dict(H=H, W=W, hp=HP, wp=WP, stride=s, ys=dev_ys, xs=dev_xs))
         return maps
+
+    # ---- focal stack from one depth estimate ----------------------------------------------------------------------------
+    @torch.no_grad()
+    def refocus_stack(self, maps, rho_primes=None, focus_depths=None):
+        """maps: what __call__, run_big or run_any returned.  Exactly one of rho_primes (optical powers, dioptres) and
+        focus_depths (metres, through DepthEtas.focus2rho) -> [K,3,H,W]: the pair refocused at each of them.  Plane k is what
+        maps["refoc"] would be had the pipeline been built with rho_prime = rho_primes[k] - the colours and wedge depths in
+        maps["records"] do not depend on rho_prime, so pass B is not run again and one launch folds all K planes
+        (native.fold_refocus_stack)."""
+        if (rho_primes is None) == (focus_depths is None):
+            raise ValueError("refocus_stack: give exactly one of rho_primes (optical powers) and focus_depths (metres)")
+        if not isinstance(maps, dict) or "records" not in maps or "grid" not in maps:
+            missing = [k for k in ("records", "grid") if not isinstance(maps, dict) or k not in maps]
+            raise ValueError(f"refocus_stack: maps lacks {missing}; pass the dict DepthPipeline.__call__, run_big or run_any returned")
+        rec, g = maps["records"], maps["grid"]
+        if not isinstance(rec, torch.Tensor) or not rec.is_cuda:
+            raise ValueError("refocus_stack: maps['records'] is not on the GPU; nothing here computes on the CPU "
+                             "(keep the dict the pipeline returned, or move records - and the ys / xs of grid - back to the device)")
+        if focus_depths is not None:
+            if isinstance(focus_depths, torch.Tensor):
+                rho_primes = self.dcal.focus2rho(focus_depths.detach().double().cpu()).tolist()
+            else:
+                rho_primes = [self.dcal.focus2rho(z) for z in focus_depths]
+        return native.fold_refocus_stack(self.helper.render_opts(False), self.dcal.consts, rec, rho_primes, g["H"], g["W"],
+                                         hp=g["hp"], wp=g["wp"], stride=g["stride"], ys=g["ys"], xs=g["xs"])

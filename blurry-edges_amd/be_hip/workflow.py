@@ -7,6 +7,7 @@ formats (argument names and defaults = utils/args.py of the reference):
     python -m be_hip.workflow global_train     global_training.py:168-224   (ShapeDataset 'global' -> best_run_exp_global_stage.pth)
     python -m be_hip.workflow eval [--big]     blurry_edges_test.py:102-176 / blurry_edges_test_big.py (TestDataset -> metrics)
     python -m be_hip.workflow eval --any       the same for image pairs of any size >= 147 x 147 (DepthPipeline.run_any)
+    ... eval --refocus_stack K [--focus_range NEAR FAR] [--out_path DIR]   also write every pair's K-plane focal stack
 
 Data parallel (BASELINE configs[4]): the two training commands run under torchrun, one process per GPU -
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m be_hip.workflow local_train ...
@@ -289,10 +290,22 @@ def global_train(args, quiet=False):
 
 
 # ------------------------------------------------------------------------- blurry_edges_test.py / blurry_edges_test_big.py
+def focus_sweep(dcal, k, near, far):
+    """The optical powers of `eval --refocus_stack k --focus_range near far`: k values evenly spaced in dioptres (= evenly spaced in
+    blur radius) from focus2rho(far) up to focus2rho(near), float64 [k]; k = 1 focuses at `far`."""
+    if k < 1:
+        raise ValueError(f"--refocus_stack: the number of planes must be >= 1, got {k}")
+    if not 0 < near < far:
+        raise ValueError(f"--focus_range: expected 0 < NEAR < FAR (metres), got {near} {far}")
+    return np.linspace(dcal.focus2rho(far), dcal.focus2rho(near), k)
+
+
 @torch.no_grad()
 def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weights=None, quiet=False, any_size=False):
     """-> dict(delta1, delta2, delta3, RMSE, AbsRel, seconds_per_pair), averaged over the test set as the scripts do.
-    any_size: pairs of any size >= 147 x 147 through DepthPipeline.run_any (checkpoint names and arguments as big)."""
+    any_size: pairs of any size >= 147 x 147 through DepthPipeline.run_any (checkpoint names and arguments as big).
+    args.refocus_stack = K > 0 (not in the reference): every pair's focal stack over args.focus_range goes to
+    {args.out_path}/refoc_stack_{j:04d}.npy ([K,3,H,W] float32) and the powers to rho_primes.npy, outside the timed region."""
     import data, models, utils
     from .pipeline import DepthPipeline
     dev = _device(args)
@@ -309,6 +322,11 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     pipe = DepthPipeline(local, globl, utils.PostProcessGlobalBase(args, dev), utils.DepthEtas(args, dev),
                          rho_prime=args.rho_prime, densify=args.densify, stride=args.stride, densify_pp_module=pp)
     ds = data.TestDataset(dev, data_path=args.data_path)
+    sweep = None
+    if getattr(args, "refocus_stack", 0):
+        sweep = focus_sweep(pipe.dcal, args.refocus_stack, *args.focus_range)
+        os.makedirs(args.out_path, exist_ok=True)
+        np.save(os.path.join(args.out_path, "rho_primes.npy"), sweep.astype(np.float32))
     tot = np.zeros(5)
     secs = 0.0
     for j in range(len(ds)):
@@ -322,6 +340,8 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
             maps = pipe.run_big(img, n_margin=args.n_margin_patch) if big else pipe(img)
         torch.cuda.synchronize()
         secs += time.perf_counter() - t0
+        if sweep is not None:
+            np.save(os.path.join(args.out_path, f"refoc_stack_{j:04d}.npy"), pipe.refocus_stack(maps, rho_primes=sweep.tolist()).cpu().numpy())
         depth = maps["depth_map"][None]
         m = np.array(utils.eval_depth(depth, gt[None].to(depth.dtype), depth, crop=args.crop))
         tot += m

@@ -311,6 +311,107 @@ void k_fold_records(be_render_opts o, FoldArgs a) {
     if (a.conf) a.conf[at] = (float)cntz / n;
 }
 
+// ------------------------------------------------------------------------------------------------ focal stack
+// K refocused images from ONE record grid: the refocus radius of a wedge is sqrt(2) * depth2sigma(z, rho') (or sqrt(2) * 1e-4
+// when the wedge owns no mask pixel), a function of the record's R_DEPTH / R_FLAGS and the plane's optical power alone, so the
+// record fetch, wedge_dists and the run search of k_fold_records are done once per covering patch and shared by the planes of a
+// chunk.  Plane k is k_render_records(rho_prime = rho_k) + k_fold_records(refoc) bit for bit: same radius expression, same
+// indicators / composite under contract(off), same visiting order, one division by the number of patches visited.
+struct StackArgs {
+    const float* records;    // [hp*wp,32]
+    const float* rho_primes; // [K] optical powers, device
+    float* out;              // [K,3,H,W]
+    int hp, wp, H, W, stride, K;
+    const int32_t* ys;       // [hp] / [wp] patch origins (k_fold_refocus_stack<true> only)
+    const int32_t* xs;
+};
+
+constexpr int FOLD_KC = BE_REFOCUS_STACK_KC;        // planes per workgroup (blockIdx.z = chunk; the last chunk may be short)
+
+template <bool TABLES>
+__global__ __launch_bounds__(256)
+void k_fold_refocus_stack(be_render_opts o, be_depth_consts dc, StackArgs a) {
+    __shared__ float lin[R];
+    __shared__ int sy[TABLES ? FOLD_LINES : 1], sx[TABLES ? FOLD_LINES : 1];
+    if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
+    int i0 = 0, j0 = 0;                                         // grid line held by sy[0] / sx[0]
+    if constexpr (TABLES) {
+        i0 = lower_bound(a.ys, a.hp, (int)blockIdx.y * FOLD_TILE - (R - 1));
+        j0 = lower_bound(a.xs, a.wp, (int)blockIdx.x * FOLD_TILE - (R - 1));
+        const int t = threadIdx.x;
+        if (t < FOLD_LINES) sy[t] = i0 + t < a.hp ? a.ys[i0 + t] : LINE_NONE;
+        else if (t >= 64 && t < 64 + FOLD_LINES) sx[t - 64] = j0 + t - 64 < a.wp ? a.xs[j0 + t - 64] : LINE_NONE;
+    }
+    __syncthreads();
+    const int x = blockIdx.x * FOLD_TILE + (threadIdx.x & 15);
+    const int y = blockIdx.y * FOLD_TILE + (threadIdx.x >> 4);
+    if (x >= a.W || y >= a.H) return;
+    const int k0 = blockIdx.z * FOLD_KC;
+    const int nk = min(FOLD_KC, a.K - k0);                      // planes of this chunk (uniform over the workgroup)
+    float rho[FOLD_KC];
+#pragma unroll
+    for (int k = 0; k < FOLD_KC; ++k) rho[k] = a.rho_primes[k0 + min(k, nk - 1)];
+    const int s = a.stride;
+    int i_lo, j_lo, i_hi, j_hi;
+    if constexpr (TABLES) {
+        i_lo = 0; while (i_lo < FOLD_LINES && sy[i_lo] < y - (R - 1)) ++i_lo;
+        j_lo = 0; while (j_lo < FOLD_LINES && sx[j_lo] < x - (R - 1)) ++j_lo;
+        i_hi = i_lo - 1; while (i_hi + 1 < FOLD_LINES && sy[i_hi + 1] <= y) ++i_hi;
+        j_hi = j_lo - 1; while (j_hi + 1 < FOLD_LINES && sx[j_hi + 1] <= x) ++j_hi;
+    } else {
+        i_lo = (y - (R - 1) + s - 1) / s; if (y - (R - 1) < 0) i_lo = 0;
+        j_lo = (x - (R - 1) + s - 1) / s; if (x - (R - 1) < 0) j_lo = 0;
+        i_hi = y / s; if (i_hi > a.hp - 1) i_hi = a.hp - 1;
+        j_hi = x / s; if (j_hi > a.wp - 1) j_hi = a.wp - 1;
+    }
+    float acc[FOLD_KC][3];
+#pragma unroll
+    for (int k = 0; k < FOLD_KC; ++k) { acc[k][0] = 0.f; acc[k][1] = 0.f; acc[k][2] = 0.f; }
+    int cnt = 0;
+    for (int i = i_lo; i <= i_hi; ++i) {
+        const float py = lin[y - (TABLES ? sy[i] : s * i)];
+        for (int j = j_lo; j <= j_hi; ++j) {
+            const float px = lin[x - (TABLES ? sx[j] : s * j)];
+            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)((i0 + i) * a.wp + (j0 + j)) * REC);
+            float r[REC];
+#pragma unroll
+            for (int k = 0; k < REC / 4; ++k) { const float4 t = rp[k]; r[4 * k] = t.x; r[4 * k + 1] = t.y; r[4 * k + 2] = t.z; r[4 * k + 3] = t.w; }
+            be::WedgeGeom g;
+            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
+            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
+            g.sg1 = r[12]; g.sg2 = r[13];
+            float d1, d2;
+            be::wedge_dists(g, px, py, o.w, d1, d2);
+            const float* col = r + R_COL;
+            const float z1 = r[R_DEPTH], z2 = r[R_DEPTH + 1];
+            const int flags = (int)r[R_FLAGS];
+            const bool has1 = (flags & 1) != 0, has2 = (flags & 2) != 0;
+#pragma unroll
+            for (int k = 0; k < FOLD_KC; ++k) {
+                if (k < nk) {
+#pragma clang fp contract(off)
+                    const float s1 = has1 ? be::depth2sigma(dc, z1, rho[k]) : 1e-4f;       // as k_render_records writes R_RADF
+                    const float s2 = has2 ? be::depth2sigma(dc, z2, rho[k]) : 1e-4f;
+                    float u0, u1, u2;
+                    be::indicators(d1, d2, be::kRoot2 * s1, be::kRoot2 * s2, u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc[k][c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                }
+            }
+            ++cnt;
+        }
+    }
+    const size_t hw = (size_t)a.H * a.W, at = (size_t)y * a.W + x;
+    const float n = (float)cnt;
+#pragma unroll
+    for (int k = 0; k < FOLD_KC; ++k) {
+        if (k < nk) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.out[((size_t)(k0 + k) * 3 + c) * hw + at] = acc[k][c] / n;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ glue
 __global__ void k_unfold(const float* __restrict__ img, float* __restrict__ out, int B, int C, int H, int W, int hp,
                          int wp, int stride) {
@@ -435,6 +536,33 @@ extern "C" int be_fold_records_grid_f32(const be_render_opts* o, const float* re
     hipLaunchKernelGGL(k_fold_records<true>, dim3((W + FOLD_TILE - 1) / FOLD_TILE, (H + FOLD_TILE - 1) / FOLD_TILE), dim3(256), 0,
                        be::as_stream(stream), *o, a);
     return be::check_launch("be_fold_records_grid_f32");
+}
+
+extern "C" int be_refocus_stack_chunk(void) { return FOLD_KC; }
+
+extern "C" int be_fold_refocus_stack_f32(const be_render_opts* o, const be_depth_consts* dc, const float* records, int HP, int WP,
+                                         int H, int W, int stride, const int32_t* ys, const int32_t* xs, const float* rho_primes,
+                                         int K, float* out, void* stream) {
+    BE_REQUIRE(o && dc && records && rho_primes && out, "be_fold_refocus_stack_f32: null pointer");
+    BE_REQUIRE((ys == nullptr) == (xs == nullptr), "be_fold_refocus_stack_f32: ys and xs must both be given (origin tables) or both be null (uniform grid)");
+    BE_REQUIRE(K >= 1 && (K + FOLD_KC - 1) / FOLD_KC <= 65535, "be_fold_refocus_stack_f32: K must be in [1, 65535 * BE_REFOCUS_STACK_KC]");
+    BE_REQUIRE(HP > 0 && WP > 0 && H >= R && W >= R, "be_fold_refocus_stack_f32: bad sizes");
+    BE_REQUIRE((H + FOLD_TILE - 1) / FOLD_TILE <= 65535 && (int64_t)HP * WP <= 0x7fffffff, "be_fold_refocus_stack_f32: image too large");
+    BE_REQUIRE(be::aligned16(records), "be_fold_refocus_stack_f32: records must be 16-byte aligned");
+    const dim3 grid((W + FOLD_TILE - 1) / FOLD_TILE, (H + FOLD_TILE - 1) / FOLD_TILE, (K + FOLD_KC - 1) / FOLD_KC);
+    if (ys) {
+        BE_REQUIRE(HP <= H - R + 1 && WP <= W - R + 1,
+                   "be_fold_refocus_stack_f32: HP / WP must be in [1, H-20] / [1, W-20] (origins are distinct pixels)");
+        StackArgs a{records, rho_primes, out, HP, WP, H, W, 0, K, ys, xs};
+        hipLaunchKernelGGL(k_fold_refocus_stack<true>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a);
+    } else {
+        BE_REQUIRE(stride > 0, "be_fold_refocus_stack_f32: bad sizes");
+        BE_REQUIRE((int64_t)stride * (HP - 1) + R <= H && (int64_t)stride * (WP - 1) + R <= W,
+                   "be_fold_refocus_stack_f32: patch grid exceeds the image");
+        StackArgs a{records, rho_primes, out, HP, WP, H, W, stride, K, nullptr, nullptr};
+        hipLaunchKernelGGL(k_fold_refocus_stack<false>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a);
+    }
+    return be::check_launch("be_fold_refocus_stack_f32");
 }
 
 extern "C" int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream) {

@@ -465,6 +465,32 @@ std::vector<Tensor> fold_records_grid(const Tensor& opts, const Tensor& records,
     return r;
 }
 
+// focal stack: records [hp*wp,32] + rho_primes [K] (fp32 on the GPU) -> [K,3,H,W]; ys / xs both given = origin tables, both
+// absent = the uniform grid of `stride`
+Tensor fold_refocus_stack(const Tensor& opts, const Tensor& consts, const Tensor& records, const Tensor& rho_primes,
+                          const c10::optional<Tensor>& ys, const c10::optional<Tensor>& xs, int64_t hp, int64_t wp, int64_t H, int64_t W,
+                          int64_t stride) {
+    TORCH_CHECK(ys.has_value() == xs.has_value(), "fold_refocus_stack: ys and xs must both be given (origin tables) or both be None");
+    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS,
+                "fold_refocus_stack: records [hp*wp,32]");
+    TORCH_CHECK(rho_primes.dim() == 1 && rho_primes.numel() > 0, "fold_refocus_stack: rho_primes [K], K >= 1");
+    TORCH_CHECK(rho_primes.device() == records.device(), "fold_refocus_stack: rho_primes and records on one device");
+    const int32_t *py = nullptr, *px = nullptr;
+    if (ys.has_value()) {
+        py = origin_table(*ys, "fold_refocus_stack(ys)");
+        px = origin_table(*xs, "fold_refocus_stack(xs)");
+        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, "fold_refocus_stack: ys [hp], xs [wp]");
+    }
+    const int64_t K = rho_primes.numel();
+    fp(records, "records");
+    Tensor out = at::empty({K, 3, H, W}, records.options());
+    check(be_fold_refocus_stack_f32(host_struct<be_render_opts>(opts, "fold_refocus_stack(opts)"),
+                                    host_struct<be_depth_consts>(consts, "fold_refocus_stack(consts)"), records.data_ptr<float>(), (int)hp,
+                                    (int)wp, (int)H, (int)W, (int)stride, py, px, fp(rho_primes, "rho_primes"), (int)K,
+                                    out.data_ptr<float>(), stream_of(records)), "be_fold_refocus_stack_f32");
+    return out;
+}
+
 // LocalLoss forward + analytic backward in one launch -> (partial [B,3], grad_est [B,10] or an empty tensor)
 std::tuple<Tensor, Tensor> local_loss(const Tensor& opts, const Tensor& est, const Tensor& img_fit, const Tensor& gt, const Tensor& bdist,
                                       const Tensor& deri, double beta_b, double beta_s, bool want_grad) {
@@ -583,6 +609,7 @@ TORCH_LIBRARY(be, m) {
     m.def("fold_records(Tensor opts, Tensor records, int hp, int wp, int H, int W, int stride, bool densify_w, int want) -> Tensor[]");
     m.def("render_full_grid(Tensor opts, Tensor consts, float rho_prime, bool densify_w, Tensor params12, Tensor img, Tensor ys, Tensor xs) -> Tensor");
     m.def("fold_records_grid(Tensor opts, Tensor records, Tensor ys, Tensor xs, int H, int W, bool densify_w, int want) -> Tensor[]");
+    m.def("fold_refocus_stack(Tensor opts, Tensor consts, Tensor records, Tensor rho_primes, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride) -> Tensor");
     m.def("local_loss(Tensor opts, Tensor est, Tensor img_fit, Tensor gt, Tensor bdist, Tensor deri, float beta_b, float beta_s, bool want_grad) -> (Tensor, Tensor)");
     m.def("local_loss_finish(Tensor partial, float beta_b, float beta_s) -> Tensor");
     m.def("global_loss(Tensor opts, Tensor consts, Tensor est, Tensor img_fit, Tensor img_gt, Tensor G, Tensor Gd, Tensor Gb, Tensor bdist, Tensor deri, "
@@ -635,6 +662,7 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("fold_records", fold_records);
     m.impl("render_full_grid", render_full_grid);
     m.impl("fold_records_grid", fold_records_grid);
+    m.impl("fold_refocus_stack", fold_refocus_stack);
     m.impl("local_loss", local_loss);
     m.impl("local_loss_finish", local_loss_finish);
     m.impl("global_loss", global_loss);

@@ -79,6 +79,11 @@ _GROUPS = {
         ('--crop', dict(type=int, default=10)),
         ('--rho_prime', dict(type=float, default=10.39)),
         ('--densify', dict(type=str, default=None, choices=[None, 'pp', 'w'])),
+        # not in the reference: a focal stack per pair (be_hip.workflow eval) - K planes evenly spaced in optical power over the
+        # depth range NEAR FAR (metres; default = the depth range the models are trained on), written to out_path
+        ('--refocus_stack', dict(type=int, default=0)),
+        ('--focus_range', dict(type=float, nargs=2, default=[0.75, 1.18])),
+        ('--out_path', dict(type=str, default='./logs/refocus_stack')),
     ],
 }
 

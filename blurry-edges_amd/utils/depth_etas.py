@@ -51,6 +51,18 @@ class DepthEtas:
             return torch.abs((1 / depth - rho_prime) * self.s + 1) / self.denominator_factor_root
         return ag.Depth2Sigma.apply(depth, self._consts, rho_prime)
 
+    def focus2rho(self, depth):
+        """The optical power rho' that puts `depth` (metres, > 0; a float or a tensor) in focus: the zero of depth2sigma,
+        (1 / depth - rho') * s + 1 = 0  ->  rho' = 1 / depth + 1 / s.  The default rho' = 10.39 focuses at 0.751 m."""
+        if isinstance(depth, torch.Tensor):
+            if not bool((depth > 0).all()):
+                raise ValueError("focus2rho: depths must be > 0 (metres)")
+            return 1 / depth + 1 / self.s
+        depth = float(depth)
+        if not depth > 0:
+            raise ValueError(f"focus2rho: depth must be > 0 (metres), got {depth}")
+        return 1 / depth + 1 / self.s
+
     def _etas2depth_cpu(self, e1, e2):
         """CPU tensors (BASELINE configs[0], "PyTorch-CPU, plumbing"): the same solve as a torch expression, with the reference's
         operation order (utils/depth_etas.py:23-34) so that fp32 results are the reference's bit for bit (golden g5).  The point

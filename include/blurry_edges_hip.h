@@ -168,6 +168,19 @@ int be_fold_records_grid_f32(const be_render_opts* opts_host, const float* recor
                              const int32_t* ys, const int32_t* xs, int densify_w, float* image, float* shpd, float* refoc,
                              float* bndry, float* depth, float* conf, void* stream);
 
+/* Focal stack: K refocused images from ONE record grid.  out [K,3,H,W]; plane k is, bit for bit, the `refoc` map that
+ * be_render_full*_f32(rho_prime = rho_primes[k]) followed by be_fold_records*_f32 gives - the refocus radii are recomputed
+ * from the record's wedge depths and mask-presence flags (sqrt2 * depth2sigma(z, rho'), or sqrt2 * 1e-4 where the flag is
+ * clear; the radii stored in the record are not read), everything else of the fold is shared by the planes of a chunk.
+ * rho_primes [K]: DEVICE fp32.  ys == xs == NULL: the uniform grid (origin = stride * index, as be_fold_records_f32);
+ * both non-NULL: origin tables as be_fold_records_grid_f32 takes them (stride is ignored).  A workgroup accumulates
+ * BE_REFOCUS_STACK_KC planes; be_refocus_stack_chunk() returns that constant. */
+#define BE_REFOCUS_STACK_KC 8
+int be_refocus_stack_chunk(void);
+int be_fold_refocus_stack_f32(const be_render_opts* opts_host, const be_depth_consts* consts_host, const float* records,
+                              int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs,
+                              const float* rho_primes, int K, float* out, void* stream);
+
 /* nn.Unfold(21, stride) in the order blurry_edges_test.py:120-121 consumes it:
  * img [B,C,H,W] -> out [B, Hp*Wp, C, 21, 21], patch (i,j) = rows stride*i.., cols stride*j.., index i*Wp+j. */
 int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream);
