@@ -151,6 +151,9 @@ _SIGNATURES = {
     "be_fold_records_grid_f32": (C.c_int, [C.POINTER(RenderOpts), _P] + [C.c_int] * 4 + [_P, _P, C.c_int] + [_P] * 6 + [_P]),
     "be_refocus_stack_chunk": (C.c_int, []),
     "be_fold_refocus_stack_f32": (C.c_int, [C.POINTER(RenderOpts), C.POINTER(DepthConsts), _P] + [C.c_int] * 5 + [_P, _P, _P, C.c_int, _P, _P]),
+    "be_fold_records_at_f32": (C.c_int, [C.POINTER(RenderOpts), _P] + [C.c_int] * 5 + [_P, _P] + [C.c_int] * 6 + [_P] * 6 + [_P]),
+    "be_fold_refocus_stack_at_f32": (C.c_int, [C.POINTER(RenderOpts), C.POINTER(DepthConsts), _P] + [C.c_int] * 5 + [_P, _P] + [C.c_int] * 5
+                                     + [_P, C.c_int, _P, _P]),
     "be_unfold_patches_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "be_local_features_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "be_global_denorm_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
@@ -1042,6 +1045,73 @@ def fold_refocus_stack(opts, consts, records, rho_primes, H, W, hp=None, wp=None
     check(lib().be_fold_refocus_stack_f32(C.byref(opts), C.byref(consts), dptr(records, "records", (torch.float32,)), hp, wp, H, W,
                                           stride, dptr(ys), dptr(xs), dptr(rho), len(vals), dptr(out), stream_ptr(dev)),
           "be_fold_refocus_stack_f32")
+    return out
+
+
+def _at_grid(who, records, H, W, scale, window, hp, wp, ys, xs):
+    """The host side the two *_at wrappers share, before the library is touched: the lattice (tiling.lattice), ys / xs both or
+    neither, the tables (origin_table, cover=True), the record shape, records on the GPU.  -> (lattice, records, ys, xs, hp, wp)."""
+    from . import tiling
+    lat = tiling.lattice(H, W, scale, window)
+    if (ys is None) != (xs is None):
+        raise ValueError(f"{who}: ys and xs must both be given (origin tables) or both be None (uniform grid)")
+    if not isinstance(records, torch.Tensor) or records.dim() != 2:
+        raise RuntimeError(f"{who}: records must be a [P,{RECORD_FLOATS}] tensor")
+    dev = records.device
+    if ys is not None:
+        ys, xs = origin_table(ys, H, dev, f"{who}(ys)", cover=True), origin_table(xs, W, dev, f"{who}(xs)", cover=True)
+        if (hp is not None and hp != ys.numel()) or (wp is not None and wp != xs.numel()):
+            raise RuntimeError(f"{who}: hp / wp ({hp}, {wp}) do not match the tables ({ys.numel()}, {xs.numel()})")
+        hp, wp = ys.numel(), xs.numel()
+    elif hp is None or wp is None:
+        raise RuntimeError(f"{who}: the uniform grid needs hp and wp")
+    if tuple(records.shape) != (hp * wp, RECORD_FLOATS):
+        raise RuntimeError(f"{who}: records must be [{hp * wp},{RECORD_FLOATS}], got {tuple(records.shape)}")
+    records = records.contiguous()
+    dptr(records, "records", (torch.float32,))
+    return lat, records, ys, xs, hp, wp
+
+
+def fold_records_at(opts, records, H, W, scale=1, window=None, hp=None, wp=None, stride=2, ys=None, xs=None, densify_w=False,
+                    want=FOLD_MAPS):
+    """records [hp*wp,32] -> the maps of fold_records / fold_records_grid sampled on a lattice `scale` times finer than the pixels,
+    over window = (top, left, h, w) of the H x W image (None: all of it): each map [..,Ho,Wo], Ho = (h-1)*scale + 1.  Sample
+    (iy, ix) sits at pixel position (top + iy / scale, left + ix / scale); out[..., ::scale, ::scale] equals the integer-pixel fold
+    over the window bit for bit.  ys / xs (both): origin tables (hp / wp then come from them); neither: the uniform grid."""
+    lat, records, ys, xs, hp, wp = _at_grid("fold_records_at", records, H, W, scale, window, hp, wp, ys, xs)
+    dev, (top, left, h, w), Ho, Wo = records.device, lat["window"], lat["Ho"], lat["Wo"]
+    o = ops()
+    if o is not None:
+        mask = sum(1 << i for i, k in enumerate(FOLD_MAPS) if k in want)
+        r = o.fold_records_at(struct_tensor(opts), records, ys, xs, hp, wp, H, W, stride, scale, top, left, h, w, bool(densify_w), mask)
+        return dict(zip([k for k in FOLD_MAPS if k in want], r))
+    shapes = dict(image=(2, 3, Ho, Wo), shpd=(3, Ho, Wo), refoc=(3, Ho, Wo), bndry=(Ho, Wo), depth=(Ho, Wo), conf=(Ho, Wo))
+    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in FOLD_MAPS if k in want}
+    g = lambda k: dptr(out.get(k))
+    check(lib().be_fold_records_at_f32(C.byref(opts), dptr(records, "records", (torch.float32,)), hp, wp, H, W, stride, dptr(ys), dptr(xs),
+                                       scale, top, left, h, w, int(bool(densify_w)), g("image"), g("shpd"), g("refoc"), g("bndry"),
+                                       g("depth"), g("conf"), stream_ptr(dev)), "be_fold_records_at_f32")
+    return out
+
+
+def fold_refocus_stack_at(opts, consts, records, rho_primes, H, W, scale=1, window=None, hp=None, wp=None, stride=2, ys=None, xs=None):
+    """fold_refocus_stack on the lattice of fold_records_at: [K,3,Ho,Wo]; plane k at [::scale, ::scale] equals fold_refocus_stack's
+    plane over the window bit for bit."""
+    vals = rho_prime_list(rho_primes, "fold_refocus_stack_at(rho_primes)")
+    lat, records, ys, xs, hp, wp = _at_grid("fold_refocus_stack_at", records, H, W, scale, window, hp, wp, ys, xs)
+    dev, (top, left, h, w) = records.device, lat["window"]
+    if isinstance(rho_primes, torch.Tensor) and rho_primes.device == dev and rho_primes.dtype == torch.float32 and rho_primes.is_contiguous():
+        rho = rho_primes
+    else:
+        rho = torch.tensor(vals, dtype=torch.float32, device=dev)
+    o = ops()
+    if o is not None:
+        return o.fold_refocus_stack_at(struct_tensor(opts), struct_tensor(consts), records, rho, ys, xs, hp, wp, H, W, stride, scale, top,
+                                       left, h, w)
+    out = torch.empty(len(vals), 3, lat["Ho"], lat["Wo"], dtype=torch.float32, device=dev)
+    check(lib().be_fold_refocus_stack_at_f32(C.byref(opts), C.byref(consts), dptr(records, "records", (torch.float32,)), hp, wp, H, W,
+                                             stride, dptr(ys), dptr(xs), scale, top, left, h, w, dptr(rho), len(vals), dptr(out),
+                                             stream_ptr(dev)), "be_fold_refocus_stack_at_f32")
     return out
 
 

@@ -235,12 +235,13 @@ class DepthPipeline:
 
     # ---- focal stack from one depth estimate ----------------------------------------------------------------------------
     @torch.no_grad()
-    def refocus_stack(self, maps, rho_primes=None, focus_depths=None):
+    def refocus_stack(self, maps, rho_primes=None, focus_depths=None, scale=1, window=None):
         """maps: what __call__, run_big or run_any returned.  Exactly one of rho_primes (optical powers, dioptres) and
         focus_depths (metres, through DepthEtas.focus2rho) -> [K,3,H,W]: the pair refocused at each of them.  Plane k is what
         maps["refoc"] would be had the pipeline been built with rho_prime = rho_primes[k] - the colours and wedge depths in
         maps["records"] do not depend on rho_prime, so pass B is not run again and one launch folds all K planes
-        (native.fold_refocus_stack)."""
+        (native.fold_refocus_stack).  scale / window other than (1, None): the planes on the lattice of render_at,
+        [K,3,Ho,Wo] (native.fold_refocus_stack_at); their [::scale, ::scale] samples are the pixels of the default call."""
         if (rho_primes is None) == (focus_depths is None):
             raise ValueError("refocus_stack: give exactly one of rho_primes (optical powers) and focus_depths (metres)")
         if not isinstance(maps, dict) or "records" not in maps or "grid" not in maps:
@@ -255,5 +256,41 @@ class DepthPipeline:
                 rho_primes = self.dcal.focus2rho(focus_depths.detach().double().cpu()).tolist()
             else:
                 rho_primes = [self.dcal.focus2rho(z) for z in focus_depths]
-        return native.fold_refocus_stack(self.helper.render_opts(False), self.dcal.consts, rec, rho_primes, g["H"], g["W"],
-                                         hp=g["hp"], wp=g["wp"], stride=g["stride"], ys=g["ys"], xs=g["xs"])
+        if scale == 1 and window is None:
+            return native.fold_refocus_stack(self.helper.render_opts(False), self.dcal.consts, rec, rho_primes, g["H"], g["W"],
+                                             hp=g["hp"], wp=g["wp"], stride=g["stride"], ys=g["ys"], xs=g["xs"])
+        return native.fold_refocus_stack_at(self.helper.render_opts(False), self.dcal.consts, rec, rho_primes, g["H"], g["W"], scale=scale,
+                                            window=window, hp=g["hp"], wp=g["wp"], stride=g["stride"], ys=g["ys"], xs=g["xs"])
+
+    # ---- the folded maps on a finer lattice -----------------------------------------------------------------------------
+    @torch.no_grad()
+    def render_at(self, maps, scale=1, window=None, want=None, depth_thres=None):
+        """maps: what __call__, run_big or run_any returned (maps["records"], maps["grid"] are read) -> the folded maps sampled on a
+        lattice `scale` (an integer k in 1..16) times finer than the pixels, over window = (top, left, h, w) in input pixels (None:
+        the whole image): each map [..,Ho,Wo] with Ho = (h-1) k + 1, Wo = (w-1) k + 1.  The record grid is a continuous description
+        of the scene, so the finer samples are evaluated from the wedges, not interpolated from the pixel maps; out[..., ::k, ::k]
+        equals the pixel map over the window bit for bit.  want: names out of native.FOLD_MAPS (None: all six).  Also returned:
+        lattice = dict(scale, window, Ho, Wo) and - unless densify == 'pp', whose U-Net is not defined off its native resolution -
+        depth_map = where(conf > depth_thres, depth, 0).  depth_thres defaults to self.depth_thres, the threshold of __call__;
+        run_big and run_any use 0.05 whatever densify is, so pass depth_thres=0.05 to continue their depth_map."""
+        if not isinstance(maps, dict) or "records" not in maps or "grid" not in maps:
+            missing = [k for k in ("records", "grid") if not isinstance(maps, dict) or k not in maps]
+            raise ValueError(f"render_at: maps lacks {missing}; pass the dict DepthPipeline.__call__, run_big or run_any returned")
+        rec, g = maps["records"], maps["grid"]
+        lat = tiling.lattice(g["H"], g["W"], scale, window)
+        want = native.FOLD_MAPS if want is None else tuple(want)
+        unknown = [k for k in want if k not in native.FOLD_MAPS]
+        if unknown:
+            raise ValueError(f"render_at: unknown maps {unknown}; choose from {native.FOLD_MAPS}")
+        if not isinstance(rec, torch.Tensor) or not rec.is_cuda:
+            raise ValueError("render_at: maps['records'] is not on the GPU; nothing here computes on the CPU "
+                             "(keep the dict the pipeline returned, or move records - and the ys / xs of grid - back to the device)")
+        need = want if self.densify == "pp" else tuple(k for k in native.FOLD_MAPS if k in want or k in ("depth", "conf"))
+        out = native.fold_records_at(self.helper.render_opts(False), rec, g["H"], g["W"], scale=scale, window=window, hp=g["hp"], wp=g["wp"],
+                                     stride=g["stride"], ys=g["ys"], xs=g["xs"], densify_w=self.densify == "w", want=need)
+        res = {k: out[k] for k in want}
+        if self.densify != "pp":
+            thres = self.depth_thres if depth_thres is None else depth_thres
+            res["depth_map"] = torch.where(out["conf"] > thres, out["depth"], torch.zeros_like(out["depth"]))
+        res["lattice"] = lat
+        return res

@@ -17,6 +17,7 @@ lines is smaller than `s` pixels.
 from __future__ import annotations
 
 R = 21          # patch side (BE_R)
+MAX_SCALE = 16  # BE_RENDER_AT_MAX_SCALE: the finest sampling lattice of render_at
 
 
 def patch_grid(size: int, stride: int = 2, r: int = R) -> list:
@@ -40,6 +41,49 @@ def check_grid(lines, size: int, stride: int, r: int = R) -> None:
     for a, b in zip(lines, lines[1:]):
         if not 0 < b - a <= stride:
             raise ValueError(f"patch grid must be strictly increasing with gaps <= {stride}: {a} -> {b}")
+
+
+def lattice(H: int, W: int, scale: int = 1, window=None) -> dict:
+    """The sampling lattice of DepthPipeline.render_at, checked: `scale` = k, an integer in 1..16; window = (top, left, h, w) in
+    input pixels, inside the H x W image with h, w >= 1 (None: the whole image).  -> dict(scale, window, Ho, Wo) with
+    Ho = (h - 1) k + 1, Wo = (w - 1) k + 1: output sample (iy, ix) sits at Y = top k + iy, X = left k + ix in units of 1/k pixel,
+    the samples with iy % k == 0 are input pixels and the lattice ends on the window's last pixel centre."""
+    if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= MAX_SCALE:
+        raise ValueError(f"lattice: scale must be an integer in [1, {MAX_SCALE}], got {scale!r}")
+    if window is None:
+        window = (0, 0, H, W)
+    try:
+        top, left, h, w = (int(v) for v in window)
+        exact = all(int(v) == v for v in window)
+    except (TypeError, ValueError):
+        raise ValueError(f"lattice: window must be (top, left, h, w), got {window!r}") from None
+    if not exact or top < 0 or left < 0 or h < 1 or w < 1 or top + h > H or left + w > W:
+        raise ValueError(f"lattice: window (top, left, h, w) = {tuple(window)} leaves the {H} x {W} image (or has h, w < 1)")
+    return dict(scale=scale, window=(top, left, h, w), Ho=(h - 1) * scale + 1, Wo=(w - 1) * scale + 1)
+
+
+def lattice_runs(origins, size_out: int, scale: int, first: int = 0, r: int = R) -> list:
+    """Per output sample iy of one axis (Y = first * scale + iy), the grid lines that cover it: [(i_lo, i_hi, [(q, rem)])] with
+    origins[i] * k <= Y <= (origins[i] + r - 1) * k for i_lo <= i <= i_hi (integer arithmetic, a contiguous run; i_hi < i_lo when
+    no line covers the sample) and the patch-local position t = Y - origins[i] * k = q * k + rem of each.  The host statement of
+    what k_fold_records_at computes; with scale 1 it is k_fold_records' run."""
+    origins = list(origins)
+    out = []
+    for iy in range(size_out):
+        Y = first * scale + iy
+        cover = [i for i, o in enumerate(origins) if o * scale <= Y <= (o + r - 1) * scale]
+        if cover and cover != list(range(cover[0], cover[-1] + 1)):
+            raise ValueError("lattice_runs: the covering lines are not contiguous (origins must increase)")
+        lo, hi = (cover[0], cover[-1]) if cover else (0, -1)
+        out.append((lo, hi, [divmod(Y - origins[i] * scale, scale) for i in cover]))
+    return out
+
+
+def uniform_run(Y: int, scale: int, stride: int, n: int, r: int = R):
+    """The closed form of lattice_runs on the uniform grid origins = stride * index, index < n:
+    i_lo = max(0, ceil((Y - (r-1) k) / (s k))), i_hi = min(n - 1, floor(Y / (s k)))."""
+    sk = stride * scale
+    return max(0, -((-(Y - (r - 1) * scale)) // sk)), min(n - 1, Y // sk)
 
 
 def block_schedule(n: int, hp: int = 64, n_margin: int = 10) -> list:

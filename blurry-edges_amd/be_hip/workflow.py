@@ -8,6 +8,7 @@ formats (argument names and defaults = utils/args.py of the reference):
     python -m be_hip.workflow eval [--big]     blurry_edges_test.py:102-176 / blurry_edges_test_big.py (TestDataset -> metrics)
     python -m be_hip.workflow eval --any       the same for image pairs of any size >= 147 x 147 (DepthPipeline.run_any)
     ... eval --refocus_stack K [--focus_range NEAR FAR] [--out_path DIR]   also write every pair's K-plane focal stack
+    ... eval --render_scale K [--render_window T L H W] [--out_path DIR]   also write every pair's maps on a K times finer lattice
 
 Data parallel (BASELINE configs[4]): the two training commands run under torchrun, one process per GPU -
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m be_hip.workflow local_train ...
@@ -305,7 +306,12 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     """-> dict(delta1, delta2, delta3, RMSE, AbsRel, seconds_per_pair), averaged over the test set as the scripts do.
     any_size: pairs of any size >= 147 x 147 through DepthPipeline.run_any (checkpoint names and arguments as big).
     args.refocus_stack = K > 0 (not in the reference): every pair's focal stack over args.focus_range goes to
-    {args.out_path}/refoc_stack_{j:04d}.npy ([K,3,H,W] float32) and the powers to rho_primes.npy, outside the timed region."""
+    {args.out_path}/refoc_stack_{j:04d}.npy ([K,3,H,W] float32) and the powers to rho_primes.npy, outside the timed region.
+    args.render_scale = k > 1 (not in the reference; 1 = off): every pair's maps on the k times finer lattice of
+    DepthPipeline.render_at, over args.render_window (top left h w; default the whole image), go to
+    {args.out_path}/render_x{k}_{j:04d}.npz (shpd, refoc, bndry, depth, conf and - unless --densify pp - depth_map, float32; depth_map
+    with the threshold of the mode: 0.05 under --big / --any), outside the timed region; a focal stack asked for in the same run
+    is written on the same lattice."""
     import data, models, utils
     from .pipeline import DepthPipeline
     dev = _device(args)
@@ -322,6 +328,13 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     pipe = DepthPipeline(local, globl, utils.PostProcessGlobalBase(args, dev), utils.DepthEtas(args, dev),
                          rho_prime=args.rho_prime, densify=args.densify, stride=args.stride, densify_pp_module=pp)
     ds = data.TestDataset(dev, data_path=args.data_path)
+    rscale, rwin = getattr(args, "render_scale", 1), getattr(args, "render_window", None)
+    rwin = None if rwin is None else tuple(rwin)
+    render = rscale != 1 or rwin is not None
+    if render:
+        from . import tiling
+        tiling.lattice(1, 1, rscale, (0, 0, 1, 1))                                  # the scale now; the window against each pair's size
+        os.makedirs(args.out_path, exist_ok=True)
     sweep = None
     if getattr(args, "refocus_stack", 0):
         sweep = focus_sweep(pipe.dcal, args.refocus_stack, *args.focus_range)
@@ -341,7 +354,13 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
         torch.cuda.synchronize()
         secs += time.perf_counter() - t0
         if sweep is not None:
-            np.save(os.path.join(args.out_path, f"refoc_stack_{j:04d}.npy"), pipe.refocus_stack(maps, rho_primes=sweep.tolist()).cpu().numpy())
+            stack = pipe.refocus_stack(maps, rho_primes=sweep.tolist(), scale=rscale, window=rwin)
+            np.save(os.path.join(args.out_path, f"refoc_stack_{j:04d}.npy"), stack.cpu().numpy())
+        if render:
+            fine = pipe.render_at(maps, scale=rscale, window=rwin, want=("shpd", "refoc", "bndry", "depth", "conf"),
+                                  depth_thres=0.05 if (big or any_size) else None)
+            np.savez(os.path.join(args.out_path, f"render_x{rscale}_{j:04d}.npz"),
+                     **{k: v.cpu().numpy() for k, v in fine.items() if k != "lattice"})
         depth = maps["depth_map"][None]
         m = np.array(utils.eval_depth(depth, gt[None].to(depth.dtype), depth, crop=args.crop))
         tot += m

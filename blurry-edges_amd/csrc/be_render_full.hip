@@ -412,6 +412,216 @@ void k_fold_refocus_stack(be_render_opts o, be_depth_consts dc, StackArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the folds on a finer lattice
+// The record grid is a continuous description: wedge_dists, indicators, boundary_value and depth_mask take a real position.
+// The two kernels below are k_fold_records and k_fold_refocus_stack evaluated on a lattice `scale` (k) times finer, over a
+// window of the image: output sample (iy, ix) sits at Y = top * k + iy, X = left * k + ix in units of 1/k pixel.  With
+// Y = yq * k + yr (0 <= yr < k) a grid line of origin oy covers the sample iff oy * k <= Y <= (oy + 20) * k, i.e. iff
+// yq + (yr > 0) - 20 <= oy <= yq: integer arithmetic, a contiguous run of lines, and - the origins being whole pixels - the
+// remainder yr is the same for every covering line, so the one division by k is per thread and axis, not per patch.  The
+// patch-local coordinate is lin[q] (q = yq - oy, READ, not computed) when yr == 0 and lin[q] + (yr / k) * (lin[q+1] - lin[q])
+// otherwise (then q <= 19).  Everything after the coordinate is the body of the integer-pixel kernel, so every k-th sample
+// equals that kernel's pixel bit for bit.
+struct Lattice {
+    int scale;               // k, 1..16
+    int top, left;           // window origin, input pixels
+    int Ho, Wo;              // (h - 1) * k + 1, (w - 1) * k + 1
+};
+
+// the run of grid lines covering a sample at pq + pr / k: staged origins sl[0..FOLD_LINES) (TABLES) or stride * index
+template <bool TABLES>
+__device__ __forceinline__ void lattice_run(const int* sl, int s, int n, int pq, int pr, int& lo, int& hi) {
+    const int first = pq + (pr ? 1 : 0) - (R - 1);              // the smallest origin that still covers the sample
+    if constexpr (TABLES) {
+        lo = 0; while (lo < FOLD_LINES && sl[lo] < first) ++lo;
+        hi = lo - 1; while (hi + 1 < FOLD_LINES && sl[hi + 1] <= pq) ++hi;
+    } else {
+        lo = first > 0 ? (first + s - 1) / s : 0;
+        hi = pq / s; if (hi > n - 1) hi = n - 1;
+    }
+}
+
+// first grid line a 16-sample tile starting at sample P0 (units of 1/k pixel) can be covered by
+__device__ __forceinline__ int lattice_tile_first(int P0, int k) { return P0 / k + (P0 % k ? 1 : 0) - (R - 1); }
+
+__device__ __forceinline__ float lattice_coord(const float* lin, int q, int pr, float frac) {
+#pragma clang fp contract(off)
+    const float l0 = lin[q];
+    if (pr == 0) return l0;                                     // an input pixel: lin[q + 1] is not read (q may be 20)
+    return l0 + frac * (lin[q + 1] - l0);
+}
+
+template <bool TABLES>
+__global__ __launch_bounds__(256)
+void k_fold_records_at(be_render_opts o, FoldArgs a, Lattice l) {
+    __shared__ float lin[R];
+    __shared__ int sy[TABLES ? FOLD_LINES : 1], sx[TABLES ? FOLD_LINES : 1];
+    if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
+    const int k = l.scale;
+    const int Y0 = l.top * k + (int)blockIdx.y * FOLD_TILE, X0 = l.left * k + (int)blockIdx.x * FOLD_TILE;
+    int i0 = 0, j0 = 0;                                         // grid line held by sy[0] / sx[0]
+    if constexpr (TABLES) {
+        // a tile spans at most 16 pixels, so at most FOLD_LINES distinct origins lie in [tile_first, (P0 + 15) / k]
+        i0 = lower_bound(a.ys, a.hp, lattice_tile_first(Y0, k));
+        j0 = lower_bound(a.xs, a.wp, lattice_tile_first(X0, k));
+        const int t = threadIdx.x;
+        if (t < FOLD_LINES) sy[t] = i0 + t < a.hp ? a.ys[i0 + t] : LINE_NONE;
+        else if (t >= 64 && t < 64 + FOLD_LINES) sx[t - 64] = j0 + t - 64 < a.wp ? a.xs[j0 + t - 64] : LINE_NONE;
+    }
+    __syncthreads();
+    const int ix = blockIdx.x * FOLD_TILE + (threadIdx.x & 15);
+    const int iy = blockIdx.y * FOLD_TILE + (threadIdx.x >> 4);
+    if (ix >= l.Wo || iy >= l.Ho) return;
+    const int Y = l.top * k + iy, X = l.left * k + ix;
+    const int yq = Y / k, yr = Y - yq * k, xq = X / k, xr = X - xq * k;
+    const float fy = (float)yr / (float)k, fx = (float)xr / (float)k;
+    const int s = a.stride;
+    int i_lo, j_lo, i_hi, j_hi;
+    lattice_run<TABLES>(sy, s, a.hp, yq, yr, i_lo, i_hi);
+    lattice_run<TABLES>(sx, s, a.wp, xq, xr, j_lo, j_hi);
+    float acc1[3] = {0, 0, 0}, acc2[3] = {0, 0, 0}, accs[3] = {0, 0, 0}, accf[3] = {0, 0, 0};
+    float accb = 0.f, accz = 0.f;
+    int cnt = 0, cntz = 0;
+    const float rs = be::kRoot2 * 1e-4f;
+    for (int i = i_lo; i <= i_hi; ++i) {
+        const float py = lattice_coord(lin, yq - (TABLES ? sy[i] : s * i), yr, fy);
+        for (int j = j_lo; j <= j_hi; ++j) {
+            const float px = lattice_coord(lin, xq - (TABLES ? sx[j] : s * j), xr, fx);
+            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)((i0 + i) * a.wp + (j0 + j)) * REC);
+            float r[REC];
+#pragma unroll
+            for (int q = 0; q < REC / 4; ++q) { const float4 t = rp[q]; r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w; }
+            be::WedgeGeom g;
+            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
+            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
+            g.sg1 = r[12]; g.sg2 = r[13];
+            float d1, d2;
+            be::wedge_dists(g, px, py, o.w, d1, d2);
+            const float* col = r + R_COL;
+            float u0, u1, u2;
+            {
+#pragma clang fp contract(off)
+                if (a.image) {
+                    be::indicators(d1, d2, r[R_RAD1], r[R_RAD1 + 1], u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc1[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                    be::indicators(d1, d2, r[R_RAD2], r[R_RAD2 + 1], u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc2[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                }
+                if (a.shpd) {
+                    be::indicators(d1, d2, rs, rs, u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) accs[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                }
+                if (a.refoc) {
+                    be::indicators(d1, d2, r[R_RADF], r[R_RADF + 1], u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) accf[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                }
+                if (a.bndry) accb += be::boundary_value(d1, d2, o.delta_sq);
+                if (a.depth || a.conf) {
+                    const int m = be::depth_mask(d1, d2, o.delta_sq, a.densify_w != 0);
+                    if (m == 1) { accz += r[R_DEPTH]; ++cntz; }
+                    else if (m == 2) { accz += r[R_DEPTH + 1]; ++cntz; }
+                }
+            }
+            ++cnt;
+        }
+    }
+    const size_t hw = (size_t)l.Ho * l.Wo, at = (size_t)iy * l.Wo + ix;
+    const float n = (float)cnt;                         // the patches visited (0 only where a uniform grid stops short of the edge)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (a.image) { a.image[c * hw + at] = acc1[c] / n; a.image[(3 + c) * hw + at] = acc2[c] / n; }
+        if (a.shpd) a.shpd[c * hw + at] = accs[c] / n;
+        if (a.refoc) a.refoc[c * hw + at] = accf[c] / n;
+    }
+    if (a.bndry) a.bndry[at] = accb / n;
+    if (a.depth) a.depth[at] = accz / (cntz > 0 ? (float)cntz : 1.0f);
+    if (a.conf) a.conf[at] = (float)cntz / n;
+}
+
+template <bool TABLES>
+__global__ __launch_bounds__(256)
+void k_fold_refocus_stack_at(be_render_opts o, be_depth_consts dc, StackArgs a, Lattice l) {
+    __shared__ float lin[R];
+    __shared__ int sy[TABLES ? FOLD_LINES : 1], sx[TABLES ? FOLD_LINES : 1];
+    if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
+    const int sc = l.scale;
+    const int Y0 = l.top * sc + (int)blockIdx.y * FOLD_TILE, X0 = l.left * sc + (int)blockIdx.x * FOLD_TILE;
+    int i0 = 0, j0 = 0;
+    if constexpr (TABLES) {
+        i0 = lower_bound(a.ys, a.hp, lattice_tile_first(Y0, sc));
+        j0 = lower_bound(a.xs, a.wp, lattice_tile_first(X0, sc));
+        const int t = threadIdx.x;
+        if (t < FOLD_LINES) sy[t] = i0 + t < a.hp ? a.ys[i0 + t] : LINE_NONE;
+        else if (t >= 64 && t < 64 + FOLD_LINES) sx[t - 64] = j0 + t - 64 < a.wp ? a.xs[j0 + t - 64] : LINE_NONE;
+    }
+    __syncthreads();
+    const int ix = blockIdx.x * FOLD_TILE + (threadIdx.x & 15);
+    const int iy = blockIdx.y * FOLD_TILE + (threadIdx.x >> 4);
+    if (ix >= l.Wo || iy >= l.Ho) return;
+    const int Y = l.top * sc + iy, X = l.left * sc + ix;
+    const int yq = Y / sc, yr = Y - yq * sc, xq = X / sc, xr = X - xq * sc;
+    const float fy = (float)yr / (float)sc, fx = (float)xr / (float)sc;
+    const int k0 = blockIdx.z * FOLD_KC;
+    const int nk = min(FOLD_KC, a.K - k0);                      // planes of this chunk (uniform over the workgroup)
+    float rho[FOLD_KC];
+#pragma unroll
+    for (int k = 0; k < FOLD_KC; ++k) rho[k] = a.rho_primes[k0 + min(k, nk - 1)];
+    const int s = a.stride;
+    int i_lo, j_lo, i_hi, j_hi;
+    lattice_run<TABLES>(sy, s, a.hp, yq, yr, i_lo, i_hi);
+    lattice_run<TABLES>(sx, s, a.wp, xq, xr, j_lo, j_hi);
+    float acc[FOLD_KC][3];
+#pragma unroll
+    for (int k = 0; k < FOLD_KC; ++k) { acc[k][0] = 0.f; acc[k][1] = 0.f; acc[k][2] = 0.f; }
+    int cnt = 0;
+    for (int i = i_lo; i <= i_hi; ++i) {
+        const float py = lattice_coord(lin, yq - (TABLES ? sy[i] : s * i), yr, fy);
+        for (int j = j_lo; j <= j_hi; ++j) {
+            const float px = lattice_coord(lin, xq - (TABLES ? sx[j] : s * j), xr, fx);
+            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)((i0 + i) * a.wp + (j0 + j)) * REC);
+            float r[REC];
+#pragma unroll
+            for (int q = 0; q < REC / 4; ++q) { const float4 t = rp[q]; r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w; }
+            be::WedgeGeom g;
+            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
+            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
+            g.sg1 = r[12]; g.sg2 = r[13];
+            float d1, d2;
+            be::wedge_dists(g, px, py, o.w, d1, d2);
+            const float* col = r + R_COL;
+            const float z1 = r[R_DEPTH], z2 = r[R_DEPTH + 1];
+            const int flags = (int)r[R_FLAGS];
+            const bool has1 = (flags & 1) != 0, has2 = (flags & 2) != 0;
+#pragma unroll
+            for (int k = 0; k < FOLD_KC; ++k) {
+                if (k < nk) {
+#pragma clang fp contract(off)
+                    const float s1 = has1 ? be::depth2sigma(dc, z1, rho[k]) : 1e-4f;       // as k_render_records writes R_RADF
+                    const float s2 = has2 ? be::depth2sigma(dc, z2, rho[k]) : 1e-4f;
+                    float u0, u1, u2;
+                    be::indicators(d1, d2, be::kRoot2 * s1, be::kRoot2 * s2, u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc[k][c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                }
+            }
+            ++cnt;
+        }
+    }
+    const size_t hw = (size_t)l.Ho * l.Wo, at = (size_t)iy * l.Wo + ix;
+    const float n = (float)cnt;
+#pragma unroll
+    for (int k = 0; k < FOLD_KC; ++k) {
+        if (k < nk) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.out[((size_t)(k0 + k) * 3 + c) * hw + at] = acc[k][c] / n;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ glue
 __global__ void k_unfold(const float* __restrict__ img, float* __restrict__ out, int B, int C, int H, int W, int hp,
                          int wp, int stride) {
@@ -563,6 +773,59 @@ extern "C" int be_fold_refocus_stack_f32(const be_render_opts* o, const be_depth
         hipLaunchKernelGGL(k_fold_refocus_stack<false>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a);
     }
     return be::check_launch("be_fold_refocus_stack_f32");
+}
+
+// the host checks the two *_at entries share: the grid (uniform or tables), the scale and the window -> the lattice
+static int check_lattice(const char* who, int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs, int scale,
+                         int top, int left, int h, int w, Lattice* l) {
+    BE_REQUIRE((ys == nullptr) == (xs == nullptr), "%s: ys and xs must both be given (origin tables) or both be null (uniform grid)", who);
+    BE_REQUIRE(scale >= 1 && scale <= BE_RENDER_AT_MAX_SCALE, "%s: scale must be in [1, %d], got %d", who, BE_RENDER_AT_MAX_SCALE, scale);
+    BE_REQUIRE(HP > 0 && WP > 0 && H >= R && W >= R, "%s: bad sizes", who);
+    BE_REQUIRE((int64_t)HP * WP <= 0x7fffffff && (int64_t)H * scale <= 0x7fffffff && (int64_t)W * scale <= 0x7fffffff,
+               "%s: image too large (HP * WP, H * scale and W * scale must fit 31 bits)", who);
+    BE_REQUIRE(top >= 0 && left >= 0 && h >= 1 && w >= 1 && (int64_t)top + h <= H && (int64_t)left + w <= W,
+               "%s: window (%d, %d, %d, %d) leaves the %d x %d image", who, top, left, h, w, H, W);
+    if (ys) {
+        BE_REQUIRE(HP <= H - R + 1 && WP <= W - R + 1, "%s: HP / WP must be in [1, H-20] / [1, W-20] (origins are distinct pixels)", who);
+    } else {
+        BE_REQUIRE(stride > 0, "%s: bad sizes", who);
+        BE_REQUIRE((int64_t)stride * (HP - 1) + R <= H && (int64_t)stride * (WP - 1) + R <= W, "%s: patch grid exceeds the image", who);
+    }
+    const int64_t Ho = (int64_t)(h - 1) * scale + 1, Wo = (int64_t)(w - 1) * scale + 1;
+    BE_REQUIRE(Ho * Wo <= 0x7fffffff && (Ho + FOLD_TILE - 1) / FOLD_TILE <= 65535,
+               "%s: lattice %lld x %lld too large (Ho * Wo must fit 31 bits, Ho <= 16 * 65535)", who, (long long)Ho, (long long)Wo);
+    *l = Lattice{scale, top, left, (int)Ho, (int)Wo};
+    return BE_OK;
+}
+
+extern "C" int be_fold_records_at_f32(const be_render_opts* o, const float* records, int HP, int WP, int H, int W, int stride,
+                                      const int32_t* ys, const int32_t* xs, int scale, int top, int left, int h, int w,
+                                      int densify_w, float* image, float* shpd, float* refoc, float* bndry, float* depth,
+                                      float* conf, void* stream) {
+    BE_REQUIRE(o && records, "be_fold_records_at_f32: null pointer");
+    BE_REQUIRE(be::aligned16(records), "be_fold_records_at_f32: records must be 16-byte aligned");
+    Lattice l;
+    if (const int rc = check_lattice("be_fold_records_at_f32", HP, WP, H, W, stride, ys, xs, scale, top, left, h, w, &l)) return rc;
+    FoldArgs a{records, HP, WP, H, W, ys ? 0 : stride, densify_w, image, shpd, refoc, bndry, depth, conf, 0, ys, xs};
+    const dim3 grid((l.Wo + FOLD_TILE - 1) / FOLD_TILE, (l.Ho + FOLD_TILE - 1) / FOLD_TILE);
+    if (ys) hipLaunchKernelGGL(k_fold_records_at<true>, grid, dim3(256), 0, be::as_stream(stream), *o, a, l);
+    else hipLaunchKernelGGL(k_fold_records_at<false>, grid, dim3(256), 0, be::as_stream(stream), *o, a, l);
+    return be::check_launch("be_fold_records_at_f32");
+}
+
+extern "C" int be_fold_refocus_stack_at_f32(const be_render_opts* o, const be_depth_consts* dc, const float* records, int HP, int WP,
+                                            int H, int W, int stride, const int32_t* ys, const int32_t* xs, int scale, int top,
+                                            int left, int h, int w, const float* rho_primes, int K, float* out, void* stream) {
+    BE_REQUIRE(o && dc && records && rho_primes && out, "be_fold_refocus_stack_at_f32: null pointer");
+    BE_REQUIRE(be::aligned16(records), "be_fold_refocus_stack_at_f32: records must be 16-byte aligned");
+    BE_REQUIRE(K >= 1 && (K + FOLD_KC - 1) / FOLD_KC <= 65535, "be_fold_refocus_stack_at_f32: K must be in [1, 65535 * BE_REFOCUS_STACK_KC]");
+    Lattice l;
+    if (const int rc = check_lattice("be_fold_refocus_stack_at_f32", HP, WP, H, W, stride, ys, xs, scale, top, left, h, w, &l)) return rc;
+    StackArgs a{records, rho_primes, out, HP, WP, H, W, ys ? 0 : stride, K, ys, xs};
+    const dim3 grid((l.Wo + FOLD_TILE - 1) / FOLD_TILE, (l.Ho + FOLD_TILE - 1) / FOLD_TILE, (K + FOLD_KC - 1) / FOLD_KC);
+    if (ys) hipLaunchKernelGGL(k_fold_refocus_stack_at<true>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a, l);
+    else hipLaunchKernelGGL(k_fold_refocus_stack_at<false>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a, l);
+    return be::check_launch("be_fold_refocus_stack_at_f32");
 }
 
 extern "C" int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream) {

@@ -491,6 +491,65 @@ Tensor fold_refocus_stack(const Tensor& opts, const Tensor& consts, const Tensor
     return out;
 }
 
+// the folds on a lattice `scale` times finer over the window (top, left, h, w): ys / xs both given = origin tables, both absent =
+// the uniform grid of `stride`; maps [..,Ho,Wo] named by `want` as fold_records
+std::vector<Tensor> fold_records_at(const Tensor& opts, const Tensor& records, const c10::optional<Tensor>& ys, const c10::optional<Tensor>& xs,
+                                    int64_t hp, int64_t wp, int64_t H, int64_t W, int64_t stride, int64_t scale, int64_t top, int64_t left,
+                                    int64_t h, int64_t w, bool densify_w, int64_t want) {
+    TORCH_CHECK(ys.has_value() == xs.has_value(), "fold_records_at: ys and xs must both be given (origin tables) or both be None");
+    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS, "fold_records_at: records [hp*wp,32]");
+    TORCH_CHECK(scale >= 1 && scale <= BE_RENDER_AT_MAX_SCALE && h >= 1 && w >= 1 && h <= H && w <= W, "fold_records_at: bad scale or window");
+    const int32_t *py = nullptr, *px = nullptr;
+    if (ys.has_value()) {
+        py = origin_table(*ys, "fold_records_at(ys)");
+        px = origin_table(*xs, "fold_records_at(xs)");
+        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, "fold_records_at: ys [hp], xs [wp]");
+    }
+    fp(records, "records");
+    const int64_t Ho = (h - 1) * scale + 1, Wo = (w - 1) * scale + 1;
+    auto o = records.options();
+    Tensor t[6];
+    if (want & 1) t[0] = at::empty({2, 3, Ho, Wo}, o);
+    if (want & 2) t[1] = at::empty({3, Ho, Wo}, o);
+    if (want & 4) t[2] = at::empty({3, Ho, Wo}, o);
+    if (want & 8) t[3] = at::empty({Ho, Wo}, o);
+    if (want & 16) t[4] = at::empty({Ho, Wo}, o);
+    if (want & 32) t[5] = at::empty({Ho, Wo}, o);
+    auto f = [&](int i) { return t[i].defined() ? t[i].data_ptr<float>() : nullptr; };
+    check(be_fold_records_at_f32(host_struct<be_render_opts>(opts, "fold_records_at(opts)"), records.data_ptr<float>(), (int)hp, (int)wp, (int)H,
+                                 (int)W, (int)stride, py, px, (int)scale, (int)top, (int)left, (int)h, (int)w, densify_w ? 1 : 0, f(0), f(1),
+                                 f(2), f(3), f(4), f(5), stream_of(records)), "be_fold_records_at_f32");
+    std::vector<Tensor> r;
+    for (int i = 0; i < 6; ++i) if (t[i].defined()) r.push_back(t[i]);
+    return r;
+}
+
+Tensor fold_refocus_stack_at(const Tensor& opts, const Tensor& consts, const Tensor& records, const Tensor& rho_primes,
+                             const c10::optional<Tensor>& ys, const c10::optional<Tensor>& xs, int64_t hp, int64_t wp, int64_t H, int64_t W,
+                             int64_t stride, int64_t scale, int64_t top, int64_t left, int64_t h, int64_t w) {
+    TORCH_CHECK(ys.has_value() == xs.has_value(), "fold_refocus_stack_at: ys and xs must both be given (origin tables) or both be None");
+    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS,
+                "fold_refocus_stack_at: records [hp*wp,32]");
+    TORCH_CHECK(rho_primes.dim() == 1 && rho_primes.numel() > 0, "fold_refocus_stack_at: rho_primes [K], K >= 1");
+    TORCH_CHECK(rho_primes.device() == records.device(), "fold_refocus_stack_at: rho_primes and records on one device");
+    TORCH_CHECK(scale >= 1 && scale <= BE_RENDER_AT_MAX_SCALE && h >= 1 && w >= 1 && h <= H && w <= W, "fold_refocus_stack_at: bad scale or window");
+    const int32_t *py = nullptr, *px = nullptr;
+    if (ys.has_value()) {
+        py = origin_table(*ys, "fold_refocus_stack_at(ys)");
+        px = origin_table(*xs, "fold_refocus_stack_at(xs)");
+        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, "fold_refocus_stack_at: ys [hp], xs [wp]");
+    }
+    const int64_t K = rho_primes.numel();
+    fp(records, "records");
+    Tensor out = at::empty({K, 3, (h - 1) * scale + 1, (w - 1) * scale + 1}, records.options());
+    check(be_fold_refocus_stack_at_f32(host_struct<be_render_opts>(opts, "fold_refocus_stack_at(opts)"),
+                                       host_struct<be_depth_consts>(consts, "fold_refocus_stack_at(consts)"), records.data_ptr<float>(), (int)hp,
+                                       (int)wp, (int)H, (int)W, (int)stride, py, px, (int)scale, (int)top, (int)left, (int)h, (int)w,
+                                       fp(rho_primes, "rho_primes"), (int)K, out.data_ptr<float>(), stream_of(records)),
+          "be_fold_refocus_stack_at_f32");
+    return out;
+}
+
 // LocalLoss forward + analytic backward in one launch -> (partial [B,3], grad_est [B,10] or an empty tensor)
 std::tuple<Tensor, Tensor> local_loss(const Tensor& opts, const Tensor& est, const Tensor& img_fit, const Tensor& gt, const Tensor& bdist,
                                       const Tensor& deri, double beta_b, double beta_s, bool want_grad) {
@@ -610,6 +669,8 @@ TORCH_LIBRARY(be, m) {
     m.def("render_full_grid(Tensor opts, Tensor consts, float rho_prime, bool densify_w, Tensor params12, Tensor img, Tensor ys, Tensor xs) -> Tensor");
     m.def("fold_records_grid(Tensor opts, Tensor records, Tensor ys, Tensor xs, int H, int W, bool densify_w, int want) -> Tensor[]");
     m.def("fold_refocus_stack(Tensor opts, Tensor consts, Tensor records, Tensor rho_primes, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride) -> Tensor");
+    m.def("fold_records_at(Tensor opts, Tensor records, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, int scale, int top, int left, int h, int w, bool densify_w, int want) -> Tensor[]");
+    m.def("fold_refocus_stack_at(Tensor opts, Tensor consts, Tensor records, Tensor rho_primes, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, int scale, int top, int left, int h, int w) -> Tensor");
     m.def("local_loss(Tensor opts, Tensor est, Tensor img_fit, Tensor gt, Tensor bdist, Tensor deri, float beta_b, float beta_s, bool want_grad) -> (Tensor, Tensor)");
     m.def("local_loss_finish(Tensor partial, float beta_b, float beta_s) -> Tensor");
     m.def("global_loss(Tensor opts, Tensor consts, Tensor est, Tensor img_fit, Tensor img_gt, Tensor G, Tensor Gd, Tensor Gb, Tensor bdist, Tensor deri, "
@@ -663,6 +724,8 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("render_full_grid", render_full_grid);
     m.impl("fold_records_grid", fold_records_grid);
     m.impl("fold_refocus_stack", fold_refocus_stack);
+    m.impl("fold_records_at", fold_records_at);
+    m.impl("fold_refocus_stack_at", fold_refocus_stack_at);
     m.impl("local_loss", local_loss);
     m.impl("local_loss_finish", local_loss_finish);
     m.impl("global_loss", global_loss);

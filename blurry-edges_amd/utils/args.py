@@ -84,6 +84,10 @@ _GROUPS = {
         ('--refocus_stack', dict(type=int, default=0)),
         ('--focus_range', dict(type=float, nargs=2, default=[0.75, 1.18])),
         ('--out_path', dict(type=str, default='./logs/refocus_stack')),
+        # not in the reference: every pair's folded maps on a lattice K times finer than the pixels (DepthPipeline.render_at), over
+        # the whole image or the window TOP LEFT H W (input pixels), written to out_path; 1 = off
+        ('--render_scale', dict(type=int, default=1)),
+        ('--render_window', dict(type=int, nargs=4, default=None)),
     ],
 }
 

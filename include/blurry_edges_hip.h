@@ -181,6 +181,25 @@ int be_fold_refocus_stack_f32(const be_render_opts* opts_host, const be_depth_co
                               int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs,
                               const float* rho_primes, int K, float* out, void* stream);
 
+/* The folds on a lattice `scale` (k, 1..BE_RENDER_AT_MAX_SCALE) times finer than the pixels, over the window (top, left, h, w)
+ * of the H x W image (input pixels; inside the image, h, w >= 1).  The maps are Ho x Wo with Ho = (h-1)*k + 1,
+ * Wo = (w-1)*k + 1; output sample (iy, ix) sits at pixel position ((top*k + iy) / k, (left*k + ix) / k), so the lattice ends
+ * on the window's last pixel centre and nothing is extrapolated.  be_fold_records_at_f32 restates be_fold_records_f32 /
+ * be_fold_records_grid_f32 (`local2global_color / _bndry / _depth` utils/postprocessing_loss.py:151-173, with the wedge
+ * functions of utils/postprocessing_loss.py evaluated at a real-valued patch coordinate): a patch of origin oy covers the
+ * sample Y = top*k + iy iff oy*k <= Y <= (oy+20)*k (integers), its coordinate is lin[q] for t = Y - oy*k = q*k + r with r == 0
+ * and lin[q] + ((float)r / (float)k) * (lin[q+1] - lin[q]) in fp32 otherwise, and everything after the coordinate is that
+ * entry's fold - so the samples with iy % k == 0 and ix % k == 0 equal its pixels bit for bit, and scale 1 over the whole
+ * image equals it entirely.  be_fold_refocus_stack_at_f32 restates be_fold_refocus_stack_f32 (out [K,3,Ho,Wo]) the same way.
+ * ys == xs == NULL: the uniform grid of `stride`; both non-NULL: origin tables (stride ignored).  Every map may be NULL. */
+#define BE_RENDER_AT_MAX_SCALE 16
+int be_fold_records_at_f32(const be_render_opts* opts_host, const float* records, int HP, int WP, int H, int W, int stride,
+                           const int32_t* ys, const int32_t* xs, int scale, int top, int left, int h, int w, int densify_w,
+                           float* image, float* shpd, float* refoc, float* bndry, float* depth, float* conf, void* stream);
+int be_fold_refocus_stack_at_f32(const be_render_opts* opts_host, const be_depth_consts* consts_host, const float* records,
+                                 int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs, int scale,
+                                 int top, int left, int h, int w, const float* rho_primes, int K, float* out, void* stream);
+
 /* nn.Unfold(21, stride) in the order blurry_edges_test.py:120-121 consumes it:
  * img [B,C,H,W] -> out [B, Hp*Wp, C, 21, 21], patch (i,j) = rows stride*i.., cols stride*j.., index i*Wp+j. */
 int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream);
