@@ -154,6 +154,9 @@ _SIGNATURES = {
     "be_fold_records_at_f32": (C.c_int, [C.POINTER(RenderOpts), _P] + [C.c_int] * 5 + [_P, _P] + [C.c_int] * 6 + [_P] * 6 + [_P]),
     "be_fold_refocus_stack_at_f32": (C.c_int, [C.POINTER(RenderOpts), C.POINTER(DepthConsts), _P] + [C.c_int] * 5 + [_P, _P] + [C.c_int] * 5
                                      + [_P, C.c_int, _P, _P]),
+    "be_fold_records_points_f32": (C.c_int, [C.POINTER(RenderOpts), _P] + [C.c_int] * 5 + [_P, _P, _P, C.c_int64, C.c_int] + [_P] * 6 + [_P]),
+    "be_fold_refocus_stack_points_f32": (C.c_int, [C.POINTER(RenderOpts), C.POINTER(DepthConsts), _P] + [C.c_int] * 5
+                                         + [_P, _P, _P, C.c_int64, _P, C.c_int, _P, _P]),
     "be_unfold_patches_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "be_local_features_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "be_global_denorm_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
@@ -1048,11 +1051,9 @@ def fold_refocus_stack(opts, consts, records, rho_primes, H, W, hp=None, wp=None
     return out
 
 
-def _at_grid(who, records, H, W, scale, window, hp, wp, ys, xs):
-    """The host side the two *_at wrappers share, before the library is touched: the lattice (tiling.lattice), ys / xs both or
-    neither, the tables (origin_table, cover=True), the record shape, records on the GPU.  -> (lattice, records, ys, xs, hp, wp)."""
-    from . import tiling
-    lat = tiling.lattice(H, W, scale, window)
+def _record_grid(who, records, H, W, hp, wp, ys, xs):
+    """The host side the *_at and *_points wrappers share, before the library is touched: ys / xs both or neither, the tables
+    (origin_table, cover=True), the record shape, records on the GPU.  -> (records, ys, xs, hp, wp)."""
     if (ys is None) != (xs is None):
         raise ValueError(f"{who}: ys and xs must both be given (origin tables) or both be None (uniform grid)")
     if not isinstance(records, torch.Tensor) or records.dim() != 2:
@@ -1069,7 +1070,14 @@ def _at_grid(who, records, H, W, scale, window, hp, wp, ys, xs):
         raise RuntimeError(f"{who}: records must be [{hp * wp},{RECORD_FLOATS}], got {tuple(records.shape)}")
     records = records.contiguous()
     dptr(records, "records", (torch.float32,))
-    return lat, records, ys, xs, hp, wp
+    return records, ys, xs, hp, wp
+
+
+def _at_grid(who, records, H, W, scale, window, hp, wp, ys, xs):
+    """The lattice (tiling.lattice), then _record_grid.  -> (lattice, records, ys, xs, hp, wp)."""
+    from . import tiling
+    lat = tiling.lattice(H, W, scale, window)
+    return (lat,) + _record_grid(who, records, H, W, hp, wp, ys, xs)
 
 
 def fold_records_at(opts, records, H, W, scale=1, window=None, hp=None, wp=None, stride=2, ys=None, xs=None, densify_w=False,
@@ -1113,6 +1121,64 @@ def fold_refocus_stack_at(opts, consts, records, rho_primes, H, W, scale=1, wind
                                              stride, dptr(ys), dptr(xs), scale, top, left, h, w, dptr(rho), len(vals), dptr(out),
                                              stream_ptr(dev)), "be_fold_refocus_stack_at_f32")
     return out
+
+
+def _point_list(who, points):
+    """points [...,2] float32 (y, x) -> (the contiguous [N,2] view the kernels read, the leading shape).  Checked before the library."""
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32:
+        raise ValueError(f"{who}: points must be a float32 tensor [...,2] of (y, x) positions, got "
+                         f"{getattr(points, 'dtype', type(points).__name__)}")
+    if points.dim() < 1 or points.shape[-1] != 2 or points.numel() == 0:
+        raise ValueError(f"{who}: points must be [...,2] with at least one point, got {tuple(points.shape)}")
+    return points.reshape(-1, 2).contiguous(), tuple(points.shape[:-1])
+
+
+def fold_records_points(opts, records, H, W, points, hp=None, wp=None, stride=2, ys=None, xs=None, densify_w=False, want=FOLD_MAPS):
+    """records [hp*wp,32] -> the maps of fold_records / fold_records_grid evaluated at points [...,2]: float32 (y, x) positions on the
+    records' device, in input-pixel coordinates (pixel centres at the integers, the domain 0 <= y <= H-1, 0 <= x <= W-1 closed).
+    Each map keeps the points' leading shape: image [2,3,*lead], shpd / refoc [3,*lead], bndry / depth / conf [*lead].  A point on a
+    pixel centre equals the integer-pixel fold bit for bit; a point outside the domain (NaN included) gives 0 in every map.
+    ys / xs (both): origin tables (hp / wp then come from them); neither: the uniform grid."""
+    pts, lead = _point_list("fold_records_points", points)
+    records, ys, xs, hp, wp = _record_grid("fold_records_points", records, H, W, hp, wp, ys, xs)
+    dev, N = records.device, pts.shape[0]
+    dptr(pts, "points", (torch.float32,))
+    shapes = dict(image=(2, 3) + lead, shpd=(3,) + lead, refoc=(3,) + lead, bndry=lead, depth=lead, conf=lead)
+    o = ops()
+    if o is not None:
+        mask = sum(1 << i for i, k in enumerate(FOLD_MAPS) if k in want)
+        r = o.fold_records_points(struct_tensor(opts), records, ys, xs, hp, wp, H, W, stride, pts, bool(densify_w), mask)
+        return {k: v.view(shapes[k]) for k, v in zip([k for k in FOLD_MAPS if k in want], r)}
+    flat = dict(image=(6, N), shpd=(3, N), refoc=(3, N), bndry=(N,), depth=(N,), conf=(N,))
+    out = {k: torch.empty(flat[k], dtype=torch.float32, device=dev) for k in FOLD_MAPS if k in want}
+    g = lambda k: dptr(out.get(k))
+    check(lib().be_fold_records_points_f32(C.byref(opts), dptr(records, "records", (torch.float32,)), hp, wp, H, W, stride, dptr(ys), dptr(xs),
+                                           dptr(pts), N, int(bool(densify_w)), g("image"), g("shpd"), g("refoc"), g("bndry"), g("depth"),
+                                           g("conf"), stream_ptr(dev)), "be_fold_records_points_f32")
+    return {k: v.view(shapes[k]) for k, v in out.items()}
+
+
+def fold_refocus_stack_points(opts, consts, records, rho_primes, H, W, points, hp=None, wp=None, stride=2, ys=None, xs=None):
+    """fold_refocus_stack at the points of fold_records_points: [K,3,*lead]; plane k at a pixel centre equals fold_refocus_stack's
+    pixel bit for bit."""
+    vals = rho_prime_list(rho_primes, "fold_refocus_stack_points(rho_primes)")
+    pts, lead = _point_list("fold_refocus_stack_points", points)
+    records, ys, xs, hp, wp = _record_grid("fold_refocus_stack_points", records, H, W, hp, wp, ys, xs)
+    dev, N = records.device, pts.shape[0]
+    dptr(pts, "points", (torch.float32,))
+    if isinstance(rho_primes, torch.Tensor) and rho_primes.device == dev and rho_primes.dtype == torch.float32 and rho_primes.is_contiguous():
+        rho = rho_primes
+    else:
+        rho = torch.tensor(vals, dtype=torch.float32, device=dev)
+    o = ops()
+    if o is not None:
+        out = o.fold_refocus_stack_points(struct_tensor(opts), struct_tensor(consts), records, rho, ys, xs, hp, wp, H, W, stride, pts)
+    else:
+        out = torch.empty(len(vals), 3, N, dtype=torch.float32, device=dev)
+        check(lib().be_fold_refocus_stack_points_f32(C.byref(opts), C.byref(consts), dptr(records, "records", (torch.float32,)), hp, wp, H, W,
+                                                     stride, dptr(ys), dptr(xs), dptr(pts), N, dptr(rho), len(vals), dptr(out),
+                                                     stream_ptr(dev)), "be_fold_refocus_stack_points_f32")
+    return out.view((len(vals), 3) + lead)
 
 
 def unfold_patches(img: torch.Tensor, stride: int = 2) -> torch.Tensor:

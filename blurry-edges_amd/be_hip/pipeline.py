@@ -235,15 +235,19 @@ class DepthPipeline:
 
     # ---- focal stack from one depth estimate ----------------------------------------------------------------------------
     @torch.no_grad()
-    def refocus_stack(self, maps, rho_primes=None, focus_depths=None, scale=1, window=None):
+    def refocus_stack(self, maps, rho_primes=None, focus_depths=None, scale=1, window=None, points=None):
         """maps: what __call__, run_big or run_any returned.  Exactly one of rho_primes (optical powers, dioptres) and
         focus_depths (metres, through DepthEtas.focus2rho) -> [K,3,H,W]: the pair refocused at each of them.  Plane k is what
         maps["refoc"] would be had the pipeline been built with rho_prime = rho_primes[k] - the colours and wedge depths in
         maps["records"] do not depend on rho_prime, so pass B is not run again and one launch folds all K planes
         (native.fold_refocus_stack).  scale / window other than (1, None): the planes on the lattice of render_at,
-        [K,3,Ho,Wo] (native.fold_refocus_stack_at); their [::scale, ::scale] samples are the pixels of the default call."""
+        [K,3,Ho,Wo] (native.fold_refocus_stack_at); their [::scale, ::scale] samples are the pixels of the default call.
+        points [...,2] (instead of scale / window): the planes at those (y, x) positions, the positions of sample_at (float32),
+        [K,3,*lead] (native.fold_refocus_stack_points); a point outside the image gives 0 in every plane."""
         if (rho_primes is None) == (focus_depths is None):
             raise ValueError("refocus_stack: give exactly one of rho_primes (optical powers) and focus_depths (metres)")
+        if points is not None and (scale != 1 or window is not None):
+            raise ValueError("refocus_stack: points replaces the lattice; pass it without scale / window")
         if not isinstance(maps, dict) or "records" not in maps or "grid" not in maps:
             missing = [k for k in ("records", "grid") if not isinstance(maps, dict) or k not in maps]
             raise ValueError(f"refocus_stack: maps lacks {missing}; pass the dict DepthPipeline.__call__, run_big or run_any returned")
@@ -256,6 +260,10 @@ class DepthPipeline:
                 rho_primes = self.dcal.focus2rho(focus_depths.detach().double().cpu()).tolist()
             else:
                 rho_primes = [self.dcal.focus2rho(z) for z in focus_depths]
+        if points is not None:
+            return native.fold_refocus_stack_points(self.helper.render_opts(False), self.dcal.consts, rec, rho_primes, g["H"], g["W"],
+                                                    _points_on(points, rec.device, "refocus_stack"), hp=g["hp"], wp=g["wp"],
+                                                    stride=g["stride"], ys=g["ys"], xs=g["xs"])
         if scale == 1 and window is None:
             return native.fold_refocus_stack(self.helper.render_opts(False), self.dcal.consts, rec, rho_primes, g["H"], g["W"],
                                              hp=g["hp"], wp=g["wp"], stride=g["stride"], ys=g["ys"], xs=g["xs"])
@@ -294,3 +302,63 @@ class DepthPipeline:
             res["depth_map"] = torch.where(out["conf"] > thres, out["depth"], torch.zeros_like(out["depth"]))
         res["lattice"] = lat
         return res
+
+    # ---- the folded maps at arbitrary positions -------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample_at(self, maps, points, want=None, depth_thres=None):
+        """maps: what __call__, run_big or run_any returned (maps["records"], maps["grid"] are read); points [...,2]: (y, x)
+        positions in input-pixel coordinates, pixel centres at the integers, the coordinate top + iy / k of render_at -> the
+        folded maps at those positions, evaluated from the wedges, not interpolated: image [2,3,*lead], shpd / refoc [3,*lead],
+        bndry / depth / conf [*lead].  Positions are float32: a tensor, or anything torch.as_tensor takes, of another dtype or on
+        another device is converted.  The domain is closed, 0 <= y <= H-1 and 0 <= x <= W-1; valid [*lead] (bool, computed on the
+        device, no sync) says which points lie in it, the others (NaN included) have 0 in every map.  A point on a pixel centre
+        equals the pixel map bit for bit, a point of render_at's lattice at scale 2, 4, 8 or 16 equals that sample, and every
+        point is evaluated on its own.  want, depth_thres and depth_map (absent under densify == 'pp'): as render_at."""
+        if not isinstance(maps, dict) or "records" not in maps or "grid" not in maps:
+            missing = [k for k in ("records", "grid") if not isinstance(maps, dict) or k not in maps]
+            raise ValueError(f"sample_at: maps lacks {missing}; pass the dict DepthPipeline.__call__, run_big or run_any returned")
+        rec, g = maps["records"], maps["grid"]
+        points = _points_on(points, None, "sample_at")
+        want = native.FOLD_MAPS if want is None else tuple(want)
+        unknown = [k for k in want if k not in native.FOLD_MAPS]
+        if unknown:
+            raise ValueError(f"sample_at: unknown maps {unknown}; choose from {native.FOLD_MAPS}")
+        if not isinstance(rec, torch.Tensor) or not rec.is_cuda:
+            raise ValueError("sample_at: maps['records'] is not on the GPU; nothing here computes on the CPU "
+                             "(keep the dict the pipeline returned, or move records - and the ys / xs of grid - back to the device)")
+        points = points.to(rec.device)
+        need = want if self.densify == "pp" else tuple(k for k in native.FOLD_MAPS if k in want or k in ("depth", "conf"))
+        out = native.fold_records_points(self.helper.render_opts(False), rec, g["H"], g["W"], points, hp=g["hp"], wp=g["wp"],
+                                         stride=g["stride"], ys=g["ys"], xs=g["xs"], densify_w=self.densify == "w", want=need)
+        res = {k: out[k] for k in want}
+        y, x = points[..., 0], points[..., 1]
+        res["valid"] = (y >= 0) & (y <= g["H"] - 1) & (x >= 0) & (x <= g["W"] - 1)      # the kernel's predicate, in float32
+        if self.densify != "pp":
+            thres = self.depth_thres if depth_thres is None else depth_thres
+            res["depth_map"] = torch.where(out["conf"] > thres, out["depth"], torch.zeros_like(out["depth"]))
+        return res
+
+    @torch.no_grad()
+    def render_resized(self, maps, size, window=None, want=None, depth_thres=None):
+        """The maps of sample_at on the align-corners grid of size = (Ho, Wo) samples over window = (top, left, h, w) in input
+        pixels (None: the whole image), tiling.resize_points: each map [..,Ho,Wo], the first and last samples on the window's
+        first and last pixel centres.  Any ratio, up or down; (k (h-1) + 1, k (w-1) + 1) with k = 2, 4, 8, 16 is
+        render_at(scale=k) bit for bit.  Also returned: lattice = dict(size, window); valid is all True."""
+        if not isinstance(maps, dict) or "grid" not in maps:
+            raise ValueError("render_resized: maps lacks ['grid']; pass the dict DepthPipeline.__call__, run_big or run_any returned")
+        g = maps["grid"]
+        pts = tiling.resize_points(g["H"], g["W"], size, window)
+        res = self.sample_at(maps, torch.from_numpy(pts), want=want, depth_thres=depth_thres)
+        res["lattice"] = dict(size=(pts.shape[0], pts.shape[1]), window=tiling.lattice(g["H"], g["W"], 1, window)["window"])
+        return res
+
+
+def _points_on(points, device, who):
+    """points: a tensor or array-like [...,2] of (y, x) -> float32, on `device` when one is given."""
+    try:
+        points = torch.as_tensor(points)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{who}: points must be a tensor or array-like [...,2] of (y, x) positions") from None
+    if points.dim() < 1 or points.shape[-1] != 2 or points.numel() == 0 or points.is_complex():
+        raise ValueError(f"{who}: points must be [...,2] (y, x) with at least one point, got shape {tuple(points.shape)}")
+    return points.detach().to(device=device, dtype=torch.float32)

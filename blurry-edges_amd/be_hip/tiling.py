@@ -86,6 +86,52 @@ def uniform_run(Y: int, scale: int, stride: int, n: int, r: int = R):
     return max(0, -((-(Y - (r - 1) * scale)) // sk)), min(n - 1, Y // sk)
 
 
+def resize_points(H: int, W: int, size, window=None):
+    """The align-corners sampling grid of DepthPipeline.render_resized: size = (Ho, Wo) output samples over window = (top, left, h, w)
+    of the H x W image (None: all of it) -> float32 numpy [Ho,Wo,2] of (y, x) positions.  Sample iy sits at
+    top + (iy * (h-1)) / (Ho-1) - an integer product, one float64 division, then the cast to float32 - and at top when Ho == 1, so
+    the first and last samples are the window's first and last pixel centres.  With Ho - 1 = k (h - 1), k in {2, 4, 8, 16}, the
+    positions are exactly top + iy / k: the lattice of render_at."""
+    import numpy as np
+    top, left, h, w = lattice(H, W, 1, window)["window"]
+    try:
+        Ho, Wo = size
+        ok = all(not isinstance(v, bool) and int(v) == v and v >= 1 for v in (Ho, Wo))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"resize_points: size must be (Ho, Wo), integers >= 1, got {size!r}")
+    Ho, Wo = int(Ho), int(Wo)
+
+    def axis(first, n, n_out):
+        if n_out == 1:
+            return np.full(1, first, np.float32)
+        return (first + (np.arange(n_out, dtype=np.int64) * (n - 1)) / np.float64(n_out - 1)).astype(np.float32)
+    pts = np.empty((Ho, Wo, 2), np.float32)
+    pts[..., 0] = axis(top, h, Ho)[:, None]
+    pts[..., 1] = axis(left, w, Wo)[None, :]
+    return pts
+
+
+def point_run(origins, y: float, r: int = R):
+    """The grid lines that cover the real-valued position y on one axis: (i_lo, i_hi, q, f) with yq = floor(y), f = y - yq and
+    yq + (f > 0) - (r-1) <= origins[i] <= yq for i_lo <= i <= i_hi (a contiguous run; i_hi < i_lo when no line covers y) and
+    q = [yq - origins[i]], the index into the patch's coordinate table - at most r-1, and at most r-2 when f > 0.  The host
+    statement of what k_fold_records_points computes; lattice_runs is this rule at y = Y / k."""
+    import math
+    origins = list(origins)
+    yq = math.floor(y)
+    f = y - yq
+    first = yq + (1 if f > 0 else 0) - (r - 1)
+    lo = 0
+    while lo < len(origins) and origins[lo] < first:
+        lo += 1
+    hi = lo - 1
+    while hi + 1 < len(origins) and origins[hi + 1] <= yq:
+        hi += 1
+    return lo, hi, [yq - origins[i] for i in range(lo, hi + 1)], f
+
+
 def block_schedule(n: int, hp: int = 64, n_margin: int = 10) -> list:
     """Blocks along one axis of a grid of n lines -> [(start, ks, ke)]: the block holds grid lines start .. start + hp - 1 and
     KEEPS its local lines ks .. ke - 1 (global start + ks .. start + ke - 1).  Starts 0, step, 2 step, .. while start + hp < n,

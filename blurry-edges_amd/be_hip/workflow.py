@@ -9,6 +9,8 @@ formats (argument names and defaults = utils/args.py of the reference):
     python -m be_hip.workflow eval --any       the same for image pairs of any size >= 147 x 147 (DepthPipeline.run_any)
     ... eval --refocus_stack K [--focus_range NEAR FAR] [--out_path DIR]   also write every pair's K-plane focal stack
     ... eval --render_scale K [--render_window T L H W] [--out_path DIR]   also write every pair's maps on a K times finer lattice
+    ... eval --render_size HO WO [--out_path DIR]          also write every pair's maps resampled to HO x WO samples
+    ... eval --sample_points FILE.npy [--out_path DIR]     also write every pair's maps at the [N,2] (y, x) positions of FILE
 
 Data parallel (BASELINE configs[4]): the two training commands run under torchrun, one process per GPU -
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m be_hip.workflow local_train ...
@@ -311,7 +313,11 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     DepthPipeline.render_at, over args.render_window (top left h w; default the whole image), go to
     {args.out_path}/render_x{k}_{j:04d}.npz (shpd, refoc, bndry, depth, conf and - unless --densify pp - depth_map, float32; depth_map
     with the threshold of the mode: 0.05 under --big / --any), outside the timed region; a focal stack asked for in the same run
-    is written on the same lattice."""
+    is written on the same lattice.
+    args.render_size = (HO, WO) (not in the reference): every pair's maps resampled to HO x WO samples, DepthPipeline.render_resized,
+    go to {args.out_path}/render_{HO}x{WO}_{j:04d}.npz (the arrays of --render_scale); args.sample_points = an .npy file holding an
+    [N,2] array of (y, x) positions: the same maps at those positions, DepthPipeline.sample_at, and `valid` go to
+    {args.out_path}/samples_{j:04d}.npz.  Both outside the timed region."""
     import data, models, utils
     from .pipeline import DepthPipeline
     dev = _device(args)
@@ -335,6 +341,14 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
         from . import tiling
         tiling.lattice(1, 1, rscale, (0, 0, 1, 1))                                  # the scale now; the window against each pair's size
         os.makedirs(args.out_path, exist_ok=True)
+    rsize, spoints = getattr(args, "render_size", None), getattr(args, "sample_points", None)
+    if spoints is not None:
+        spoints = np.load(spoints)
+        if spoints.ndim != 2 or spoints.shape[1] != 2 or spoints.shape[0] == 0:
+            raise ValueError(f"--sample_points: the file must hold an [N,2] array of (y, x) positions, got {spoints.shape}")
+    if rsize is not None or spoints is not None:
+        os.makedirs(args.out_path, exist_ok=True)
+    fine_maps, fine_thres = ("shpd", "refoc", "bndry", "depth", "conf"), 0.05 if (big or any_size) else None
     sweep = None
     if getattr(args, "refocus_stack", 0):
         sweep = focus_sweep(pipe.dcal, args.refocus_stack, *args.focus_range)
@@ -361,6 +375,13 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
                                   depth_thres=0.05 if (big or any_size) else None)
             np.savez(os.path.join(args.out_path, f"render_x{rscale}_{j:04d}.npz"),
                      **{k: v.cpu().numpy() for k, v in fine.items() if k != "lattice"})
+        if rsize is not None:
+            fine = pipe.render_resized(maps, tuple(rsize), want=fine_maps, depth_thres=fine_thres)
+            np.savez(os.path.join(args.out_path, f"render_{rsize[0]}x{rsize[1]}_{j:04d}.npz"),
+                     **{k: v.cpu().numpy() for k, v in fine.items() if k not in ("lattice", "valid")})
+        if spoints is not None:
+            fine = pipe.sample_at(maps, spoints, want=fine_maps, depth_thres=fine_thres)
+            np.savez(os.path.join(args.out_path, f"samples_{j:04d}.npz"), **{k: v.cpu().numpy() for k, v in fine.items()})
         depth = maps["depth_map"][None]
         m = np.array(utils.eval_depth(depth, gt[None].to(depth.dtype), depth, crop=args.crop))
         tot += m

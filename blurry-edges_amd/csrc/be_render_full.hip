@@ -622,6 +622,211 @@ void k_fold_refocus_stack_at(be_render_opts o, be_depth_consts dc, StackArgs a, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the folds at arbitrary positions
+// The lattice kernels above sample on an axis-aligned lattice with an integer scale; nothing after the coordinate needs that.
+// The two kernels below take a list of N real-valued positions (y, x) in input-pixel coordinates (pixel centres at the integers,
+// the coordinate top + iy / k of the lattice), one thread per point.  Per axis yq = floor(y), fy = y - yq (exact in float32); a
+// grid line of origin oy covers the point iff oy <= y <= oy + 20, i.e. iff yq + (fy > 0) - 20 <= oy <= yq: the lattice rule
+// with `yr > 0` replaced by `fy > 0`.  The coordinate is lattice_coord, so a point with fy == fx == 0 equals the pixel kernels
+// bit for bit and a dyadic point equals the lattice kernels bit for bit.  Points are not tiled: origin tables are searched in
+// global memory (lower_bound, then a forward scan), not staged.  Outputs are channel-major over the points ([C,N]), so a point
+// grid [Ho,Wo] reshapes to the lattice layout without a transpose.  A point outside the closed domain [0, H-1] x [0, W-1]
+// (NaN included) gets 0 in every requested output.
+struct Points {
+    const float* pts;        // [N,2] (y, x), device
+    int64_t N;
+};
+
+// the run of grid lines covering a position pq + f (0 <= f < 1): the global origin table t[0..n) (TABLES) or stride * index
+template <bool TABLES>
+__device__ __forceinline__ void point_run(const int32_t* __restrict__ t, int s, int n, int pq, bool frac, int& lo, int& hi) {
+    const int first = pq + (frac ? 1 : 0) - (R - 1);            // the smallest origin that still covers the position
+    if constexpr (TABLES) {
+        lo = lower_bound(t, n, first);
+        hi = lo - 1; while (hi + 1 < n && t[hi + 1] <= pq) ++hi;
+    } else {
+        lo = first > 0 ? (first + s - 1) / s : 0;
+        hi = pq / s; if (hi > n - 1) hi = n - 1;
+    }
+}
+
+// the point's position, split per axis; false (outside the closed domain, or not a number): the caller writes zeros
+__device__ __forceinline__ bool point_split(const float* __restrict__ pts, int64_t p, int H, int W, int& yq, int& xq, float& fy, float& fx) {
+    const float y = pts[2 * p], x = pts[2 * p + 1];
+    if (!(y >= 0.f && y <= (float)(H - 1) && x >= 0.f && x <= (float)(W - 1))) return false;
+    yq = (int)floorf(y); xq = (int)floorf(x);
+    fy = y - (float)yq; fx = x - (float)xq;
+    return true;
+}
+
+template <bool TABLES>
+__global__ __launch_bounds__(256)
+void k_fold_records_points(be_render_opts o, FoldArgs a, Points l) {
+    __shared__ float lin[R];
+    if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
+    __syncthreads();
+    const int64_t at = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (at >= l.N) return;
+    const size_t hw = (size_t)l.N;
+    int yq, xq;
+    float fy, fx;
+    if (!point_split(l.pts, at, a.H, a.W, yq, xq, fy, fx)) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (a.image) { a.image[c * hw + at] = 0.f; a.image[(3 + c) * hw + at] = 0.f; }
+            if (a.shpd) a.shpd[c * hw + at] = 0.f;
+            if (a.refoc) a.refoc[c * hw + at] = 0.f;
+        }
+        if (a.bndry) a.bndry[at] = 0.f;
+        if (a.depth) a.depth[at] = 0.f;
+        if (a.conf) a.conf[at] = 0.f;
+        return;
+    }
+    const int yr = fy > 0.f, xr = fx > 0.f;
+    const int s = a.stride;
+    int i_lo, j_lo, i_hi, j_hi;
+    point_run<TABLES>(a.ys, s, a.hp, yq, yr, i_lo, i_hi);
+    point_run<TABLES>(a.xs, s, a.wp, xq, xr, j_lo, j_hi);
+    float acc1[3] = {0, 0, 0}, acc2[3] = {0, 0, 0}, accs[3] = {0, 0, 0}, accf[3] = {0, 0, 0};
+    float accb = 0.f, accz = 0.f;
+    int cnt = 0, cntz = 0;
+    const float rs = be::kRoot2 * 1e-4f;
+    for (int i = i_lo; i <= i_hi; ++i) {
+        const float py = lattice_coord(lin, yq - (TABLES ? a.ys[i] : s * i), yr, fy);
+        for (int j = j_lo; j <= j_hi; ++j) {
+            const float px = lattice_coord(lin, xq - (TABLES ? a.xs[j] : s * j), xr, fx);
+            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)(i * a.wp + j) * REC);
+            float r[REC];
+#pragma unroll
+            for (int q = 0; q < REC / 4; ++q) { const float4 t = rp[q]; r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w; }
+            be::WedgeGeom g;
+            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
+            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
+            g.sg1 = r[12]; g.sg2 = r[13];
+            float d1, d2;
+            be::wedge_dists(g, px, py, o.w, d1, d2);
+            const float* col = r + R_COL;
+            float u0, u1, u2;
+            {
+#pragma clang fp contract(off)
+                if (a.image) {
+                    be::indicators(d1, d2, r[R_RAD1], r[R_RAD1 + 1], u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc1[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                    be::indicators(d1, d2, r[R_RAD2], r[R_RAD2 + 1], u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc2[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                }
+                if (a.shpd) {
+                    be::indicators(d1, d2, rs, rs, u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) accs[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                }
+                if (a.refoc) {
+                    be::indicators(d1, d2, r[R_RADF], r[R_RADF + 1], u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) accf[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                }
+                if (a.bndry) accb += be::boundary_value(d1, d2, o.delta_sq);
+                if (a.depth || a.conf) {
+                    const int m = be::depth_mask(d1, d2, o.delta_sq, a.densify_w != 0);
+                    if (m == 1) { accz += r[R_DEPTH]; ++cntz; }
+                    else if (m == 2) { accz += r[R_DEPTH + 1]; ++cntz; }
+                }
+            }
+            ++cnt;
+        }
+    }
+    const float n = (float)cnt;                         // the patches visited (0 only where a uniform grid stops short of the edge)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (a.image) { a.image[c * hw + at] = acc1[c] / n; a.image[(3 + c) * hw + at] = acc2[c] / n; }
+        if (a.shpd) a.shpd[c * hw + at] = accs[c] / n;
+        if (a.refoc) a.refoc[c * hw + at] = accf[c] / n;
+    }
+    if (a.bndry) a.bndry[at] = accb / n;
+    if (a.depth) a.depth[at] = accz / (cntz > 0 ? (float)cntz : 1.0f);
+    if (a.conf) a.conf[at] = (float)cntz / n;
+}
+
+template <bool TABLES>
+__global__ __launch_bounds__(256)
+void k_fold_refocus_stack_points(be_render_opts o, be_depth_consts dc, StackArgs a, Points l) {
+    __shared__ float lin[R];
+    if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
+    __syncthreads();
+    const int64_t at = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (at >= l.N) return;
+    const size_t hw = (size_t)l.N;
+    const int k0 = blockIdx.y * FOLD_KC;
+    const int nk = min(FOLD_KC, a.K - k0);                      // planes of this chunk (uniform over the workgroup)
+    int yq, xq;
+    float fy, fx;
+    if (!point_split(l.pts, at, a.H, a.W, yq, xq, fy, fx)) {
+#pragma unroll
+        for (int k = 0; k < FOLD_KC; ++k) {
+            if (k < nk) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) a.out[((size_t)(k0 + k) * 3 + c) * hw + at] = 0.f;
+            }
+        }
+        return;
+    }
+    const int yr = fy > 0.f, xr = fx > 0.f;
+    float rho[FOLD_KC];
+#pragma unroll
+    for (int k = 0; k < FOLD_KC; ++k) rho[k] = a.rho_primes[k0 + min(k, nk - 1)];
+    const int s = a.stride;
+    int i_lo, j_lo, i_hi, j_hi;
+    point_run<TABLES>(a.ys, s, a.hp, yq, yr, i_lo, i_hi);
+    point_run<TABLES>(a.xs, s, a.wp, xq, xr, j_lo, j_hi);
+    float acc[FOLD_KC][3];
+#pragma unroll
+    for (int k = 0; k < FOLD_KC; ++k) { acc[k][0] = 0.f; acc[k][1] = 0.f; acc[k][2] = 0.f; }
+    int cnt = 0;
+    for (int i = i_lo; i <= i_hi; ++i) {
+        const float py = lattice_coord(lin, yq - (TABLES ? a.ys[i] : s * i), yr, fy);
+        for (int j = j_lo; j <= j_hi; ++j) {
+            const float px = lattice_coord(lin, xq - (TABLES ? a.xs[j] : s * j), xr, fx);
+            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)(i * a.wp + j) * REC);
+            float r[REC];
+#pragma unroll
+            for (int q = 0; q < REC / 4; ++q) { const float4 t = rp[q]; r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w; }
+            be::WedgeGeom g;
+            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
+            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
+            g.sg1 = r[12]; g.sg2 = r[13];
+            float d1, d2;
+            be::wedge_dists(g, px, py, o.w, d1, d2);
+            const float* col = r + R_COL;
+            const float z1 = r[R_DEPTH], z2 = r[R_DEPTH + 1];
+            const int flags = (int)r[R_FLAGS];
+            const bool has1 = (flags & 1) != 0, has2 = (flags & 2) != 0;
+#pragma unroll
+            for (int k = 0; k < FOLD_KC; ++k) {
+                if (k < nk) {
+#pragma clang fp contract(off)
+                    const float s1 = has1 ? be::depth2sigma(dc, z1, rho[k]) : 1e-4f;       // as k_render_records writes R_RADF
+                    const float s2 = has2 ? be::depth2sigma(dc, z2, rho[k]) : 1e-4f;
+                    float u0, u1, u2;
+                    be::indicators(d1, d2, be::kRoot2 * s1, be::kRoot2 * s2, u0, u1, u2);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc[k][c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
+                }
+            }
+            ++cnt;
+        }
+    }
+    const float n = (float)cnt;
+#pragma unroll
+    for (int k = 0; k < FOLD_KC; ++k) {
+        if (k < nk) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.out[((size_t)(k0 + k) * 3 + c) * hw + at] = acc[k][c] / n;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ glue
 __global__ void k_unfold(const float* __restrict__ img, float* __restrict__ out, int B, int C, int H, int W, int hp,
                          int wp, int stride) {
@@ -826,6 +1031,56 @@ extern "C" int be_fold_refocus_stack_at_f32(const be_render_opts* o, const be_de
     if (ys) hipLaunchKernelGGL(k_fold_refocus_stack_at<true>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a, l);
     else hipLaunchKernelGGL(k_fold_refocus_stack_at<false>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a, l);
     return be::check_launch("be_fold_refocus_stack_at_f32");
+}
+
+// the host checks the two *_points entries share: the grid (uniform or tables), the point list and its launch
+constexpr int64_t POINTS_MAX = (int64_t)0x00ffffff * 256;      // workgroups * 256 threads stay below 2^32
+
+static int check_points(const char* who, int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs,
+                        const float* points, int64_t N) {
+    BE_REQUIRE((ys == nullptr) == (xs == nullptr), "%s: ys and xs must both be given (origin tables) or both be null (uniform grid)", who);
+    BE_REQUIRE(points, "%s: null pointer", who);
+    BE_REQUIRE(HP > 0 && WP > 0 && H >= R && W >= R, "%s: bad sizes", who);
+    BE_REQUIRE((int64_t)HP * WP <= 0x7fffffff && H <= (1 << 24) && W <= (1 << 24),
+               "%s: image too large (HP * WP must fit 31 bits, H and W 24 bits: positions are float32)", who);
+    BE_REQUIRE(N >= 1 && N <= POINTS_MAX, "%s: N must be in [1, %lld], got %lld", who, (long long)POINTS_MAX, (long long)N);
+    if (ys) {
+        BE_REQUIRE(HP <= H - R + 1 && WP <= W - R + 1, "%s: HP / WP must be in [1, H-20] / [1, W-20] (origins are distinct pixels)", who);
+    } else {
+        BE_REQUIRE(stride > 0, "%s: bad sizes", who);
+        BE_REQUIRE((int64_t)stride * (HP - 1) + R <= H && (int64_t)stride * (WP - 1) + R <= W, "%s: patch grid exceeds the image", who);
+    }
+    return BE_OK;
+}
+
+extern "C" int be_fold_records_points_f32(const be_render_opts* o, const float* records, int HP, int WP, int H, int W, int stride,
+                                          const int32_t* ys, const int32_t* xs, const float* points, int64_t N, int densify_w,
+                                          float* image, float* shpd, float* refoc, float* bndry, float* depth, float* conf,
+                                          void* stream) {
+    BE_REQUIRE(o && records, "be_fold_records_points_f32: null pointer");
+    BE_REQUIRE(be::aligned16(records), "be_fold_records_points_f32: records must be 16-byte aligned");
+    if (const int rc = check_points("be_fold_records_points_f32", HP, WP, H, W, stride, ys, xs, points, N)) return rc;
+    FoldArgs a{records, HP, WP, H, W, ys ? 0 : stride, densify_w, image, shpd, refoc, bndry, depth, conf, 0, ys, xs};
+    const Points l{points, N};
+    const dim3 grid((unsigned)((N + 255) / 256));
+    if (ys) hipLaunchKernelGGL(k_fold_records_points<true>, grid, dim3(256), 0, be::as_stream(stream), *o, a, l);
+    else hipLaunchKernelGGL(k_fold_records_points<false>, grid, dim3(256), 0, be::as_stream(stream), *o, a, l);
+    return be::check_launch("be_fold_records_points_f32");
+}
+
+extern "C" int be_fold_refocus_stack_points_f32(const be_render_opts* o, const be_depth_consts* dc, const float* records, int HP, int WP,
+                                                int H, int W, int stride, const int32_t* ys, const int32_t* xs, const float* points,
+                                                int64_t N, const float* rho_primes, int K, float* out, void* stream) {
+    BE_REQUIRE(o && dc && records && rho_primes && out, "be_fold_refocus_stack_points_f32: null pointer");
+    BE_REQUIRE(be::aligned16(records), "be_fold_refocus_stack_points_f32: records must be 16-byte aligned");
+    BE_REQUIRE(K >= 1 && (K + FOLD_KC - 1) / FOLD_KC <= 65535, "be_fold_refocus_stack_points_f32: K must be in [1, 65535 * BE_REFOCUS_STACK_KC]");
+    if (const int rc = check_points("be_fold_refocus_stack_points_f32", HP, WP, H, W, stride, ys, xs, points, N)) return rc;
+    StackArgs a{records, rho_primes, out, HP, WP, H, W, ys ? 0 : stride, K, ys, xs};
+    const Points l{points, N};
+    const dim3 grid((unsigned)((N + 255) / 256), (K + FOLD_KC - 1) / FOLD_KC);
+    if (ys) hipLaunchKernelGGL(k_fold_refocus_stack_points<true>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a, l);
+    else hipLaunchKernelGGL(k_fold_refocus_stack_points<false>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a, l);
+    return be::check_launch("be_fold_refocus_stack_points_f32");
 }
 
 extern "C" int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream) {

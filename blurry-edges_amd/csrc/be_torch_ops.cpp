@@ -550,6 +550,67 @@ Tensor fold_refocus_stack_at(const Tensor& opts, const Tensor& consts, const Ten
     return out;
 }
 
+// the folds at arbitrary positions: points [N,2] (y, x) float32 on the records' device; maps channel-major over the points
+// ([6,N], [3,N], [N]) named by `want` as fold_records
+std::vector<Tensor> fold_records_points(const Tensor& opts, const Tensor& records, const c10::optional<Tensor>& ys, const c10::optional<Tensor>& xs,
+                                        int64_t hp, int64_t wp, int64_t H, int64_t W, int64_t stride, const Tensor& points, bool densify_w,
+                                        int64_t want) {
+    TORCH_CHECK(ys.has_value() == xs.has_value(), "fold_records_points: ys and xs must both be given (origin tables) or both be None");
+    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS, "fold_records_points: records [hp*wp,32]");
+    TORCH_CHECK(points.dim() == 2 && points.size(1) == 2 && points.size(0) > 0, "fold_records_points: points [N,2], N >= 1");
+    TORCH_CHECK(points.device() == records.device(), "fold_records_points: points and records on one device");
+    const int32_t *py = nullptr, *px = nullptr;
+    if (ys.has_value()) {
+        py = origin_table(*ys, "fold_records_points(ys)");
+        px = origin_table(*xs, "fold_records_points(xs)");
+        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, "fold_records_points: ys [hp], xs [wp]");
+    }
+    fp(records, "records");
+    const int64_t N = points.size(0);
+    auto o = records.options();
+    Tensor t[6];
+    if (want & 1) t[0] = at::empty({6, N}, o);
+    if (want & 2) t[1] = at::empty({3, N}, o);
+    if (want & 4) t[2] = at::empty({3, N}, o);
+    if (want & 8) t[3] = at::empty({N}, o);
+    if (want & 16) t[4] = at::empty({N}, o);
+    if (want & 32) t[5] = at::empty({N}, o);
+    auto f = [&](int i) { return t[i].defined() ? t[i].data_ptr<float>() : nullptr; };
+    check(be_fold_records_points_f32(host_struct<be_render_opts>(opts, "fold_records_points(opts)"), records.data_ptr<float>(), (int)hp, (int)wp,
+                                     (int)H, (int)W, (int)stride, py, px, fp(points, "points"), N, densify_w ? 1 : 0, f(0), f(1), f(2), f(3),
+                                     f(4), f(5), stream_of(records)), "be_fold_records_points_f32");
+    std::vector<Tensor> r;
+    for (int i = 0; i < 6; ++i) if (t[i].defined()) r.push_back(t[i]);
+    return r;
+}
+
+Tensor fold_refocus_stack_points(const Tensor& opts, const Tensor& consts, const Tensor& records, const Tensor& rho_primes,
+                                 const c10::optional<Tensor>& ys, const c10::optional<Tensor>& xs, int64_t hp, int64_t wp, int64_t H, int64_t W,
+                                 int64_t stride, const Tensor& points) {
+    TORCH_CHECK(ys.has_value() == xs.has_value(), "fold_refocus_stack_points: ys and xs must both be given (origin tables) or both be None");
+    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS,
+                "fold_refocus_stack_points: records [hp*wp,32]");
+    TORCH_CHECK(rho_primes.dim() == 1 && rho_primes.numel() > 0, "fold_refocus_stack_points: rho_primes [K], K >= 1");
+    TORCH_CHECK(rho_primes.device() == records.device(), "fold_refocus_stack_points: rho_primes and records on one device");
+    TORCH_CHECK(points.dim() == 2 && points.size(1) == 2 && points.size(0) > 0, "fold_refocus_stack_points: points [N,2], N >= 1");
+    TORCH_CHECK(points.device() == records.device(), "fold_refocus_stack_points: points and records on one device");
+    const int32_t *py = nullptr, *px = nullptr;
+    if (ys.has_value()) {
+        py = origin_table(*ys, "fold_refocus_stack_points(ys)");
+        px = origin_table(*xs, "fold_refocus_stack_points(xs)");
+        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, "fold_refocus_stack_points: ys [hp], xs [wp]");
+    }
+    const int64_t K = rho_primes.numel(), N = points.size(0);
+    fp(records, "records");
+    Tensor out = at::empty({K, 3, N}, records.options());
+    check(be_fold_refocus_stack_points_f32(host_struct<be_render_opts>(opts, "fold_refocus_stack_points(opts)"),
+                                           host_struct<be_depth_consts>(consts, "fold_refocus_stack_points(consts)"), records.data_ptr<float>(),
+                                           (int)hp, (int)wp, (int)H, (int)W, (int)stride, py, px, fp(points, "points"), N,
+                                           fp(rho_primes, "rho_primes"), (int)K, out.data_ptr<float>(), stream_of(records)),
+          "be_fold_refocus_stack_points_f32");
+    return out;
+}
+
 // LocalLoss forward + analytic backward in one launch -> (partial [B,3], grad_est [B,10] or an empty tensor)
 std::tuple<Tensor, Tensor> local_loss(const Tensor& opts, const Tensor& est, const Tensor& img_fit, const Tensor& gt, const Tensor& bdist,
                                       const Tensor& deri, double beta_b, double beta_s, bool want_grad) {
@@ -671,6 +732,8 @@ TORCH_LIBRARY(be, m) {
     m.def("fold_refocus_stack(Tensor opts, Tensor consts, Tensor records, Tensor rho_primes, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride) -> Tensor");
     m.def("fold_records_at(Tensor opts, Tensor records, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, int scale, int top, int left, int h, int w, bool densify_w, int want) -> Tensor[]");
     m.def("fold_refocus_stack_at(Tensor opts, Tensor consts, Tensor records, Tensor rho_primes, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, int scale, int top, int left, int h, int w) -> Tensor");
+    m.def("fold_records_points(Tensor opts, Tensor records, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, Tensor points, bool densify_w, int want) -> Tensor[]");
+    m.def("fold_refocus_stack_points(Tensor opts, Tensor consts, Tensor records, Tensor rho_primes, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, Tensor points) -> Tensor");
     m.def("local_loss(Tensor opts, Tensor est, Tensor img_fit, Tensor gt, Tensor bdist, Tensor deri, float beta_b, float beta_s, bool want_grad) -> (Tensor, Tensor)");
     m.def("local_loss_finish(Tensor partial, float beta_b, float beta_s) -> Tensor");
     m.def("global_loss(Tensor opts, Tensor consts, Tensor est, Tensor img_fit, Tensor img_gt, Tensor G, Tensor Gd, Tensor Gb, Tensor bdist, Tensor deri, "
@@ -726,6 +789,8 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("fold_refocus_stack", fold_refocus_stack);
     m.impl("fold_records_at", fold_records_at);
     m.impl("fold_refocus_stack_at", fold_refocus_stack_at);
+    m.impl("fold_records_points", fold_records_points);
+    m.impl("fold_refocus_stack_points", fold_refocus_stack_points);
     m.impl("local_loss", local_loss);
     m.impl("local_loss_finish", local_loss_finish);
     m.impl("global_loss", global_loss);

@@ -88,6 +88,10 @@ _GROUPS = {
         # the whole image or the window TOP LEFT H W (input pixels), written to out_path; 1 = off
         ('--render_scale', dict(type=int, default=1)),
         ('--render_window', dict(type=int, nargs=4, default=None)),
+        # not in the reference: every pair's folded maps resampled to HO x WO samples (DepthPipeline.render_resized), and at the
+        # (y, x) positions of an [N,2] .npy file (DepthPipeline.sample_at), written to out_path; absent = off
+        ('--render_size', dict(type=int, nargs=2, default=None)),
+        ('--sample_points', dict(type=str, default=None)),
     ],
 }
 

@@ -200,6 +200,27 @@ int be_fold_refocus_stack_at_f32(const be_render_opts* opts_host, const be_depth
                                  int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs, int scale,
                                  int top, int left, int h, int w, const float* rho_primes, int K, float* out, void* stream);
 
+/* The folds at N arbitrary positions: points [N,2] float32 on the device, (y, x) in input-pixel coordinates with pixel centres
+ * at the integers - the coordinate top + iy / k of the *_at entries, without the lattice.  The domain is closed,
+ * 0 <= y <= H-1 and 0 <= x <= W-1; a point outside it (NaN and the infinities included) gets 0 in every requested output and
+ * reads nothing.  Per axis yq = floorf(y), fy = y - yq (exact in fp32): a patch of origin oy covers the point iff
+ * yq + (fy > 0) - 20 <= oy <= yq, its coordinate is lin[yq - oy] when fy == 0 and
+ * lin[q] + fy * (lin[q+1] - lin[q]) in fp32 otherwise, and everything after the coordinate is the fold of
+ * be_fold_records_f32 / be_fold_records_grid_f32 (be_fold_refocus_stack_f32) - so a point on a pixel centre equals that
+ * entry's pixel bit for bit, and a point (top + iy / k, left + ix / k) with k a power of two equals sample (iy, ix) of the
+ * *_at entries bit for bit.  Every point is evaluated on its own: the outputs do not depend on the order or the number of
+ * the points.  The outputs are channel-major over the points: image [6,N] (pair image 1, then 2), shpd / refoc [3,N],
+ * bndry / depth / conf [N], out [K,3,N]; a point grid [Ho,Wo] (N = Ho*Wo) then has the layout of the *_at entries.  A point
+ * inside the domain but under no patch (a uniform grid that stops short of the edge) gives 0/0, as the pixel folds do.
+ * ys == xs == NULL: the uniform grid of `stride`; both non-NULL: origin tables (stride ignored).  Every map may be NULL.
+ * 1 <= N <= 0xffffff * 256; H, W <= 2^24 (positions are fp32). */
+int be_fold_records_points_f32(const be_render_opts* opts_host, const float* records, int HP, int WP, int H, int W, int stride,
+                               const int32_t* ys, const int32_t* xs, const float* points, int64_t N, int densify_w,
+                               float* image, float* shpd, float* refoc, float* bndry, float* depth, float* conf, void* stream);
+int be_fold_refocus_stack_points_f32(const be_render_opts* opts_host, const be_depth_consts* consts_host, const float* records,
+                                     int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs,
+                                     const float* points, int64_t N, const float* rho_primes, int K, float* out, void* stream);
+
 /* nn.Unfold(21, stride) in the order blurry_edges_test.py:120-121 consumes it:
  * img [B,C,H,W] -> out [B, Hp*Wp, C, 21, 21], patch (i,j) = rows stride*i.., cols stride*j.., index i*Wp+j. */
 int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream);
