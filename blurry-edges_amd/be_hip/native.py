@@ -157,6 +157,8 @@ _SIGNATURES = {
     "be_fold_records_points_f32": (C.c_int, [C.POINTER(RenderOpts), _P] + [C.c_int] * 5 + [_P, _P, _P, C.c_int64, C.c_int] + [_P] * 6 + [_P]),
     "be_fold_refocus_stack_points_f32": (C.c_int, [C.POINTER(RenderOpts), C.POINTER(DepthConsts), _P] + [C.c_int] * 5
                                          + [_P, _P, _P, C.c_int64, _P, C.c_int, _P, _P]),
+    "be_unproject_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float)] * 2 + [_P, _P]),
+    "be_reproject_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float)] * 3 + [C.c_float, C.c_int, C.c_int, _P, C.c_int] + [_P] * 4 + [_P]),
     "be_unfold_patches_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "be_local_features_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "be_global_denorm_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
@@ -1179,6 +1181,100 @@ def fold_refocus_stack_points(opts, consts, records, rho_primes, H, W, points, h
                                                      stride, dptr(ys), dptr(xs), dptr(pts), N, dptr(rho), len(vals), dptr(out),
                                                      stream_ptr(dev)), "be_fold_refocus_stack_points_f32")
     return out.view((len(vals), 3) + lead)
+
+
+def _reproject_args(who, depth, cams, pose, scale, window_origin):
+    """The host side unproject and reproject share, before the library is touched: depth [Hs,Ws] float32 on the GPU, the cameras
+    (camera.Pinhole, (fy, fx, cy, cx) or a 3x3 K) and the pose (camera.as_pose) as float32 numpy, scale in 1..16, the window
+    origin.  -> (depth, [camera float32 [4]], pose float32 [12], top, left)."""
+    from . import camera, tiling
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 2 or depth.numel() == 0:
+        raise ValueError(f"{who}: depth must be a float32 tensor [Hs,Ws], got "
+                         f"{getattr(depth, 'dtype', type(depth).__name__)} {tuple(getattr(depth, 'shape', ()))}")
+    if not depth.is_cuda:
+        raise ValueError(f"{who}: depth is not on the GPU; nothing here computes on the CPU (camera.splat_f32 is the host statement)")
+    if depth.numel() > 0x7fffffff:
+        raise ValueError(f"{who}: {depth.numel()} source samples; at most 2^31 - 1 (the index map is int32)")
+    if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= tiling.MAX_SCALE:
+        raise ValueError(f"{who}: scale must be an integer in [1, {tiling.MAX_SCALE}], got {scale!r}")
+    try:
+        top, left = window_origin
+        ok = all(not isinstance(v, bool) and int(v) == v and 0 <= v <= 1 << 24 for v in (top, left))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{who}: window_origin must be (top, left), integers >= 0, got {window_origin!r}")
+    cams = [camera.as_pinhole(c, f"{who}({n})").f32() for n, c in cams]
+    return depth.contiguous(), cams, camera.as_pose(pose, f"{who}(pose)"), int(top), int(left)
+
+
+def _fptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def unproject(depth, cam_src, pose=None, scale=1, window_origin=(0, 0)):
+    """depth [Hs,Ws] (metres along the optical axis; sample (iy, ix) at (top + iy / scale, left + ix / scale) in source pixels)
+    -> xyz [3,Hs,Ws]: the samples as points (X, Y, Z) in the frame `pose` maps the source camera's to (None: the camera's own);
+    0 in all three where the depth is not a finite number > 0.  camera.unproject_f32 is the host statement, bit for bit."""
+    depth, (cs,), p12, top, left = _reproject_args("unproject", depth, [("cam_src", cam_src)], pose, scale, window_origin)
+    Hs, Ws = depth.shape
+    o = ops()
+    if o is not None:
+        return o.unproject(depth, torch.from_numpy(cs), torch.from_numpy(p12), scale, top, left)
+    xyz = torch.empty(3, Hs, Ws, dtype=torch.float32, device=depth.device)
+    check(lib().be_unproject_f32(dptr(depth, "depth", (torch.float32,)), Hs, Ws, scale, top, left, _fptr(cs), _fptr(p12), dptr(xyz),
+                                 stream_ptr(depth.device)), "be_unproject_f32")
+    return xyz
+
+
+def reproject(depth, cam_src, cam_dst, pose, size, feat=None, near=1e-3, scale=1, window_origin=(0, 0)):
+    """Forward warp of depth [Hs,Ws] (the samples of unproject) from cam_src to cam_dst, size = (Ho, Wo): every sample with a
+    finite depth > 0 whose depth in the target frame exceeds `near` and whose projection rounds to a pixel of the target is
+    splatted there; the nearest wins, on equal depth the lowest source index.  -> dict(depth [Ho,Wo] in the target frame,
+    index [Ho,Wo] int32 = the winner's iy * Ws + ix, valid = index >= 0 (on the device, no sync), feat [C,Ho,Wo] gathered from
+    feat [C,Hs,Ws] or [C,Hs*Ws] - None when feat is None); +0 / -1 / False / +0 where nothing landed.  The result does not depend
+    on the order of execution; camera.splat_f32 is the host statement, bit for bit."""
+    depth, (cs, cd), p12, top, left = _reproject_args("reproject", depth, [("cam_src", cam_src), ("cam_dst", cam_dst)], pose, scale,
+                                                      window_origin)
+    try:
+        Ho, Wo = size
+        ok = all(not isinstance(v, bool) and int(v) == v and 1 <= v <= 1 << 24 for v in (Ho, Wo)) and Ho * Wo <= 0x7fffffff
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"reproject: size must be (Ho, Wo), integers >= 1 with Ho * Wo < 2^31, got {size!r}")
+    Ho, Wo = int(Ho), int(Wo)
+    try:
+        near = float(near)
+    except (TypeError, ValueError):
+        near = -1.0
+    if not 0 <= near < float("inf"):
+        raise ValueError("reproject: near must be a finite number >= 0")
+    Hs, Ws = depth.shape
+    dev = depth.device
+    if feat is not None:
+        if (not isinstance(feat, torch.Tensor) or feat.dtype != torch.float32 or feat.dim() not in (2, 3)
+                or tuple(feat.shape[1:]) not in ((Hs, Ws), (Hs * Ws,))):
+            raise ValueError(f"reproject: feat must be a float32 tensor [C,{Hs},{Ws}] or [C,{Hs * Ws}], got "
+                             f"{getattr(feat, 'dtype', type(feat).__name__)} {tuple(getattr(feat, 'shape', ()))}")
+        if feat.device != dev:
+            raise ValueError(f"reproject: feat is on {feat.device}, depth on {dev}")
+        feat = feat.reshape(feat.shape[0], Hs * Ws).contiguous()
+    o = ops()
+    if o is not None:
+        d, index, f = o.reproject(depth, torch.from_numpy(cs), torch.from_numpy(cd), torch.from_numpy(p12), near, Ho, Wo, feat, scale,
+                                  top, left)
+        f = f if feat is not None else None
+    else:
+        zbuf = torch.empty(Ho * Wo, dtype=torch.int64, device=dev)
+        d = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
+        index = torch.empty(Ho, Wo, dtype=torch.int32, device=dev)
+        C_ = 0 if feat is None else feat.shape[0]
+        f = None if feat is None else torch.empty(C_, Ho, Wo, dtype=torch.float32, device=dev)
+        check(lib().be_reproject_f32(dptr(depth, "depth", (torch.float32,)), Hs, Ws, scale, top, left, _fptr(cs), _fptr(cd), _fptr(p12),
+                                     near, Ho, Wo, dptr(feat if C_ else None), C_, dptr(zbuf, "zbuf", (torch.int64,)), dptr(d),
+                                     dptr(index), dptr(f if C_ else None), stream_ptr(dev)), "be_reproject_f32")
+    return dict(depth=d, index=index, valid=index >= 0, feat=f)
 
 
 def unfold_patches(img: torch.Tensor, stride: int = 2) -> torch.Tensor:

@@ -353,6 +353,89 @@ class DepthPipeline:
         return res
 
 
+    # ---- forward reprojection: the depth map and the maps that ride on it, seen from another camera ----------------------
+    def _depth_samples(self, who, maps, scale, window, want, depth_thres):
+        """The source of point_cloud and reproject: the samples of render_at(scale, window) with their depth_map.  At the defaults
+        the maps already in `maps` are used and nothing is launched.  -> (dict of the wanted maps and depth_map, lattice)."""
+        if not isinstance(maps, dict) or "records" not in maps or "grid" not in maps:
+            missing = [k for k in ("records", "grid") if not isinstance(maps, dict) or k not in maps]
+            raise ValueError(f"{who}: maps lacks {missing}; pass the dict DepthPipeline.__call__, run_big or run_any returned")
+        rec, g = maps["records"], maps["grid"]
+        lat = tiling.lattice(g["H"], g["W"], scale, window)
+        unknown = [k for k in want if k not in native.FOLD_MAPS]
+        if unknown:
+            raise ValueError(f"{who}: unknown maps {unknown}; choose from {native.FOLD_MAPS}")
+        if not isinstance(rec, torch.Tensor) or not rec.is_cuda:
+            raise ValueError(f"{who}: maps['records'] is not on the GPU; nothing here computes on the CPU "
+                             "(keep the dict the pipeline returned, or move records - and the ys / xs of grid - back to the device)")
+        if self.densify == "pp" and scale != 1:
+            raise ValueError(f"{who}: densify='pp' has no depth_map off the pixels (the U-Net is not defined off its native "
+                             f"resolution): scale must be 1, got {scale}")
+        if "depth_map" not in maps and (self.densify == "pp" or (scale == 1 and window is None and depth_thres is None)):
+            raise ValueError(f"{who}: maps lacks ['depth_map']; pass the dict DepthPipeline.__call__, run_big or run_any returned")
+        if scale == 1 and window is None and depth_thres is None:
+            # the pixels themselves: maps["depth_map"] is the depth source whatever threshold its entry point used (run_big and
+            # run_any: 0.05), and only a wanted map that `maps` does not hold is rendered again
+            missing = tuple(k for k in want if k not in maps)
+            src = {k: maps[k] for k in want if k in maps}
+            if missing:
+                src.update({k: v for k, v in self.render_at(maps, want=missing).items() if k in missing})
+            src["depth_map"] = maps["depth_map"]
+            return src, lat
+        src = self.render_at(maps, scale=scale, window=window, want=want, depth_thres=depth_thres)
+        if self.densify == "pp":
+            top, left, h, w = lat["window"]
+            src["depth_map"] = maps["depth_map"][top:top + h, left:left + w].contiguous()
+        return src, lat
+
+    @torch.no_grad()
+    def point_cloud(self, maps, pose=None, scale=1, window=None, depth_thres=None):
+        """maps: what __call__, run_big or run_any returned -> the samples of render_at(scale, window) (the pixels by default) as
+        points in space: xyz [3,Ho,Wo] = (X, Y, Z) in metres, Z = depth_map along the optical axis, through the pinhole camera
+        dcal.intrinsics(H, W), in the frame `pose` maps the camera's to (camera.pose; None: the camera's own).  valid [Ho,Wo]:
+        depth_map is a finite number > 0 (on the device, no sync); xyz is 0 elsewhere.  Also returned: shpd [3,Ho,Wo] and conf of
+        the same samples, and lattice.  depth_thres: as render_at."""
+        src, lat = self._depth_samples("point_cloud", maps, scale, window, ("shpd", "conf"), depth_thres)
+        g = maps["grid"]
+        z = src["depth_map"]
+        xyz = native.unproject(z, self.dcal.intrinsics(g["H"], g["W"]), pose, scale=lat["scale"], window_origin=lat["window"][:2])
+        return dict(xyz=xyz, valid=(z > 0) & torch.isfinite(z), shpd=src["shpd"], conf=src["conf"], lattice=lat)
+
+    @torch.no_grad()
+    def reproject(self, maps, cam_dst=None, pose=None, size=None, want=("shpd",), scale=1, window=None, near=1e-3, depth_thres=None,
+                  cam_src=None):
+        """"Align depth to colour": maps (what __call__, run_big or run_any returned) forward-warped to the camera cam_dst
+        (camera.Pinhole, (fy, fx, cy, cx) or a 3x3 K) that sits at `pose` (camera.pose: X' = R X + t from this camera's frame to
+        that one's), size = (Ho, Wo) pixels -> depth [Ho,Wo] along cam_dst's axis, valid, index (the winner's linear index in the
+        source lattice, -1 where nothing landed) and the `want`ed maps out of native.FOLD_MAPS gathered from the winning sample,
+        with the channel counts render_at gives them.  Where two samples land on one pixel the nearer wins; where none lands
+        every map is 0 - holes are left open.  The source samples and their depth_map are those of render_at(scale, window,
+        depth_thres=..) - at scale 1 without a window and a depth_thres, maps["depth_map"] itself, with the threshold of the entry
+        that made it; off those defaults pass depth_thres=0.05 to continue run_big's / run_any's: scale = k splats k^2 samples per pixel, each evaluated from the wedges, which closes the cracks of a
+        magnifying view.  Defaults: cam_src = dcal.intrinsics(H, W), cam_dst = cam_src, size = (H, W), the identity pose - which
+        returns the maps themselves wherever depth_map > 0.  Under densify == 'pp' the depth source is maps["depth_map"] and scale
+        must be 1.  lattice: the source lattice."""
+        want = tuple(want)
+        src, lat = self._depth_samples("reproject", maps, scale, window, want, depth_thres)
+        g = maps["grid"]
+        cam_src = self.dcal.intrinsics(g["H"], g["W"]) if cam_src is None else cam_src
+        cam_dst = cam_src if cam_dst is None else cam_dst
+        size = (g["H"], g["W"]) if size is None else size
+        z = src["depth_map"]
+        Ns = z.numel()
+        feat = torch.cat([src[k].reshape(-1, Ns) for k in want]) if want else None
+        out = native.reproject(z, cam_src, cam_dst, pose, size, feat=feat, near=near, scale=lat["scale"],
+                               window_origin=lat["window"][:2])
+        res = dict(depth=out["depth"], valid=out["valid"], index=out["index"], lattice=lat)
+        c = 0
+        for k in want:
+            lead = tuple(src[k].shape[:-2])
+            n = src[k].numel() // Ns
+            res[k] = out["feat"][c:c + n].reshape(lead + tuple(out["depth"].shape))
+            c += n
+        return res
+
+
 def _points_on(points, device, who):
     """points: a tensor or array-like [...,2] of (y, x) -> float32, on `device` when one is given."""
     try:

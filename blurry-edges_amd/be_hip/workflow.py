@@ -11,6 +11,8 @@ formats (argument names and defaults = utils/args.py of the reference):
     ... eval --render_scale K [--render_window T L H W] [--out_path DIR]   also write every pair's maps on a K times finer lattice
     ... eval --render_size HO WO [--out_path DIR]          also write every pair's maps resampled to HO x WO samples
     ... eval --sample_points FILE.npy [--out_path DIR]     also write every pair's maps at the [N,2] (y, x) positions of FILE
+    ... eval --point_cloud [--out_path DIR]                also write every pair's depth map as points in space
+    ... eval --reproject CAM.npz [--out_path DIR]          also write every pair's depth and colours as the camera of CAM sees them
 
 Data parallel (BASELINE configs[4]): the two training commands run under torchrun, one process per GPU -
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m be_hip.workflow local_train ...
@@ -303,6 +305,24 @@ def focus_sweep(dcal, k, near, far):
     return np.linspace(dcal.focus2rho(far), dcal.focus2rho(near), k)
 
 
+def load_camera(path):
+    """The settings file of `eval --reproject`: an .npz holding K ([4] = fy, fx, cy, cx, or [3,3]), R [3,3] and t [3] (the pose from
+    the depth camera's frame to this camera's; absent: the identity, zero), size = (Ho, Wo) and optionally scale (the source
+    lattice, default 1) -> dict(cam, pose, size, scale), checked by be_hip.camera."""
+    from . import camera
+    with np.load(path) as f:
+        missing = [k for k in ("K", "size") if k not in f]
+        if missing:
+            raise ValueError(f"--reproject: {path} lacks {missing}; it must hold K, size and optionally R, t, scale")
+        size = np.asarray(f["size"]).reshape(-1)
+        if size.shape != (2,) or not all(int(v) == v and v >= 1 for v in size):
+            raise ValueError(f"--reproject: size must be (Ho, Wo), integers >= 1, got {f['size']!r}")
+        scale = int(np.asarray(f["scale"]).reshape(-1)[0]) if "scale" in f else 1
+        return dict(cam=camera.as_pinhole(f["K"], "--reproject(K)"),
+                    pose=camera.pose(f["R"] if "R" in f else None, f["t"] if "t" in f else None),
+                    size=(int(size[0]), int(size[1])), scale=scale)
+
+
 @torch.no_grad()
 def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weights=None, quiet=False, any_size=False):
     """-> dict(delta1, delta2, delta3, RMSE, AbsRel, seconds_per_pair), averaged over the test set as the scripts do.
@@ -317,7 +337,12 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     args.render_size = (HO, WO) (not in the reference): every pair's maps resampled to HO x WO samples, DepthPipeline.render_resized,
     go to {args.out_path}/render_{HO}x{WO}_{j:04d}.npz (the arrays of --render_scale); args.sample_points = an .npy file holding an
     [N,2] array of (y, x) positions: the same maps at those positions, DepthPipeline.sample_at, and `valid` go to
-    {args.out_path}/samples_{j:04d}.npz.  Both outside the timed region."""
+    {args.out_path}/samples_{j:04d}.npz.  Both outside the timed region.
+    args.point_cloud (not in the reference): every pair's depth_map as points in the camera's frame, DepthPipeline.point_cloud, goes
+    to {args.out_path}/cloud_{j:04d}.npz (xyz [3,H,W], valid, shpd, conf); args.reproject = an .npz file of settings (load_camera: K,
+    R, t, size, optional scale): the pair forward-warped to that camera, DepthPipeline.reproject, goes to
+    {args.out_path}/reproj_{j:04d}.npz (depth, valid, index, shpd, refoc at `size`).  Both outside the timed region, with the
+    depth threshold of the mode."""
     import data, models, utils
     from .pipeline import DepthPipeline
     dev = _device(args)
@@ -346,7 +371,10 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
         spoints = np.load(spoints)
         if spoints.ndim != 2 or spoints.shape[1] != 2 or spoints.shape[0] == 0:
             raise ValueError(f"--sample_points: the file must hold an [N,2] array of (y, x) positions, got {spoints.shape}")
-    if rsize is not None or spoints is not None:
+    cloud, rcam = getattr(args, "point_cloud", False), getattr(args, "reproject", None)
+    if rcam is not None:
+        rcam = load_camera(rcam)
+    if rsize is not None or spoints is not None or cloud or rcam is not None:
         os.makedirs(args.out_path, exist_ok=True)
     fine_maps, fine_thres = ("shpd", "refoc", "bndry", "depth", "conf"), 0.05 if (big or any_size) else None
     sweep = None
@@ -382,6 +410,15 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
         if spoints is not None:
             fine = pipe.sample_at(maps, spoints, want=fine_maps, depth_thres=fine_thres)
             np.savez(os.path.join(args.out_path, f"samples_{j:04d}.npz"), **{k: v.cpu().numpy() for k, v in fine.items()})
+        if cloud:
+            pc = pipe.point_cloud(maps)
+            np.savez(os.path.join(args.out_path, f"cloud_{j:04d}.npz"), **{k: v.cpu().numpy() for k, v in pc.items() if k != "lattice"})
+        if rcam is not None:
+            # at scale 1 the maps the mode produced are the source (its own threshold); finer samples continue that threshold
+            warped = pipe.reproject(maps, cam_dst=rcam["cam"], pose=rcam["pose"], size=rcam["size"], want=("shpd", "refoc"),
+                                    scale=rcam["scale"], depth_thres=fine_thres if rcam["scale"] > 1 else None)
+            np.savez(os.path.join(args.out_path, f"reproj_{j:04d}.npz"),
+                     **{k: v.cpu().numpy() for k, v in warped.items() if k != "lattice"})
         depth = maps["depth_map"][None]
         m = np.array(utils.eval_depth(depth, gt[None].to(depth.dtype), depth, crop=args.crop))
         tot += m

@@ -611,6 +611,52 @@ Tensor fold_refocus_stack_points(const Tensor& opts, const Tensor& consts, const
     return out;
 }
 
+// forward reprojection: depth [Hs,Ws] on the GPU; cam_src / cam_dst [4] (fy, fx, cy, cx) and pose [12] (R row-major, t) are CPU
+// float32 tensors, read on the host as the C entries read them
+static const float* host_floats(const Tensor& t, int64_t n, const char* what) {
+    TORCH_CHECK(!t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n, what, ": expected a CPU float32 tensor of ",
+                n, " numbers");
+    return t.data_ptr<float>();
+}
+
+Tensor unproject(const Tensor& depth, const Tensor& cam_src, const Tensor& pose, int64_t scale, int64_t top, int64_t left) {
+    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "unproject: depth [Hs,Ws], 1 .. 2^31 - 1 samples");
+    fp(depth, "depth");
+    Tensor xyz = at::empty({3, depth.size(0), depth.size(1)}, depth.options());
+    check(be_unproject_f32(depth.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)scale, (int)top, (int)left,
+                           host_floats(cam_src, 4, "unproject(cam_src)"), host_floats(pose, 12, "unproject(pose)"), xyz.data_ptr<float>(),
+                           stream_of(depth)), "be_unproject_f32");
+    return xyz;
+}
+
+// -> (depth [Ho,Wo], index [Ho,Wo] int32, feat_out [C,Ho,Wo] or an empty tensor when feat is None)
+std::tuple<Tensor, Tensor, Tensor> reproject(const Tensor& depth, const Tensor& cam_src, const Tensor& cam_dst, const Tensor& pose, double near,
+                                             int64_t Ho, int64_t Wo, const c10::optional<Tensor>& feat, int64_t scale, int64_t top,
+                                             int64_t left) {
+    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "reproject: depth [Hs,Ws], 1 .. 2^31 - 1 samples");
+    TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= (1 << 24) && Wo <= (1 << 24), "reproject: bad target size");
+    fp(depth, "depth");
+    const int64_t Ns = depth.numel();
+    int64_t C = 0;
+    const float* pf = nullptr;
+    if (feat.has_value() && feat->defined()) {
+        TORCH_CHECK(feat->dim() == 2 && feat->size(1) == Ns, "reproject: feat [C,Hs*Ws]");
+        TORCH_CHECK(feat->device() == depth.device(), "reproject: feat and depth on one device");
+        C = feat->size(0);
+        if (C > 0) pf = fp(*feat, "feat");
+    }
+    auto o = depth.options();
+    Tensor zbuf = at::empty({Ho * Wo}, o.dtype(at::kLong));
+    Tensor dout = at::empty({Ho, Wo}, o), index = at::empty({Ho, Wo}, o.dtype(at::kInt));
+    Tensor fout = feat.has_value() && feat->defined() ? at::empty({C, Ho, Wo}, o) : at::empty({0}, o);
+    check(be_reproject_f32(depth.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)scale, (int)top, (int)left,
+                           host_floats(cam_src, 4, "reproject(cam_src)"), host_floats(cam_dst, 4, "reproject(cam_dst)"),
+                           host_floats(pose, 12, "reproject(pose)"), (float)near, (int)Ho, (int)Wo, pf, (int)C,
+                           reinterpret_cast<uint64_t*>(zbuf.data_ptr<int64_t>()), dout.data_ptr<float>(), index.data_ptr<int32_t>(),
+                           C > 0 ? fout.data_ptr<float>() : nullptr, stream_of(depth)), "be_reproject_f32");
+    return {dout, index, fout};
+}
+
 // LocalLoss forward + analytic backward in one launch -> (partial [B,3], grad_est [B,10] or an empty tensor)
 std::tuple<Tensor, Tensor> local_loss(const Tensor& opts, const Tensor& est, const Tensor& img_fit, const Tensor& gt, const Tensor& bdist,
                                       const Tensor& deri, double beta_b, double beta_s, bool want_grad) {
@@ -734,6 +780,8 @@ TORCH_LIBRARY(be, m) {
     m.def("fold_refocus_stack_at(Tensor opts, Tensor consts, Tensor records, Tensor rho_primes, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, int scale, int top, int left, int h, int w) -> Tensor");
     m.def("fold_records_points(Tensor opts, Tensor records, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, Tensor points, bool densify_w, int want) -> Tensor[]");
     m.def("fold_refocus_stack_points(Tensor opts, Tensor consts, Tensor records, Tensor rho_primes, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, Tensor points) -> Tensor");
+    m.def("unproject(Tensor depth, Tensor cam_src, Tensor pose, int scale, int top, int left) -> Tensor");
+    m.def("reproject(Tensor depth, Tensor cam_src, Tensor cam_dst, Tensor pose, float near, int Ho, int Wo, Tensor? feat, int scale, int top, int left) -> (Tensor, Tensor, Tensor)");
     m.def("local_loss(Tensor opts, Tensor est, Tensor img_fit, Tensor gt, Tensor bdist, Tensor deri, float beta_b, float beta_s, bool want_grad) -> (Tensor, Tensor)");
     m.def("local_loss_finish(Tensor partial, float beta_b, float beta_s) -> Tensor");
     m.def("global_loss(Tensor opts, Tensor consts, Tensor est, Tensor img_fit, Tensor img_gt, Tensor G, Tensor Gd, Tensor Gb, Tensor bdist, Tensor deri, "
@@ -791,6 +839,8 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("fold_refocus_stack_at", fold_refocus_stack_at);
     m.impl("fold_records_points", fold_records_points);
     m.impl("fold_refocus_stack_points", fold_refocus_stack_points);
+    m.impl("unproject", unproject);
+    m.impl("reproject", reproject);
     m.impl("local_loss", local_loss);
     m.impl("local_loss_finish", local_loss_finish);
     m.impl("global_loss", global_loss);

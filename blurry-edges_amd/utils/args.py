@@ -92,6 +92,10 @@ _GROUPS = {
         # (y, x) positions of an [N,2] .npy file (DepthPipeline.sample_at), written to out_path; absent = off
         ('--render_size', dict(type=int, nargs=2, default=None)),
         ('--sample_points', dict(type=str, default=None)),
+        # not in the reference: every pair's depth map as points in space (DepthPipeline.point_cloud), and the pair forward-warped
+        # to the camera of an .npz settings file - K, R, t, size, optional scale - (DepthPipeline.reproject), written to out_path
+        ('--point_cloud', dict(action='store_true')),
+        ('--reproject', dict(type=str, default=None)),
     ],
 }
 

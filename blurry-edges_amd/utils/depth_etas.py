@@ -36,10 +36,18 @@ class DepthEtas:
         self.intercept = icpt.to(device)
         self.theta_mid = th_mid.to(device)
         self.theta_wng = th_wng.to(device)
+        # the pinhole focal length of the pixels the pipeline sees (pitch pixel_pitch * mag), in pixels: 4709.9 at the defaults
+        self.focal_px = self.s / (cam['pixel_pitch'] * args.mag)
 
     @property
     def consts(self):
         return self._consts
+
+    def intrinsics(self, H, W):
+        """The pinhole camera an H x W image of the pipeline belongs to (be_hip.camera.Pinhole): fy = fx = focal_px, the optical
+        axis through the middle of the image, pixel centres at the integers."""
+        from be_hip import camera
+        return camera.Pinhole(self.focal_px, self.focal_px, (H - 1) / 2, (W - 1) / 2)
 
     def etas2depth(self, eta1, eta2):
         if not (eta1.is_cuda or eta2.is_cuda):

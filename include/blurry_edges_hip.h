@@ -221,6 +221,28 @@ int be_fold_refocus_stack_points_f32(const be_render_opts* opts_host, const be_d
                                      int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs,
                                      const float* points, int64_t N, const float* rho_primes, int K, float* out, void* stream);
 
+/* Forward, depth-dependent reprojection ("align depth to colour"): the depth map of a pinhole camera, and channels that ride on
+ * it, as another pinhole camera sees them.  depth [Hs,Ws] float32 on the device, metres along the optical axis, sample (iy, ix)
+ * at (y, x) = (top + iy / scale, left + ix / scale) in source pixels - the coordinate of the *_at entries (scale 1: the
+ * pixels).  cam_src, cam_dst: 4 host floats (fy, fx, cy, cx), pixel centres at the integers.  pose: 12 host floats, row-major R
+ * [3,3] then t [3], X' = R X + t from the source frame to the target frame.  All arithmetic is fp32, one rounding per
+ * operation, in this order:
+ *   xn = (x - cx) / fx, yn = (y - cy) / fy;  X = xn * Z, Y = yn * Z;  Xd = ((r00 X + r01 Y) + r02 Z) + t0 (Yd, Zd likewise);
+ *   u = (fxd Xd) / Zd + cxd, v = (fyd Yd) / Zd + cyd;  fu = floorf(u + 0.5f), fv = floorf(v + 0.5f).
+ * be_unproject_f32: xyz [3,Ns] = (Xd, Yd, Zd), Ns = Hs * Ws; 0 in all three where Z is not a finite number > 0.
+ * be_reproject_f32: a sample takes part iff Z > 0 and finite, near < Zd < inf, 0 <= fu < Wo and 0 <= fv < Ho (tested in fp32; NaN
+ * fails).  Per target pixel the sample with the smallest key (bits of Zd) << 32 | source linear index wins: the nearest
+ * surface, and on equal Zd the lowest source index - a minimum, so the outputs do not depend on the order of execution.
+ * depth_out [Ho,Wo] its Zd, index [Ho,Wo] its linear index iy * Ws + ix, feat_out [C,Ho*Wo] gathered from feat [C,Ns]
+ * (C >= 0; both may be NULL when C == 0); where nothing landed +0, -1, +0.  Every output element is written exactly once.
+ * zbuf: [Ho*Wo] 64-bit words of device scratch; the entry sets it to all-ones, splats and resolves, all on `stream`.
+ * 1 <= Ns, Ho*Wo <= 2^31 - 1 (the index map is int32); 1 <= scale <= BE_RENDER_AT_MAX_SCALE; near >= 0. */
+int be_unproject_f32(const float* depth, int Hs, int Ws, int scale, int top, int left, const float* cam_src, const float* pose,
+                     float* xyz, void* stream);
+int be_reproject_f32(const float* depth, int Hs, int Ws, int scale, int top, int left, const float* cam_src, const float* cam_dst,
+                     const float* pose, float near, int Ho, int Wo, const float* feat, int C, uint64_t* zbuf, float* depth_out,
+                     int32_t* index, float* feat_out, void* stream);
+
 /* nn.Unfold(21, stride) in the order blurry_edges_test.py:120-121 consumes it:
  * img [B,C,H,W] -> out [B, Hp*Wp, C, 21, 21], patch (i,j) = rows stride*i.., cols stride*j.., index i*Wp+j. */
 int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream);
