@@ -159,6 +159,7 @@ _SIGNATURES = {
                                          + [_P, _P, _P, C.c_int64, _P, C.c_int, _P, _P]),
     "be_unproject_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float)] * 2 + [_P, _P]),
     "be_reproject_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float)] * 3 + [C.c_float, C.c_int, C.c_int, _P, C.c_int] + [_P] * 4 + [_P]),
+    "be_fill_nearest_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int] + [_P] * 4 + [_P]),
     "be_unfold_patches_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "be_local_features_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "be_global_denorm_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
@@ -1275,6 +1276,59 @@ def reproject(depth, cam_src, cam_dst, pose, size, feat=None, near=1e-3, scale=1
                                      near, Ho, Wo, dptr(feat if C_ else None), C_, dptr(zbuf, "zbuf", (torch.int64,)), dptr(d),
                                      dptr(index), dptr(f if C_ else None), stream_ptr(dev)), "be_reproject_f32")
     return dict(depth=d, index=index, valid=index >= 0, feat=f)
+
+
+FILL_MAX_SIDE, FILL_MAX_SMOOTH = 16384, 8
+
+
+def fill_nearest(depth, weight=None, smooth=2, sigma_z=0.02, fuse=True):
+    """Dense depth from sparse samples: depth [H,W] float32 on the GPU, weight [H,W] (None: 1 everywhere).  A pixel is a seed iff
+    its weight is > 0 and its depth a finite number > 0; every other pixel takes the depth of the seed jump flooding assigns it -
+    the nearest seed on almost every pixel, a near-nearest one on the rest (fill.nearest_seed; ties to the lower index).
+    smooth = r in 0..8: 0 copies the seed's depth, r > 0 takes the robust mean of the seeds within r of it, weighted
+    w / (1 + ((z - z_seed) / sigma_z)^2).  -> dict(depth [H,W]: the input at seeds, the filled depth at holes; index [H,W] int32:
+    the seed's linear index y * W + x; dist2 [H,W] int32: the squared distance to it); 0 / -1 / -1 everywhere when there is no
+    seed.  fuse: run the last passes (steps <= 8) as one launch over LDS tiles - the same integers either way.  The result is a
+    function of the inputs alone; fill.fill_nearest_f32 is the host statement, bit for bit.  General: with depth=out["depth"],
+    weight=out["valid"] (a bool mask counts as weights 1 / 0) it closes the holes of a reproject result."""
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 2 or depth.numel() == 0:
+        raise ValueError(f"fill_nearest: depth must be a float32 tensor [H,W], got "
+                         f"{getattr(depth, 'dtype', type(depth).__name__)} {tuple(getattr(depth, 'shape', ()))}")
+    if not depth.is_cuda:
+        raise ValueError("fill_nearest: depth is not on the GPU; nothing here computes on the CPU (fill.fill_nearest_f32 is the host statement)")
+    H, W = depth.shape
+    if H > FILL_MAX_SIDE or W > FILL_MAX_SIDE:
+        raise ValueError(f"fill_nearest: H and W must be at most {FILL_MAX_SIDE} (squared distances are int32), got {H} x {W}")
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dtype not in (torch.float32, torch.bool) or tuple(weight.shape) != (H, W):
+            raise ValueError(f"fill_nearest: weight must be a float32 (or bool: a mask) tensor [{H},{W}], got "
+                             f"{getattr(weight, 'dtype', type(weight).__name__)} {tuple(getattr(weight, 'shape', ()))}")
+        if weight.device != depth.device:
+            raise ValueError(f"fill_nearest: weight is on {weight.device}, depth on {depth.device}")
+        weight = weight.to(torch.float32).contiguous()
+    if isinstance(smooth, bool) or not isinstance(smooth, int) or not 0 <= smooth <= FILL_MAX_SMOOTH:
+        raise ValueError(f"fill_nearest: smooth must be an integer in [0, {FILL_MAX_SMOOTH}], got {smooth!r}")
+    try:
+        sigma_z = float(sigma_z)
+    except (TypeError, ValueError):
+        sigma_z = -1.0
+    if not 0 < sigma_z < float("inf"):
+        raise ValueError("fill_nearest: sigma_z must be a finite number > 0")
+    depth = depth.contiguous()
+    fuse = bool(fuse)
+    o = ops()
+    if o is not None:
+        d, index, dist2 = o.fill_nearest(depth, weight, smooth, sigma_z, fuse)
+    else:
+        dev = depth.device
+        scratch = torch.empty(3 if smooth > 0 else 2, H, W, dtype=torch.int32, device=dev)
+        d = torch.empty(H, W, dtype=torch.float32, device=dev)
+        index = torch.empty(H, W, dtype=torch.int32, device=dev)
+        dist2 = torch.empty(H, W, dtype=torch.int32, device=dev)
+        check(lib().be_fill_nearest_f32(dptr(depth, "depth", (torch.float32,)), dptr(weight), H, W, smooth, sigma_z, int(fuse),
+                                        dptr(scratch, "scratch", (torch.int32,)), dptr(d), dptr(index, "index", (torch.int32,)),
+                                        dptr(dist2, "dist2", (torch.int32,)), stream_ptr(dev)), "be_fill_nearest_f32")
+    return dict(depth=d, index=index, dist2=dist2)
 
 
 def unfold_patches(img: torch.Tensor, stride: int = 2) -> torch.Tensor:

@@ -436,6 +436,40 @@ class DepthPipeline:
         return res
 
 
+    # ---- dense depth: the holes of depth_map closed by nearest-sample flood fill ---------------------------------------------
+    @torch.no_grad()
+    def complete(self, maps, smooth=2, sigma_z=0.02):
+        """maps: what __call__, run_big or run_any returned (maps["depth_map"], maps["conf"] are read) -> a dense depth map.
+        depth_map holds depth only where conf passes the threshold, a band on both sides of every boundary; the nearest sample of a
+        hole therefore lies on the hole's own side of the nearest boundary, and every hole takes the depth of its nearest sample
+        (native.fill_nearest: jump flooding, weights conf; smooth = r > 0 replaces a sample's depth by the conf-weighted robust mean
+        of the samples within r of it, which averages their noise down; sigma_z in metres).  -> depth_dense [H,W] (depth_map itself
+        wherever it is a finite number > 0 under conf > 0), measured [H,W] bool (those pixels), index [H,W] int32 (the sample's linear
+        index y * W + x, the pixel's own where measured) and dist [H,W] float32 (pixels to that sample; -1, with index -1 and depth 0,
+        when the pair has no sample at all).  Nothing synchronises with the host.  Under densify == 'pp' or 'w' depth_map is already
+        dense: it is returned unchanged, every pixel measured.
+        native.fill_nearest is general: with depth=out["depth"], weight=out["valid"] it also closes the holes of a reproject
+        result - a separate call, because a disocclusion wants a rule that prefers the background, which this one is not."""
+        if not isinstance(maps, dict) or "depth_map" not in maps or "conf" not in maps:
+            missing = [k for k in ("depth_map", "conf") if not isinstance(maps, dict) or k not in maps]
+            raise ValueError(f"complete: maps lacks {missing}; pass the dict DepthPipeline.__call__, run_big or run_any returned")
+        z, conf = maps["depth_map"], maps["conf"]
+        for k, t in (("depth_map", z), ("conf", conf)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f"complete: maps['{k}'] is not on the GPU; nothing here computes on the CPU "
+                                 "(keep the dict the pipeline returned, or move it back to the device)")
+        if z.dim() != 2 or conf.shape != z.shape:
+            raise ValueError(f"complete: depth_map and conf must be [H,W], got {tuple(z.shape)} and {tuple(conf.shape)}")
+        if self.densify in ("pp", "w"):
+            H, W = z.shape
+            return dict(depth_dense=z, measured=torch.ones_like(z, dtype=torch.bool),
+                        index=torch.arange(H * W, dtype=torch.int32, device=z.device).view(H, W), dist=torch.zeros_like(z))
+        out = native.fill_nearest(z, conf, smooth=smooth, sigma_z=sigma_z)
+        d2 = out["dist2"]
+        return dict(depth_dense=out["depth"], measured=d2 == 0, index=out["index"],
+                    dist=torch.where(d2 >= 0, d2.to(torch.float32).sqrt(), torch.full_like(z, -1.0)))
+
+
 def _points_on(points, device, who):
     """points: a tensor or array-like [...,2] of (y, x) -> float32, on `device` when one is given."""
     try:

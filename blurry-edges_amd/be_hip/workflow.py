@@ -13,6 +13,7 @@ formats (argument names and defaults = utils/args.py of the reference):
     ... eval --sample_points FILE.npy [--out_path DIR]     also write every pair's maps at the [N,2] (y, x) positions of FILE
     ... eval --point_cloud [--out_path DIR]                also write every pair's depth map as points in space
     ... eval --reproject CAM.npz [--out_path DIR]          also write every pair's depth and colours as the camera of CAM sees them
+    ... eval --complete [--out_path DIR]                   also write and score every pair's depth map completed to a dense one
 
 Data parallel (BASELINE configs[4]): the two training commands run under torchrun, one process per GPU -
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m be_hip.workflow local_train ...
@@ -342,7 +343,11 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     to {args.out_path}/cloud_{j:04d}.npz (xyz [3,H,W], valid, shpd, conf); args.reproject = an .npz file of settings (load_camera: K,
     R, t, size, optional scale): the pair forward-warped to that camera, DepthPipeline.reproject, goes to
     {args.out_path}/reproj_{j:04d}.npz (depth, valid, index, shpd, refoc at `size`).  Both outside the timed region, with the
-    depth threshold of the mode."""
+    depth threshold of the mode.
+    args.complete (not in the reference): every pair's depth_map completed to a dense one, DepthPipeline.complete, goes to
+    {args.out_path}/complete_{j:04d}.npz (depth_dense, measured, index, dist), outside the timed region; one more metrics line per
+    pair and in the average scores depth_dense with the same utils.eval_depth call, and the averages are returned under the key
+    `dense`.  Without the flag, output and return value are what they were."""
     import data, models, utils
     from .pipeline import DepthPipeline
     dev = _device(args)
@@ -374,7 +379,8 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     cloud, rcam = getattr(args, "point_cloud", False), getattr(args, "reproject", None)
     if rcam is not None:
         rcam = load_camera(rcam)
-    if rsize is not None or spoints is not None or cloud or rcam is not None:
+    complete = getattr(args, "complete", False)
+    if rsize is not None or spoints is not None or cloud or rcam is not None or complete:
         os.makedirs(args.out_path, exist_ok=True)
     fine_maps, fine_thres = ("shpd", "refoc", "bndry", "depth", "conf"), 0.05 if (big or any_size) else None
     sweep = None
@@ -382,7 +388,7 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
         sweep = focus_sweep(pipe.dcal, args.refocus_stack, *args.focus_range)
         os.makedirs(args.out_path, exist_ok=True)
         np.save(os.path.join(args.out_path, "rho_primes.npy"), sweep.astype(np.float32))
-    tot = np.zeros(5)
+    tot, tot_dense = np.zeros(5), np.zeros(5)
     secs = 0.0
     for j in range(len(ds)):
         img_ny, gt = ds[j]
@@ -425,11 +431,24 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
         if not quiet:
             print(f'Image pair #{j}: delta1 ={m[0]: .3f}, delta2 ={m[1]: .3f}, delta3 ={m[2]: .3f}, RMSE ={m[3]: .3f} cm, '
                   f'AbsRel ={m[4]: .3f} cm')
+        if complete:
+            done = pipe.complete(maps)
+            np.savez(os.path.join(args.out_path, f"complete_{j:04d}.npz"), **{k: v.cpu().numpy() for k, v in done.items()})
+            dense = done["depth_dense"][None]
+            m = np.array(utils.eval_depth(dense, gt[None].to(dense.dtype), dense, crop=args.crop))
+            tot_dense += m
+            if not quiet:
+                print(f'Image pair #{j} (completed): delta1 ={m[0]: .3f}, delta2 ={m[1]: .3f}, delta3 ={m[2]: .3f}, RMSE ={m[3]: .3f} cm, '
+                      f'AbsRel ={m[4]: .3f} cm')
     n = max(len(ds), 1)
     res = dict(zip(("delta1", "delta2", "delta3", "RMSE", "AbsRel"), (tot / n).tolist()), seconds_per_pair=secs / n)
     if not quiet:
         print(f'\nAverage running time:{secs / n: .3f} s')
         print('Average metrics for whole dataset: ' + ', '.join(f'{k} ={v: .3f}' for k, v in res.items() if k != "seconds_per_pair"))
+    if complete:
+        res["dense"] = dict(zip(("delta1", "delta2", "delta3", "RMSE", "AbsRel"), (tot_dense / n).tolist()))
+        if not quiet:
+            print('Average metrics for whole dataset (completed): ' + ', '.join(f'{k} ={v: .3f}' for k, v in res["dense"].items()))
     return res
 
 

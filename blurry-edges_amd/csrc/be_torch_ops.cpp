@@ -657,6 +657,26 @@ std::tuple<Tensor, Tensor, Tensor> reproject(const Tensor& depth, const Tensor& 
     return {dout, index, fout};
 }
 
+// nearest-sample flood fill: depth [H,W], weight [H,W] or None -> (depth_out [H,W], index [H,W] int32, dist2 [H,W] int32); the seed
+// maps and the per-seed means are scratch allocated here
+std::tuple<Tensor, Tensor, Tensor> fill_nearest(const Tensor& depth, const c10::optional<Tensor>& weight, int64_t smooth_r, double sigma_z,
+                                                bool fuse) {
+    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.size(0) <= 16384 && depth.size(1) <= 16384,
+                "fill_nearest: depth [H,W], 1 <= H, W <= 16384");
+    TORCH_CHECK(smooth_r >= 0 && smooth_r <= 8, "fill_nearest: smooth_r must be in [0, 8]");
+    fp(depth, "depth");
+    const int64_t H = depth.size(0), W = depth.size(1);
+    if (weight.has_value() && weight->defined())
+        TORCH_CHECK(weight->sizes() == depth.sizes() && weight->device() == depth.device(), "fill_nearest: weight [H,W] on depth's device");
+    auto o = depth.options();
+    Tensor scratch = at::empty({smooth_r > 0 ? 3 : 2, H, W}, o.dtype(at::kInt));
+    Tensor dout = at::empty({H, W}, o), index = at::empty({H, W}, o.dtype(at::kInt)), dist2 = at::empty({H, W}, o.dtype(at::kInt));
+    check(be_fill_nearest_f32(depth.data_ptr<float>(), fpo(weight, "weight"), (int)H, (int)W, (int)smooth_r, (float)sigma_z, fuse ? 1 : 0,
+                              scratch.data_ptr<int32_t>(), dout.data_ptr<float>(), index.data_ptr<int32_t>(), dist2.data_ptr<int32_t>(),
+                              stream_of(depth)), "be_fill_nearest_f32");
+    return {dout, index, dist2};
+}
+
 // LocalLoss forward + analytic backward in one launch -> (partial [B,3], grad_est [B,10] or an empty tensor)
 std::tuple<Tensor, Tensor> local_loss(const Tensor& opts, const Tensor& est, const Tensor& img_fit, const Tensor& gt, const Tensor& bdist,
                                       const Tensor& deri, double beta_b, double beta_s, bool want_grad) {
@@ -782,6 +802,7 @@ TORCH_LIBRARY(be, m) {
     m.def("fold_refocus_stack_points(Tensor opts, Tensor consts, Tensor records, Tensor rho_primes, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, Tensor points) -> Tensor");
     m.def("unproject(Tensor depth, Tensor cam_src, Tensor pose, int scale, int top, int left) -> Tensor");
     m.def("reproject(Tensor depth, Tensor cam_src, Tensor cam_dst, Tensor pose, float near, int Ho, int Wo, Tensor? feat, int scale, int top, int left) -> (Tensor, Tensor, Tensor)");
+    m.def("fill_nearest(Tensor depth, Tensor? weight, int smooth_r, float sigma_z, bool fuse) -> (Tensor, Tensor, Tensor)");
     m.def("local_loss(Tensor opts, Tensor est, Tensor img_fit, Tensor gt, Tensor bdist, Tensor deri, float beta_b, float beta_s, bool want_grad) -> (Tensor, Tensor)");
     m.def("local_loss_finish(Tensor partial, float beta_b, float beta_s) -> Tensor");
     m.def("global_loss(Tensor opts, Tensor consts, Tensor est, Tensor img_fit, Tensor img_gt, Tensor G, Tensor Gd, Tensor Gb, Tensor bdist, Tensor deri, "
@@ -841,6 +862,7 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("fold_refocus_stack_points", fold_refocus_stack_points);
     m.impl("unproject", unproject);
     m.impl("reproject", reproject);
+    m.impl("fill_nearest", fill_nearest);
     m.impl("local_loss", local_loss);
     m.impl("local_loss_finish", local_loss_finish);
     m.impl("global_loss", global_loss);

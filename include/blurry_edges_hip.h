@@ -243,6 +243,24 @@ int be_reproject_f32(const float* depth, int Hs, int Ws, int scale, int top, int
                      const float* pose, float near, int Ho, int Wo, const float* feat, int C, uint64_t* zbuf, float* depth_out,
                      int32_t* index, float* feat_out, void* stream);
 
+/* Dense depth from sparse samples by nearest-sample flood fill.  depth [H,W] float32 on the device; weight [H,W] float32 or NULL
+ * (weight 1 everywhere).  Pixel p is a seed iff weight[p] > 0, depth[p] > 0 and depth[p] < inf (NaN fails all three).  Every pixel
+ * is given a seed by jump flooding: an int32 seed map holds each pixel's current seed as the linear index y * W + x (-1: none); one
+ * pass with step s gives each pixel, of the nine positions p + (dy, dx) s (dy, dx in {-1, 0, 1}) inside the image that hold a seed,
+ * the candidate c with the smallest key (d2(p, c), c), d2 the integer squared distance - ties to the lower index; passes are double
+ * buffered.  The steps are 1, 2^(L-1), .., 4, 2, 1 with L = ceil(log2(max(H, W))) ("1+JFA"; a 1 x 1 image: the single step 1).  The
+ * assignment is the nearest seed on almost every pixel and a near-nearest one on the rest (jump flooding is approximate).
+ * fuse = 1 runs the final run of steps <= 8 as one launch over LDS tiles with a 15-pixel halo, fuse = 0 one launch per pass: the
+ * same integers either way.  smooth_r = r in 0..8: a seed keeps its depth bit for bit; r = 0: a hole takes its seed's depth;
+ * r > 0: a hole with seed s takes num / den over the seeds q of the window [sy-r, sy+r] x [sx-r, sx+r] clipped to the image, in
+ * row-major order, fp32 with one rounding per operation: d = z_q - z_s; k = w_q / (1 + (d d) inv), inv = 1 / (sigma_z sigma_z);
+ * num += k z_q; den += k.  Outputs [H,W]: depth_out (the input at seeds, the filled depth at holes), index int32 (the seed's linear
+ * index; the pixel's own at a seed), dist2 int32 (the squared distance to it; 0 at a seed); with no seed in the image 0, -1, -1.
+ * Every output element is written exactly once; nothing synchronises with the host.  scratch: device memory for 2 H W int32 (the
+ * two seed maps), and H W float32 more when smooth_r > 0 (the per-seed means).  1 <= H, W <= 16384; sigma_z > 0; fuse 0 or 1. */
+int be_fill_nearest_f32(const float* depth, const float* weight, int H, int W, int smooth_r, float sigma_z, int fuse,
+                        int32_t* scratch, float* depth_out, int32_t* index, int32_t* dist2, void* stream);
+
 /* nn.Unfold(21, stride) in the order blurry_edges_test.py:120-121 consumes it:
  * img [B,C,H,W] -> out [B, Hp*Wp, C, 21, 21], patch (i,j) = rows stride*i.., cols stride*j.., index i*Wp+j. */
 int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream);
