@@ -102,6 +102,9 @@ _SIGNATURES = {
     "be_gemm_rows_bf6_packed_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "be_gemm_rows_bf6_pack_f32": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "be_gemm_rows_bf6_f32": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P]),
+    "be_conv3x3_pm_bf6_packed_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "be_conv3x3_pm_bf6_pack_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "be_conv3x3_pm_bf6_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
     "be_wino_pair_workspace_floats": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "be_wino_conv3x3_pair_6x6_f32": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P,
                                                C.c_size_t, _P]),
@@ -756,6 +759,29 @@ def gemm_rows_bf6(x, planes, n, bias=None, residual=None, act=0, out=None):
     y = torch.empty(m, n, dtype=torch.float32, device=x.device) if out is None else out
     check(lib().be_gemm_rows_bf6_f32(dptr(x, "x"), m, k, dptr(planes), n, dptr(bias), dptr(residual), int(act), dptr(y), y.shape[-1],
                                      stream_ptr(x.device)), "be_gemm_rows_bf6_f32")
+    return y
+
+
+def conv3x3_pm_bf6_pack(pw, cout, cin, cin2=0):
+    """pw: the packed fp32 matrix [96][9 cin + cin2] of a 3x3 convolution (conv_pack) or of a 3x3 + 1x1 pair (conv_pack_fused2)
+    -> its hi / mid / lo bf16 planes (as float32 storage) for conv3x3_pm_bf6."""
+    nfl = lib().be_conv3x3_pm_bf6_packed_floats(cout, cin, cin2)
+    if nfl == 0:
+        raise RuntimeError(f"conv3x3_pm_bf6_pack: unsupported shape cout={cout} cin={cin} cin2={cin2}")
+    planes = torch.empty(nfl, dtype=torch.float32, device=pw.device)
+    check(lib().be_conv3x3_pm_bf6_pack_f32(dptr(pw, "pw"), cout, cin, cin2, dptr(planes), stream_ptr(pw.device)),
+          "be_conv3x3_pm_bf6_pack_f32")
+    return planes
+
+
+def conv3x3_pm_bf6(x, planes, pb, cout, act=0, x2=None, out=None):
+    """x [N,H,W,Cin] NHWC -> act(conv3x3(x) (+ conv1x1(x2)) + bias) [N,H,W,cout] in split-bf16 arithmetic; out = an [N,H,W,ld]
+    tensor whose first cout channels receive it."""
+    n, h, w, cin = x.shape
+    y = torch.empty(n, h, w, cout, dtype=torch.float32, device=x.device) if out is None else out
+    d = ConvDesc(n, h, w, cin, cout, 3, int(act))
+    check(lib().be_conv3x3_pm_bf6_f32(C.byref(d), dptr(x, "x"), dptr(x2), 0 if x2 is None else x2.shape[-1], dptr(planes), dptr(pb),
+                                      dptr(y), y.shape[-1], stream_ptr(x.device)), "be_conv3x3_pm_bf6_f32")
     return y
 
 

@@ -87,6 +87,13 @@ int vec_add_inplace(float* a, const float* b, int n, void* stream);
 int conv_pm(const be_conv_desc* d, const float* x, int wrow, const float* x2, int cin2, const float* pw, const float* pb,
             float* y, int ldy, int ktot, void* stream);
 
+// be_conv_pm_bf6.hip: the pixel-major 3x3 convolution (+ fused 1x1 on x2) for cout_pad32 = 96 in split-bf16 arithmetic on the planes
+// of be_conv3x3_pm_bf6_pack_f32, any n >= 1: the body of be_conv3x3_pm_bf6_f32 (LocalStage's layer0 on the Winograd path).
+// l0_bf6_enabled(): false under BE_L0_F32=1 or BE_WINO_F32=1 (read once per process)
+int conv3x3_pm_bf6(const be_conv_desc* d, const float* x, const float* x2, int cin2, const float* planes, const float* bias,
+                   float* y, int ldy, void* stream);
+bool l0_bf6_enabled();
+
 // be_wino.hip: be_wino_conv3x3_pair_6x6_f32; pool2 = 1 writes the 2x2 max-pool of the block's output, [n,3,3,cout]
 int wino_pair(const float* x, const float* packed_w1, const float* packed_bias1, int act1, const float* packed_w2,
               const float* packed_bias2, const float* residual, int act2, float* y, int64_t n, int cin, int cmid, int cout,

@@ -1,0 +1,309 @@
+// Pixel-major 3x3 convolution (optionally with a fused 1x1 on x2) for Cout <= 96 in split-bf16 arithmetic (gfx950): LocalStage's
+// layer0 wherever the Winograd path runs.
+//
+// k_conv_pm<., ., PM_TAPS3>'s tile and K walk (be_conv_pm.hip) around k_wino_gemm_ps's loop (be_wino.hip):
+//   - one output pixel of BM = 128 consecutive images per workgroup, so the list of taps inside the image is wave-uniform: taps
+//     outside are skipped for the whole tile, nothing is zero-filled; interior pixels first, the border ring last; a group's pixel
+//     tiles stay on one XCD; the K walk (32-channel chunk, valid tap, 16-float half), then the 16-float chunks of the 1x1 on x2, is
+//     scalar arithmetic; A goes global -> LDS by global_load_lds_dwordx4 in 1-KB pieces with the quads XOR-swizzled; rows past
+//     the batch load a valid row and are never stored;
+//   - A stays fp32 in HBM and LDS and is split after the fragment read (split8); B's hi / mid / lo planes are read ready-made
+//     from the 12-KB blocks of be_gemm_rows_bf6_pack_f32 applied to the packed fp32 matrix [96][Ktot] (whose K order is the
+//     walk's order: chunk = (cc * 9 + tap) * 2 + half, the 1x1 behind ncc * 9 * 2); six v_mfma_f32_32x32x16_bf16 per 16-deep
+//     chunk in the fixed order lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi, fp32 accumulation, K ascending from a zero
+//     accumulator; a ring of four 20-KB stages (80 KB: two workgroups per CU) with the DMA three chunks ahead, counted vmcnt
+//     waits and one raw s_barrier per chunk; the next chunk's fragments are read and split behind the current chunk's MFMAs.
+// Wave tile 32 images x 96 channels (all MFMAs useful: three 32-column accumulators, one A fragment): per chunk a wave issues
+// 18 MFMAs for 2 + 9 fragment reads, one split8 and 5 DMA pieces (2 A + 3 B) - the SAME five in the tap segment and in the x2
+// segment, which is what "vmcnt(5)" = "all but the newest chunk have landed" relies on.  Past the end of the walk the last chunk
+// is fetched again (into slots nobody reads any more), so the count never changes; the last wait drains everything: no DMA into
+// LDS outlives the workgroup.
+// One body for every batch size: an output element sees the same chain of operations whatever the batch, the position in it or
+// the tile it falls in.
+#include "be_common.h"
+#include "be_device_math.h"
+#include "be_split_bf16.h"
+#include <cstdlib>
+
+namespace {
+
+using be::bf6::bf16x8;
+using be::bf6::f32x4;
+using be::bf6::split8;
+using be::bf6::PS_BLOCK;
+using be::bf6::ps_slot;
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef const __attribute__((address_space(1))) void* glb_ptr_t;
+
+constexpr int L0_BM = 128, L0_BKT = 16, L0_STAGES = 4;
+constexpr int L0_ABYTES = L0_BM * L0_BKT * 4, L0_BBYTES = PS_BLOCK * 2, L0_STAGE = L0_ABYTES + L0_BBYTES;   // 8 KB + 12 KB
+
+struct PmBf6Args {
+    const float* x;       // NHWC [N,H,W,Cin]
+    const float* x2;      // optional second input [N,H,W,Cin2]: its 1x1 conv is appended to the K loop
+    const float* planes;  // hi / mid / lo blocks of the packed [96][Ktot] matrix, one 12-KB block per 16-deep chunk
+    const float* bias;
+    float* y;             // NHWC [N,H,W,ldy]
+    int Nimg, H, W, HW, Cin, Cin2, Cout, ldy, act, groups, ncc;
+    int64_t istride, istride2;      // floats per image in x / x2
+};
+
+__global__ __launch_bounds__(256, 2)
+void k_conv_pm_bf6(PmBf6Args a) {
+    constexpr int BM = L0_BM, BKT = L0_BKT, NS = L0_STAGES, ABYTES = L0_ABYTES, BBYTES = L0_BBYTES, STAGE = L0_STAGE;
+    extern __shared__ __attribute__((aligned(16))) float smem_l0[];
+    char* const lds = reinterpret_cast<char*>(smem_l0);
+
+    // ---- workgroup -> (group of BM images, pixel): a group's pixel tiles stay on one XCD (shared input lines)
+    const int bid = blockIdx.x;
+    const int xcd = bid & 7, t = bid >> 3;
+    const int grp = (t / a.HW) * 8 + xcd;
+    if (grp >= a.groups) return;
+    const int img0 = grp * BM;
+    int py, px;
+    {   // interior pixels (all taps) first, the border ring (fewer taps) last: the short tiles fill the tail
+        const int idx = t % a.HW, ni = (a.H - 2) * (a.W - 2);
+        if (idx < ni) { py = 1 + idx / (a.W - 2); px = 1 + idx % (a.W - 2); }
+        else {
+            const int e = idx - ni;
+            if (e < a.W) { py = 0; px = e; }
+            else if (e < 2 * a.W) { py = a.H - 1; px = e - a.W; }
+            else if (e < 2 * a.W + a.H - 2) { px = 0; py = 1 + e - 2 * a.W; }
+            else { px = a.W - 1; py = 1 + e - 2 * a.W - (a.H - 2); }
+        }
+    }
+    // taps of the 3x3 kernel this pixel has inside the image, 4 bits each
+    unsigned long long tap_list = 0;
+    int ntap = 0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const bool ok = (unsigned)(py + k / 3 - 1) < (unsigned)a.H && (unsigned)(px + k % 3 - 1) < (unsigned)a.W;
+        if (ok) { tap_list |= (unsigned long long)k << (4 * ntap); ++ntap; }
+    }
+
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int li = lane & 31, lh = lane >> 5;
+    float bias_v[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int c = j * 32 + li;
+        bias_v[j] = (c < a.Cout && a.bias) ? a.bias[c] : 0.0f;
+    }
+    // ---- A staging: wave w fills pieces 2w, 2w+1 of the tile; lane -> (row lane >> 2 of the piece, the quad the swizzle puts there)
+    const int srow = lane >> 2, sq = (lane & 3) ^ ((lane >> 4) & 3);
+    unsigned a_off[2], a_off2[2];                      // byte offsets from the tile's first row
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int r = (2 * wave + p) * 16 + srow;
+        const int rr = img0 + r < a.Nimg ? r : 0;      // images past the batch: a valid image (never stored)
+        a_off[p] = (unsigned)(rr * a.istride + 4 * sq) * 4u;
+        a_off2[p] = (unsigned)(rr * a.istride2 + 4 * sq) * 4u;
+    }
+    const float* xpix = a.x + (int64_t)img0 * a.istride + (py * a.W + px) * a.Cin;
+    const float* x2pix = a.x2 ? a.x2 + (int64_t)img0 * a.istride2 + (py * a.W + px) * a.Cin2 : nullptr;
+    // B: pieces 3w .. 3w+2 of the chunk's 12-KB block, which is already the LDS image (lane-linear: this lane's 16 B)
+    const char* wt = reinterpret_cast<const char*>(a.planes) + lane * 16;
+
+    // ---- K walk: main part (cc, valid tap j, half), then the 1x1 on x2 (16-float chunks)
+    const int n_main = a.ncc * ntap * 2;
+    const int total = n_main + (a.x2 ? a.Cin2 / BKT : 0);
+    int w_cc = 0, w_j = 0, w_sub = 0, w_k = 0, l_buf = 0;      // walker state of the next chunk to load and its ring slot
+#define L0_DMA()                                                                                                \
+    do {                                                                                                        \
+        char* st_ = lds + l_buf * STAGE;                                                                        \
+        const char* xs_;                                                                                        \
+        int chunk_;                                                                                             \
+        unsigned o0_, o1_;                                                                                      \
+        if (w_k < n_main) {                                                                                     \
+            const int tap_ = (int)((tap_list >> (4 * w_j)) & 15ull);                                            \
+            const int ty_ = (tap_ * 11) >> 5, tx_ = tap_ - 3 * ty_;                    /* tap / 3, tap % 3 */     \
+            xs_ = reinterpret_cast<const char*>(xpix + ((ty_ - 1) * a.W + tx_ - 1) * a.Cin + w_cc * 32 + w_sub * BKT); \
+            chunk_ = (w_cc * 9 + tap_) * 2 + w_sub;                                                             \
+            o0_ = a_off[0]; o1_ = a_off[1];                                                                     \
+        } else {                                                                                                \
+            const int k2_ = w_k - n_main;                                                                       \
+            xs_ = reinterpret_cast<const char*>(x2pix + k2_ * BKT);                                             \
+            chunk_ = a.ncc * 18 + k2_;                                                                          \
+            o0_ = a_off2[0]; o1_ = a_off2[1];                                                                   \
+        }                                                                                                       \
+        __builtin_amdgcn_global_load_lds((glb_ptr_t)(xs_ + o0_), (lds_ptr_t)(st_ + (2 * wave) * 1024), 16, 0, 0);     \
+        __builtin_amdgcn_global_load_lds((glb_ptr_t)(xs_ + o1_), (lds_ptr_t)(st_ + (2 * wave + 1) * 1024), 16, 0, 0); \
+        const char* ws_ = wt + (int64_t)chunk_ * BBYTES;                                                        \
+        _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                        \
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(ws_ + (3 * wave + p_) * 1024),                         \
+                                             (lds_ptr_t)(st_ + ABYTES + (3 * wave + p_) * 1024), 16, 0, 0);     \
+        if (w_k + 1 < total) {                         /* past the end: the last chunk again */                  \
+            ++w_k;                                                                                              \
+            if (++w_sub == 2) { w_sub = 0; if (++w_j == ntap) { w_j = 0; ++w_cc; } }                            \
+        }                                                                                                       \
+        l_buf = (l_buf + 1) % NS;                                                                               \
+    } while (0)
+
+    // ---- fragment reads: A row 32 wave + li, quads 2 lh, 2 lh + 1 (swizzled as stored); B plane p, row 32 j + li, half lh
+    const int fsw = (li >> 2) & 3;
+    const int a_fr0 = ((wave * 32 + li) * BKT + 4 * ((2 * lh) ^ fsw)) * 4;
+    const int a_fr1 = ((wave * 32 + li) * BKT + 4 * ((2 * lh + 1) ^ fsw)) * 4;
+    const int b_fr = ABYTES + li * 32 + ps_slot(li, lh) * 16;
+    f32x16 acc[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+    // the pieces of the chunk being multiplied: read from LDS and split (A) while the chunk before is still on the matrix pipe
+    bf16x8 ap[3], bp[3][3];                            // [hi, mid, lo]([j])
+    int r_buf = 0;                                     // ring slot whose fragments are read next
+#define L0_FRAGS()                                                                                              \
+    do {                                                                                                        \
+        const char* sb_ = lds + r_buf * STAGE;                                                                  \
+        const f32x4 af0_ = *reinterpret_cast<const f32x4*>(sb_ + a_fr0);                                        \
+        const f32x4 af1_ = *reinterpret_cast<const f32x4*>(sb_ + a_fr1);                                        \
+        _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                        \
+            _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_)                                                    \
+                bp[p_][j_] = *reinterpret_cast<const bf16x8*>(sb_ + b_fr + p_ * 4096 + j_ * 32 * 32);           \
+        split8(af0_, af1_, ap[0], ap[1], ap[2]);                                                                \
+        r_buf = (r_buf + 1) % NS;                                                                               \
+    } while (0)
+
+    __builtin_amdgcn_sched_barrier(0);                 // (the bias loads are older than every DMA: no count below depends on them)
+    L0_DMA();                                          // chunk 0
+    L0_DMA();                                          // chunk 1
+    L0_DMA();                                          // chunk 2
+    __builtin_amdgcn_s_waitcnt(0x0F75);                // vmcnt(5): chunks 0 and 1 have landed
+    __builtin_amdgcn_s_barrier();                      // ... every wave's
+    L0_FRAGS();                                        // chunk 0's pieces
+    bool landed = true;                                // the NEXT chunk's DMA is known to be in LDS
+    for (int kc = 0; kc < total; ++kc) {
+        if (!landed) __builtin_amdgcn_s_waitcnt(0x0F75);                               // vmcnt(5): chunk + 1 has landed
+        landed = false;
+        __builtin_amdgcn_s_barrier();                  // ... every wave's; everyone has read the slot of chunk - 1 (a chunk ago)
+        L0_DMA();                                      // chunk + 3, into that slot
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi
+#pragma unroll
+            for (int p = 0; p < 6; ++p)
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[PA[p]], bp[PB[p]][j], acc[j], 0, 0, 0);
+            L0_FRAGS();                                // chunk + 1's pieces, under this chunk's MFMAs
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#undef L0_DMA
+#undef L0_FRAGS
+    __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): nothing left in flight into LDS
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- epilogue: D[row][col], col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); row = image of the group
+    const int64_t rs = (int64_t)a.HW * a.ldy;          // floats between the same pixel of consecutive images
+    char* yt = reinterpret_cast<char*>(a.y + ((int64_t)img0 * a.HW + py * a.W + px) * a.ldy);                 // uniform
+    const unsigned y_off = (unsigned)((wave * 32 + 4 * lh) * rs + li) * 4u;
+    const bool interior = img0 + BM <= a.Nimg && a.Cout == 96;
+#define L0_STORE(J)                                                                                             \
+    do {                                                                                                        \
+        float v_ = acc[J][r] + bias_v[J];                                                                       \
+        if (a.act == 1) v_ = be::smish(v_); else if (a.act == 2) v_ = fmaxf(v_, 0.0f);                          \
+        reinterpret_cast<float*>(yt + (size_t)ro * rs * 4 + y_off)[(J) * 32] = v_;                              \
+    } while (0)
+    if (interior) {                                    // no per-element bounds checks
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int ro = (r & 3) + 8 * (r >> 2);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) L0_STORE(j);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const bool c_ok = j * 32 + li < a.Cout;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int ro = (r & 3) + 8 * (r >> 2);
+                if (c_ok && img0 + wave * 32 + 4 * lh + ro < a.Nimg) L0_STORE(j);
+            }
+        }
+    }
+#undef L0_STORE
+}
+
+inline int ktot_of(int cin, int cin2) { return 9 * cin + cin2; }
+inline bool shape_ok(int cout, int cin, int cin2) {
+    return cout > 0 && (cout + 31) / 32 * 32 == 96 && cin > 0 && cin % 32 == 0 && cin2 >= 0 && cin2 % 16 == 0;
+}
+
+}  // namespace
+
+bool be::l0_bf6_enabled() {
+    // A/B knobs: BE_L0_F32=1 sends only layer0 back to the fp32 kernels; BE_WINO_F32=1 restores fp32 everywhere
+    static const bool f32 = (getenv("BE_L0_F32") != nullptr && atoi(getenv("BE_L0_F32")) != 0) ||
+                            (getenv("BE_WINO_F32") != nullptr && atoi(getenv("BE_WINO_F32")) != 0);
+    return !f32;
+}
+
+extern "C" size_t be_conv3x3_pm_bf6_packed_floats(int cout, int cin, int cin2) {
+    if (!shape_ok(cout, cin, cin2)) return 0;
+    return be_gemm_rows_bf6_packed_floats(cout, ktot_of(cin, cin2));
+}
+
+extern "C" int be_conv3x3_pm_bf6_pack_f32(const float* packed_w, int cout, int cin, int cin2, float* planes, void* stream) {
+    BE_REQUIRE(packed_w && planes, "be_conv3x3_pm_bf6_pack_f32: null pointer");
+    BE_REQUIRE(shape_ok(cout, cin, cin2),
+               "be_conv3x3_pm_bf6_pack_f32: unsupported shape (cout %d: cout_pad32 must be 96; cin %d %% 32; cin2 %d %% 16)", cout, cin, cin2);
+    return be_gemm_rows_bf6_pack_f32(packed_w, cout, ktot_of(cin, cin2), planes, stream);
+}
+
+int be::conv3x3_pm_bf6(const be_conv_desc* d, const float* x, const float* x2, int cin2, const float* planes, const float* bias,
+                       float* y, int ldy, void* stream) {
+    BE_REQUIRE(d && x && planes && y, "be_conv3x3_pm_bf6_f32: null pointer");
+    BE_REQUIRE(d->ksize == 3 && d->n >= 0 && (unsigned)d->act <= 2u, "be_conv3x3_pm_bf6_f32: bad descriptor (ksize %d, n %d, act %d)",
+               d->ksize, d->n, d->act);
+    BE_REQUIRE(x2 || cin2 == 0, "be_conv3x3_pm_bf6_f32: cin2 %d without x2", cin2);
+    BE_REQUIRE(shape_ok(d->cout, d->cin, cin2) && (!x2 || cin2 > 0),
+               "be_conv3x3_pm_bf6_f32: unsupported shape (cout %d: cout_pad32 must be 96; cin %d %% 32; cin2 %d %% 16)", d->cout, d->cin, cin2);
+    BE_REQUIRE(d->h >= 3 && d->w >= 3 && ldy >= d->cout, "be_conv3x3_pm_bf6_f32: unsupported map (h %d, w %d >= 3; ldy %d >= cout)",
+               d->h, d->w, ldy);
+    BE_REQUIRE(be::aligned16(x) && be::aligned16(x2) && be::aligned16(planes) && (reinterpret_cast<uintptr_t>(y) & 3u) == 0 &&
+               (!bias || (reinterpret_cast<uintptr_t>(bias) & 3u) == 0),
+               "be_conv3x3_pm_bf6_f32: x / x2 / planes must be 16-byte aligned, y / bias 4-byte");
+    if (d->n == 0) return BE_OK;
+    PmBf6Args a;
+    a.x = x; a.x2 = x2; a.planes = planes; a.bias = bias; a.y = y;
+    a.Nimg = d->n; a.H = d->h; a.W = d->w; a.HW = d->h * d->w; a.Cin = d->cin; a.Cin2 = x2 ? cin2 : 0; a.Cout = d->cout; a.ldy = ldy;
+    a.act = d->act; a.ncc = d->cin / 32;
+    a.istride = (int64_t)a.HW * d->cin;
+    a.istride2 = (int64_t)a.HW * a.Cin2;
+    // 32-bit lane offsets: 256 images of input / output must span < 2^32 bytes
+    const int64_t span = 256 * 4 * (a.istride > a.istride2 ? a.istride : a.istride2);
+    BE_REQUIRE(span < ((int64_t)1 << 32) && 256 * 4 * (int64_t)a.HW * ldy < ((int64_t)1 << 32),
+               "be_conv3x3_pm_bf6_f32: 256 images must span < 2^32 bytes");
+    a.groups = (d->n + L0_BM - 1) / L0_BM;
+    const int64_t grid = (int64_t)8 * ((a.groups + 7) / 8) * a.HW;
+    BE_REQUIRE(grid < ((int64_t)1 << 31), "be_conv3x3_pm_bf6_f32: too many tiles (n %d, %d x %d)", d->n, d->h, d->w);
+    hipStream_t s = be::as_stream(stream);
+    constexpr size_t lds = (size_t)L0_STAGES * L0_STAGE;
+    static be::DeviceFlags attr_set{};                      // dynamic-LDS cap raised once per device (thread-safe)
+    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_conv_pm_bf6), lds, attr_set)) return rc_;
+    {   // algorithmic work: 2*M*K*Cout with the real K, in fp32-equivalent products; executed: the chunks the tiles visit x 2*BM*96*16
+        const double M = (double)a.Nimg * a.HW, k_real = 9.0 * a.Cin, k2 = (double)a.Cin2;
+        double chunks = 0.0;
+        for (int py = 0; py < a.H; ++py)
+            for (int px = 0; px < a.W; ++px) {
+                int nt = 0;
+                for (int k = 0; k < 9; ++k) nt += (unsigned)(py + k / 3 - 1) < (unsigned)a.H && (unsigned)(px + k % 3 - 1) < (unsigned)a.W;
+                chunks += 2.0 * nt * a.ncc + a.Cin2 / 16;
+            }
+        chunks *= (double)a.groups;
+        be::ProfileScope prof(s, BE_KERNEL_CONV_128x96, 2.0 * M * (k_real + k2) * a.Cout,
+                              4.0 * (M * (a.Cin + k2) + M * a.Cout) + 6.0 * (k_real + k2) * 128,
+                              chunks * 2.0 * L0_BM * 96 * 16);
+        hipLaunchKernelGGL(k_conv_pm_bf6, dim3((unsigned)grid), dim3(256), lds, s, a);
+    }
+    return be::check_launch("be_conv3x3_pm_bf6_f32");
+}
+
+extern "C" int be_conv3x3_pm_bf6_f32(const be_conv_desc* desc_host, const float* x, const float* x2, int cin2, const float* planes,
+                                     const float* packed_bias, float* y, int ldy, void* stream) {
+    return be::conv3x3_pm_bf6(desc_host, x, x2, cin2, planes, packed_bias, y, ldy, stream);
+}

@@ -8,7 +8,8 @@
 // be_wino.hip), fc.1, fc.4.  Sub-batches of 512 patches and more take the LDS-DMA kernels (be_conv_pm.hip for conv1 on a
 // row-padded staging and for layer0, the row GEMM of be_wino.hip for the 1x1s and fc.1); smaller ones k_conv_igemm - same
 // results bit for bit.  On the Winograd path the 1x1 downsamples of layers 1-3 and fc.1 run in split-bf16 arithmetic on ONE kernel for
-// every sub-batch size (be::gemm_rows_bf6; BE_ROWS_F32=1 / BE_WINO_F32=1: the fp32 kernels just named).  No allocation, no
+// every sub-batch size (be::gemm_rows_bf6; BE_ROWS_F32=1 / BE_WINO_F32=1: the fp32 kernels just named), and so does layer0
+// (be::conv3x3_pm_bf6, be_conv_pm_bf6.hip; BE_L0_F32=1 / BE_WINO_F32=1: the fp32 kernels).  No allocation, no
 // synchronisation, no process-wide state: graph-capturable, re-entrant.  opts->winograd = 0 runs layers 1-3 as direct launches
 // like layer0, all in fp32.
 #include "be_common.h"
@@ -61,6 +62,9 @@ struct PackedLayout {
         for (int i = 0; i < 15; ++i) sw_off[i] = 0;
         for (int i : {6, 9, 12, 13}) {     // hi / mid / lo bf16 planes of the downsamples' and fc.1's packed matrices (split-bf16 row GEMMs)
             sw_off[i] = o; o += be_gemm_rows_bf6_packed_floats(kLayers[i].cout, kLayers[i].cin);
+        }
+        for (int i : {1, 2}) {             // layer0's two pixel-major 3x3 matrices (conv2's with the downsample's columns) likewise
+            sw_off[i] = o; o += be_conv3x3_pm_bf6_packed_floats(kLayers[i].cout, kLayers[i].cin, i == 2 ? kLayers[3].cin : 0);
         }
         total = o;
     }
@@ -138,6 +142,10 @@ extern "C" int be_local_stage_pack_f32(const float* const* t, float bn_eps, floa
         const float* src = packed + (i == 13 ? L.w_off[13] : L.dw_off[i]);
         if ((rc = be_gemm_rows_bf6_pack_f32(src, kLayers[i].cout, kLayers[i].cin, packed + L.sw_off[i], stream))) return rc;
     }
+    for (int i : {1, 2}) {                            // layer0: K order of the packed matrices = the pixel-major K walk
+        if ((rc = be_conv3x3_pm_bf6_pack_f32(packed + L.w_off[i], kLayers[i].cout, kLayers[i].cin, i == 2 ? kLayers[3].cin : 0,
+                                             packed + L.sw_off[i], stream))) return rc;
+    }
     return BE_OK;
 }
 
@@ -163,6 +171,16 @@ int block(const float* packed, int l0, const float* x, float* t, float* o, int n
     be_conv_desc d;
     d.n = n; d.h = hw; d.w = hw; d.cin = kLayers[l0 + 1].cin; d.cout = c; d.ksize = 3; d.act = 1;
     return be_conv_nhwc_fused2_f32(&d, t, x, kLayers[l0 + 2].cin, packed + L.w_off[l0 + 1], packed + L.b_off[l0 + 1], o, c, stream);
+}
+
+// layer0's block in split-bf16 arithmetic (be_conv_pm_bf6.hip): the same two launches on ONE kernel for every sub-batch size
+int block_l0_bf6(const float* packed, const float* x, float* t, float* o, int n, void* stream) {
+    const PackedLayout& L = layout();
+    be_conv_desc d;
+    d.n = n; d.h = 11; d.w = 11; d.cin = kLayers[1].cin; d.cout = 96; d.ksize = 3; d.act = 1;
+    if (int rc = be::conv3x3_pm_bf6(&d, x, nullptr, 0, packed + L.sw_off[1], packed + L.b_off[1], t, 96, stream)) return rc;
+    d.cin = kLayers[2].cin;
+    return be::conv3x3_pm_bf6(&d, t, x, kLayers[3].cin, packed + L.sw_off[2], packed + L.b_off[2], o, 96, stream);
 }
 
 // The same block on a 6x6 map with both 3x3 convolutions in Winograd F(3x3,3x3) form (be_wino.hip): 2.56x fewer multiplies
@@ -248,7 +266,9 @@ int forward_impl(const float* packed, const float* x, const be_patch_view* view,
         }
         if (!pooled && (rc = be_maxpool_nhwc_f32(ra, p1, nb, 21, 21, 64, 3, 2, 1, stream))) return rc;
         // layer0 @11x11: t in RA, out in RC
-        if ((rc = block(packed, 1, p1, ra, rc_, nb, 11, stream))) return rc;
+        // (Winograd path: split-bf16 at every sub-batch size; BE_L0_F32=1 / BE_WINO_F32=1 and opts->winograd = 0: the fp32 kernels)
+        if ((rc = (wino && be::l0_bf6_enabled()) ? block_l0_bf6(packed, p1, ra, rc_, nb, stream)
+                                                 : block(packed, 1, p1, ra, rc_, nb, 11, stream))) return rc;
         float* p2 = rb;                                   // nb*3456
         if ((rc = be_maxpool_nhwc_f32(rc_, p2, nb, 11, 11, 96, 3, 2, 1, stream))) return rc;
         // layer1: in RB, t RA, out RC

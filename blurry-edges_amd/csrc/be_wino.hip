@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include "be_common.h"
 #include "be_device_math.h"
+#include "be_split_bf16.h"
 #include "be_wino_math.h"
 
 namespace {
@@ -331,37 +332,11 @@ struct GemmArgs {
 };
 
 // ---- split-bf16 operands (BF6 = 1) --------------------------------------------------------------------------------------------
-// x = hi + mid + lo exactly, each a bf16 rounded to nearest-even from what is left: |mid| <= 2^-8 |x|, |lo| <= 2^-16 |x| (finite x
-// whose lo stays a bf16 normal, |x| >= ~2^-110; below that lo loses bits to the bf16 subnormal grid, an absolute error < 2^-133).
-// A product of two split operands is the six bf16 MFMAs of all pieces but mid.lo, lo.mid, lo.lo (<= 3 x 2^-24 relative), in fp32
-// accumulation.  Inf / NaN: hi keeps them, x - hi is NaN, so the products stay non-finite.  The residuals are formed with plain
-// v_sub_f32: hipcc's SLP pass otherwise packs them into v_pk_add_f32, which beside MFMAs costs more issue than two scalar ops.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ float sub_f32(float x, float y) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-}
-// the 8 values of two fp32 quads -> the hi / mid / lo fragments of one 32x32x16 bf16 MFMA operand
-__device__ __forceinline__ void split8(f32x4 a, f32x4 b, bf16x8& h, bf16x8& m, bf16x8& l) {
-    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int e = 0; e < 8; e += 2) {
-        const bf16x2 hb = __builtin_convertvector((f32x2){x[e], x[e + 1]}, bf16x2);          // v_cvt_pk_bf16_f32: RNE
-        const unsigned hu = __builtin_bit_cast(unsigned, hb);
-        const float r0 = sub_f32(x[e], bf_lo(hu)), r1 = sub_f32(x[e + 1], bf_hi(hu));        // exact
-        const bf16x2 mb = __builtin_convertvector((f32x2){r0, r1}, bf16x2);
-        const unsigned mu = __builtin_bit_cast(unsigned, mb);
-        const bf16x2 lb = __builtin_convertvector((f32x2){sub_f32(r0, bf_lo(mu)), sub_f32(r1, bf_hi(mu))}, bf16x2);   // exact
-        h[e] = hb[0]; h[e + 1] = hb[1];
-        m[e] = mb[0]; m[e + 1] = mb[1];
-        l[e] = lb[0]; l[e + 1] = lb[1];
-    }
-}
+// x = hi + mid + lo, the six products per K chunk and split8: be_split_bf16.h (shared with be_conv_pm_bf6.hip)
+using be::bf6::bf16x8;
+using be::bf6::split8;
+using be::bf6::PS_BLOCK;
+using be::bf6::ps_slot;
 
 // ---- the weights pre-split (round 8) -------------------------------------------------------------------------------------------
 // k_wino_pack_split writes the hi / mid / lo pieces of U behind it, formed by split8 - the very pieces k_wino_gemm<0, 1> forms in
@@ -369,9 +344,8 @@ __device__ __forceinline__ void split8(f32x4 a, f32x4 b, bf16x8& h, bf16x8& m, b
 // block [plane hi, mid, lo][128 rows][2 x 16 B], the 16-B half h of a row (k = 8 h .. 8 h + 7) at slot h ^ ((row >> 3) & 1).  With
 // the swap a ds_read_b128 of one half for 32 rows puts each 16-lane group (rows 0-3, 12-15, 20-27 / 4-11, 16-19, 28-31) on 16
 // distinct 16-B slots of the 256-B bank row: conflict-free.  Rows from cout_pad up to the 128-row tile are zero.
-constexpr int PS_BLOCK = 3 * 128 * 16;                 // bf16 values per block (12 KB)
+// (PS_BLOCK = 3 * 128 * 16 bf16 values per block and ps_slot: be_split_bf16.h)
 constexpr int PS_STAGES = 4;                           // k_wino_gemm_ps's LDS ring: 4 x 20 KB, two workgroups per CU (160 KB)
-__device__ __forceinline__ int ps_slot(int row, int half) { return half ^ ((row >> 3) & 1); }
 
 __global__ void k_wino_pack_split(const float* __restrict__ U, int npos, int cout_pad, int cin, int n_tiles, __bf16* __restrict__ P) {
     const int kg = cin / 8, rows = 128 * n_tiles;      // one thread = one (position, row, 8-deep K group); a plain matrix is npos = 1

@@ -481,6 +481,20 @@ int be_gemm_rows_bf6_pack_f32(const float* packed_w, int cout, int cin, float* p
 int be_gemm_rows_bf6_f32(const float* x, int64_t m, int k, const float* planes, int n, const float* bias, const float* residual,
                          int act, float* y, int ldy, void* stream);
 
+/* 3x3 convolution (pad 1) + bias + activation on NHWC maps, optionally with a 1x1 convolution of x2 appended to the K loop (the
+ * ResidualBlock tail of be_conv_nhwc_fused2_f32; x2 NULL and cin2 0: the plain convolution), in the same split-bf16 arithmetic (bf16x6)
+ * on a pixel-major kernel.  LocalStage's layer0 runs on it wherever the Winograd path runs; environment BE_L0_F32=1 (read once per
+ * process) sends layer0 back to the fp32 kernels (BE_WINO_F32=1 does too).  One kernel body for every n >= 1: an image's bits do not
+ * depend on the batch it is computed in.  Shapes: cout_pad32 == 96, cin %% 32 == 0, cin2 %% 16 == 0, h and w >= 3, 256 images spanning
+ * < 2^32 bytes; others return BE_EINVAL before any launch.  be_conv3x3_pm_bf6_pack_f32 reads the packed fp32 matrix [96][9 cin + cin2]
+ * of be_conv_pack_f32 / be_conv_pack_fused2_f32 and writes its hi / mid / lo bf16 planes in be_gemm_rows_bf6_pack_f32's block layout:
+ * be_conv3x3_pm_bf6_packed_floats = 1.5 x 128 x (9 cin + cin2) floats (0 for unsupported shapes).  The bias is the packed fp32 bias.
+ * x, x2, packed_w and planes 16-byte aligned. */
+size_t be_conv3x3_pm_bf6_packed_floats(int cout, int cin, int cin2);
+int be_conv3x3_pm_bf6_pack_f32(const float* packed_w, int cout, int cin, int cin2, float* planes, void* stream);
+int be_conv3x3_pm_bf6_f32(const be_conv_desc* desc_host, const float* x, const float* x2, int cin2, const float* planes,
+                          const float* packed_bias, float* y, int ldy, void* stream);
+
 /* nn.MaxPool2d(k, stride, pad) on NHWC (models/local_stage.py:42-43). */
 int be_maxpool_nhwc_f32(const float* x, float* y, int n, int h, int w, int c, int k, int stride, int pad,
                         void* stream);
