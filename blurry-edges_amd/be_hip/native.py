@@ -145,6 +145,7 @@ _SIGNATURES = {
     "be_view_to_nhwc4p_f32": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int, _P]),
     "be_conv7x7_nhwc4p_f32": (C.c_int, [C.POINTER(ConvDesc), _P, C.c_int, _P, _P, _P, C.c_int, _P]),
     "be_conv7x7_pool_nhwc4p_f32": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    "be_conv7x7_pool_bf6_nhwc4p_f32": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
     "be_render_full_f32": (C.c_int, [C.POINTER(RenderOpts), C.POINTER(DepthConsts), C.c_float, C.c_int, _P,
                                      C.POINTER(PatchView), _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "be_fold_records_f32": (C.c_int, [C.POINTER(RenderOpts), _P] + [C.c_int] * 6 + [_P] * 6 + [_P]),
@@ -689,6 +690,17 @@ def conv7x7_pool_nhwc4p(xp, pw, pb):
     return y
 
 
+def conv7x7_pool_bf6_nhwc4p(xp, pw, pb):
+    """conv7x7_pool_nhwc4p in split-bf16 arithmetic (k_conv1_pool_bf6): same operands, [N,21,28,4] -> [N,11,11,64]."""
+    n, h, wrow, c4 = xp.shape
+    if (h, wrow, c4) != (21, 28, 4):
+        raise RuntimeError(f"conv7x7_pool_bf6_nhwc4p: expected [N,21,28,4], got {tuple(xp.shape)}")
+    y = torch.empty(n, 11, 11, 64, dtype=torch.float32, device=xp.device)
+    check(lib().be_conv7x7_pool_bf6_nhwc4p_f32(dptr(xp, "x"), n, dptr(pw), dptr(pb), dptr(y), stream_ptr(xp.device)),
+          "be_conv7x7_pool_bf6_nhwc4p_f32")
+    return y
+
+
 def local_stage_pack(tensors, eps=1e-5):
     """tensors: the 86 fp32 state-dict tensors on the GPU, in the order documented in the header."""
     if len(tensors) != NTENSORS:
@@ -835,7 +847,7 @@ KERNEL_NAMES = {0: "k_conv_igemm<2,2,2,2,TAPS> (128x128)", 1: "k_conv_igemm<4,1,
                 8: "k_wino_in / k_wino_out_in / k_wino_out / k_wino_out_pool2 (Winograd transforms)", 9: "k_maxpool_nhwc",
                 10: "k_render_colors (pass A)", 11: "conv1 input staging",
                 12: "k_unit_gemms / k_unit_gemms_sk (training units: weight-gradient GEMMs + data-gradient convolutions of one or two units in one launch; a residual block's two forward convolutions)",
-                13: "k_conv1_pool (conv1 7x7 + Smish + max-pool 3/2/1 in one image-major kernel)"}
+                13: "k_conv1_pool_bf6 (conv1 7x7 + Smish + max-pool 3/2/1 in one image-major kernel, in split-bf16 arithmetic with the image pre-split in LDS, FLOPs counted as fp32 products; BE_C1_F32=1 / BE_WINO_F32=1: the fp32 k_conv1_pool)"}
 HBM_KERNEL_IDS = (8, 9, 10, 11)
 
 

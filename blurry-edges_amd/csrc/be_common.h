@@ -93,6 +93,9 @@ int conv_pm(const be_conv_desc* d, const float* x, int wrow, const float* x2, in
 int conv3x3_pm_bf6(const be_conv_desc* d, const float* x, const float* x2, int cin2, const float* planes, const float* bias,
                    float* y, int ldy, void* stream);
 bool l0_bf6_enabled();
+// be_conv1_pool_bf6.hip: c1_bf6_enabled(): false under BE_C1_F32=1 or BE_WINO_F32=1 (read once per process): LocalStage's conv1 +
+// max-pool then keeps the fp32 routing (be_conv7x7_pool_nhwc4p_f32 for large sub-batches, conv1 and the pool kernel for small ones)
+bool c1_bf6_enabled();
 
 // be_wino.hip: be_wino_conv3x3_pair_6x6_f32; pool2 = 1 writes the 2x2 max-pool of the block's output, [n,3,3,cout]
 int wino_pair(const float* x, const float* packed_w1, const float* packed_bias1, int act1, const float* packed_w2,

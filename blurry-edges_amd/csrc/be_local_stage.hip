@@ -9,7 +9,8 @@
 // row-padded staging and for layer0, the row GEMM of be_wino.hip for the 1x1s and fc.1); smaller ones k_conv_igemm - same
 // results bit for bit.  On the Winograd path the 1x1 downsamples of layers 1-3 and fc.1 run in split-bf16 arithmetic on ONE kernel for
 // every sub-batch size (be::gemm_rows_bf6; BE_ROWS_F32=1 / BE_WINO_F32=1: the fp32 kernels just named), and so does layer0
-// (be::conv3x3_pm_bf6, be_conv_pm_bf6.hip; BE_L0_F32=1 / BE_WINO_F32=1: the fp32 kernels).  No allocation, no
+// (be::conv3x3_pm_bf6, be_conv_pm_bf6.hip; BE_L0_F32=1 / BE_WINO_F32=1: the fp32 kernels), and so do conv1 + the first pool
+// (be_conv1_pool_bf6.hip on the row-padded staging; BE_C1_F32=1 / BE_WINO_F32=1: the fp32 routing by sub-batch size).  No allocation, no
 // synchronisation, no process-wide state: graph-capturable, re-entrant.  opts->winograd = 0 runs layers 1-3 as direct launches
 // like layer0, all in fp32.
 #include "be_common.h"
@@ -241,16 +242,23 @@ int forward_impl(const float* packed, const float* x, const be_patch_view* view,
         // large sub-batches: conv1 on the pixel-major LDS-DMA kernel, which reads a staging with 28 pixels per row (3 zero
         // pixels left, 4 right; 2352 floats per patch, still in front of p1)
         static const bool no_pm = getenv("BE_NO_CONV_PM") != nullptr;
+        static const bool no_c1p = getenv("BE_NO_CONV1_POOL") != nullptr;
+        // Winograd path: conv1 + Smish + the first max-pool in split-bf16 arithmetic (be_conv1_pool_bf6.hip) at EVERY sub-batch size,
+        // so that a patch's bits depend on neither batch nor chunk (the padded staging fits in front of p1 at any nb);
+        // BE_C1_F32=1 / BE_WINO_F32=1 (and the two A/B knobs of the fp32 routing): the fp32 routing below, unchanged
+        const bool c1_bf6 = wino && be::c1_bf6_enabled() && !no_pm && !no_c1p;
         bool pooled = false;
-        if (nb >= 512 && !no_pm) {
+        if (c1_bf6 || (nb >= 512 && !no_pm)) {
             if (x) rc = be_nchw3_to_nhwc4p_f32(x + first * 3 * BE_NPIX, x4, nb, BE_R, BE_R, 28, stream);
             else rc = be_view_to_nhwc4p_f32(view, P, first, x4, nb, 28, stream);
             if (rc) return rc;
             const PackedLayout& L = layout();
             // conv1 + Smish + the first max-pool in one image-major launch (be_conv1_pool.hip): the 21 x 21 x 64 map never reaches
             // HBM; bit-identical to the pixel-major conv1 followed by the pool kernel (BE_NO_CONV1_POOL=1: that pair, for A/B runs)
-            static const bool no_c1p = getenv("BE_NO_CONV1_POOL") != nullptr;
-            if (!no_c1p) {
+            if (c1_bf6) {
+                if ((rc = be_conv7x7_pool_bf6_nhwc4p_f32(x4, nb, packed + L.w_off[0], packed + L.b_off[0], p1, stream))) return rc;
+                pooled = true;
+            } else if (!no_c1p) {
                 if ((rc = be_conv7x7_pool_nhwc4p_f32(x4, nb, packed + L.w_off[0], packed + L.b_off[0], p1, stream))) return rc;
                 pooled = true;
             } else {

@@ -1,5 +1,5 @@
 // Split-bf16 (bf16x6) operand helpers shared by the kernels that multiply fp32 operands on v_mfma_f32_32x32x16_bf16
-// (be_wino.hip: k_wino_gemm<., 1>, k_wino_gemm_ps; be_conv_pm_bf6.hip: k_conv_pm_bf6).
+// (be_wino.hip: k_wino_gemm<., 1>, k_wino_gemm_ps; be_conv_pm_bf6.hip: k_conv_pm_bf6; be_conv1_pool_bf6.hip: k_conv1_pool_bf6).
 //
 // x = hi + mid + lo exactly, each a bf16 rounded to nearest-even from what is left: |mid| <= 2^-8 |x|, |lo| <= 2^-16 |x| (finite x
 // whose lo stays a bf16 normal, |x| >= ~2^-110; below that lo loses bits to the bf16 subnormal grid, an absolute error < 2^-133).
@@ -35,6 +35,24 @@ __device__ __forceinline__ void split8(f32x4 a, f32x4 b, bf16x8& h, bf16x8& m, b
         const bf16x2 mb = __builtin_convertvector((f32x2){r0, r1}, bf16x2);
         const unsigned mu = __builtin_bit_cast(unsigned, mb);
         const bf16x2 lb = __builtin_convertvector((f32x2){sub_f32(r0, bf_lo(mu)), sub_f32(r1, bf_hi(mu))}, bf16x2);   // exact
+        h[e] = hb[0]; h[e + 1] = hb[1];
+        m[e] = mb[0]; m[e + 1] = mb[1];
+        l[e] = lb[0]; l[e + 1] = lb[1];
+    }
+}
+
+// the 4 values of one fp32 quad -> 8 bytes of each plane: the same split, for a producer that stores the pieces (k_conv1_pool_bf6)
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void split4(f32x4 a, bf16x4& h, bf16x4& m, bf16x4& l) {
+    const float x[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int e = 0; e < 4; e += 2) {
+        const bf16x2 hb = __builtin_convertvector((f32x2){x[e], x[e + 1]}, bf16x2);
+        const unsigned hu = __builtin_bit_cast(unsigned, hb);
+        const float r0 = sub_f32(x[e], bf_lo(hu)), r1 = sub_f32(x[e + 1], bf_hi(hu));
+        const bf16x2 mb = __builtin_convertvector((f32x2){r0, r1}, bf16x2);
+        const unsigned mu = __builtin_bit_cast(unsigned, mb);
+        const bf16x2 lb = __builtin_convertvector((f32x2){sub_f32(r0, bf_lo(mu)), sub_f32(r1, bf_hi(mu))}, bf16x2);
         h[e] = hb[0]; h[e + 1] = hb[1];
         m[e] = mb[0]; m[e + 1] = mb[1];
         l[e] = lb[0]; l[e + 1] = lb[1];

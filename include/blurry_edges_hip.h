@@ -518,6 +518,13 @@ int be_conv7x7_nhwc4p_f32(const be_conv_desc* d, const float* x, int wrow, const
  * the 7x7 pack of be_conv_pack_f32 (cout 64, K = 224), y [n,11,11,64].  A workgroup keeps whole images in LDS, the weights in
  * registers, and writes only the pooled map.  Bit-identical to be_conv7x7_nhwc4p_f32 (act 1) followed by be_maxpool_nhwc_f32(3,2,1). */
 int be_conv7x7_pool_nhwc4p_f32(const float* x4p, int64_t n, const float* packed_w, const float* packed_bias, float* y, void* stream);
+/* The same head in split-bf16 arithmetic (bf16x6: the image split to hi / mid / lo bf16 planes once, in LDS; the weights once per wave,
+ * in registers; six v_mfma_f32_32x32x16_bf16 per 16-deep K chunk, fp32 accumulation).  Same arguments, same checks, same packed fp32
+ * weights and bias: nothing new is packed.  One kernel body for every n >= 1: an image's bits do not depend on the batch it is
+ * computed in.  Against a float64 reference it errs at most 2 x what be_conv7x7_pool_nhwc4p_f32 errs.  LocalStage takes it wherever
+ * the Winograd path runs, at every sub-batch size; environment BE_C1_F32=1 (read once per process) restores the fp32 routing of
+ * conv1 + pool (BE_WINO_F32=1 does too). */
+int be_conv7x7_pool_bf6_nhwc4p_f32(const float* x4p, int64_t n, const float* packed_w, const float* packed_bias, float* y, void* stream);
 /* Patches [first, first+n) of a view -> [n,21,21,4] (the staging be_local_stage_forward_view_f32 uses). */
 int be_view_to_nhwc4_f32(const be_patch_view* view_host, int64_t patches_per_image, int64_t first, float* y,
                          int64_t n, void* stream);

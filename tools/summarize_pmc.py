@@ -17,7 +17,7 @@ NAMES = {"k_conv_igemm<2, 2, 2, 2, 0,": "conv128x128", "k_conv_igemm<4, 1, 1, 3,
          "k_wino_in": "wino_in", "k_wino_out_in": "wino_out_in", "k_wino_out(": "wino_out", "k_wino_out_pool2": "wino_out_pool2",
          "k_wino_gemm_ws<6, 1>": "gemm_rows_ws", "k_wino_gemm_ws<16, 1>": "gemm_rows_ws", "k_wino_gemm_ws<24, 1>": "gemm_rows_ws",
          "k_wino_gemm_ws": "wino_gemm", "k_wino_gemm<0>": "wino_gemm", "k_wino_gemm<1>": "gemm_rows", "k_wino_gemm(": "wino_gemm",
-         "k_conv1_pool": "conv1_pool_image_major", "k_conv_pm<2, 3, 0>": "conv_pm_256x96", "k_conv_pm<2, 2, 1>": "conv_pm_conv1", "k_maxpool_nhwc": "maxpool",
+         "k_conv1_pool_bf6": "conv1_pool_bf6", "k_conv1_pool": "conv1_pool_image_major", "k_conv_pm<2, 3, 0>": "conv_pm_256x96", "k_conv_pm<2, 2, 1>": "conv_pm_conv1", "k_maxpool_nhwc": "maxpool",
          # the training step (tools/pmc_train.sh)
          "k_unit_gemms_sk": "train_unit_gemms_balanced", "k_unit_gemms<0>": "train_unit_gemms_64x64", "k_unit_gemms<1>": "train_unit_gemms_128x32", "k_unit_gemms<2>": "train_unit_gemms_64x64_uniform", "k_conv_igemm<2, 2, 1, 1, 0,": "train_conv_64x64",
          "k_conv_igemm<4, 1, 1, 1, 0,": "train_conv_128x32", "k_bwd_post": "train_bwd_post", "k_bn_stats": "train_bn_stats",
