@@ -164,6 +164,8 @@ _SIGNATURES = {
     "be_unproject_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float)] * 2 + [_P, _P]),
     "be_reproject_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float)] * 3 + [C.c_float, C.c_int, C.c_int, _P, C.c_int] + [_P] * 4 + [_P]),
     "be_fill_nearest_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int] + [_P] * 4 + [_P]),
+    "be_fill_diffuse_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "be_fill_diffuse_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int] + [_P] * 5 + [_P]),
     "be_unfold_patches_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "be_local_features_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "be_global_denorm_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
@@ -1367,6 +1369,79 @@ def fill_nearest(depth, weight=None, smooth=2, sigma_z=0.02, fuse=True):
                                         dptr(scratch, "scratch", (torch.int32,)), dptr(d), dptr(index, "index", (torch.int32,)),
                                         dptr(dist2, "dist2", (torch.int32,)), stream_ptr(dev)), "be_fill_nearest_f32")
     return dict(depth=d, index=index, dist2=dist2)
+
+
+FILL_MAX_ITERS = 4096
+
+
+def fill_diffuse(depth, weight=None, edge=None, smooth=2, sigma_z=0.02, leak=1e-3, iters=None, fuse=True):
+    """Dense depth from sparse samples by edge-aware diffusion: depth [H,W] float32 on the GPU, weight [H,W] (None: 1 everywhere),
+    edge [H,W] float32 (None: 0 everywhere).  The seeds are fill_nearest's; a seed's boundary value is what fill_nearest copies from
+    it (its depth at smooth = 0, the robust mean of the seeds within r of it at smooth = r > 0).  Every hole takes the harmonic
+    interpolant of the boundary values under the conductances c_pq = max(leak, 1 - max(e_p, e_q)), e = edge clamped to [0, 1] (NaN
+    counts as 0), between 4-neighbours, with no term across the image border: a surface between two samples comes out as the plane
+    through them where fill_nearest puts a step, and an edge of 1 keeps two regions from mixing (leak > 0 keeps the system
+    connected).  -> dict(depth [H,W]: the input at seeds, the interpolant at holes; index, dist2 [H,W] int32: fill_nearest's, bit
+    for bit; residual [1] float32 on the GPU: max over the holes of |avg - u| after the last sweep); 0 / -1 / -1 / 0 when there is
+    no seed.  iters None: the default schedule (4 x the longer side sweeps on every pyramid level), an int in 1..4096: that many
+    sweeps per level.  fuse False runs one sweep per launch (the baseline tools/bench_diffuse.py times).  The schedule depends on
+    (H, W, iters) alone; nothing synchronises with the host; repeated calls give the same bits.  diffuse.fill_diffuse is the host
+    statement (close, not bit-equal: the kernels contract to FMA), diffuse.solve_exact the float64 direct solve."""
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 2 or depth.numel() == 0:
+        raise ValueError(f"fill_diffuse: depth must be a float32 tensor [H,W], got "
+                         f"{getattr(depth, 'dtype', type(depth).__name__)} {tuple(getattr(depth, 'shape', ()))}")
+    if not depth.is_cuda:
+        raise ValueError("fill_diffuse: depth is not on the GPU; nothing here computes on the CPU (diffuse.fill_diffuse is the host statement)")
+    H, W = depth.shape
+    if H > FILL_MAX_SIDE or W > FILL_MAX_SIDE:
+        raise ValueError(f"fill_diffuse: H and W must be at most {FILL_MAX_SIDE} (squared distances are int32), got {H} x {W}")
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dtype not in (torch.float32, torch.bool) or tuple(weight.shape) != (H, W):
+            raise ValueError(f"fill_diffuse: weight must be a float32 (or bool: a mask) tensor [{H},{W}], got "
+                             f"{getattr(weight, 'dtype', type(weight).__name__)} {tuple(getattr(weight, 'shape', ()))}")
+        if weight.device != depth.device:
+            raise ValueError(f"fill_diffuse: weight is on {weight.device}, depth on {depth.device}")
+        weight = weight.to(torch.float32).contiguous()
+    if edge is not None:
+        if not isinstance(edge, torch.Tensor) or edge.dtype != torch.float32 or tuple(edge.shape) != (H, W):
+            raise ValueError(f"fill_diffuse: edge must be a float32 tensor [{H},{W}], got "
+                             f"{getattr(edge, 'dtype', type(edge).__name__)} {tuple(getattr(edge, 'shape', ()))}")
+        if edge.device != depth.device:
+            raise ValueError(f"fill_diffuse: edge is on {edge.device}, depth on {depth.device}")
+        edge = edge.contiguous()
+    if isinstance(smooth, bool) or not isinstance(smooth, int) or not 0 <= smooth <= FILL_MAX_SMOOTH:
+        raise ValueError(f"fill_diffuse: smooth must be an integer in [0, {FILL_MAX_SMOOTH}], got {smooth!r}")
+    try:
+        sigma_z = float(sigma_z)
+    except (TypeError, ValueError):
+        sigma_z = -1.0
+    if not 0 < sigma_z < float("inf"):
+        raise ValueError("fill_diffuse: sigma_z must be a finite number > 0")
+    try:
+        leak = float(leak)
+    except (TypeError, ValueError):
+        leak = -1.0
+    if not 0 < leak <= 1:
+        raise ValueError("fill_diffuse: leak must be a number in (0, 1]")
+    if iters is not None and (isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= FILL_MAX_ITERS):
+        raise ValueError(f"fill_diffuse: iters must be None or an integer in [1, {FILL_MAX_ITERS}], got {iters!r}")
+    depth = depth.contiguous()
+    iters = 0 if iters is None else iters
+    fuse = bool(fuse)
+    o = ops()
+    if o is not None:
+        d, index, dist2, residual = o.fill_diffuse(depth, weight, edge, smooth, sigma_z, leak, iters, fuse)
+    else:
+        dev = depth.device
+        scratch = torch.empty(lib().be_fill_diffuse_scratch_bytes(H, W) // 4, dtype=torch.int32, device=dev)
+        d = torch.empty(H, W, dtype=torch.float32, device=dev)
+        index = torch.empty(H, W, dtype=torch.int32, device=dev)
+        dist2 = torch.empty(H, W, dtype=torch.int32, device=dev)
+        residual = torch.empty(1, dtype=torch.float32, device=dev)
+        check(lib().be_fill_diffuse_f32(dptr(depth, "depth", (torch.float32,)), dptr(weight), dptr(edge), H, W, smooth, sigma_z, leak, iters,
+                                        int(fuse), dptr(scratch, "scratch", (torch.int32,)), dptr(d), dptr(index, "index", (torch.int32,)),
+                                        dptr(dist2, "dist2", (torch.int32,)), dptr(residual), stream_ptr(dev)), "be_fill_diffuse_f32")
+    return dict(depth=d, index=index, dist2=dist2, residual=residual)
 
 
 def unfold_patches(img: torch.Tensor, stride: int = 2) -> torch.Tensor:

@@ -436,9 +436,9 @@ class DepthPipeline:
         return res
 
 
-    # ---- dense depth: the holes of depth_map closed by nearest-sample flood fill ---------------------------------------------
+    # ---- dense depth: the holes of depth_map closed by nearest-sample flood fill or by edge-aware diffusion -----------------
     @torch.no_grad()
-    def complete(self, maps, smooth=2, sigma_z=0.02):
+    def complete(self, maps, smooth=2, sigma_z=0.02, method="nearest", edges=True, leak=1e-3, iters=None):
         """maps: what __call__, run_big or run_any returned (maps["depth_map"], maps["conf"] are read) -> a dense depth map.
         depth_map holds depth only where conf passes the threshold, a band on both sides of every boundary; the nearest sample of a
         hole therefore lies on the hole's own side of the nearest boundary, and every hole takes the depth of its nearest sample
@@ -449,7 +449,15 @@ class DepthPipeline:
         when the pair has no sample at all).  Nothing synchronises with the host.  Under densify == 'pp' or 'w' depth_map is already
         dense: it is returned unchanged, every pixel measured.
         native.fill_nearest is general: with depth=out["depth"], weight=out["valid"] it also closes the holes of a reproject
-        result - a separate call, because a disocclusion wants a rule that prefers the background, which this one is not."""
+        result - a separate call, because a disocclusion wants a rule that prefers the background, which this one is not.
+        method="diffuse": the holes take the edge-aware harmonic interpolant of the same samples instead (native.fill_diffuse): a
+        surface whose depth changes between two boundaries comes out as the smooth surface through both bands, where the nearest
+        sample puts a step halfway.  edges=True passes maps["bndry"] as the edge map, which keeps two regions from mixing where the
+        samples along a boundary are missing (leak: the conductance left across a full edge); iters: the sweeps per pyramid level,
+        None for the default schedule.  The same keys (measured, index and dist are those of "nearest") plus residual [1]: the
+        largest |average of the neighbours - value| left at a hole, 0 under densify 'pp' / 'w'."""
+        if method not in ("nearest", "diffuse"):
+            raise ValueError(f"complete: method must be 'nearest' or 'diffuse', got {method!r}")
         if not isinstance(maps, dict) or "depth_map" not in maps or "conf" not in maps:
             missing = [k for k in ("depth_map", "conf") if not isinstance(maps, dict) or k not in maps]
             raise ValueError(f"complete: maps lacks {missing}; pass the dict DepthPipeline.__call__, run_big or run_any returned")
@@ -460,14 +468,35 @@ class DepthPipeline:
                                  "(keep the dict the pipeline returned, or move it back to the device)")
         if z.dim() != 2 or conf.shape != z.shape:
             raise ValueError(f"complete: depth_map and conf must be [H,W], got {tuple(z.shape)} and {tuple(conf.shape)}")
+        H, W = z.shape
+        edge = None
+        if method == "diffuse" and edges:
+            edge = maps.get("bndry")
+            if edge is None:
+                raise ValueError("complete: maps lacks ['bndry'], the edge map of method='diffuse'; pass the dict DepthPipeline.__call__, "
+                                 "run_big or run_any returned, or edges=False")
+            if not isinstance(edge, torch.Tensor) or not edge.is_cuda:
+                raise ValueError("complete: maps['bndry'] is not on the GPU; nothing here computes on the CPU "
+                                 "(keep the dict the pipeline returned, or move it back to the device)")
+            if edge.numel() != H * W or tuple(edge.shape[-2:]) != (H, W):
+                raise ValueError(f"complete: bndry must be [..,{H},{W}] with leading dimensions of 1, got {tuple(edge.shape)}")
+            edge = edge.reshape(H, W).to(torch.float32)
         if self.densify in ("pp", "w"):
-            H, W = z.shape
-            return dict(depth_dense=z, measured=torch.ones_like(z, dtype=torch.bool),
-                        index=torch.arange(H * W, dtype=torch.int32, device=z.device).view(H, W), dist=torch.zeros_like(z))
-        out = native.fill_nearest(z, conf, smooth=smooth, sigma_z=sigma_z)
+            res = dict(depth_dense=z, measured=torch.ones_like(z, dtype=torch.bool),
+                       index=torch.arange(H * W, dtype=torch.int32, device=z.device).view(H, W), dist=torch.zeros_like(z))
+            if method == "diffuse":
+                res["residual"] = torch.zeros(1, dtype=torch.float32, device=z.device)
+            return res
+        if method == "diffuse":
+            out = native.fill_diffuse(z, conf, edge, smooth=smooth, sigma_z=sigma_z, leak=leak, iters=iters)
+        else:
+            out = native.fill_nearest(z, conf, smooth=smooth, sigma_z=sigma_z)
         d2 = out["dist2"]
-        return dict(depth_dense=out["depth"], measured=d2 == 0, index=out["index"],
-                    dist=torch.where(d2 >= 0, d2.to(torch.float32).sqrt(), torch.full_like(z, -1.0)))
+        res = dict(depth_dense=out["depth"], measured=d2 == 0, index=out["index"],
+                   dist=torch.where(d2 >= 0, d2.to(torch.float32).sqrt(), torch.full_like(z, -1.0)))
+        if method == "diffuse":
+            res["residual"] = out["residual"]
+        return res
 
 
 def _points_on(points, device, who):

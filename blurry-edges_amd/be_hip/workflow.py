@@ -14,6 +14,7 @@ formats (argument names and defaults = utils/args.py of the reference):
     ... eval --point_cloud [--out_path DIR]                also write every pair's depth map as points in space
     ... eval --reproject CAM.npz [--out_path DIR]          also write every pair's depth and colours as the camera of CAM sees them
     ... eval --complete [--out_path DIR]                   also write and score every pair's depth map completed to a dense one
+    ... eval --complete --complete_method diffuse          ... by edge-aware diffusion instead of the nearest sample's depth
 
 Data parallel (BASELINE configs[4]): the two training commands run under torchrun, one process per GPU -
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m be_hip.workflow local_train ...
@@ -347,7 +348,8 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     args.complete (not in the reference): every pair's depth_map completed to a dense one, DepthPipeline.complete, goes to
     {args.out_path}/complete_{j:04d}.npz (depth_dense, measured, index, dist), outside the timed region; one more metrics line per
     pair and in the average scores depth_dense with the same utils.eval_depth call, and the averages are returned under the key
-    `dense`.  Without the flag, output and return value are what they were."""
+    `dense`.  Without the flag, output and return value are what they were.  args.complete_method 'diffuse' completes by edge-aware
+    diffusion (DepthPipeline.complete(method="diffuse")): the npz also holds `residual`, and the lines read "(completed, diffuse)"."""
     import data, models, utils
     from .pipeline import DepthPipeline
     dev = _device(args)
@@ -380,6 +382,8 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     if rcam is not None:
         rcam = load_camera(rcam)
     complete = getattr(args, "complete", False)
+    cmethod = getattr(args, "complete_method", "nearest")
+    clabel = "completed" if cmethod == "nearest" else f"completed, {cmethod}"
     if rsize is not None or spoints is not None or cloud or rcam is not None or complete:
         os.makedirs(args.out_path, exist_ok=True)
     fine_maps, fine_thres = ("shpd", "refoc", "bndry", "depth", "conf"), 0.05 if (big or any_size) else None
@@ -432,13 +436,13 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
             print(f'Image pair #{j}: delta1 ={m[0]: .3f}, delta2 ={m[1]: .3f}, delta3 ={m[2]: .3f}, RMSE ={m[3]: .3f} cm, '
                   f'AbsRel ={m[4]: .3f} cm')
         if complete:
-            done = pipe.complete(maps)
+            done = pipe.complete(maps) if cmethod == "nearest" else pipe.complete(maps, method=cmethod)
             np.savez(os.path.join(args.out_path, f"complete_{j:04d}.npz"), **{k: v.cpu().numpy() for k, v in done.items()})
             dense = done["depth_dense"][None]
             m = np.array(utils.eval_depth(dense, gt[None].to(dense.dtype), dense, crop=args.crop))
             tot_dense += m
             if not quiet:
-                print(f'Image pair #{j} (completed): delta1 ={m[0]: .3f}, delta2 ={m[1]: .3f}, delta3 ={m[2]: .3f}, RMSE ={m[3]: .3f} cm, '
+                print(f'Image pair #{j} ({clabel}): delta1 ={m[0]: .3f}, delta2 ={m[1]: .3f}, delta3 ={m[2]: .3f}, RMSE ={m[3]: .3f} cm, '
                       f'AbsRel ={m[4]: .3f} cm')
     n = max(len(ds), 1)
     res = dict(zip(("delta1", "delta2", "delta3", "RMSE", "AbsRel"), (tot / n).tolist()), seconds_per_pair=secs / n)
@@ -448,7 +452,7 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     if complete:
         res["dense"] = dict(zip(("delta1", "delta2", "delta3", "RMSE", "AbsRel"), (tot_dense / n).tolist()))
         if not quiet:
-            print('Average metrics for whole dataset (completed): ' + ', '.join(f'{k} ={v: .3f}' for k, v in res["dense"].items()))
+            print(f'Average metrics for whole dataset ({clabel}): ' + ', '.join(f'{k} ={v: .3f}' for k, v in res["dense"].items()))
     return res
 
 

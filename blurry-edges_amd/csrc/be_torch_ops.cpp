@@ -677,6 +677,34 @@ std::tuple<Tensor, Tensor, Tensor> fill_nearest(const Tensor& depth, const c10::
     return {dout, index, dist2};
 }
 
+// diffusion depth completion: depth [H,W], weight / edge [H,W] or None -> (depth_out [H,W], index [H,W] int32, dist2 [H,W] int32,
+// residual [1]); iters 0: the default schedule; the pyramid is scratch allocated here
+std::tuple<Tensor, Tensor, Tensor, Tensor> fill_diffuse(const Tensor& depth, const c10::optional<Tensor>& weight,
+                                                        const c10::optional<Tensor>& edge, int64_t smooth_r, double sigma_z, double leak,
+                                                        int64_t iters, bool fuse) {
+    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.size(0) <= 16384 && depth.size(1) <= 16384,
+                "fill_diffuse: depth [H,W], 1 <= H, W <= 16384");
+    TORCH_CHECK(smooth_r >= 0 && smooth_r <= 8, "fill_diffuse: smooth_r must be in [0, 8]");
+    TORCH_CHECK(iters >= 0 && iters <= 4096, "fill_diffuse: iters must be in [0, 4096]");
+    fp(depth, "depth");
+    const int64_t H = depth.size(0), W = depth.size(1);
+    if (weight.has_value() && weight->defined())
+        TORCH_CHECK(weight->sizes() == depth.sizes() && weight->device() == depth.device(), "fill_diffuse: weight [H,W] on depth's device");
+    if (edge.has_value() && edge->defined())
+        TORCH_CHECK(edge->sizes() == depth.sizes() && edge->device() == depth.device(), "fill_diffuse: edge [H,W] on depth's device");
+    auto o = depth.options();
+    const int64_t bytes = be_fill_diffuse_scratch_bytes((int)H, (int)W);
+    TORCH_CHECK(bytes > 0, "fill_diffuse: no scratch size for ", H, " x ", W);
+    Tensor scratch = at::empty({bytes / 4}, o.dtype(at::kInt));
+    Tensor dout = at::empty({H, W}, o), index = at::empty({H, W}, o.dtype(at::kInt)), dist2 = at::empty({H, W}, o.dtype(at::kInt));
+    Tensor residual = at::empty({1}, o);
+    check(be_fill_diffuse_f32(depth.data_ptr<float>(), fpo(weight, "weight"), fpo(edge, "edge"), (int)H, (int)W, (int)smooth_r,
+                              (float)sigma_z, (float)leak, (int)iters, fuse ? 1 : 0, scratch.data_ptr<int32_t>(), dout.data_ptr<float>(),
+                              index.data_ptr<int32_t>(), dist2.data_ptr<int32_t>(), residual.data_ptr<float>(), stream_of(depth)),
+          "be_fill_diffuse_f32");
+    return {dout, index, dist2, residual};
+}
+
 // LocalLoss forward + analytic backward in one launch -> (partial [B,3], grad_est [B,10] or an empty tensor)
 std::tuple<Tensor, Tensor> local_loss(const Tensor& opts, const Tensor& est, const Tensor& img_fit, const Tensor& gt, const Tensor& bdist,
                                       const Tensor& deri, double beta_b, double beta_s, bool want_grad) {
@@ -803,6 +831,8 @@ TORCH_LIBRARY(be, m) {
     m.def("unproject(Tensor depth, Tensor cam_src, Tensor pose, int scale, int top, int left) -> Tensor");
     m.def("reproject(Tensor depth, Tensor cam_src, Tensor cam_dst, Tensor pose, float near, int Ho, int Wo, Tensor? feat, int scale, int top, int left) -> (Tensor, Tensor, Tensor)");
     m.def("fill_nearest(Tensor depth, Tensor? weight, int smooth_r, float sigma_z, bool fuse) -> (Tensor, Tensor, Tensor)");
+    m.def("fill_diffuse(Tensor depth, Tensor? weight, Tensor? edge, int smooth_r, float sigma_z, float leak, int iters, bool fuse) -> "
+          "(Tensor, Tensor, Tensor, Tensor)");
     m.def("local_loss(Tensor opts, Tensor est, Tensor img_fit, Tensor gt, Tensor bdist, Tensor deri, float beta_b, float beta_s, bool want_grad) -> (Tensor, Tensor)");
     m.def("local_loss_finish(Tensor partial, float beta_b, float beta_s) -> Tensor");
     m.def("global_loss(Tensor opts, Tensor consts, Tensor est, Tensor img_fit, Tensor img_gt, Tensor G, Tensor Gd, Tensor Gb, Tensor bdist, Tensor deri, "
@@ -863,6 +893,7 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("unproject", unproject);
     m.impl("reproject", reproject);
     m.impl("fill_nearest", fill_nearest);
+    m.impl("fill_diffuse", fill_diffuse);
     m.impl("local_loss", local_loss);
     m.impl("local_loss_finish", local_loss_finish);
     m.impl("global_loss", global_loss);

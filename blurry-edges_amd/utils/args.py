@@ -99,6 +99,8 @@ _GROUPS = {
         # not in the reference: every pair's depth map completed to a dense one by nearest-sample flood fill (DepthPipeline.complete),
         # written to out_path and scored with the same metrics
         ('--complete', dict(action='store_true')),
+        # how --complete closes the holes: 'nearest' (the nearest sample's depth) or 'diffuse' (the edge-aware harmonic interpolant)
+        ('--complete_method', dict(type=str, default='nearest', choices=['nearest', 'diffuse'])),
     ],
 }
 

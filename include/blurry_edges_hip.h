@@ -261,6 +261,30 @@ int be_reproject_f32(const float* depth, int Hs, int Ws, int scale, int top, int
 int be_fill_nearest_f32(const float* depth, const float* weight, int H, int W, int smooth_r, float sigma_z, int fuse,
                         int32_t* scratch, float* depth_out, int32_t* index, int32_t* dist2, void* stream);
 
+/* Dense depth from sparse samples by edge-aware diffusion: the holes take the harmonic interpolant of the seeds.  depth, weight as
+ * be_fill_nearest_f32 (the same seeds); edge [H,W] float32 or NULL.  A seed's boundary value b is what be_fill_nearest_f32 copies
+ * from it: its depth at smooth_r = 0, its robust local mean at smooth_r > 0.  With e = min(max(edge, 0), 1) (NaN: 0; NULL: 0) the
+ * conductance between 4-neighbours p, q is c_pq = max(leak, 1 - max(e_p, e_q)); the image border has no neighbour and no term.
+ * Every hole satisfies u_p sum_q c_pq = sum_q c_pq u_q, a neighbouring seed contributing b.  Outputs [H,W]: depth_out (the input
+ * at seeds, bit for bit; u at holes), index and dist2 exactly as be_fill_nearest_f32 writes them, and residual [1] float32: the
+ * maximum over the holes of |sum_q c_pq u_q / sum_q c_pq - u_p| after the last sweep.  No seed in the image: 0, -1, -1, 0; every
+ * pixel a seed: a copy of the input.
+ * The fixed point is reached by a fixed schedule: be_fill_nearest_f32's result is the start; a pyramid of 2 x 2 poolings (down to a
+ * longer side <= 4) is relaxed from the coarsest level up, each level the start value of the holes of the next; a level is relaxed
+ * by red-black over-relaxed sweeps (omega = 2 / (1 + sin(pi / longer side))) on LDS regions of up to 128 x 128, a level of several
+ * 96 x 96 tiles in launches of 16 sweeps between which the 16-pixel halos are refreshed.  iters = 0: 4 x the longer side sweeps on
+ * every level (rounded up to a multiple of 16); iters in 1..4096: that many on every level.  fuse = 0 runs one sweep per launch
+ * (the baseline the tiled launch is timed against; the tiled levels then refresh their halos every sweep, so the values differ
+ * within the convergence error).  The schedule is a function of (H, W, iters, fuse) alone: nothing depends on the data, nothing
+ * synchronises with the host, no float is accumulated atomically, and repeated calls give the same bits.
+ * scratch: be_fill_diffuse_scratch_bytes(H, W) bytes of device memory (-1 for a size out of range); its first 3 H W words are
+ * be_fill_nearest_f32's scratch, whose third image (the per-seed means) is read here.  1 <= H, W <= 16384; sigma_z > 0;
+ * 0 < leak <= 1. */
+int64_t be_fill_diffuse_scratch_bytes(int H, int W);
+int be_fill_diffuse_f32(const float* depth, const float* weight, const float* edge, int H, int W, int smooth_r, float sigma_z,
+                        float leak, int iters, int fuse, int32_t* scratch, float* depth_out, int32_t* index, int32_t* dist2,
+                        float* residual, void* stream);
+
 /* nn.Unfold(21, stride) in the order blurry_edges_test.py:120-121 consumes it:
  * img [B,C,H,W] -> out [B, Hp*Wp, C, 21, 21], patch (i,j) = rows stride*i.., cols stride*j.., index i*Wp+j. */
 int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream);
