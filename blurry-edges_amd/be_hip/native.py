@@ -163,6 +163,9 @@ _SIGNATURES = {
                                          + [_P, _P, _P, C.c_int64, _P, C.c_int, _P, _P]),
     "be_unproject_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float)] * 2 + [_P, _P]),
     "be_reproject_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float)] * 3 + [C.c_float, C.c_int, C.c_int, _P, C.c_int] + [_P] * 4 + [_P]),
+    "be_fuse_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "be_fuse_views_f32": (C.c_int, [C.c_int, _P, _P, _P, C.c_int] + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_float)] * 3
+                          + [C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [_P] * 7 + [_P]),
     "be_fill_nearest_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int] + [_P] * 4 + [_P]),
     "be_fill_diffuse_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "be_fill_diffuse_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int] + [_P] * 5 + [_P]),
@@ -1318,6 +1321,113 @@ def reproject(depth, cam_src, cam_dst, pose, size, feat=None, near=1e-3, scale=1
     return dict(depth=d, index=index, valid=index >= 0, feat=f)
 
 
+FUSE_VIEW_KEYS = ("depth", "weight", "feat", "cam_src", "pose", "scale", "window_origin")
+
+
+def fuse_views(views, cam_dst, size, tau=0.05, min_views=1, recentre=True, peel=0, near=1e-3):
+    """The depth of several views merged in one camera.  views: a list of 1..32 dicts with the keys depth [Hs,Ws] (float32 on the
+    GPU, the samples of reproject), weight [Hs,Ws] or None (1 everywhere), feat [C,Hs,Ws] / [C,Hs*Ws] or None (the same C in
+    every view), cam_src, pose (this view's frame -> the target's; None: the identity), scale and window_origin (as reproject;
+    1 and (0, 0) when absent).  Every sample is projected into cam_dst, size = (Ho, Wo), as reproject projects it.  Per target
+    pixel the samples with a weight > 0 that lie within tau (metres) behind the nearest one are averaged with their weights;
+    recentre repeats the average over the window of half-width tau about that first mean, which removes the bias of measuring
+    from a noisy front.  A pixel is kept when samples of at least min_views distinct views agree; otherwise its front cluster is
+    peeled off and the next of `peel` further rounds looks behind it - a sample no second view confirms does not hide the
+    surface behind it.  -> dict(depth [Ho,Wo], valid = layer >= 0 (on the device, no sync), weight [Ho,Wo] = the sum of the
+    members' weights, views, count, layer [Ho,Wo] int32 = the distinct views and the samples that agreed and the round that kept
+    the pixel, feat [C,Ho,Wo] = the weighted mean of the members' channels, None without feat); +0 / False / 0 / 0 / 0 / -1 / +0
+    where no pixel was kept - holes are left open (fill_nearest / fill_diffuse with (out["depth"], out["weight"]) close them).
+    The sums are integers in fixed point (weights in 2^-16, clamped to 16; depth offsets in 2^-20 m; channels in 2^-16, clamped to
+    +-2048) under integer atomics: the result depends neither on the order of execution nor on the order of the views, and is
+    exact while fewer than 2^16 samples agree on one pixel.  Nothing synchronises with the host.  fusion.fuse is the host
+    statement, bit for bit; with tau=0, recentre=False, peel=0 and one view depth and valid are reproject's."""
+    from . import camera, fusion
+    try:
+        views = list(views)
+    except TypeError:
+        raise ValueError(f"fuse_views: views must be a list of dicts with the keys {FUSE_VIEW_KEYS}, got {type(views).__name__}") from None
+    tau, min_views, recentre, peel = fusion.check_params("fuse_views", len(views), tau, min_views, recentre, peel)
+    try:
+        Ho, Wo = size
+        ok = all(not isinstance(v, bool) and int(v) == v and 1 <= v <= 1 << 24 for v in (Ho, Wo)) and Ho * Wo <= 0x7fffffff
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"fuse_views: size must be (Ho, Wo), integers >= 1 with Ho * Wo < 2^31, got {size!r}")
+    Ho, Wo = int(Ho), int(Wo)
+    try:
+        near = float(near)
+    except (TypeError, ValueError):
+        near = -1.0
+    if not 0 <= near < float("inf"):
+        raise ValueError("fuse_views: near must be a finite number >= 0")
+    cd = camera.as_pinhole(cam_dst, "fuse_views(cam_dst)").f32()
+    depths, weights, feats, cams, poses, scales, tops, lefts = [], [], [], [], [], [], [], []
+    dev = None
+    for i, v in enumerate(views):
+        who = f"fuse_views(views[{i}])"
+        if not isinstance(v, dict) or "depth" not in v or "cam_src" not in v:
+            raise ValueError(f"{who}: a view is a dict with the keys {FUSE_VIEW_KEYS} (depth and cam_src at least)")
+        unknown = [k for k in v if k not in FUSE_VIEW_KEYS]
+        if unknown:
+            raise ValueError(f"{who}: unknown keys {unknown}; a view holds {FUSE_VIEW_KEYS}")
+        depth, (cs,), p12, top, left = _reproject_args(who, v["depth"], [("cam_src", v["cam_src"])], v.get("pose"), v.get("scale", 1),
+                                                       v.get("window_origin", (0, 0)))
+        Hs, Ws = depth.shape
+        dev = depth.device if dev is None else dev
+        if depth.device != dev:
+            raise ValueError(f"{who}: depth is on {depth.device}, the first view's on {dev}")
+        w = v.get("weight")
+        if w is not None:
+            if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != (Hs, Ws):
+                raise ValueError(f"{who}: weight must be a float32 tensor [{Hs},{Ws}], got "
+                                 f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}")
+            if w.device != dev:
+                raise ValueError(f"{who}: weight is on {w.device}, depth on {dev}")
+            w = w.contiguous()
+        f = v.get("feat")
+        if f is not None:
+            if (not isinstance(f, torch.Tensor) or f.dtype != torch.float32 or f.dim() not in (2, 3)
+                    or tuple(f.shape[1:]) not in ((Hs, Ws), (Hs * Ws,))):
+                raise ValueError(f"{who}: feat must be a float32 tensor [C,{Hs},{Ws}] or [C,{Hs * Ws}], got "
+                                 f"{getattr(f, 'dtype', type(f).__name__)} {tuple(getattr(f, 'shape', ()))}")
+            if f.device != dev:
+                raise ValueError(f"{who}: feat is on {f.device}, depth on {dev}")
+            f = f.reshape(f.shape[0], Hs * Ws).contiguous()
+        depths.append(depth); weights.append(w); feats.append(f); cams.append(cs); poses.append(p12)
+        scales.append(v.get("scale", 1)); tops.append(top); lefts.append(left)
+    Cs = sorted({0 if f is None else f.shape[0] for f in feats})
+    if len(Cs) != 1:
+        raise ValueError(f"fuse_views: every view must carry the same number of feat channels (or none), got {Cs}")
+    C_ = Cs[0]
+    if C_ > FUSE_MAX_CHANNELS:
+        raise ValueError(f"fuse_views: feat holds {C_} channels; at most {FUSE_MAX_CHANNELS}")
+    import numpy as np
+    V = len(views)
+    cam_all, pose_all = np.ascontiguousarray(np.stack(cams), np.float32), np.ascontiguousarray(np.stack(poses), np.float32)
+    o = ops()
+    if o is not None:
+        empty = torch.empty(0, dtype=torch.float32, device=dev)
+        d, wsum, nviews, count, layer, f = o.fuse_views(depths, [empty if w is None else w for w in weights], feats if C_ else [],
+                                                        torch.from_numpy(cam_all), torch.from_numpy(pose_all), torch.from_numpy(cd), near, Ho, Wo,
+                                                        scales, tops, lefts, tau, min_views, recentre, peel)
+    else:
+        scratch = torch.empty(lib().be_fuse_scratch_bytes(Ho, Wo, C_) // 8 + 1, dtype=torch.int64, device=dev)
+        d = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
+        wsum = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
+        nviews, count, layer = (torch.empty(Ho, Wo, dtype=torch.int32, device=dev) for _ in range(3))
+        f = torch.empty(C_, Ho, Wo, dtype=torch.float32, device=dev)
+        ptrs = lambda ts: (C.c_void_p * V)(*[None if t is None else t.data_ptr() for t in ts])
+        ints = lambda xs: (C.c_int * V)(*xs)
+        check(lib().be_fuse_views_f32(V, ptrs(depths), ptrs(weights), ptrs(feats) if C_ else None, C_, ints([t.shape[0] for t in depths]),
+                                      ints([t.shape[1] for t in depths]), ints(scales), ints(tops), ints(lefts), _fptr(cam_all),
+                                      _fptr(pose_all), _fptr(cd), near, Ho, Wo, tau, min_views, int(recentre), peel,
+                                      dptr(scratch, "scratch", (torch.int64,)), dptr(d), dptr(wsum), dptr(nviews), dptr(count), dptr(layer),
+                                      dptr(f if C_ else None), stream_ptr(dev)), "be_fuse_views_f32")
+    return dict(depth=d, valid=layer >= 0, weight=wsum, views=nviews, count=count, layer=layer, feat=f if C_ else None)
+
+
+FUSE_MAX_CHANNELS = 64
 FILL_MAX_SIDE, FILL_MAX_SMOOTH = 16384, 8
 
 

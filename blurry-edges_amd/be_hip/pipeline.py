@@ -436,6 +436,59 @@ class DepthPipeline:
         return res
 
 
+    # ---- multi-view fusion: the depth of several pairs, each with its pose, merged in one camera -----------------------------
+    @torch.no_grad()
+    def fuse(self, views, cam_dst=None, size=None, want=("shpd",), tau=0.05, min_views=1, recentre=True, peel=0, scale=1, near=1e-3,
+             depth_thres=None):
+        """views: a list of 1..32 (maps, pose) - what __call__, run_big or run_any returned for one pair, and the pose of that
+        pair's camera into the target frame (camera.pose: X' = R X + t; None: the identity) -> the depth of all of them merged in
+        the camera cam_dst, size = (Ho, Wo): depth [Ho,Wo] along cam_dst's axis, valid, weight (the sum of the conf of the samples
+        that agreed), views and count (how many distinct views and how many samples agreed), layer (the round that kept the pixel,
+        -1 where none did) and the `want`ed maps out of native.FOLD_MAPS as the conf-weighted mean over those samples, with the
+        channel counts reproject gives them.  Each view's samples are those reproject would splat (render_at(scale, depth_thres)
+        with their depth_map; the maps themselves at the defaults), each in the camera dcal.intrinsics(H, W) of its own size;
+        their weights are conf.  tau (metres), min_views, recentre, peel: native.fuse_views - samples within tau behind the
+        nearest are averaged, a pixel needs min_views distinct views, and a front that too few views confirm is peeled off in up to
+        `peel` further rounds.  More views give more coverage and less noise, and min_views >= 2 rejects what no second view
+        confirms.  Defaults: the first view's camera and size.  The result does not depend on the order of the views.  Holes are
+        left open: native.fill_nearest and native.fill_diffuse, called as (out["depth"], out["weight"]), close what is left."""
+        want = tuple(want)
+        try:
+            views = list(views)
+        except TypeError:
+            raise ValueError(f"fuse: views must be a list of (maps, pose), got {type(views).__name__}") from None
+        if not views:
+            raise ValueError("fuse: views must hold at least one (maps, pose)")
+        vs, srcs = [], []
+        for i, item in enumerate(views):
+            try:
+                maps, pose = item
+            except (TypeError, ValueError):
+                raise ValueError(f"fuse: views[{i}] must be (maps, pose)") from None
+            src, lat = self._depth_samples(f"fuse(views[{i}])", maps, scale, None, want + ("conf",), depth_thres)
+            g = maps["grid"]
+            cam = self.dcal.intrinsics(g["H"], g["W"])
+            if i == 0:
+                cam_dst = cam if cam_dst is None else cam_dst
+                size = (g["H"], g["W"]) if size is None else size
+            z = src["depth_map"]
+            Ns = z.numel()
+            feat = torch.cat([src[k].reshape(-1, Ns) for k in want]) if want else None
+            vs.append(dict(depth=z, weight=src["conf"].reshape(z.shape).to(torch.float32), feat=feat, cam_src=cam, pose=pose,
+                           scale=lat["scale"], window_origin=lat["window"][:2]))
+            srcs.append(src)
+        out = native.fuse_views(vs, cam_dst, size, tau=tau, min_views=min_views, recentre=recentre, peel=peel, near=near)
+        res = {k: out[k] for k in ("depth", "valid", "weight", "views", "count", "layer")}
+        c, src = 0, srcs[0]
+        for k in want:
+            Ns = src["depth_map"].numel()
+            lead = tuple(src[k].shape[:-2])
+            n = src[k].numel() // Ns
+            res[k] = out["feat"][c:c + n].reshape(lead + tuple(out["depth"].shape))
+            c += n
+        return res
+
+
     # ---- dense depth: the holes of depth_map closed by nearest-sample flood fill or by edge-aware diffusion -----------------
     @torch.no_grad()
     def complete(self, maps, smooth=2, sigma_z=0.02, method="nearest", edges=True, leak=1e-3, iters=None):

@@ -13,6 +13,7 @@ formats (argument names and defaults = utils/args.py of the reference):
     ... eval --sample_points FILE.npy [--out_path DIR]     also write every pair's maps at the [N,2] (y, x) positions of FILE
     ... eval --point_cloud [--out_path DIR]                also write every pair's depth map as points in space
     ... eval --reproject CAM.npz [--out_path DIR]          also write every pair's depth and colours as the camera of CAM sees them
+    ... eval --fuse FILE.npz [--out_path DIR]              also merge every V consecutive pairs, with the poses of FILE, in one camera
     ... eval --complete [--out_path DIR]                   also write and score every pair's depth map completed to a dense one
     ... eval --complete --complete_method diffuse          ... by edge-aware diffusion instead of the nearest sample's depth
 
@@ -325,6 +326,32 @@ def load_camera(path):
                     size=(int(size[0]), int(size[1])), scale=scale)
 
 
+def load_fusion(path):
+    """The settings file of `eval --fuse`: an .npz holding poses [V,12], [V,3,4] or [V,4,4] (pair i of a group -> the target frame,
+    1 <= V <= 32) and optionally K ([4] = fy, fx, cy, cx, or [3,3]) and size = (Ho, Wo) of the target camera (absent: the first
+    pair's), tau, min_views, peel, recentre and scale (the source lattice) -> dict(poses, cam, size, scale, kw = the keywords of
+    DepthPipeline.fuse that the file sets), checked by be_hip.camera; tau, min_views and peel by native.fuse_views."""
+    from . import camera
+    with np.load(path) as f:
+        if "poses" not in f:
+            raise ValueError(f"--fuse: {path} lacks ['poses']; it must hold poses [V,..] and optionally K, size, tau, min_views, peel, "
+                             "recentre, scale")
+        P = np.asarray(f["poses"], np.float64)
+        if P.ndim < 2 or not 1 <= P.shape[0] <= 32 or tuple(P.shape[1:]) not in ((12,), (3, 4), (4, 4)):
+            raise ValueError(f"--fuse: poses must be [V,12], [V,3,4] or [V,4,4] with 1 <= V <= 32, got {P.shape}")
+        poses = [camera.as_pose(p, f"--fuse(poses[{i}])") for i, p in enumerate(P)]
+        size = None
+        if "size" in f:
+            size = np.asarray(f["size"]).reshape(-1)
+            if size.shape != (2,) or not all(int(v) == v and v >= 1 for v in size):
+                raise ValueError(f"--fuse: size must be (Ho, Wo), integers >= 1, got {f['size']!r}")
+            size = (int(size[0]), int(size[1]))
+        one = lambda k, t: t(np.asarray(f[k]).reshape(-1)[0])
+        kw = {k: one(k, t) for k, t in (("tau", float), ("min_views", int), ("peel", int), ("recentre", bool)) if k in f}
+        return dict(poses=poses, cam=camera.as_pinhole(f["K"], "--fuse(K)") if "K" in f else None, size=size,
+                    scale=one("scale", int) if "scale" in f else 1, kw=kw)
+
+
 @torch.no_grad()
 def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weights=None, quiet=False, any_size=False):
     """-> dict(delta1, delta2, delta3, RMSE, AbsRel, seconds_per_pair), averaged over the test set as the scripts do.
@@ -349,7 +376,11 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     {args.out_path}/complete_{j:04d}.npz (depth_dense, measured, index, dist), outside the timed region; one more metrics line per
     pair and in the average scores depth_dense with the same utils.eval_depth call, and the averages are returned under the key
     `dense`.  Without the flag, output and return value are what they were.  args.complete_method 'diffuse' completes by edge-aware
-    diffusion (DepthPipeline.complete(method="diffuse")): the npz also holds `residual`, and the lines read "(completed, diffuse)"."""
+    diffusion (DepthPipeline.complete(method="diffuse")): the npz also holds `residual`, and the lines read "(completed, diffuse)".
+    args.fuse = an .npz file of settings (load_fusion: poses [V,..], optional K, size, tau, min_views, peel, recentre, scale; not in
+    the reference): every V consecutive pairs of the test set are one group whose pair i has pose i; the group merged in one camera,
+    DepthPipeline.fuse, goes to {args.out_path}/fused_{g:04d}.npz (depth, valid, weight, views, count, layer, shpd), outside the
+    timed region; a remainder of fewer than V pairs is skipped, with a printed note."""
     import data, models, utils
     from .pipeline import DepthPipeline
     dev = _device(args)
@@ -381,10 +412,14 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     cloud, rcam = getattr(args, "point_cloud", False), getattr(args, "reproject", None)
     if rcam is not None:
         rcam = load_camera(rcam)
+    fcfg = getattr(args, "fuse", None)
+    if fcfg is not None:
+        fcfg = load_fusion(fcfg)
+    group = []
     complete = getattr(args, "complete", False)
     cmethod = getattr(args, "complete_method", "nearest")
     clabel = "completed" if cmethod == "nearest" else f"completed, {cmethod}"
-    if rsize is not None or spoints is not None or cloud or rcam is not None or complete:
+    if rsize is not None or spoints is not None or cloud or rcam is not None or complete or fcfg is not None:
         os.makedirs(args.out_path, exist_ok=True)
     fine_maps, fine_thres = ("shpd", "refoc", "bndry", "depth", "conf"), 0.05 if (big or any_size) else None
     sweep = None
@@ -429,6 +464,13 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
                                     scale=rcam["scale"], depth_thres=fine_thres if rcam["scale"] > 1 else None)
             np.savez(os.path.join(args.out_path, f"reproj_{j:04d}.npz"),
                      **{k: v.cpu().numpy() for k, v in warped.items() if k != "lattice"})
+        if fcfg is not None:
+            group.append(maps)
+            if len(group) == len(fcfg["poses"]):
+                fused = pipe.fuse(list(zip(group, fcfg["poses"])), cam_dst=fcfg["cam"], size=fcfg["size"], scale=fcfg["scale"],
+                                  depth_thres=fine_thres if fcfg["scale"] > 1 else None, **fcfg["kw"])
+                np.savez(os.path.join(args.out_path, f"fused_{j // len(group):04d}.npz"), **{k: v.cpu().numpy() for k, v in fused.items()})
+                group = []
         depth = maps["depth_map"][None]
         m = np.array(utils.eval_depth(depth, gt[None].to(depth.dtype), depth, crop=args.crop))
         tot += m
@@ -444,6 +486,8 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
             if not quiet:
                 print(f'Image pair #{j} ({clabel}): delta1 ={m[0]: .3f}, delta2 ={m[1]: .3f}, delta3 ={m[2]: .3f}, RMSE ={m[3]: .3f} cm, '
                       f'AbsRel ={m[4]: .3f} cm')
+    if group and not quiet:
+        print(f'--fuse: the last {len(group)} pair(s) do not fill a group of {len(fcfg["poses"])} and were not fused')
     n = max(len(ds), 1)
     res = dict(zip(("delta1", "delta2", "delta3", "RMSE", "AbsRel"), (tot / n).tolist()), seconds_per_pair=secs / n)
     if not quiet:

@@ -657,6 +657,55 @@ std::tuple<Tensor, Tensor, Tensor> reproject(const Tensor& depth, const Tensor& 
     return {dout, index, fout};
 }
 
+// multi-view depth fusion: depth[v] [Hs,Ws] on the GPU, weight[v] of the same shape or an empty tensor (1 everywhere), feat[v] [C,Hs*Ws]
+// (an empty list when C == 0); cam_src [V,4], pose [V,12], cam_dst [4] CPU float32; scale / top / left one int per view
+// -> (depth, weight [Ho,Wo], views, count, layer [Ho,Wo] int32, feat [C,Ho,Wo]); the per-pixel state is scratch allocated here
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fuse_views(at::TensorList depth, at::TensorList weight, at::TensorList feat,
+                                                                      const Tensor& cam_src, const Tensor& pose, const Tensor& cam_dst,
+                                                                      double near, int64_t Ho, int64_t Wo, at::IntArrayRef scale,
+                                                                      at::IntArrayRef top, at::IntArrayRef left, double tau, int64_t min_views,
+                                                                      bool recentre, int64_t peel) {
+    const int64_t V = (int64_t)depth.size();
+    TORCH_CHECK(V >= 1 && V <= BE_FUSE_MAX_VIEWS, "fuse_views: 1 .. ", BE_FUSE_MAX_VIEWS, " views");
+    TORCH_CHECK((int64_t)weight.size() == V && (feat.size() == 0 || (int64_t)feat.size() == V), "fuse_views: weight and feat hold one entry per view");
+    TORCH_CHECK((int64_t)scale.size() == V && (int64_t)top.size() == V && (int64_t)left.size() == V, "fuse_views: scale, top, left hold one entry per view");
+    TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= (1 << 24) && Wo <= (1 << 24), "fuse_views: bad target size");
+    const int64_t C = feat.size() == 0 ? 0 : feat[0].size(0);
+    std::vector<const float*> pd(V), pw(V), pf(V);
+    std::vector<int> hs(V), ws(V), sc(V), tp(V), lf(V);
+    for (int64_t v = 0; v < V; ++v) {
+        const Tensor& d = depth[v];
+        TORCH_CHECK(d.dim() == 2 && d.numel() > 0 && d.numel() <= 0x7fffffff, "fuse_views: depth [Hs,Ws], 1 .. 2^31 - 1 samples");
+        TORCH_CHECK(d.device() == depth[0].device(), "fuse_views: every view on one device");
+        pd[v] = fp(d, "depth");
+        pw[v] = nullptr;
+        if (weight[v].numel() > 0) {
+            TORCH_CHECK(weight[v].sizes() == d.sizes() && weight[v].device() == d.device(), "fuse_views: weight [Hs,Ws] on depth's device");
+            pw[v] = fp(weight[v], "weight");
+        }
+        pf[v] = nullptr;
+        if (C > 0) {
+            TORCH_CHECK(feat[v].dim() == 2 && feat[v].size(0) == C && feat[v].size(1) == d.numel() && feat[v].device() == d.device(),
+                        "fuse_views: feat [C,Hs*Ws] on depth's device, the same C in every view");
+            pf[v] = fp(feat[v], "feat");
+        }
+        hs[v] = (int)d.size(0); ws[v] = (int)d.size(1); sc[v] = (int)scale[v]; tp[v] = (int)top[v]; lf[v] = (int)left[v];
+    }
+    const int64_t bytes = be_fuse_scratch_bytes((int)Ho, (int)Wo, (int)C);
+    TORCH_CHECK(bytes > 0, "fuse_views: no scratch size for ", Ho, " x ", Wo, " with ", C, " channels");
+    auto o = depth[0].options();
+    Tensor scratch = at::empty({bytes / 8 + 1}, o.dtype(at::kLong));
+    Tensor dout = at::empty({Ho, Wo}, o), wout = at::empty({Ho, Wo}, o), fout = at::empty({C, Ho, Wo}, o);
+    Tensor views = at::empty({Ho, Wo}, o.dtype(at::kInt)), count = at::empty({Ho, Wo}, o.dtype(at::kInt)), layer = at::empty({Ho, Wo}, o.dtype(at::kInt));
+    check(be_fuse_views_f32((int)V, pd.data(), pw.data(), C > 0 ? pf.data() : nullptr, (int)C, hs.data(), ws.data(), sc.data(), tp.data(), lf.data(),
+                            host_floats(cam_src, 4 * V, "fuse_views(cam_src)"), host_floats(pose, 12 * V, "fuse_views(pose)"),
+                            host_floats(cam_dst, 4, "fuse_views(cam_dst)"), (float)near, (int)Ho, (int)Wo, (float)tau, (int)min_views,
+                            recentre ? 1 : 0, (int)peel, scratch.data_ptr<int64_t>(), dout.data_ptr<float>(), wout.data_ptr<float>(),
+                            views.data_ptr<int32_t>(), count.data_ptr<int32_t>(), layer.data_ptr<int32_t>(),
+                            C > 0 ? fout.data_ptr<float>() : nullptr, stream_of(depth[0])), "be_fuse_views_f32");
+    return {dout, wout, views, count, layer, fout};
+}
+
 // nearest-sample flood fill: depth [H,W], weight [H,W] or None -> (depth_out [H,W], index [H,W] int32, dist2 [H,W] int32); the seed
 // maps and the per-seed means are scratch allocated here
 std::tuple<Tensor, Tensor, Tensor> fill_nearest(const Tensor& depth, const c10::optional<Tensor>& weight, int64_t smooth_r, double sigma_z,
@@ -830,6 +879,8 @@ TORCH_LIBRARY(be, m) {
     m.def("fold_refocus_stack_points(Tensor opts, Tensor consts, Tensor records, Tensor rho_primes, Tensor? ys, Tensor? xs, int hp, int wp, int H, int W, int stride, Tensor points) -> Tensor");
     m.def("unproject(Tensor depth, Tensor cam_src, Tensor pose, int scale, int top, int left) -> Tensor");
     m.def("reproject(Tensor depth, Tensor cam_src, Tensor cam_dst, Tensor pose, float near, int Ho, int Wo, Tensor? feat, int scale, int top, int left) -> (Tensor, Tensor, Tensor)");
+    m.def("fuse_views(Tensor[] depth, Tensor[] weight, Tensor[] feat, Tensor cam_src, Tensor pose, Tensor cam_dst, float near, int Ho, int Wo, "
+          "int[] scale, int[] top, int[] left, float tau, int min_views, bool recentre, int peel) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("fill_nearest(Tensor depth, Tensor? weight, int smooth_r, float sigma_z, bool fuse) -> (Tensor, Tensor, Tensor)");
     m.def("fill_diffuse(Tensor depth, Tensor? weight, Tensor? edge, int smooth_r, float sigma_z, float leak, int iters, bool fuse) -> "
           "(Tensor, Tensor, Tensor, Tensor)");
@@ -892,6 +943,7 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("fold_refocus_stack_points", fold_refocus_stack_points);
     m.impl("unproject", unproject);
     m.impl("reproject", reproject);
+    m.impl("fuse_views", fuse_views);
     m.impl("fill_nearest", fill_nearest);
     m.impl("fill_diffuse", fill_diffuse);
     m.impl("local_loss", local_loss);

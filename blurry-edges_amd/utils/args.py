@@ -96,6 +96,9 @@ _GROUPS = {
         # to the camera of an .npz settings file - K, R, t, size, optional scale - (DepthPipeline.reproject), written to out_path
         ('--point_cloud', dict(action='store_true')),
         ('--reproject', dict(type=str, default=None)),
+        # not in the reference: every V consecutive pairs merged in one camera (DepthPipeline.fuse) with the poses of an .npz settings
+        # file - poses [V,..], optional K, size, tau, min_views, peel, recentre, scale - written to out_path
+        ('--fuse', dict(type=str, default=None)),
         # not in the reference: every pair's depth map completed to a dense one by nearest-sample flood fill (DepthPipeline.complete),
         # written to out_path and scored with the same metrics
         ('--complete', dict(action='store_true')),

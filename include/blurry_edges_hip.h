@@ -243,6 +243,39 @@ int be_reproject_f32(const float* depth, int Hs, int Ws, int scale, int top, int
                      const float* pose, float near, int Ho, int Wo, const float* feat, int C, uint64_t* zbuf, float* depth_out,
                      int32_t* index, float* feat_out, void* stream);
 
+/* Multi-view depth fusion: V views (1 <= V <= BE_FUSE_MAX_VIEWS), each a depth map with the lattice, camera and pose arguments of
+ * be_reproject_f32, merged in the camera cam_dst, size Ho x Wo.  Host arrays of V entries: depth[v] [Hs[v],Ws[v]] float32 on the
+ * device; weight[v] of the same shape or NULL (1 everywhere; the array itself may be NULL); feat[v] [C,Hs[v]*Ws[v]] (the array may
+ * be NULL when C == 0); Hs, Ws, scale, top, left; cam_src [V,4] and pose [V,12] host floats (pose: view v's frame -> the target's);
+ * cam_dst [4].  The projection is be_reproject_f32's, operation by operation.  A sample takes part iff it passes be_reproject_f32's
+ * test, its weight w is > 0 (NaN fails) and wq = floorf(min(w, 16) * 65536 + 0.5) is non-zero (NULL weight: wq = 65536).
+ * Per target pixel, floor = +0 at the start; in rounds r = 0 .. peel, all in fp32 without contraction:
+ *   front   zmin = min over the samples on the pixel that take part with Zd > floor of the bits of Zd (uint32); all-ones = none
+ *   add     base = zmin as a float, span = tau; a sample agrees iff d = Zd - base satisfies d >= 0 && d <= span; it adds
+ *           wq to sw, wq * dq to swd (dq = floorf(d * 2^20 + 0.5)), 1 to cnt, bit v to mask and, per channel,
+ *           wq * fq to swf (fq = floorf(min(max(f, -2048), 2048) * 65536 + 0.5); a NaN f counts as 0)
+ *   mean    where cnt > 0: m = (float)((double) base + (double) swd / (double) sw * 2^-20)
+ *   recentre != 0: base = m - tau (NaN where cnt == 0), span = tau + tau, the sums cleared, add and mean again
+ *   decide  a pixel not yet finalised with cnt > 0 and popcount(mask) >= min_views is finalised: depth_out = m,
+ *           weight_out = (float)((double) sw * 2^-16), views_out = popcount(mask), count_out = cnt, layer_out = r,
+ *           feat_out[c] = (float)((double) swf[c] / (double) sw * 2^-16); with cnt > 0 and too few views floor = base + span (its
+ *           front cluster is peeled off and the next round starts behind it); with cnt == 0 floor = +inf.
+ * A pixel never finalised gets depth +0, weight 0, views 0, count 0, layer -1, feat +0.  Every output element is written exactly
+ * once.  Every accumulation is an integer atomic (min, add, or), so the outputs depend neither on the order of execution nor on
+ * the order of the views; the sums are exact in 64 bits while fewer than 2^16 samples agree on one pixel (not checked).  The
+ * schedule of launches is a function of (V, recentre, peel) alone, nothing synchronises with the host, and everything runs on
+ * `stream` in `scratch`: be_fuse_scratch_bytes(Ho, Wo, C) bytes of device memory, 8-byte aligned (-1 for sizes out of range).
+ * 0 <= tau <= 4 (metres); 1 <= min_views <= V; 0 <= peel <= BE_FUSE_MAX_PEEL; 0 <= C <= BE_FUSE_MAX_CHANNELS. */
+#define BE_FUSE_MAX_VIEWS 32
+#define BE_FUSE_MAX_PEEL 8
+#define BE_FUSE_MAX_CHANNELS 64
+int64_t be_fuse_scratch_bytes(int Ho, int Wo, int C);
+int be_fuse_views_f32(int V, const float* const* depth, const float* const* weight, const float* const* feat, int C, const int* Hs,
+                      const int* Ws, const int* scale, const int* top, const int* left, const float* cam_src, const float* pose,
+                      const float* cam_dst, float near, int Ho, int Wo, float tau, int min_views, int recentre, int peel,
+                      void* scratch, float* depth_out, float* weight_out, int32_t* views_out, int32_t* count_out, int32_t* layer_out,
+                      float* feat_out, void* stream);
+
 /* Dense depth from sparse samples by nearest-sample flood fill.  depth [H,W] float32 on the device; weight [H,W] float32 or NULL
  * (weight 1 everywhere).  Pixel p is a seed iff weight[p] > 0, depth[p] > 0 and depth[p] < inf (NaN fails all three).  Every pixel
  * is given a seed by jump flooding: an int32 seed map holds each pixel's current seed as the linear index y * W + x (-1: none); one
