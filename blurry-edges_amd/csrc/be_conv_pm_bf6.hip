@@ -12,12 +12,22 @@
 //     walk's order: chunk = (cc * 9 + tap) * 2 + half, the 1x1 behind ncc * 9 * 2); six v_mfma_f32_32x32x16_bf16 per 16-deep
 //     chunk in the fixed order lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi, fp32 accumulation, K ascending from a zero
 //     accumulator; a ring of four 20-KB stages (80 KB: two workgroups per CU) with the DMA three chunks ahead, counted vmcnt
-//     waits and one raw s_barrier per chunk; the next chunk's fragments are read and split behind the current chunk's MFMAs.
+//     waits and one raw s_barrier per chunk; the next chunk's fragments are read and split between the current chunk's MFMAs.
 // Wave tile 32 images x 96 channels (all MFMAs useful: three 32-column accumulators, one A fragment): per chunk a wave issues
 // 18 MFMAs for 2 + 9 fragment reads, one split8 and 5 DMA pieces (2 A + 3 B) - the SAME five in the tap segment and in the x2
 // segment, which is what "vmcnt(5)" = "all but the newest chunk have landed" relies on.  Past the end of the walk the last chunk
 // is fetched again (into slots nobody reads any more), so the count never changes; the last wait drains everything: no DMA into
 // LDS outlives the workgroup.
+// The pieces live in two register sets; the next chunk's reads and split sit between this chunk's MFMAs, every gap closed by
+// __builtin_amdgcn_sched_barrier(0) (L0_CHUNK; k_wino_gemm_ps's scheme and the reasons for it: be_wino.hip).  No result bit depends
+// on it.  The emitted loop (hipcc -S, gfx950, read by hand; hipcc rotates the loop into four bodies, all alike):
+//   [vmcnt(5)] s_barrier, the walker's scalar arithmetic, 5 global_load_lds_dwordx4
+//   gaps 0-4    MFMA, 2 ds_read_b128 each;  gap 5  MFMA, 1 ds_read_b128;  gaps 6-9  MFMA alone
+//   gap 10      MFMA, s_waitcnt lgkmcnt(0) (the youngest read is four MFMAs old), half A: 6 VALU + 1 s_nop
+//   gaps 11-17  MFMA, half B (5 VALU + s_nop) and half A (6 VALU + s_nop) in turn
+//   consecutive MFMAs write different accumulators (v[32:47] v[16:31] v[0:15] in turn); no v_pk_* f32 instruction, no scratch.
+// Compiler report (gfx950): 166 VGPRs (one set: 123), 0 AGPRs, scratch 0, no spills, 34.2 KB of code (32.2); LDS 80 KB: two
+// workgroups per CU.
 // One body for every batch size: an output element sees the same chain of operations whatever the batch, the position in it or
 // the tile it falls in.
 #include "be_common.h"
@@ -30,6 +40,7 @@ namespace {
 using be::bf6::bf16x8;
 using be::bf6::f32x4;
 using be::bf6::split8;
+using be::bf6::u32x4;
 using be::bf6::PS_BLOCK;
 using be::bf6::ps_slot;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -151,18 +162,53 @@ void k_conv_pm_bf6(PmBf6Args a) {
     for (int j = 0; j < 3; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-    // the pieces of the chunk being multiplied: read from LDS and split (A) while the chunk before is still on the matrix pipe
-    bf16x8 ap[3], bp[3][3];                            // [hi, mid, lo]([j])
+    // two sets of pieces: chunk c's MFMAs read set c & 1 while chunk c + 1's fragments are read and split into the other set, one
+    // piece of that work in every gap between two MFMAs (L0_CHUNK, k_wino_gemm_ps's scheme).  The set is a compile-time parameter
+    // of the body (a run-time index would send the pieces to scratch): the loop walks two chunks per trip, an odd total ends
+    // behind body 0.
+    u32x4 ap[2][3];                                    // [set][hi, mid, lo], one dword per pair unit
+    bf16x8 bp[2][3][3];                                // [set][hi, mid, lo][j]
     int r_buf = 0;                                     // ring slot whose fragments are read next
-#define L0_FRAGS()                                                                                              \
+    // One chunk: 18 groups, each closed by a sched_barrier(0) (nothing crosses it, so the order below is the emitted order).
+    // Group g issues MFMA g - product p = g / 3 (lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi), accumulator j = g % 3: consecutive
+    // MFMAs never share an accumulator - and, for chunk + 1 out of ring slot r_buf into set S ^ 1:
+    //   g = 0       the two fp32 A fragment reads (quads 2 lh, 2 lh + 1)
+    //   g = 1..5    two B reads each (the last gap one), planes hi, mid, lo in turn
+    //   g = 10..17  one half of one of the four pair units of the split8 (unit u = (g - 10) / 2; half A, then half B)
+    // The LDS reads are plain loads and the compiler places their wait, a full lgkmcnt(0) in front of the first split group, where
+    // the youngest read is four MFMAs old.
+#define L0_CHUNK(S)                                                                                             \
     do {                                                                                                        \
+        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};                                   \
         const char* sb_ = lds + r_buf * STAGE;                                                                  \
-        const f32x4 af0_ = *reinterpret_cast<const f32x4*>(sb_ + a_fr0);                                        \
-        const f32x4 af1_ = *reinterpret_cast<const f32x4*>(sb_ + a_fr1);                                        \
-        _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                        \
-            _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_)                                                    \
-                bp[p_][j_] = *reinterpret_cast<const bf16x8*>(sb_ + b_fr + p_ * 4096 + j_ * 32 * 32);           \
-        split8(af0_, af1_, ap[0], ap[1], ap[2]);                                                                \
+        f32x4 af_[2];                                  /* [quad] */                                             \
+        float r0_[4], r1_[4];                                                                                   \
+        _Pragma("unroll") for (int g_ = 0; g_ < 18; ++g_) {                                                     \
+            acc[g_ % 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ap[S][PA[g_ / 3]]),\
+                                                                  bp[S][PB[g_ / 3]][g_ % 3], acc[g_ % 3], 0, 0, 0); \
+            if (g_ == 0) {                                                                                      \
+                af_[0] = *reinterpret_cast<const f32x4*>(sb_ + a_fr0);                                          \
+                af_[1] = *reinterpret_cast<const f32x4*>(sb_ + a_fr1);                                          \
+            }                                                                                                   \
+            if (g_ >= 1 && g_ < 6)                                                                              \
+                _Pragma("unroll") for (int b_ = 2 * (g_ - 1); b_ < 2 * g_ && b_ < 9; ++b_)                      \
+                    bp[(S) ^ 1][b_ / 3][b_ % 3] =                                                               \
+                        *reinterpret_cast<const bf16x8*>(sb_ + b_fr + (b_ / 3) * 4096 + (b_ % 3) * 32 * 32);    \
+            if (g_ >= 10) {                                                                                     \
+                const int u_ = (g_ - 10) >> 1;                                                                  \
+                if ((g_ & 1) == 0) {                                                                            \
+                    unsigned h_, m_;                                                                            \
+                    be::bf6::split_pair_a(af_[u_ >> 1][(2 * u_) & 3], af_[u_ >> 1][(2 * u_ + 1) & 3], h_, m_, r0_[u_], r1_[u_]); \
+                    ap[(S) ^ 1][0][u_] = h_;                                                                    \
+                    ap[(S) ^ 1][1][u_] = m_;                                                                    \
+                } else {                                                                                        \
+                    unsigned l_ = be::bf6::split_pair_b(r0_[u_], r1_[u_], ap[(S) ^ 1][1][u_]);                  \
+                    asm volatile("" : "+v"(l_));       /* (keeps the last cvt_pk in its group) */               \
+                    ap[(S) ^ 1][2][u_] = l_;                                                                    \
+                }                                                                                               \
+            }                                                                                                   \
+            __builtin_amdgcn_sched_barrier(0);                                                                  \
+        }                                                                                                       \
         r_buf = (r_buf + 1) % NS;                                                                               \
     } while (0)
 
@@ -172,27 +218,42 @@ void k_conv_pm_bf6(PmBf6Args a) {
     L0_DMA();                                          // chunk 2
     __builtin_amdgcn_s_waitcnt(0x0F75);                // vmcnt(5): chunks 0 and 1 have landed
     __builtin_amdgcn_s_barrier();                      // ... every wave's
-    L0_FRAGS();                                        // chunk 0's pieces
-    bool landed = true;                                // the NEXT chunk's DMA is known to be in LDS
-    for (int kc = 0; kc < total; ++kc) {
-        if (!landed) __builtin_amdgcn_s_waitcnt(0x0F75);                               // vmcnt(5): chunk + 1 has landed
-        landed = false;
-        __builtin_amdgcn_s_barrier();                  // ... every wave's; everyone has read the slot of chunk - 1 (a chunk ago)
-        L0_DMA();                                      // chunk + 3, into that slot
-        __builtin_amdgcn_sched_barrier(0);
-        {
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi
+    {                                                  // chunk 0's pieces into set 0, in one piece
+        const f32x4 af0_ = *reinterpret_cast<const f32x4*>(lds + a_fr0);
+        const f32x4 af1_ = *reinterpret_cast<const f32x4*>(lds + a_fr1);
 #pragma unroll
-            for (int p = 0; p < 6; ++p)
+        for (int p = 0; p < 3; ++p)
 #pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[PA[p]], bp[PB[p]][j], acc[j], 0, 0, 0);
-            L0_FRAGS();                                // chunk + 1's pieces, under this chunk's MFMAs
-        }
-        __builtin_amdgcn_sched_barrier(0);
+            for (int j = 0; j < 3; ++j) bp[0][p][j] = *reinterpret_cast<const bf16x8*>(lds + b_fr + p * 4096 + j * 32 * 32);
+        bf16x8 h, m, l;
+        split8(af0_, af1_, h, m, l);
+        ap[0][0] = __builtin_bit_cast(u32x4, h);
+        ap[0][1] = __builtin_bit_cast(u32x4, m);
+        ap[0][2] = __builtin_bit_cast(u32x4, l);
+        r_buf = 1;
     }
+    bool landed = true;                                // the NEXT chunk's DMA is known to be in LDS
+#define L0_TOP()                                                                                                \
+    do {                                                                                                        \
+        if (!landed) __builtin_amdgcn_s_waitcnt(0x0F75);                               /* vmcnt(5): chunk + 1 has landed */ \
+        landed = false;                                                                                         \
+        __builtin_amdgcn_s_barrier();                  /* ... every wave's; everyone has read the slot of chunk - 1 (a chunk ago) */ \
+        L0_DMA();                                      /* chunk + 3, into that slot */                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                      \
+    } while (0)
+    for (int kc = 0; kc < total; kc += 2) {
+        L0_TOP();
+        L0_CHUNK(0);                                   // this chunk's MFMAs with chunk + 1's reads and split in their gaps
+        __builtin_amdgcn_sched_barrier(0);
+        if (kc + 1 < total) {
+            L0_TOP();
+            L0_CHUNK(1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#undef L0_TOP
 #undef L0_DMA
-#undef L0_FRAGS
+#undef L0_CHUNK
     __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): nothing left in flight into LDS
     __builtin_amdgcn_sched_barrier(0);
 

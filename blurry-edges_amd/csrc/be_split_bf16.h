@@ -24,39 +24,56 @@ __device__ __forceinline__ float sub_f32(float x, float y) {
     asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
     return r;
 }
+// One pair unit of the split - two neighbouring values -> one packed dword of each plane - in two halves that a loop can place
+// separately between its MFMAs (k_wino_gemm_ps, k_conv_pm_bf6: one half per MFMA gap; a half's issue fits under one 32-cycle MFMA):
+//   half A (6 VALU): cvt_pk hi, shift, and, two exact v_sub_f32, cvt_pk mid;  it leaves the residuals r0, r1 for half B
+//   half B (5 VALU): shift, and, two exact v_sub_f32, cvt_pk lo
+// Every split below is built on these two, so the arithmetic exists once.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void split_pair_a(float x0, float x1, unsigned& hu, unsigned& mu, float& r0, float& r1) {
+    hu = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){x0, x1}, bf16x2));     // v_cvt_pk_bf16_f32: RNE
+    r0 = sub_f32(x0, bf_lo(hu));                                                             // exact
+    r1 = sub_f32(x1, bf_hi(hu));
+    mu = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){r0, r1}, bf16x2));
+}
+__device__ __forceinline__ unsigned split_pair_b(float r0, float r1, unsigned mu) {
+    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){sub_f32(r0, bf_lo(mu)), sub_f32(r1, bf_hi(mu))}, bf16x2));   // exact
+}
+
 // the 8 values of two fp32 quads -> the hi / mid / lo fragments of one 32x32x16 bf16 MFMA operand
 __device__ __forceinline__ void split8(f32x4 a, f32x4 b, bf16x8& h, bf16x8& m, bf16x8& l) {
     const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    u32x4 hu, mu, lu;
 #pragma unroll
-    for (int e = 0; e < 8; e += 2) {
-        const bf16x2 hb = __builtin_convertvector((f32x2){x[e], x[e + 1]}, bf16x2);          // v_cvt_pk_bf16_f32: RNE
-        const unsigned hu = __builtin_bit_cast(unsigned, hb);
-        const float r0 = sub_f32(x[e], bf_lo(hu)), r1 = sub_f32(x[e + 1], bf_hi(hu));        // exact
-        const bf16x2 mb = __builtin_convertvector((f32x2){r0, r1}, bf16x2);
-        const unsigned mu = __builtin_bit_cast(unsigned, mb);
-        const bf16x2 lb = __builtin_convertvector((f32x2){sub_f32(r0, bf_lo(mu)), sub_f32(r1, bf_hi(mu))}, bf16x2);   // exact
-        h[e] = hb[0]; h[e + 1] = hb[1];
-        m[e] = mb[0]; m[e + 1] = mb[1];
-        l[e] = lb[0]; l[e + 1] = lb[1];
+    for (int u = 0; u < 4; ++u) {
+        float r0, r1;
+        unsigned h_, m_;
+        split_pair_a(x[2 * u], x[2 * u + 1], h_, m_, r0, r1);
+        hu[u] = h_; mu[u] = m_;
+        lu[u] = split_pair_b(r0, r1, m_);
     }
+    h = __builtin_bit_cast(bf16x8, hu);
+    m = __builtin_bit_cast(bf16x8, mu);
+    l = __builtin_bit_cast(bf16x8, lu);
 }
 
 // the 4 values of one fp32 quad -> 8 bytes of each plane: the same split, for a producer that stores the pieces (k_conv1_pool_bf6)
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void split4(f32x4 a, bf16x4& h, bf16x4& m, bf16x4& l) {
     const float x[4] = {a.x, a.y, a.z, a.w};
+    u32x2 hu, mu, lu;
 #pragma unroll
-    for (int e = 0; e < 4; e += 2) {
-        const bf16x2 hb = __builtin_convertvector((f32x2){x[e], x[e + 1]}, bf16x2);
-        const unsigned hu = __builtin_bit_cast(unsigned, hb);
-        const float r0 = sub_f32(x[e], bf_lo(hu)), r1 = sub_f32(x[e + 1], bf_hi(hu));
-        const bf16x2 mb = __builtin_convertvector((f32x2){r0, r1}, bf16x2);
-        const unsigned mu = __builtin_bit_cast(unsigned, mb);
-        const bf16x2 lb = __builtin_convertvector((f32x2){sub_f32(r0, bf_lo(mu)), sub_f32(r1, bf_hi(mu))}, bf16x2);
-        h[e] = hb[0]; h[e + 1] = hb[1];
-        m[e] = mb[0]; m[e + 1] = mb[1];
-        l[e] = lb[0]; l[e + 1] = lb[1];
+    for (int u = 0; u < 2; ++u) {
+        float r0, r1;
+        unsigned h_, m_;
+        split_pair_a(x[2 * u], x[2 * u + 1], h_, m_, r0, r1);
+        hu[u] = h_; mu[u] = m_;
+        lu[u] = split_pair_b(r0, r1, m_);
     }
+    h = __builtin_bit_cast(bf16x4, hu);
+    m = __builtin_bit_cast(bf16x4, mu);
+    l = __builtin_bit_cast(bf16x4, lu);
 }
 
 // The pre-split weights' block (k_wino_pack_split): per (position, 128-row N tile, 16-deep K chunk) one contiguous 12-KB block

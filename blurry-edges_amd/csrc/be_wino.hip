@@ -334,6 +334,7 @@ struct GemmArgs {
 // ---- split-bf16 operands (BF6 = 1) --------------------------------------------------------------------------------------------
 // x = hi + mid + lo, the six products per K chunk and split8: be_split_bf16.h (shared with be_conv_pm_bf6.hip)
 using be::bf6::bf16x8;
+using be::bf6::u32x4;
 using be::bf6::split8;
 using be::bf6::PS_BLOCK;
 using be::bf6::ps_slot;
@@ -569,6 +570,26 @@ void k_wino_gemm(GemmArgs a) {
 // "problems" may be GemmArgs' walked row tiles (nb consecutive 128-row tiles of one matrix per workgroup: mrows = 128 nb, zrows = 128,
 // xb = 128 lda, yb = 128 ldy, wb = 0; only when every walked tile is full), so that a short K loop keeps one continuous pipeline.
 // <0, 0> is the Winograd kernel of round 8, instruction for instruction.
+// Round 12, the same arithmetic on another instruction schedule (no result bit moves: the pieces, the MFMA, the lane -> k map, the
+// six-product order per accumulator and the K order from a zero accumulator are those of round 8).  Until then hipcc issued a chunk as
+// 24 MFMAs, the next chunk's 10 ds_read_b128, lgkmcnt(0), ~90 VALU of split8 in one run: an in-order wave hides at most one 32-cycle
+// MFMA of that.  Now the pieces live in two register sets and the next chunk's reads and split sit BETWEEN this chunk's MFMAs, every
+// gap closed by __builtin_amdgcn_sched_barrier(0) (PS_CHUNK; split_pair_a / split_pair_b of be_split_bf16.h).  What does not bind: a
+// sched_group_barrier sequence over the one-set loop (no group mask matches the inline-asm v_sub_f32; with plain subtractions the
+// scheduler regroups the MFMAs into runs of six dependent ones on one accumulator).  The emitted loop (hipcc -S, gfx950, read by hand;
+// both bodies alike, <0, 0> and <0, 1> alike; <1, 1> keeps the one-set loop, see the loop):
+//   [vmcnt(5)] s_barrier, 5 global_load_lds_dwordx4 + their scalar address arithmetic (7 VALU)
+//   gaps 0-4    MFMA, 2 ds_read_b128 each (gap 0 also the 3 v_add_u32 of the slot's addresses)
+//   gaps 5-7    MFMA alone
+//   gap 8       MFMA, s_waitcnt lgkmcnt(0) (the youngest read is three MFMAs old), half A: 6 VALU + 1 s_nop
+//   gaps 9-23   MFMA, half B (5 VALU + s_nop) and half A (6 VALU + s_nop) in turn; no run of VALU longer than 6
+//   consecutive MFMAs write different accumulators (v[48:63] v[16:31] v[32:47] v[0:15] in turn); no v_pk_* f32 instruction, no v_mov
+//   of a piece, no scratch access in the loop.  hipcc emits no counted lgkmcnt anywhere in this file, hence the early paired reads.
+// Compiler report (gfx950; round 8-9 build in brackets), LDS 80 KB: two workgroups per CU = 2 waves per SIMD in every case:
+//   <0, 0>  179 VGPRs [138], 0 AGPRs, scratch 0, no VGPR spills,  76 SGPR spills [126], 18.7 KB of code [11.5]
+//   <0, 1>  210 VGPRs [140], 0 AGPRs, scratch 0, no VGPR spills,  15 SGPR spills [71],  15.3 KB [10.9]
+//   <1, 1>  the one-set loop: 182 VGPRs [150], 0 AGPRs, scratch 0, no VGPR spills, 26 SGPR spills [84], 41.7 KB [43.8].  With the
+//           two-set loop and the boundary block (Smish epilogue) behind both bodies it was 222 VGPRs and 80.0 KB, and slower.
 template <int EPI, int ROWS = 0>
 __global__ __launch_bounds__(256, 2)
 void k_wino_gemm_ps(GemmArgs a) {
@@ -637,12 +658,58 @@ void k_wino_gemm_ps(GemmArgs a) {
             bias_v[j] = (a.bias && c < a.N) ? a.bias[c] : 0.0f;
         }
     }
-    // the pieces of the chunk being multiplied: read from LDS and split (A) while the chunk before is still on the matrix pipe
-    bf16x8 ap[3][2], bp[3][2];                         // [hi, mid, lo][i or j]
+    // two sets of pieces: chunk c's MFMAs read set c & 1 while chunk c + 1's fragments are read and split into the other set, one
+    // piece of that work in every gap between two MFMAs (PS_CHUNK).  The set is a compile-time parameter of the body (a run-time
+    // index would send the pieces to scratch), so the body is compiled once per set.
+    u32x4 ap[2][3][2];                                 // [set][hi, mid, lo][i], one dword per pair unit
+    bf16x8 bp[2][3][2];                                // [set][hi, mid, lo][j]
     int r_buf = 0;                                     // ring slot whose fragments are read next
-#define PS_FRAGS()                                                                                              \
+    // One chunk: 24 groups, each closed by a sched_barrier(0) (nothing crosses it, so the order below is the emitted order).
+    // Group g issues MFMA g - product p = g / 4 (lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi), accumulator (i, j) = ((g / 2) % 2, g % 2):
+    // consecutive MFMAs never share an accumulator - and, for chunk + 1 out of ring slot r_buf into set S ^ 1:
+    //   g = 0, 1    the two fp32 A fragment reads (quads 2 lh, 2 lh + 1) of i = g
+    //   g = 2..4    the two reads (j = 0, 1) of B plane g - 2
+    //   g = 8..23   one half of one of the eight pair units of the two split8 (unit u = (g - 8) / 2: i = u / 4; half A, then half B)
+    // The LDS reads are plain loads and the compiler places their wait.  It only ever emits lgkmcnt(0), in front of the first split
+    // group: hence the reads two to a gap and early, so that the youngest is three MFMAs old when the wait comes.
+#define PS_CHUNK(S)                                                                                             \
     do {                                                                                                        \
+        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};                                   \
         const char* sb_ = lds + r_buf * STAGE;                                                                  \
+        f32x4 af_[2][2];                               /* [quad][i] */                                          \
+        float r0_[8], r1_[8];                                                                                   \
+        _Pragma("unroll") for (int g_ = 0; g_ < 24; ++g_) {                                                     \
+            acc[(g_ >> 1) & 1][g_ & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                               \
+                __builtin_bit_cast(bf16x8, ap[S][PA[g_ >> 2]][(g_ >> 1) & 1]), bp[S][PB[g_ >> 2]][g_ & 1],      \
+                acc[(g_ >> 1) & 1][g_ & 1], 0, 0, 0);                                                           \
+            if (g_ < 2) {                                                                                       \
+                af_[0][g_] = *reinterpret_cast<const f32x4*>(sb_ + a_fr0 + g_ * 32 * BKT * 4);                  \
+                af_[1][g_] = *reinterpret_cast<const f32x4*>(sb_ + a_fr1 + g_ * 32 * BKT * 4);                  \
+            }                                                                                                   \
+            if (g_ >= 2 && g_ < 5)                                                                              \
+                _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                                \
+                    bp[(S) ^ 1][g_ - 2][j_] = *reinterpret_cast<const bf16x8*>(sb_ + b_fr + (g_ - 2) * 4096 + j_ * 32 * 32); \
+            if (g_ >= 8) {                                                                                      \
+                const int u_ = (g_ - 8) >> 1, i_ = u_ >> 2, e_ = u_ & 3;                                        \
+                if ((g_ & 1) == 0) {                                                                            \
+                    unsigned h_, m_;                                                                            \
+                    be::bf6::split_pair_a(af_[e_ >> 1][i_][(2 * e_) & 3], af_[e_ >> 1][i_][(2 * e_ + 1) & 3], h_, m_, r0_[u_], r1_[u_]); \
+                    ap[(S) ^ 1][0][i_][e_] = h_;                                                                \
+                    ap[(S) ^ 1][1][i_][e_] = m_;                                                                \
+                } else {                                                                                        \
+                    unsigned l_ = be::bf6::split_pair_b(r0_[u_], r1_[u_], ap[(S) ^ 1][1][i_][e_]);              \
+                    asm volatile("" : "+v"(l_));       /* (keeps the last cvt_pk in its group) */               \
+                    ap[(S) ^ 1][2][i_][e_] = l_;                                                                \
+                }                                                                                               \
+            }                                                                                                   \
+            __builtin_amdgcn_sched_barrier(0);                                                                  \
+        }                                                                                                       \
+        r_buf = (r_buf + 1) % NS;                                                                               \
+    } while (0)
+    // a chunk's pieces from ring slot SLOT into set 0 in one piece (the prologue)
+#define PS_FRAGS0(SLOT)                                                                                         \
+    do {                                                                                                        \
+        const char* sb_ = lds + (SLOT) * STAGE;                                                                 \
         f32x4 af_[2][2];                                                                                        \
         _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                      \
             af_[0][i_] = *reinterpret_cast<const f32x4*>(sb_ + a_fr0 + i_ * 32 * BKT * 4);                      \
@@ -650,36 +717,37 @@ void k_wino_gemm_ps(GemmArgs a) {
         }                                                                                                       \
         _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                        \
             _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                                    \
-                bp[p_][j_] = *reinterpret_cast<const bf16x8*>(sb_ + b_fr + p_ * 4096 + j_ * 32 * 32);           \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) split8(af_[0][i_], af_[1][i_], ap[0][i_], ap[1][i_], ap[2][i_]); \
-        r_buf = (r_buf + 1) % NS;                                                                               \
+                bp[0][p_][j_] = *reinterpret_cast<const bf16x8*>(sb_ + b_fr + p_ * 4096 + j_ * 32 * 32);        \
+        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                      \
+            bf16x8 h_, m_, l_;                                                                                  \
+            split8(af_[0][i_], af_[1][i_], h_, m_, l_);                                                         \
+            ap[0][0][i_] = __builtin_bit_cast(u32x4, h_);                                                       \
+            ap[0][1][i_] = __builtin_bit_cast(u32x4, m_);                                                       \
+            ap[0][2][i_] = __builtin_bit_cast(u32x4, l_);                                                       \
+        }                                                                                                       \
     } while (0)
     PS_DMA();                                          // chunk 0
     PS_DMA();                                          // chunk 1
     PS_DMA();                                          // chunk 2
     __builtin_amdgcn_s_waitcnt(0x0F75);                // vmcnt(5): chunks 0 and 1 have landed
     __builtin_amdgcn_s_barrier();                      // ... every wave's
-    PS_FRAGS();                                        // chunk 0's pieces
+    PS_FRAGS0(0);                                      // chunk 0's pieces
+    r_buf = 1;
     int cz = 0, ck = 0;
     bool landed = true;                                // the NEXT chunk's DMA is known to be in LDS
-    for (int kc = 0; kc < total; ++kc) {
-        if (!landed) __builtin_amdgcn_s_waitcnt(0x0F75);                               // vmcnt(5): chunk + 1 has landed
-        landed = false;
-        __builtin_amdgcn_s_barrier();                  // ... every wave's; everyone has read the slot of chunk - 1 (a chunk ago)
-        PS_DMA();                                      // chunk + 3, into that slot
-        __builtin_amdgcn_sched_barrier(0);
-        {
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi
-#pragma unroll
-            for (int p = 0; p < 6; ++p)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[PA[p]][i], bp[PB[p]][j], acc[i][j], 0, 0, 0);
-            PS_FRAGS();                                // chunk + 1's pieces, under this chunk's MFMAs
-        }
-        __builtin_amdgcn_sched_barrier(0);
+    // The loop walks two chunks per trip, body 0 then body 1, each followed by the problem-boundary block; an odd total ends behind
+    // body 0.  (One shared boundary block - body by parity, or set 1 moved / read again into set 0 behind an odd problem - was tried:
+    // the register allocator then assembles every chunk's tuples with 12 v_mov in front of the first MFMA, or spills.)  With an even
+    // chunk count per problem, K % 32 == 0 - every layer of LocalStage -, only the block behind body 1 is ever executed.
+#define PS_TOP()                                                                                                \
+    do {                                                                                                        \
+        if (!landed) __builtin_amdgcn_s_waitcnt(0x0F75);                               /* vmcnt(5): chunk + 1 has landed */ \
+        landed = false;                                                                                         \
+        __builtin_amdgcn_s_barrier();                  /* ... every wave's; everyone has read the slot of chunk - 1 (a chunk ago) */ \
+        PS_DMA();                                      /* chunk + 3, into that slot */                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                      \
+    } while (0)
+    auto boundary = [&](int kc) __attribute__((always_inline)) {   // behind chunk kc
         if (++ck == kchunks) {                          // problem cz is complete: store, clear
             if (kc + 1 < total) __builtin_amdgcn_s_waitcnt(0x0F75);                    // chunk + 2 has landed
             else __builtin_amdgcn_s_waitcnt(0x0F70);                                   // nothing left in flight
@@ -730,9 +798,47 @@ void k_wino_gemm_ps(GemmArgs a) {
                     for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
             ck = 0; ++cz;
         }
+    };
+    if constexpr (EPI) {
+        // <1, 1> (fc.1: one problem of 144 chunks per workgroup) keeps the one-set loop of rounds 8-9 - the MFMAs, then chunk + 1's
+        // pieces into set 0 in one piece: measured with the two-set loop it LOST 5.5 % (195.7 -> 206.4 us per launch, round 12), and
+        // its Smish epilogue behind both bodies made 80 KB of code
+        for (int kc = 0; kc < total; ++kc) {
+            PS_TOP();
+            {
+                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi
+#pragma unroll
+                for (int p = 0; p < 6; ++p)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ap[0][PA[p]][i]), bp[0][PB[p]][j],
+                                                                                acc[i][j], 0, 0, 0);
+                PS_FRAGS0(r_buf);                      // chunk + 1's pieces, under this chunk's MFMAs
+                r_buf = (r_buf + 1) % NS;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            boundary(kc);
+        }
+    } else {
+        for (int kc = 0; kc < total; kc += 2) {
+            PS_TOP();
+            PS_CHUNK(0);                               // this chunk's MFMAs with chunk + 1's reads and split in their gaps
+            __builtin_amdgcn_sched_barrier(0);
+            boundary(kc);
+            if (kc + 1 < total) {
+                PS_TOP();
+                PS_CHUNK(1);
+                __builtin_amdgcn_sched_barrier(0);
+                boundary(kc + 1);
+            }
+        }
     }
+#undef PS_TOP
 #undef PS_DMA
-#undef PS_FRAGS
+#undef PS_FRAGS0
+#undef PS_CHUNK
 }
 
 // ---- weight-stationary form of the same GEMMs (large batches, K = 96 / 256 / 384) ------------------------------------------
