@@ -108,6 +108,9 @@ _SIGNATURES = {
     "be_wino_pair_workspace_floats": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "be_wino_conv3x3_pair_6x6_f32": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P,
                                                C.c_size_t, _P]),
+    "be_wino_conv3x3_pair_chain_6x6_f32": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                                     _P, C.c_size_t, _P, C.c_int, C.c_int]),
+    "be_maxpool_wino_in_11x11_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "be_conv_fused2_packed_floats": (C.c_size_t, [C.c_int] * 4),
     "be_conv_pack_fused2_f32": (C.c_int, [_P] * 12 + [C.c_float] + [C.c_int] * 4 + [_P, _P, _P]),
     "be_conv_nhwc_fused2_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
@@ -829,6 +832,31 @@ def wino_conv3x3_pair(x, pw1, pb1, cmid, pw2, pb2, cout, act1=1, act2=1, residua
     return y, workspace
 
 
+def wino_conv3x3_pair_chain(x, pw1, pb1, cmid, pw2, pb2, cout, workspace, act1=1, act2=1, residual=None, x_in_v=False, next_cmid=0):
+    """wino_conv3x3_pair as a link of a chain of blocks that share `workspace` (at least be_wino_pair_workspace_floats of every link).
+    x_in_v: the start of the workspace already holds x's input transform (left by the link in front or by maxpool_wino_in);
+    next_cmid > 0: y's input transform for a following block whose conv1 has next_cmid outputs is left there.  Same bits as unchained."""
+    n_, h, w, cin = x.shape
+    y = torch.empty(n_, 6, 6, cout, dtype=torch.float32, device=x.device)
+    check(lib().be_wino_conv3x3_pair_chain_6x6_f32(dptr(x, "x"), dptr(pw1), dptr(pb1), int(act1), dptr(pw2), dptr(pb2), dptr(residual),
+                                                   int(act2), dptr(y), n_, cin, cmid, cout, dptr(workspace), workspace.numel(),
+                                                   stream_ptr(x.device), int(bool(x_in_v)), int(next_cmid)),
+          "be_wino_conv3x3_pair_chain_6x6_f32")
+    return y
+
+
+def maxpool_wino_in(x, next_cmid, workspace):
+    """x [N,11,11,C] NHWC -> its 3/2/1 max-pool [N,6,6,C] (maxpool_nhwc's bits); the pooled map's Winograd input transform for a block
+    whose conv1 has next_cmid outputs is left at the start of `workspace` (head of a wino_conv3x3_pair_chain)."""
+    n_, h, w, c = x.shape
+    if (h, w) != (11, 11):
+        raise RuntimeError(f"maxpool_wino_in: 11x11 maps only, got {h}x{w}")
+    y = torch.empty(n_, 6, 6, c, dtype=torch.float32, device=x.device)
+    check(lib().be_maxpool_wino_in_11x11_f32(dptr(x, "x"), dptr(y), n_, c, int(next_cmid), dptr(workspace), workspace.numel(),
+                                             stream_ptr(x.device)), "be_maxpool_wino_in_11x11_f32")
+    return y
+
+
 def local_stage_forward_view(packed, view, patches_per_image: int, n: int, device, out=None, workspace=None, winograd=True,
                              chunk=0):
     """LocalStage eval forward over the n = A*P patches of a PatchView (no unfolded copy) -> [n,10]."""
@@ -849,7 +877,8 @@ KERNEL_NAMES = {0: "k_conv_igemm<2,2,2,2,TAPS> (128x128)", 1: "k_conv_igemm<4,1,
                 4: "k_conv_igemm<4,1,1,2,ROW8> (conv1)", 5: "k_conv_igemm small-M tiles (64x64 / 128x32)",
                 6: "k_wino_gemm<0, 1> (128x128 tiles, the Winograd transform-domain GEMMs of a layer - one per position: 40 for the 8x5 tiles - per launch, in split-bf16 arithmetic: six v_mfma_f32_32x32x16_bf16 per product, FLOPs counted as fp32 products; BE_WINO_F32=1: the fp32 k_wino_gemm_ws / k_wino_gemm / batched k_conv_igemm)",
                 7: "row GEMMs: k_wino_gemm_ps<EPI> on pre-split weights (split-bf16 arithmetic, FLOPs counted as fp32 products: LocalStage's 1x1 downsamples and fc.1; BE_ROWS_F32=1 / BE_WINO_F32=1: fp32) and the fp32 k_wino_gemm<1> / k_wino_gemm_ws<.., 1> (1x1 convolutions / linears of large batches)",
-                8: "k_wino_in / k_wino_out_in / k_wino_out / k_wino_out_pool2 (Winograd transforms)", 9: "k_maxpool_nhwc",
+                8: "k_wino_in / k_wino_out_in / k_wino_out / k_wino_out_pool2 / k_wino_out_res_in / k_pool_wino_in (Winograd transforms; the chained LocalStage runs k_pool_wino_in - the 3/2/1 max-pool with layer1's input transform - three k_wino_out_in, two k_wino_out_res_in and k_wino_out_pool2; BE_WINO_NO_CHAIN=1: k_maxpool_nhwc and a k_wino_in and k_wino_out per block)",
+                9: "k_maxpool_nhwc",
                 10: "k_render_colors (pass A)", 11: "conv1 input staging",
                 12: "k_unit_gemms / k_unit_gemms_sk (training units: weight-gradient GEMMs + data-gradient convolutions of one or two units in one launch; a residual block's two forward convolutions)",
                 13: "k_conv1_pool_bf6 (conv1 7x7 + Smish + max-pool 3/2/1 in one image-major kernel, in split-bf16 arithmetic with the image pre-split in LDS, FLOPs counted as fp32 products; BE_C1_F32=1 / BE_WINO_F32=1: the fp32 k_conv1_pool)"}

@@ -97,10 +97,12 @@ bool l0_bf6_enabled();
 // max-pool then keeps the fp32 routing (be_conv7x7_pool_nhwc4p_f32 for large sub-batches, conv1 and the pool kernel for small ones)
 bool c1_bf6_enabled();
 
-// be_wino.hip: be_wino_conv3x3_pair_6x6_f32; pool2 = 1 writes the 2x2 max-pool of the block's output, [n,3,3,cout]
+// be_wino.hip: be_wino_conv3x3_pair_6x6_f32; pool2 = 1 writes the 2x2 max-pool of the block's output, [n,3,3,cout].
+// Chained blocks (be_wino_conv3x3_pair_chain_6x6_f32): x_in_v = 1: x's input transform already lies at the start of the workspace;
+// next_cmid > 0: y's input transform for a following block (conv1 with next_cmid outputs) is left there (not with pool2)
 int wino_pair(const float* x, const float* packed_w1, const float* packed_bias1, int act1, const float* packed_w2,
               const float* packed_bias2, const float* residual, int act2, float* y, int64_t n, int cin, int cmid, int cout,
-              float* workspace, size_t workspace_floats, void* stream, int pool2);
+              float* workspace, size_t workspace_floats, void* stream, int pool2, int x_in_v = 0, int next_cmid = 0);
 // be_conv.hip: convolution / linear of a training unit (small M).  With scratch the K loop may be split: then the S raw slices
 // are LEFT in scratch as [S][M][ldp] (S > 1 reported, nothing written to y, bias / res not applied) for the caller's kernel to sum;
 // S == 1: y = conv + bias (+ res).

@@ -3,9 +3,11 @@
 //   384->256 @6^2 -> maxpool(2,2) -> flatten -> Linear 2304->1024 + BN1d + Smish -> Linear 1024->10
 // Activations are NHWC in a caller-provided workspace; the batch is walked in sub-batches (default 8192 patches,
 // measured best) so the workspace stays bounded whatever N is.  Per sub-batch: staging, conv1, 2-3 pools, layer0 as two direct
-// launches (conv1; conv2 with the downsample fused in), layers 1-3 each as a 1x1 downsample launch + the Winograd pair
-// (input transform, 40 GEMMs, output+input transform, 40 GEMMs, output transform - layer3's with the 2x2 max-pool in it;
-// be_wino.hip), fc.1, fc.4.  Sub-batches of 512 patches and more take the LDS-DMA kernels (be_conv_pm.hip for conv1 on a
+// launches (conv1; conv2 with the downsample fused in), the second pool with layer1's input transform in it, layers 1-3 each as a
+// 1x1 downsample launch + the chained Winograd pair (40 GEMMs, output+input transform, 40 GEMMs, output transform - layers 1
+// and 2's with the next layer's input transform in it, layer3's with the 2x2 max-pool in it; be_wino.hip), fc.1, fc.4.
+// BE_WINO_NO_CHAIN=1 (read once per process): the unchained launches - k_maxpool_nhwc, and every layer from k_wino_in to
+// k_wino_out - with the same bits.  Sub-batches of 512 patches and more take the LDS-DMA kernels (be_conv_pm.hip for conv1 on a
 // row-padded staging and for layer0, the row GEMM of be_wino.hip for the 1x1s and fc.1); smaller ones k_conv_igemm - same
 // results bit for bit.  On the Winograd path the 1x1 downsamples of layers 1-3 and fc.1 run in split-bf16 arithmetic on ONE kernel for
 // every sub-batch size (be::gemm_rows_bf6; BE_ROWS_F32=1 / BE_WINO_F32=1: the fp32 kernels just named), and so does layer0
@@ -186,7 +188,9 @@ int block_l0_bf6(const float* packed, const float* x, float* t, float* o, int n,
 
 // The same block on a 6x6 map with both 3x3 convolutions in Winograd F(3x3,3x3) form (be_wino.hip): 2.56x fewer multiplies
 // than the direct form; the 1x1 downsample runs as its own convolution into `r` and joins in the output transform of conv2.
-int block_wino(const float* packed, int l0, const float* x, float* t, float* o, float* r, float* w, int n, void* stream, int pool2 = 0) {
+// x_in_v / next_cmid: the block as a link of the chain (be::wino_pair): x's transform is already in `w` / the next block's is left there
+int block_wino(const float* packed, int l0, const float* x, float* t, float* o, float* r, float* w, int n, void* stream, int pool2 = 0,
+               int x_in_v = 0, int next_cmid = 0) {
     const PackedLayout& L = layout();
     const int c = kLayers[l0].cout;
     (void)t;                                          // conv1's 6x6 result only ever exists in registers (k_wino_out_in)
@@ -206,7 +210,7 @@ int block_wino(const float* packed, int l0, const float* x, float* t, float* o, 
         }
     }
     return be::wino_pair(x, packed + L.uw_off[l0], packed + L.ub_off[l0], 1, packed + L.uw_off[l0 + 1], packed + L.ub_off[l0 + 1], r,
-                         1, o, n, kLayers[l0].cin, c, c, w, (size_t)n * RW, stream, pool2);
+                         1, o, n, kLayers[l0].cin, c, c, w, (size_t)n * RW, stream, pool2, x_in_v, next_cmid);
 }
 
 }  // namespace
@@ -278,17 +282,27 @@ int forward_impl(const float* packed, const float* x, const be_patch_view* view,
         if ((rc = (wino && be::l0_bf6_enabled()) ? block_l0_bf6(packed, p1, ra, rc_, nb, stream)
                                                  : block(packed, 1, p1, ra, rc_, nb, 11, stream))) return rc;
         float* p2 = rb;                                   // nb*3456
-        if ((rc = be_maxpool_nhwc_f32(rc_, p2, nb, 11, 11, 96, 3, 2, 1, stream))) return rc;
+        // Winograd path, at every sub-batch size: the blocks are chained through the start of RW.  The pool leaves layer1's input
+        // transform there, layers 1 and 2 end in the kernel that also writes the next layer's, so no block reads its input map a
+        // second time (the 1x1 downsample still does, hence the maps are written as before).  Lifetimes in RW: a block's V and M are
+        // dead once its last GEMMs ran, except M, which the boundary kernel reads while it writes the next V below M's start.
+        static const bool no_chain = getenv("BE_WINO_NO_CHAIN") != nullptr && atoi(getenv("BE_WINO_NO_CHAIN")) != 0;   // A/B knob
+        const int chain = wino && !no_chain;
+        if (chain) rc = be_maxpool_wino_in_11x11_f32(rc_, p2, nb, 96, kLayers[4].cout, rw, (size_t)nb * RW, stream);
+        else rc = be_maxpool_nhwc_f32(rc_, p2, nb, 11, 11, 96, 3, 2, 1, stream);
+        if (rc) return rc;
         // layer1: in RB, t RA, out RC
-        if ((rc = wino ? block_wino(packed, 4, p2, ra, rc_, rr, rw, nb, stream) : block(packed, 4, p2, ra, rc_, nb, 6, stream))) return rc;
+        if ((rc = wino ? block_wino(packed, 4, p2, ra, rc_, rr, rw, nb, stream, 0, chain, chain ? kLayers[7].cout : 0)
+                       : block(packed, 4, p2, ra, rc_, nb, 6, stream))) return rc;
         // layer2: in RC, t RA, out RB
-        if ((rc = wino ? block_wino(packed, 7, rc_, ra, rb, rr, rw, nb, stream) : block(packed, 7, rc_, ra, rb, nb, 6, stream))) return rc;
+        if ((rc = wino ? block_wino(packed, 7, rc_, ra, rb, rr, rw, nb, stream, 0, chain, chain ? kLayers[10].cout : 0)
+                       : block(packed, 7, rc_, ra, rb, nb, 6, stream))) return rc;
         // layer3: in RB, t RA, out RC; then maxpool(2,2) -> p3 [nb,3,3,256] = the (H,W,C) flatten.  Winograd path: the
         // output transform pools in registers and writes p3 directly (into RC: RB is still the block's input)
         float* p3;
         if (wino) {
             p3 = rc_;
-            if ((rc = block_wino(packed, 10, rb, ra, p3, rr, rw, nb, stream, 1))) return rc;
+            if ((rc = block_wino(packed, 10, rb, ra, p3, rr, rw, nb, stream, 1, chain))) return rc;
         } else {
             if ((rc = block(packed, 10, rb, ra, rc_, nb, 6, stream))) return rc;
             p3 = rb;                                      // nb*2304

@@ -26,6 +26,11 @@
 //   k_wino_gemm_ws the fp32 GEMMs weight-stationary (B tile in registers, A streamed through LDS by DMA): batches of >= 4096 maps
 //   k_wino_out     M -> y [N,6,6,Cout] + bias (+ residual) (+ Smish)
 //   k_wino_out_in  conv1 -> conv2 of a residual block: output transform + Smish + input transform, the map stays in registers
+//   k_wino_out_pool2   the last block's output transform with the 2x2 max-pool that follows it
+//   Chained blocks (round 13; be::wino_pair's x_in_v / next_cmid, be_wino_conv3x3_pair_chain_6x6_f32): a block's input transform is
+//   written by whatever produced its input map, out of the registers that hold the map, so no block reads its input a second time:
+//   k_wino_out_res_in  k_wino_out (+ bias, residual, activation, y stored) + the NEXT block's input transform
+//   k_pool_wino_in     max-pool 3/2/1 of [N,11,11,C] (k_maxpool_nhwc's bits) + the input transform of the pooled map
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -148,6 +153,29 @@ __device__ __forceinline__ V wino_act(V v, int act) {
     return v;
 }
 
+// input transform of a 6x6 map held in registers (the kernels below that keep one): the TPI x NPOS values of its tiles go to dst (the
+// image's first tile, this thread's channel vector; ts_o / plane_o: vectors between tiles / positions).  k_wino_in's arithmetic.
+template <int NT, class V>
+__device__ __forceinline__ void wino_in_map(const V y[6][6], V* dst, int64_t ts_o, int64_t plane_o) {
+    const V zero = V(0.f);
+#pragma unroll
+    for (int ty = 0; ty < TY; ++ty)
+#pragma unroll
+        for (int tx = 0; tx < 2; ++tx) {
+            V d[NR][5], v[NPOS];
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+#pragma unroll
+                for (int c = 0; c < 5; ++c) {
+                    const int yy = TH * ty - 1 + r, xx = 3 * tx - 1 + c;
+                    d[r][c] = (xx >= 0 && xx < 6 && yy >= 0 && yy < 6) ? y[yy < 0 ? 0 : (yy > 5 ? 5 : yy)][xx < 0 ? 0 : (xx > 5 ? 5 : xx)] : zero;
+                }
+            be::wino_in(d, v);
+#pragma unroll
+            for (int z = 0; z < NPOS; ++z) st_s<NT>(dst + (ty * 2 + tx) * ts_o + (size_t)z * plane_o, v[z]);
+        }
+}
+
 template <int NT, int VW = VW_OUT>
 __global__ __launch_bounds__(256)
 void k_wino_out(const float* __restrict__ M, const float* __restrict__ bias, const float* __restrict__ res,
@@ -219,24 +247,108 @@ void k_wino_out_in(const float* __restrict__ M, const float* __restrict__ bias, 
 #pragma unroll
                     for (int c = 0; c < 3; ++c) y[TH * ty + r][3 * tx + c] = wino_act(o[3 * r + c] + bv, act);
             }
-        const vec zero = vec(0.f);
+        wino_in_map<NT>(y, reinterpret_cast<vec*>(V) + img * TPI * ts_o + cq, ts_o, plane_o);
+    }
+}
+
+// Block boundary (round 13): conv2's output transform + bias + residual + activation, the store of y [N,6,6,C] (the next block's
+// 1x1 downsample reads it) AND the next block's input transform of that map out of the same registers - k_wino_out followed by
+// k_wino_in without k_wino_in's read of y (36 values per channel and map) and without its launch.  k_wino_out_pool2's register shape:
+// one thread = one image x one channel vector, M and the residual fetched together per tile; operation order as k_wino_out
+// (o + bias, + res, activation), so y and V carry that pair's bits.  M in the layout conv2's GEMMs wrote (tm_in), V in the one the
+// next block's conv1 GEMMs read (tm_out).
+// Compiler report (gfx950, NT = 1, hipcc -Rpass-analysis=kernel-resource-usage): 205 VGPRs, 0 AGPRs, scratch 0, no VGPR spills,
+// 189 SGPR spills (to VGPR lanes: the addresses), two waves per SIMD - as k_wino_out_pool2 (256 VGPRs, 274 SGPR spills, two waves)
+// and k_wino_out_in (172 VGPRs, 622 SGPR spills, two waves).
+template <int NT, int VW = VW_OUT>
+__global__ __launch_bounds__(256, VW_OUT == 2 ? 2 : 1)
+void k_wino_out_res_in(const float* __restrict__ M, const float* __restrict__ bias, const float* __restrict__ res,
+                       float* __restrict__ y, float* __restrict__ V, int64_t n, int c4, int act, int tm_in, int tm_out) {
+    typedef typename VecOf<VW>::type vec;
+    const int64_t total = n * c4;
+    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
+    const int64_t plane = tm_in ? c4 : n * TPI * c4, ts = tm_in ? NPOS * c4 : c4;
+    const int64_t plane_o = tm_out ? c4 : n * TPI * c4, ts_o = tm_out ? NPOS * c4 : c4;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
+        const int cq = (int)(idx % c4);
+        const int64_t img = idx / c4;
+        const vec bv = reinterpret_cast<const vec*>(bias)[cq];
+        vec v[6][6];
 #pragma unroll
         for (int ty = 0; ty < TY; ++ty)
 #pragma unroll
             for (int tx = 0; tx < 2; ++tx) {
-                vec d[NR][5], v[NPOS];
+                const vec* src = reinterpret_cast<const vec*>(M) + (img * TPI + ty * 2 + tx) * ts + cq;
+                vec m[NPOS], o[NOUT], rv[NOUT];
 #pragma unroll
-                for (int r = 0; r < NR; ++r)
+                for (int z = 0; z < NPOS; ++z) m[z] = ld_s<NT>(src + (size_t)z * plane);
+                if (res) {
 #pragma unroll
-                    for (int c = 0; c < 5; ++c) {
-                        const int yy = TH * ty - 1 + r, xx = 3 * tx - 1 + c;
-                        d[r][c] = (xx >= 0 && xx < 6 && yy >= 0 && yy < 6) ? y[yy < 0 ? 0 : (yy > 5 ? 5 : yy)][xx < 0 ? 0 : (xx > 5 ? 5 : xx)] : zero;
+                    for (int r = 0; r < TH; ++r)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c)
+                            rv[3 * r + c] = ld_s<NT>(reinterpret_cast<const vec*>(res) + ((size_t)img * 36 + (TH * ty + r) * 6 + 3 * tx + c) * c4 + cq);
+                }
+                be::wino_out(m, o);
+#pragma unroll
+                for (int r = 0; r < TH; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        vec w = o[3 * r + c] + bv;
+                        if (res) w += rv[3 * r + c];
+                        w = wino_act(w, act);
+                        v[TH * ty + r][3 * tx + c] = w;
+                        st_s<NT>(reinterpret_cast<vec*>(y) + ((size_t)img * 36 + (TH * ty + r) * 6 + 3 * tx + c) * c4 + cq, w);
                     }
-                be::wino_in(d, v);
-                vec* dst = reinterpret_cast<vec*>(V) + (img * TPI + ty * 2 + tx) * ts_o + cq;
-#pragma unroll
-                for (int z = 0; z < NPOS; ++z) st_s<NT>(dst + (size_t)z * plane_o, v[z]);
             }
+        wino_in_map<NT>(v, reinterpret_cast<vec*>(V) + img * TPI * ts_o + cq, ts_o, plane_o);
+    }
+}
+
+// The max-pool 3/2/1 between layer0 and layer1 + layer1's input transform (round 13): one thread = one image x one channel vector
+// reads [N,11,11,C] row by row (three input rows live: output row oy takes rows 2 oy - 1 .. 2 oy + 1, the last of them is the next
+// output row's first), writes the pooled [N,6,6,C] (layer1's 1x1 downsample reads it) and the TPI x NPOS transform-domain values of
+// that map.  The pooled values are k_maxpool_nhwc's bit for bit: its fold - from -inf over the nine taps, rows outer, columns inner,
+// a tap outside the map replaced by the nearest one inside (taken twice) - so signed zeros, infinities and dropped NaNs come out
+// as there.  Every input byte is read once, so the loads stream (NT) like the other transforms'.
+// Compiler report (gfx950, NT = 1): 126 VGPRs, 0 AGPRs, scratch 0, no VGPR spills, 90 SGPR spills, four waves per SIMD.
+template <int NT, int VW = VW_OUT>
+__global__ __launch_bounds__(256, VW_OUT == 2 ? 2 : 1)
+void k_pool_wino_in(const float* __restrict__ x, float* __restrict__ pooled, float* __restrict__ V, int64_t n, int c4, int tm_out) {
+    typedef typename VecOf<VW>::type vec;
+    const int64_t total = n * c4;
+    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
+    const int64_t plane_o = tm_out ? c4 : n * TPI * c4, ts_o = tm_out ? NPOS * c4 : c4;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
+        const int cq = (int)(idx % c4);
+        const int64_t img = idx / c4;
+        const vec* src = reinterpret_cast<const vec*>(x) + img * 121 * c4 + cq;
+        vec p[6][6], row[3][11];                       // row[0..2]: input rows 2 oy - 1, 2 oy, 2 oy + 1, clamped into the map
+#pragma unroll
+        for (int oy = 0; oy < 6; ++oy) {
+#pragma unroll
+            for (int c = 0; c < 11; ++c) {
+                row[0][c] = oy ? row[2][c] : ld_s<NT>(src + (size_t)c * c4);
+                row[1][c] = oy ? ld_s<NT>(src + (size_t)(22 * oy + c) * c4) : row[0][c];
+            }
+#pragma unroll
+            for (int c = 0; c < 11; ++c) row[2][c] = oy < 5 ? ld_s<NT>(src + (size_t)(22 * oy + 11 + c) * c4) : row[1][c];
+#pragma unroll
+            for (int ox = 0; ox < 6; ++ox) {
+                vec m = vec(-INFINITY);
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                    for (int dx = 0; dx < 3; ++dx) {
+                        const int xx = 2 * ox - 1 + dx < 0 ? 0 : (2 * ox - 1 + dx > 10 ? 10 : 2 * ox - 1 + dx);
+#pragma unroll
+                        for (int k = 0; k < VW; ++k) m[k] = fmaxf(m[k], row[dy][xx][k]);
+                    }
+                p[oy][ox] = m;
+                st_s<NT>(reinterpret_cast<vec*>(pooled) + ((size_t)img * 36 + oy * 6 + ox) * c4 + cq, m);
+            }
+        }
+        wino_in_map<NT>(p, reinterpret_cast<vec*>(V) + img * TPI * ts_o + cq, ts_o, plane_o);
     }
 }
 
@@ -1370,9 +1482,12 @@ extern "C" size_t be_wino_pair_workspace_floats(int64_t n, int cin, int cmid, in
 }
 
 // pool2 = 1: y is [n,3,3,cout], the 2x2 max-pool of the block's output (k_wino_out_pool2)
+// x_in_v = 1: the start of the workspace already holds x's input transform in this block's layout (left there by the block or the
+// pool kernel in front: k_wino_in is skipped).  next_cmid > 0: the last launch is k_wino_out_res_in, which writes y and, at the
+// start of the workspace, y's input transform for a following block whose conv1 has next_cmid outputs.
 int be::wino_pair(const float* x, const float* packed_w1, const float* packed_bias1, int act1, const float* packed_w2,
                   const float* packed_bias2, const float* residual, int act2, float* y, int64_t n, int cin, int cmid, int cout,
-                  float* workspace, size_t workspace_floats, void* stream, int pool2) {
+                  float* workspace, size_t workspace_floats, void* stream, int pool2, int x_in_v, int next_cmid) {
     BE_REQUIRE(x && packed_w1 && packed_bias1 && packed_w2 && packed_bias2 && y && workspace,
                "be_wino_conv3x3_pair_6x6_f32: null pointer");
     if (int rc = wino_args_ok("be_wino_conv3x3_pair_6x6_f32", n, cin, cmid)) return rc;
@@ -1385,7 +1500,14 @@ int be::wino_pair(const float* x, const float* packed_w1, const float* packed_bi
     float* V = workspace;
     float* M = workspace + (size_t)100 * n * big;
     const int tm1 = wino_large(n, cmid), tm2 = wino_large(n, cout);
-    {
+    BE_REQUIRE(next_cmid >= 0 && !(next_cmid > 0 && pool2), "be_wino_conv3x3_pair_6x6_f32: next_cmid cannot be combined with pool2");
+    if (next_cmid > 0) {
+        if (int rc = wino_args_ok("be_wino_conv3x3_pair_6x6_f32", n, cout, next_cmid)) return rc;
+        // the boundary kernel writes V' while it reads M: V' must end where M starts at the latest
+        BE_REQUIRE((size_t)(NPOS * TPI) * n * cout <= (size_t)100 * n * big,
+                   "be_wino_conv3x3_pair_6x6_f32: the next block's transform (cout %d) would reach M (max(cin, cmid) = %d)", cout, (int)big);
+    }
+    if (!x_in_v) {
         be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * cin * (36.0 + (double)(NPOS * TPI)), 0.0);
         BE_WINO_LAUNCH(k_wino_in, dim3(grid_cap(n * TPI * (cin / 4), 256)), dim3(256), 0, s, x, V, n, cin / 4, tm1);
     }
@@ -1399,8 +1521,12 @@ int be::wino_pair(const float* x, const float* packed_w1, const float* packed_bi
     if (int rc = be::check_launch("be_wino_conv3x3_pair_6x6_f32(out_in)")) return rc;
     if (int rc = wino_gemms(V, packed_w2, M, n, cmid, cout, s, stream)) return rc;
     {
-        be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * cout * ((double)(NPOS * TPI) + (residual ? 36.0 : 0.0) + (pool2 ? 9.0 : 36.0)), 0.0);
-        if (pool2)
+        be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * cout * ((double)(NPOS * TPI) + (residual ? 36.0 : 0.0) + (pool2 ? 9.0 : 36.0) +
+                                                                                   (next_cmid > 0 ? (double)(NPOS * TPI) : 0.0)), 0.0);
+        if (next_cmid > 0)
+            BE_WINO_LAUNCH(k_wino_out_res_in, dim3(grid_cap(n * (cout / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias2, residual, y, V, n,
+                               cout / VW_OUT, act2, tm2, (int)wino_large(n, next_cmid));
+        else if (pool2)
             BE_WINO_LAUNCH(k_wino_out_pool2, dim3(grid_cap(n * (cout / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias2, residual, y, n,
                                cout / VW_OUT, act2, tm2);
         else
@@ -1416,4 +1542,27 @@ extern "C" int be_wino_conv3x3_pair_6x6_f32(const float* x, const float* packed_
                                             size_t workspace_floats, void* stream) {
     return be::wino_pair(x, packed_w1, packed_bias1, act1, packed_w2, packed_bias2, residual, act2, y, n, cin, cmid, cout, workspace,
                          workspace_floats, stream, 0);
+}
+
+extern "C" int be_wino_conv3x3_pair_chain_6x6_f32(const float* x, const float* packed_w1, const float* packed_bias1, int act1,
+                                                  const float* packed_w2, const float* packed_bias2, const float* residual, int act2,
+                                                  float* y, int64_t n, int cin, int cmid, int cout, float* workspace,
+                                                  size_t workspace_floats, void* stream, int x_in_v, int next_cmid) {
+    return be::wino_pair(x, packed_w1, packed_bias1, act1, packed_w2, packed_bias2, residual, act2, y, n, cin, cmid, cout, workspace,
+                         workspace_floats, stream, 0, x_in_v, next_cmid);
+}
+
+extern "C" int be_maxpool_wino_in_11x11_f32(const float* x, float* pooled, int64_t n, int c, int next_cmid, float* workspace,
+                                            size_t workspace_floats, void* stream) {
+    BE_REQUIRE(x && pooled && workspace, "be_maxpool_wino_in_11x11_f32: null pointer");
+    if (int rc = wino_args_ok("be_maxpool_wino_in_11x11_f32", n, c, next_cmid)) return rc;
+    BE_REQUIRE(workspace_floats >= (size_t)(NPOS * TPI) * n * c, "be_maxpool_wino_in_11x11_f32: workspace too small");
+    BE_REQUIRE(be::aligned16(x) && be::aligned16(pooled) && be::aligned16(workspace), "be_maxpool_wino_in_11x11_f32: 16-byte alignment");
+    hipStream_t s = be::as_stream(stream);
+    {
+        be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * c * (121.0 + 36.0 + (double)(NPOS * TPI)), 0.0);
+        BE_WINO_LAUNCH(k_pool_wino_in, dim3(grid_cap(n * (c / VW_OUT), 256)), dim3(256), 0, s, x, pooled, workspace, n, c / VW_OUT,
+                           (int)wino_large(n, next_cmid));
+    }
+    return be::check_launch("be_maxpool_wino_in_11x11_f32");
 }

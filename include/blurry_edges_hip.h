@@ -526,6 +526,19 @@ size_t be_wino_pair_workspace_floats(int64_t n, int cin, int cmid, int cout);
 int be_wino_conv3x3_pair_6x6_f32(const float* x, const float* packed_w1, const float* packed_bias1, int act1,
                                  const float* packed_w2, const float* packed_bias2, const float* residual, int act2, float* y,
                                  int64_t n, int cin, int cmid, int cout, float* workspace, size_t workspace_floats, void* stream);
+/* The same block as a link of a chain that shares ONE workspace.  x_in_v != 0: the start of the workspace already holds x's input
+ * transform in this block's layout (left by the link in front), which is not computed again.  next_cmid > 0: besides y, the input
+ * transform of y for a following block whose first convolution has next_cmid outputs is left at the start of the workspace; refused
+ * when those positions * tiles * n * cout floats would reach past 100 n max(cin, cmid), where this block's own buffers start.
+ * be_maxpool_wino_in_11x11_f32 heads a chain: the 3/2/1 max-pool of [n,11,11,c] -> pooled [n,6,6,c] (be_maxpool_nhwc_f32's bits) and
+ * the input transform of the pooled map at the start of the workspace (positions * tiles * n * c floats; c %% 32 == 0).
+ * Results are those of the unchained calls bit for bit. */
+int be_wino_conv3x3_pair_chain_6x6_f32(const float* x, const float* packed_w1, const float* packed_bias1, int act1,
+                                       const float* packed_w2, const float* packed_bias2, const float* residual, int act2, float* y,
+                                       int64_t n, int cin, int cmid, int cout, float* workspace, size_t workspace_floats, void* stream,
+                                       int x_in_v, int next_cmid);
+int be_maxpool_wino_in_11x11_f32(const float* x, float* pooled, int64_t n, int c, int next_cmid, float* workspace,
+                                 size_t workspace_floats, void* stream);
 
 /* Row GEMM in the same split-bf16 arithmetic (bf16x6): y[m][ldy] = act(x[m][k] w^T + bias (+ residual)), act 0 none / 1 Smish / 2 ReLU,
  * residual with y's row stride; bias and residual may be NULL.  LocalStage's 1x1 downsamples of layers 1-3 and fc.1 run on it wherever
