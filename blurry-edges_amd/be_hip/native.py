@@ -169,6 +169,10 @@ _SIGNATURES = {
     "be_fuse_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "be_fuse_views_f32": (C.c_int, [C.c_int, _P, _P, _P, C.c_int] + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_float)] * 3
                           + [C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [_P] * 7 + [_P]),
+    "be_depth_normals_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.c_int, C.c_float, _P, _P]),
+    "be_icp_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "be_icp_linearize_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [C.POINTER(C.c_float), _P, _P, _P, C.c_int, C.c_int]
+                             + [C.POINTER(C.c_float)] * 2 + [C.c_float] * 3 + [_P] * 3 + [_P]),
     "be_fill_nearest_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int] + [_P] * 4 + [_P]),
     "be_fill_diffuse_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "be_fill_diffuse_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int] + [_P] * 5 + [_P]),
@@ -1454,6 +1458,126 @@ def fuse_views(views, cam_dst, size, tau=0.05, min_views=1, recentre=True, peel=
                                       dptr(scratch, "scratch", (torch.int64,)), dptr(d), dptr(wsum), dptr(nviews), dptr(count), dptr(layer),
                                       dptr(f if C_ else None), stream_ptr(dev)), "be_fuse_views_f32")
     return dict(depth=d, valid=layer >= 0, weight=wsum, views=nviews, count=count, layer=layer, feat=f if C_ else None)
+
+
+def depth_normals(depth, cam, step=3, max_jump=0.05, scale=1, window_origin=(0, 0)):
+    """Surface normals of a depth map: depth [H,W] (float32 on the GPU, the samples of unproject on the lattice (scale,
+    window_origin) of `cam`) -> dict(normal [3,H,W] = the unit normal (X, Y, Z) of the surface through each sample, facing the
+    camera (n . P <= 0), valid [H,W] = normal non-zero (on the device, no sync)).  The normal is the cross product of the
+    differences of the unprojected samples `step` apart along x and along y - central where both neighbours are inside the image,
+    hold a finite depth > 0 and lie within max_jump * step metres of the sample's depth, one-sided where one does - so that no
+    normal spans an occlusion step; (+0, +0, +0) where a direction has no such neighbour.  step > 1 trades resolution for noise.
+    registration.normals_f32 is the host statement, bit for bit."""
+    from . import registration
+    step, max_jump = registration.check_normals_params("depth_normals", step, max_jump)
+    depth, (cs,), _, top, left = _reproject_args("depth_normals", depth, [("cam", cam)], None, scale, window_origin)
+    H, W = depth.shape
+    o = ops()
+    if o is not None:
+        normal = o.depth_normals(depth, torch.from_numpy(cs), step, max_jump, scale, top, left)
+    else:
+        normal = torch.empty(3, H, W, dtype=torch.float32, device=depth.device)
+        check(lib().be_depth_normals_f32(dptr(depth, "depth", (torch.float32,)), H, W, scale, top, left, _fptr(cs), step, max_jump,
+                                         dptr(normal), stream_ptr(depth.device)), "be_depth_normals_f32")
+    return dict(normal=normal, valid=(normal != 0).any(0))
+
+
+ICP_VIEW_KEYS = ("depth", "weight", "cam", "scale", "window_origin")
+
+
+def _icp_view(who, v, dev=None):
+    """One view of icp_linearize / register_depth -> (depth, weight or None, camera float32 [4], scale, top, left)."""
+    if not isinstance(v, dict) or "depth" not in v or "cam" not in v:
+        raise ValueError(f"{who}: a view is a dict with the keys {ICP_VIEW_KEYS} (depth and cam at least)")
+    unknown = [k for k in v if k not in ICP_VIEW_KEYS]
+    if unknown:
+        raise ValueError(f"{who}: unknown keys {unknown}; a view holds {ICP_VIEW_KEYS}")
+    scale = v.get("scale", 1)
+    depth, (cs,), _, top, left = _reproject_args(who, v["depth"], [("cam", v["cam"])], None, scale, v.get("window_origin", (0, 0)))
+    if dev is not None and depth.device != dev:
+        raise ValueError(f"{who}: depth is on {depth.device}, the source's on {dev}")
+    w = v.get("weight")
+    if w is not None:
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != tuple(depth.shape):
+            raise ValueError(f"{who}: weight must be a float32 tensor [{depth.shape[0]},{depth.shape[1]}], got "
+                             f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}")
+        if w.device != depth.device:
+            raise ValueError(f"{who}: weight is on {w.device}, depth on {depth.device}")
+        w = w.contiguous()
+    return depth, w, cs, scale, top, left
+
+
+def icp_linearize(src, dst, normal_d, pose, near=1e-3, max_dist=0.1, huber=0.0, rows=False):
+    """The linearised point-to-plane step of a depth registration at `pose` (source frame -> target frame; None: the identity).
+    src, dst: dicts with the keys depth [H,W] (float32 on the GPU), weight [H,W] or None (1 everywhere), cam, scale and
+    window_origin (as reproject; the target's samples are the pixels of its camera: scale 1, origin (0, 0)); normal_d [3,Hd,Wd]:
+    the target's normals (depth_normals).  Every source sample is projected as reproject projects it; one that lands on a target
+    pixel with a finite depth > 0 and a non-zero normal, within max_dist (metres) of that pixel's point and with a weight product
+    in (0, inf), contributes its residual r = n . (P - Q) and its row J = (P x n, n), with its weight scaled by huber / |r| where
+    huber > 0 and |r| > huber.  -> dict(sums = float64 [32] on the device: the 21 sums w J[a] J[b] (a <= b), the 6 sums
+    w J[a] r, sum w r r, sum w, the number of samples, 0, 0; rows = float32 [8,Hs*Ws] (J, r, w per sample, 0 where it took no
+    part) when rows is true, else None).  The sums are double, added in an order that depends on the number of samples alone: no
+    floating-point atomics, the same bits on every run, stream and device.  Nothing synchronises with the host.
+    registration.linearize is the host statement, bit for bit."""
+    from . import camera, registration
+    near, max_dist, huber = registration.check_linearize_params("icp_linearize", near, max_dist, huber)
+    ds, ws, cs, scale, top, left = _icp_view("icp_linearize(src)", src)
+    dev = ds.device
+    dd, wd, cd, dscale, dtop, dleft = _icp_view("icp_linearize(dst)", dst, dev)
+    if dscale != 1 or (dtop, dleft) != (0, 0):
+        raise ValueError("icp_linearize(dst): the target's samples are the pixels of its camera: scale must be 1 and window_origin (0, 0)")
+    Hs, Ws = ds.shape
+    Hd, Wd = dd.shape
+    if (not isinstance(normal_d, torch.Tensor) or normal_d.dtype != torch.float32 or normal_d.dim() not in (2, 3)
+            or tuple(normal_d.shape) not in ((3, Hd, Wd), (3, Hd * Wd))):
+        raise ValueError(f"icp_linearize: normal_d must be a float32 tensor [3,{Hd},{Wd}], got "
+                         f"{getattr(normal_d, 'dtype', type(normal_d).__name__)} {tuple(getattr(normal_d, 'shape', ()))}")
+    if normal_d.device != dev:
+        raise ValueError(f"icp_linearize: normal_d is on {normal_d.device}, the source's depth on {dev}")
+    normal_d = normal_d.reshape(3, Hd, Wd).contiguous()
+    p12 = camera.as_pose(pose, "icp_linearize(pose)")
+    rows = bool(rows)
+    o = ops()
+    if o is not None:
+        sums, r = o.icp_linearize(ds, ws, torch.from_numpy(cs), scale, top, left, dd, normal_d, wd, torch.from_numpy(cd),
+                                  torch.from_numpy(p12), near, max_dist, huber, rows)
+        r = r if rows else None
+    else:
+        scratch = torch.empty(lib().be_icp_scratch_bytes(Hs, Ws) // 8, dtype=torch.float64, device=dev)
+        sums = torch.empty(32, dtype=torch.float64, device=dev)
+        r = torch.empty(8, Hs * Ws, dtype=torch.float32, device=dev) if rows else None
+        f64 = (torch.float64,)
+        check(lib().be_icp_linearize_f32(dptr(ds, "depth", (torch.float32,)), dptr(ws), Hs, Ws, scale, top, left, _fptr(cs),
+                                         dptr(dd, "depth", (torch.float32,)), dptr(normal_d), dptr(wd), Hd, Wd, _fptr(cd), _fptr(p12), near,
+                                         max_dist, huber, dptr(scratch, "scratch", f64), dptr(sums, "sums", f64), dptr(r), stream_ptr(dev)),
+              "be_icp_linearize_f32")
+    return dict(sums=sums, rows=r)
+
+
+def register_depth(src, dst, pose0=None, **kw):
+    """The pose of the source view in the target view's frame by point-to-plane ICP on their depth maps.  src, dst: the view
+    dicts of icp_linearize; pose0: the start (None: the identity); kw: the keywords of registration.register - iters=20,
+    damping=1e-6, max_dist=0.1, huber=0.0, step=3, max_jump=0.05, near=1e-3, tol=1e-9.  -> the dict of registration.register:
+    pose (12 float32 numbers: X' = R X + t from the source frame to the target's - what fuse takes), poses, rms, count, A, cond,
+    cov, converged, iters.  The loop, the 6 x 6 solve and the composition are registration.register itself, in float64 on the
+    host, with depth_normals (once) and icp_linearize (once per iteration) in place of the numpy statements: each iteration
+    copies 32 doubles to the host, one synchronisation per iteration.  The sums equal the statement's bit for bit, so the
+    iterates equal registration.register's bit for bit."""
+    from . import registration
+    unknown = [k for k in kw if k not in ("iters", "damping", "max_dist", "huber", "step", "max_jump", "near", "tol")]
+    if unknown:
+        raise ValueError(f"register_depth: unknown keywords {unknown}")
+    _icp_view("register_depth(src)", src)
+    _icp_view("register_depth(dst)", dst, src["depth"].device)
+
+    def normals(depth, cam, step, max_jump):
+        return depth_normals(depth, cam, step=step, max_jump=max_jump)["normal"]
+
+    def linearize(s, d, pose12, near, max_dist, huber):
+        view = {k: v for k, v in d.items() if k != "normal"}
+        return icp_linearize(s, view, d["normal"], pose12, near=near, max_dist=max_dist, huber=huber)["sums"].cpu().numpy()
+
+    return registration.register(src, dst, pose0, linearize=linearize, normals=normals, who="register_depth", **kw)
 
 
 FUSE_MAX_CHANNELS = 64

@@ -489,6 +489,78 @@ class DepthPipeline:
         return res
 
 
+    # ---- registration: surface normals of a depth map, and the pose between two pairs from their depth ---------------------
+    def _depth_view(self, who, maps, source, weights, complete_kw):
+        """One pair as a view of native.register_depth: its depth (depth_map, or complete()'s dense depth), its weights and its
+        camera dcal.intrinsics(H, W)."""
+        if source not in ("depth_map", "complete"):
+            raise ValueError(f"{who}: source must be 'depth_map' or 'complete', got {source!r}")
+        if weights not in ("conf", None):
+            raise ValueError(f"{who}: weights must be 'conf' or None, got {weights!r}")
+        if not isinstance(maps, dict) or "grid" not in maps:
+            raise ValueError(f"{who}: maps lacks ['grid']; pass the dict DepthPipeline.__call__, run_big or run_any returned")
+        if source == "complete":
+            done = self.complete(maps, **complete_kw)
+            z, measured, conf = done["depth_dense"], done["measured"], maps["conf"]
+        else:
+            if complete_kw:
+                raise ValueError(f"{who}: {sorted(complete_kw)} are keywords of complete; they need source='complete'")
+            src, _ = self._depth_samples(who, maps, 1, None, ("conf",) if weights else (), None)
+            z, measured, conf = src["depth_map"], None, src.get("conf")
+        w = None
+        if weights == "conf":
+            conf = conf.reshape(z.shape).to(torch.float32)
+            w = conf if measured is None else torch.where(measured, conf, torch.ones_like(conf))
+        g = maps["grid"]
+        return dict(depth=z, weight=w, cam=self.dcal.intrinsics(g["H"], g["W"]), scale=1, window_origin=(0, 0))
+
+    @torch.no_grad()
+    def normals(self, maps, step=3, max_jump=0.05, source="depth_map", scale=1, window=None, depth_thres=None, **complete_kw):
+        """maps: what __call__, run_big or run_any returned -> the surface normals of its depth: normal [3,Ho,Wo] = the unit normal
+        (X, Y, Z) in the camera's frame, facing the camera, valid [Ho,Wo] (normal non-zero; on the device, no sync) and lattice.
+        source="depth_map": the samples are those of point_cloud (render_at(scale, window, depth_thres) with their depth_map) -
+        depth_map holds depth in a band along the boundaries only, and a normal needs a neighbour `step` samples away along x and
+        along y, so most of the image stays invalid; source="complete": the depth is complete(maps, **complete_kw)["depth_dense"],
+        normals everywhere, and scale must be 1 without a window.  step, max_jump: native.depth_normals - differences over `step`
+        samples, and no difference across a depth step larger than max_jump * step metres."""
+        if source == "complete":
+            if scale != 1 or window is not None or depth_thres is not None:
+                raise ValueError("normals: source='complete' works on the pixels: scale must be 1, window and depth_thres None")
+            view = self._depth_view("normals", maps, source, None, complete_kw)
+            g = maps["grid"]
+            z, lat = view["depth"], tiling.lattice(g["H"], g["W"], 1, None)
+        elif source == "depth_map":
+            if complete_kw:
+                raise ValueError(f"normals: {sorted(complete_kw)} are keywords of complete; they need source='complete'")
+            src, lat = self._depth_samples("normals", maps, scale, window, (), depth_thres)
+            z = src["depth_map"]
+        else:
+            raise ValueError(f"normals: source must be 'depth_map' or 'complete', got {source!r}")
+        g = maps["grid"]
+        out = native.depth_normals(z, self.dcal.intrinsics(g["H"], g["W"]), step=step, max_jump=max_jump, scale=lat["scale"],
+                                   window_origin=lat["window"][:2])
+        return dict(normal=out["normal"], valid=out["valid"], lattice=lat)
+
+    @torch.no_grad()
+    def register(self, maps_src, maps_dst, pose0=None, source="complete", weights="conf", complete_kw=None, **kw):
+        """The pose of one pair's camera in another's frame, from their depth: point-to-plane ICP (native.register_depth) of
+        maps_src's depth onto maps_dst's, each in the camera dcal.intrinsics(H, W) of its own size, from pose0 (None: the
+        identity).  -> the dict of native.register_depth; its `pose` (X' = R X + t, source frame -> target frame) goes straight
+        into fuse([(maps_dst, None), (maps_src, pose)]).  source="complete": both depths are complete(maps, **complete_kw) - dense,
+        so that normals exist and samples meet; "depth_map": the thresholded depth as it is.  weights="conf": a sample weighs conf
+        where it was measured and 1 where completion filled it; None: no weights.  kw: iters, damping, max_dist, huber, step,
+        max_jump, near, tol of registration.register.  Each iteration synchronises with the host once (32 doubles).
+        Conditioning: the pipeline's own camera is narrow (4709.9 px of focal length on 147 px: under 2 degrees of view), so
+        rotations and in-plane translations are nearly interchangeable.  On a well-curved synthetic surface through such a camera
+        the 6 x 6 system's condition number was 1.9e4; on a single plane, where translation in the plane and rotation about its
+        normal are not observable at all, 2.6e8.  `cond` and `cov` are returned so that a caller can tell such cases apart: a
+        near-singular system is reported, it is not an error."""
+        complete_kw = dict(complete_kw or {})
+        src = self._depth_view("register(maps_src)", maps_src, source, weights, complete_kw)
+        dst = self._depth_view("register(maps_dst)", maps_dst, source, weights, complete_kw)
+        return native.register_depth(src, dst, pose0, **kw)
+
+
     # ---- dense depth: the holes of depth_map closed by nearest-sample flood fill or by edge-aware diffusion -----------------
     @torch.no_grad()
     def complete(self, maps, smooth=2, sigma_z=0.02, method="nearest", edges=True, leak=1e-3, iters=None):

@@ -14,6 +14,7 @@ formats (argument names and defaults = utils/args.py of the reference):
     ... eval --point_cloud [--out_path DIR]                also write every pair's depth map as points in space
     ... eval --reproject CAM.npz [--out_path DIR]          also write every pair's depth and colours as the camera of CAM sees them
     ... eval --fuse FILE.npz [--out_path DIR]              also merge every V consecutive pairs, with the poses of FILE, in one camera
+    ... eval --normals [--out_path DIR]                    also write every pair's surface normals (of its completed depth)
     ... eval --complete [--out_path DIR]                   also write and score every pair's depth map completed to a dense one
     ... eval --complete --complete_method diffuse          ... by edge-aware diffusion instead of the nearest sample's depth
 
@@ -330,7 +331,9 @@ def load_fusion(path):
     """The settings file of `eval --fuse`: an .npz holding poses [V,12], [V,3,4] or [V,4,4] (pair i of a group -> the target frame,
     1 <= V <= 32) and optionally K ([4] = fy, fx, cy, cx, or [3,3]) and size = (Ho, Wo) of the target camera (absent: the first
     pair's), tau, min_views, peel, recentre and scale (the source lattice) -> dict(poses, cam, size, scale, kw = the keywords of
-    DepthPipeline.fuse that the file sets), checked by be_hip.camera; tau, min_views and peel by native.fuse_views."""
+    DepthPipeline.fuse that the file sets), checked by be_hip.camera; tau, min_views and peel by native.fuse_views.  An optional
+    integer `register` > 0 (-> cfg["register"]) asks for every view's pose to be refined against view 0 by that many iterations of
+    DepthPipeline.register, starting from the pose given, before the group is merged."""
     from . import camera
     with np.load(path) as f:
         if "poses" not in f:
@@ -348,8 +351,29 @@ def load_fusion(path):
             size = (int(size[0]), int(size[1]))
         one = lambda k, t: t(np.asarray(f[k]).reshape(-1)[0])
         kw = {k: one(k, t) for k, t in (("tau", float), ("min_views", int), ("peel", int), ("recentre", bool)) if k in f}
-        return dict(poses=poses, cam=camera.as_pinhole(f["K"], "--fuse(K)") if "K" in f else None, size=size,
-                    scale=one("scale", int) if "scale" in f else 1, kw=kw)
+        cfg = dict(poses=poses, cam=camera.as_pinhole(f["K"], "--fuse(K)") if "K" in f else None, size=size,
+                   scale=one("scale", int) if "scale" in f else 1, kw=kw)
+        if "register" in f:                                                 # absent: the dict holds what it held before
+            n = np.asarray(f["register"]).reshape(-1)[0]
+            if int(n) != n or not 0 <= n <= 1000:
+                raise ValueError(f"--fuse: register must be an integer number of iterations in [0, 1000], got {f['register']!r}")
+            cfg["register"] = int(n)
+        return cfg
+
+
+def refine_poses(pipe, group, poses, iters):
+    """The poses of `eval --fuse` with `register` > 0: view 0 keeps its pose T0; view v's pose Tv (its frame -> the target frame)
+    gives the start inv(T0) Tv of DepthPipeline.register(view v, view 0), and the refined relative pose P comes back as T0 P.
+    -> (poses [V] as 12 float32 numbers, rms [V] = the last rms of each registration, 0 for view 0)."""
+    from . import camera
+    mat = lambda p: np.vstack([np.concatenate([np.asarray(p, np.float64)[:9].reshape(3, 3), np.asarray(p, np.float64)[9:, None]], 1), [0, 0, 0, 1]])
+    T0 = mat(poses[0])
+    out, rms = [np.asarray(poses[0], np.float32)], [0.0]
+    for maps, p in zip(group[1:], poses[1:]):
+        res = pipe.register(maps, group[0], pose0=np.linalg.inv(T0) @ mat(p), iters=iters)
+        out.append(camera.pose(T0 @ mat(res["pose"])))
+        rms.append(float(res["rms"][-1]) if len(res["rms"]) else float("nan"))
+    return out, rms
 
 
 @torch.no_grad()
@@ -380,7 +404,11 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     args.fuse = an .npz file of settings (load_fusion: poses [V,..], optional K, size, tau, min_views, peel, recentre, scale; not in
     the reference): every V consecutive pairs of the test set are one group whose pair i has pose i; the group merged in one camera,
     DepthPipeline.fuse, goes to {args.out_path}/fused_{g:04d}.npz (depth, valid, weight, views, count, layer, shpd), outside the
-    timed region; a remainder of fewer than V pairs is skipped, with a printed note."""
+    timed region; a remainder of fewer than V pairs is skipped, with a printed note.  With an integer `register` > 0 in the settings
+    file every view's pose is first refined against view 0 (refine_poses, that many iterations of DepthPipeline.register), and the
+    npz also holds poses_refined [V,12] and register_rms [V]; without the key the file holds what it held before.
+    args.normals (not in the reference): every pair's surface normals, DepthPipeline.normals(source="complete"), go to
+    {args.out_path}/normals_{j:04d}.npz (normal [3,H,W], valid), outside the timed region."""
     import data, models, utils
     from .pipeline import DepthPipeline
     dev = _device(args)
@@ -419,7 +447,8 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     complete = getattr(args, "complete", False)
     cmethod = getattr(args, "complete_method", "nearest")
     clabel = "completed" if cmethod == "nearest" else f"completed, {cmethod}"
-    if rsize is not None or spoints is not None or cloud or rcam is not None or complete or fcfg is not None:
+    want_normals = getattr(args, "normals", False)
+    if rsize is not None or spoints is not None or cloud or rcam is not None or complete or fcfg is not None or want_normals:
         os.makedirs(args.out_path, exist_ok=True)
     fine_maps, fine_thres = ("shpd", "refoc", "bndry", "depth", "conf"), 0.05 if (big or any_size) else None
     sweep = None
@@ -458,6 +487,9 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
         if cloud:
             pc = pipe.point_cloud(maps)
             np.savez(os.path.join(args.out_path, f"cloud_{j:04d}.npz"), **{k: v.cpu().numpy() for k, v in pc.items() if k != "lattice"})
+        if want_normals:
+            nrm = pipe.normals(maps, source="complete")
+            np.savez(os.path.join(args.out_path, f"normals_{j:04d}.npz"), normal=nrm["normal"].cpu().numpy(), valid=nrm["valid"].cpu().numpy())
         if rcam is not None:
             # at scale 1 the maps the mode produced are the source (its own threshold); finer samples continue that threshold
             warped = pipe.reproject(maps, cam_dst=rcam["cam"], pose=rcam["pose"], size=rcam["size"], want=("shpd", "refoc"),
@@ -467,9 +499,14 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
         if fcfg is not None:
             group.append(maps)
             if len(group) == len(fcfg["poses"]):
-                fused = pipe.fuse(list(zip(group, fcfg["poses"])), cam_dst=fcfg["cam"], size=fcfg["size"], scale=fcfg["scale"],
+                gposes, extra = fcfg["poses"], {}
+                if fcfg.get("register", 0) > 0:
+                    gposes, grms = refine_poses(pipe, group, fcfg["poses"], fcfg["register"])
+                    extra = dict(poses_refined=np.stack(gposes), register_rms=np.asarray(grms, np.float64))
+                fused = pipe.fuse(list(zip(group, gposes)), cam_dst=fcfg["cam"], size=fcfg["size"], scale=fcfg["scale"],
                                   depth_thres=fine_thres if fcfg["scale"] > 1 else None, **fcfg["kw"])
-                np.savez(os.path.join(args.out_path, f"fused_{j // len(group):04d}.npz"), **{k: v.cpu().numpy() for k, v in fused.items()})
+                np.savez(os.path.join(args.out_path, f"fused_{j // len(group):04d}.npz"), **{k: v.cpu().numpy() for k, v in fused.items()},
+                         **extra)
                 group = []
         depth = maps["depth_map"][None]
         m = np.array(utils.eval_depth(depth, gt[None].to(depth.dtype), depth, crop=args.crop))

@@ -706,6 +706,46 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fuse_views(at::Tensor
     return {dout, wout, views, count, layer, fout};
 }
 
+// depth registration: normal [3,H,W] of depth [H,W]; cam [4] a CPU float32 tensor as for unproject
+Tensor depth_normals(const Tensor& depth, const Tensor& cam, int64_t step, double max_jump, int64_t scale, int64_t top, int64_t left) {
+    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "depth_normals: depth [H,W], 1 .. 2^31 - 1 samples");
+    fp(depth, "depth");
+    Tensor normal = at::empty({3, depth.size(0), depth.size(1)}, depth.options());
+    check(be_depth_normals_f32(depth.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)scale, (int)top, (int)left,
+                               host_floats(cam, 4, "depth_normals(cam)"), (int)step, (float)max_jump, normal.data_ptr<float>(),
+                               stream_of(depth)), "be_depth_normals_f32");
+    return normal;
+}
+
+// the linearised point-to-plane step: depth_s [Hs,Ws] (weight_s or None) against depth_d [Hd,Wd], normal_d [3,Hd,Wd] (weight_d or
+// None) -> (sums [32] float64, rows [8,Hs*Ws] or an empty tensor when rows is false); the partial sums are scratch allocated here
+std::tuple<Tensor, Tensor> icp_linearize(const Tensor& depth_s, const c10::optional<Tensor>& weight_s, const Tensor& cam_src, int64_t scale,
+                                         int64_t top, int64_t left, const Tensor& depth_d, const Tensor& normal_d,
+                                         const c10::optional<Tensor>& weight_d, const Tensor& cam_dst, const Tensor& pose, double near,
+                                         double max_dist, double huber, bool rows) {
+    TORCH_CHECK(depth_s.dim() == 2 && depth_s.numel() > 0 && depth_s.numel() <= 0x7fffffff, "icp_linearize: depth_s [Hs,Ws], 1 .. 2^31 - 1 samples");
+    TORCH_CHECK(depth_d.dim() == 2 && depth_d.numel() > 0 && depth_d.numel() <= 0x7fffffff, "icp_linearize: depth_d [Hd,Wd], 1 .. 2^31 - 1 samples");
+    const int64_t Hs = depth_s.size(0), Ws = depth_s.size(1), Hd = depth_d.size(0), Wd = depth_d.size(1);
+    TORCH_CHECK(normal_d.numel() == 3 * Hd * Wd && normal_d.size(0) == 3 && normal_d.device() == depth_s.device() && depth_d.device() == depth_s.device(),
+                "icp_linearize: normal_d [3,Hd,Wd] and depth_d on depth_s's device");
+    if (weight_s.has_value() && weight_s->defined())
+        TORCH_CHECK(weight_s->sizes() == depth_s.sizes() && weight_s->device() == depth_s.device(), "icp_linearize: weight_s [Hs,Ws] on depth_s's device");
+    if (weight_d.has_value() && weight_d->defined())
+        TORCH_CHECK(weight_d->sizes() == depth_d.sizes() && weight_d->device() == depth_s.device(), "icp_linearize: weight_d [Hd,Wd] on depth_s's device");
+    const int64_t bytes = be_icp_scratch_bytes((int)Hs, (int)Ws);
+    TORCH_CHECK(bytes > 0, "icp_linearize: no scratch size for ", Hs, " x ", Ws);
+    auto o = depth_s.options();
+    Tensor scratch = at::empty({bytes / 8}, o.dtype(at::kDouble)), sums = at::empty({32}, o.dtype(at::kDouble));
+    Tensor rout = rows ? at::empty({8, Hs * Ws}, o) : at::empty({0}, o);
+    check(be_icp_linearize_f32(fp(depth_s, "depth_s"), fpo(weight_s, "weight_s"), (int)Hs, (int)Ws, (int)scale, (int)top, (int)left,
+                               host_floats(cam_src, 4, "icp_linearize(cam_src)"), fp(depth_d, "depth_d"), fp(normal_d, "normal_d"),
+                               fpo(weight_d, "weight_d"), (int)Hd, (int)Wd, host_floats(cam_dst, 4, "icp_linearize(cam_dst)"),
+                               host_floats(pose, 12, "icp_linearize(pose)"), (float)near, (float)max_dist, (float)huber,
+                               scratch.data_ptr<double>(), sums.data_ptr<double>(), rows ? rout.data_ptr<float>() : nullptr,
+                               stream_of(depth_s)), "be_icp_linearize_f32");
+    return {sums, rout};
+}
+
 // nearest-sample flood fill: depth [H,W], weight [H,W] or None -> (depth_out [H,W], index [H,W] int32, dist2 [H,W] int32); the seed
 // maps and the per-seed means are scratch allocated here
 std::tuple<Tensor, Tensor, Tensor> fill_nearest(const Tensor& depth, const c10::optional<Tensor>& weight, int64_t smooth_r, double sigma_z,
@@ -881,6 +921,9 @@ TORCH_LIBRARY(be, m) {
     m.def("reproject(Tensor depth, Tensor cam_src, Tensor cam_dst, Tensor pose, float near, int Ho, int Wo, Tensor? feat, int scale, int top, int left) -> (Tensor, Tensor, Tensor)");
     m.def("fuse_views(Tensor[] depth, Tensor[] weight, Tensor[] feat, Tensor cam_src, Tensor pose, Tensor cam_dst, float near, int Ho, int Wo, "
           "int[] scale, int[] top, int[] left, float tau, int min_views, bool recentre, int peel) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("depth_normals(Tensor depth, Tensor cam, int step, float max_jump, int scale, int top, int left) -> Tensor");
+    m.def("icp_linearize(Tensor depth_s, Tensor? weight_s, Tensor cam_src, int scale, int top, int left, Tensor depth_d, Tensor normal_d, "
+          "Tensor? weight_d, Tensor cam_dst, Tensor pose, float near, float max_dist, float huber, bool rows) -> (Tensor, Tensor)");
     m.def("fill_nearest(Tensor depth, Tensor? weight, int smooth_r, float sigma_z, bool fuse) -> (Tensor, Tensor, Tensor)");
     m.def("fill_diffuse(Tensor depth, Tensor? weight, Tensor? edge, int smooth_r, float sigma_z, float leak, int iters, bool fuse) -> "
           "(Tensor, Tensor, Tensor, Tensor)");
@@ -944,6 +987,8 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("unproject", unproject);
     m.impl("reproject", reproject);
     m.impl("fuse_views", fuse_views);
+    m.impl("depth_normals", depth_normals);
+    m.impl("icp_linearize", icp_linearize);
     m.impl("fill_nearest", fill_nearest);
     m.impl("fill_diffuse", fill_diffuse);
     m.impl("local_loss", local_loss);

@@ -97,8 +97,11 @@ _GROUPS = {
         ('--point_cloud', dict(action='store_true')),
         ('--reproject', dict(type=str, default=None)),
         # not in the reference: every V consecutive pairs merged in one camera (DepthPipeline.fuse) with the poses of an .npz settings
-        # file - poses [V,..], optional K, size, tau, min_views, peel, recentre, scale - written to out_path
+        # file - poses [V,..], optional K, size, tau, min_views, peel, recentre, scale, register (that many iterations of
+        # DepthPipeline.register refine each pose against view 0 first) - written to out_path
         ('--fuse', dict(type=str, default=None)),
+        # not in the reference: every pair's surface normals (DepthPipeline.normals on the completed depth), written to out_path
+        ('--normals', dict(action='store_true')),
         # not in the reference: every pair's depth map completed to a dense one by nearest-sample flood fill (DepthPipeline.complete),
         # written to out_path and scored with the same metrics
         ('--complete', dict(action='store_true')),

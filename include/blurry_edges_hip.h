@@ -276,6 +276,41 @@ int be_fuse_views_f32(int V, const float* const* depth, const float* const* weig
                       void* scratch, float* depth_out, float* weight_out, int32_t* views_out, int32_t* count_out, int32_t* layer_out,
                       float* feat_out, void* stream);
 
+/* Depth registration: the two kernels of a point-to-plane ICP on depth maps; the loop around them is be_hip/registration.py.
+ * Lattice, camera and pose arguments are be_reproject_f32's; all per-sample arithmetic is fp32, one rounding per operation.
+ *
+ * be_depth_normals_f32: normal [3,H*W] of depth [H,W] on the lattice (scale, top, left) of camera cam.  A pixel is good when its
+ * depth is a finite number > 0; P is its unprojection (be_unproject_f32 under the identity pose).  Along x the neighbour at x + r
+ * (r = step) counts when it is inside the image, good and |Z(x + r) - Z(x)| <= max_jump * r (one fp32 product); likewise x - r.
+ * du = P(x + r) - P(x - r) when both count, P(x + r) - P(x) or P(x) - P(x - r) when one does; dv likewise along y.
+ * n = du x dv (each component a b - c d), l = sqrtf((nx nx + ny ny) + nz nz), n = n / l, negated when (nx Px + ny Py) + nz Pz > 0:
+ * the normal faces the camera.  (+0, +0, +0) where the pixel is not good, a direction has no neighbour that counts, or l is not a
+ * finite number > 0.  Every output element is written exactly once.  1 <= step <= BE_NORMALS_MAX_STEP; max_jump >= 0, finite.
+ *
+ * be_icp_linearize_f32: source depth_s [Hs,Ws] (weight_s of the same shape or NULL: 1) in cam_src on its lattice, target depth_d
+ * [Hd,Wd], normal_d [3,Hd*Wd] (weight_d or NULL) on the pixels of cam_dst, pose: source frame -> target frame.  Source sample i
+ * with projection P = (Xd, Yd, Zd), (fu, fv) takes part iff it passes be_reproject_f32's test on the Hd x Wd frame and, with
+ * j = (int) fv * Wd + (int) fu:  Zq = depth_d[j] is a finite number > 0;  n = normal_d[:, j] has a non-zero component;
+ * D = P - Q, Q = (((fu - cxd) / fxd) Zq, ((fv - cyd) / fyd) Zq, Zq), satisfies (Dx Dx + Dy Dy) + Dz Dz <= max_dist max_dist;
+ * w = weight_s[i] weight_d[j] satisfies w > 0 and w < inf (NaN fails every test).  Then r = (nx Dx + ny Dy) + nz Dz; with
+ * huber > 0 and |r| > huber, w = w (huber / |r|); the row is J = (P x n, n) - the derivative of r under P' = P + omega x P + v.
+ * The 8 floats J[0..5], r, w are converted to double and 30 terms, each multiplied left to right in double, are added up:
+ * sums[0..20] = w J[a] J[b] (a <= b, row-major upper triangle), sums[21..26] = w J[a] r, sums[27] = w r r, sums[28] = w,
+ * sums[29] = the number of samples that took part; sums[30] = sums[31] = 0.  The order of summation is a function of Hs * Ws alone
+ * (fixed grid of at most 64 workgroups, each thread in increasing sample order, a fixed tree over lanes, waves and workgroups; no
+ * floating-point atomics): repeated calls, other streams and other devices give the same bits.  sums: 32 doubles on the device;
+ * rows_out: [8,Hs*Ws] float32 (J, r, w per sample; 0 where the sample took no part) or NULL; scratch: be_icp_scratch_bytes(Hs, Ws)
+ * bytes of device memory, 8-byte aligned (-1 for sizes out of range).  Nothing synchronises with the host.
+ * near, max_dist, huber >= 0 and finite. */
+#define BE_NORMALS_MAX_STEP 8
+int be_depth_normals_f32(const float* depth, int H, int W, int scale, int top, int left, const float* cam, int step, float max_jump,
+                         float* normal, void* stream);
+int64_t be_icp_scratch_bytes(int Hs, int Ws);
+int be_icp_linearize_f32(const float* depth_s, const float* weight_s, int Hs, int Ws, int scale, int top, int left,
+                         const float* cam_src, const float* depth_d, const float* normal_d, const float* weight_d, int Hd, int Wd,
+                         const float* cam_dst, const float* pose, float near, float max_dist, float huber, void* scratch, double* sums,
+                         float* rows_out, void* stream);
+
 /* Dense depth from sparse samples by nearest-sample flood fill.  depth [H,W] float32 on the device; weight [H,W] float32 or NULL
  * (weight 1 everywhere).  Pixel p is a seed iff weight[p] > 0, depth[p] > 0 and depth[p] < inf (NaN fails all three).  Every pixel
  * is given a seed by jump flooding: an int32 seed map holds each pixel's current seed as the linear index y * W + x (-1: none); one
