@@ -974,22 +974,35 @@ def render_full(opts, consts, rho_prime, densify_w, params12, view: PatchView, w
 FOLD_MAPS = ("image", "shpd", "refoc", "bndry", "depth", "conf")
 
 
+def _map_shapes(tail, batch=(), image=(2, 3)):
+    """The shape of each folded map over the samples `tail` ((H, W), (Ho, Wo), the points' leading shape, (N,)), after `batch`."""
+    tail, batch = tuple(tail), tuple(batch)
+    return dict(image=batch + image + tail, shpd=batch + (3,) + tail, refoc=batch + (3,) + tail, bndry=batch + tail, depth=batch + tail,
+                conf=batch + tail)
+
+
+def _fold_maps(want, shapes, dev, by_op, by_lib):
+    """The maps named in `want`, as {name: tensor} in FOLD_MAPS order, through either binding: by_op(mask) calls the torch operator
+    (bit i of mask = FOLD_MAPS[i]) and returns the requested maps in that order; without the operator library the maps are
+    allocated here with `shapes` and by_lib(*pointers) calls the C entry with the six map pointers, null where not wanted.
+    A name in `want` that is not in FOLD_MAPS is ignored, under either binding."""
+    names = [k for k in FOLD_MAPS if k in want]
+    if ops() is not None:
+        return dict(zip(names, by_op(sum(1 << FOLD_MAPS.index(k) for k in names))))
+    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in names}
+    by_lib(*(dptr(out.get(k)) for k in FOLD_MAPS))
+    return out
+
+
 def fold_records(opts, records, hp, wp, H, W, stride=2, densify_w=False, want=FOLD_MAPS):
     if tuple(records.shape) != (hp * wp, RECORD_FLOATS):
         raise RuntimeError(f"fold_records: records must be [{hp * wp},{RECORD_FLOATS}], got {tuple(records.shape)}")
     dev = records.device
-    o = ops()
-    if o is not None:
-        mask = sum(1 << i for i, k in enumerate(FOLD_MAPS) if k in want)
-        r = o.fold_records(struct_tensor(opts), records.contiguous(), hp, wp, H, W, stride, bool(densify_w), mask)
-        return dict(zip([k for k in FOLD_MAPS if k in want], r))
-    shapes = dict(image=(2, 3, H, W), shpd=(3, H, W), refoc=(3, H, W), bndry=(H, W), depth=(H, W), conf=(H, W))
-    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in want}
-    g = lambda k: dptr(out.get(k))
-    check(lib().be_fold_records_f32(C.byref(opts), dptr(records, "records"), hp, wp, H, W, stride, int(bool(densify_w)),
-                                    g("image"), g("shpd"), g("refoc"), g("bndry"), g("depth"), g("conf"),
-                                    stream_ptr(dev)), "be_fold_records_f32")
-    return out
+    return _fold_maps(
+        want, _map_shapes((H, W)), dev,
+        lambda mask: ops().fold_records(struct_tensor(opts), records.contiguous(), hp, wp, H, W, stride, bool(densify_w), mask),
+        lambda *maps: check(lib().be_fold_records_f32(C.byref(opts), dptr(records, "records"), hp, wp, H, W, stride, int(bool(densify_w)),
+                                                      *maps, stream_ptr(dev)), "be_fold_records_f32"))
 
 
 def fold_records_batch(opts, records, hp, wp, H, W, stride=2, densify_w=False, want=FOLD_MAPS):
@@ -997,18 +1010,11 @@ def fold_records_batch(opts, records, hp, wp, H, W, stride=2, densify_w=False, w
     if records.dim() != 3 or tuple(records.shape[1:]) != (hp * wp, RECORD_FLOATS):
         raise RuntimeError(f"fold_records_batch: records must be [B,{hp * wp},{RECORD_FLOATS}], got {tuple(records.shape)}")
     dev, B = records.device, records.shape[0]
-    o = ops()
-    if o is not None:
-        mask = sum(1 << i for i, k in enumerate(FOLD_MAPS) if k in want)
-        r = o.fold_records(struct_tensor(opts), records.contiguous(), hp, wp, H, W, stride, bool(densify_w), mask)
-        return dict(zip([k for k in FOLD_MAPS if k in want], r))
-    shapes = dict(image=(B, 2, 3, H, W), shpd=(B, 3, H, W), refoc=(B, 3, H, W), bndry=(B, H, W), depth=(B, H, W), conf=(B, H, W))
-    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in want}
-    g = lambda k: dptr(out.get(k))
-    check(lib().be_fold_records_batch_f32(C.byref(opts), dptr(records, "records"), B, hp, wp, H, W, stride, int(bool(densify_w)),
-                                          g("image"), g("shpd"), g("refoc"), g("bndry"), g("depth"), g("conf"),
-                                          stream_ptr(dev)), "be_fold_records_batch_f32")
-    return out
+    return _fold_maps(
+        want, _map_shapes((H, W), batch=(B,)), dev,
+        lambda mask: ops().fold_records(struct_tensor(opts), records.contiguous(), hp, wp, H, W, stride, bool(densify_w), mask),
+        lambda *maps: check(lib().be_fold_records_batch_f32(C.byref(opts), dptr(records, "records"), B, hp, wp, H, W, stride,
+                                                            int(bool(densify_w)), *maps, stream_ptr(dev)), "be_fold_records_batch_f32"))
 
 
 def origin_table(lines, size: int, device, name: str = "origins", cover: bool = False) -> torch.Tensor:
@@ -1060,21 +1066,14 @@ def fold_records_grid(opts, records, H, W, ys, xs, densify_w=False, want=FOLD_MA
     HP, WP = ys.numel(), xs.numel()
     if tuple(records.shape) != (HP * WP, RECORD_FLOATS):
         raise RuntimeError(f"fold_records_grid: records must be [{HP * WP},{RECORD_FLOATS}], got {tuple(records.shape)}")
-    o = ops()
-    if o is not None:
-        mask = sum(1 << i for i, k in enumerate(FOLD_MAPS) if k in want)
-        r = o.fold_records_grid(struct_tensor(opts), records.contiguous(), ys, xs, H, W, bool(densify_w), mask)
-        return dict(zip([k for k in FOLD_MAPS if k in want], r))
-    shapes = dict(image=(2, 3, H, W), shpd=(3, H, W), refoc=(3, H, W), bndry=(H, W), depth=(H, W), conf=(H, W))
-    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in want}
-    g = lambda k: dptr(out.get(k))
-    check(lib().be_fold_records_grid_f32(C.byref(opts), dptr(records, "records", (torch.float32,)), HP, WP, H, W, dptr(ys), dptr(xs),
-                                         int(bool(densify_w)), g("image"), g("shpd"), g("refoc"), g("bndry"), g("depth"), g("conf"),
-                                         stream_ptr(dev)), "be_fold_records_grid_f32")
-    return out
+    return _fold_maps(
+        want, _map_shapes((H, W)), dev,
+        lambda mask: ops().fold_records_grid(struct_tensor(opts), records.contiguous(), ys, xs, H, W, bool(densify_w), mask),
+        lambda *maps: check(lib().be_fold_records_grid_f32(C.byref(opts), dptr(records, "records", (torch.float32,)), HP, WP, H, W, dptr(ys),
+                                                           dptr(xs), int(bool(densify_w)), *maps, stream_ptr(dev)), "be_fold_records_grid_f32"))
 
 
-REFOCUS_STACK_KC = 8          # BE_REFOCUS_STACK_KC of the header: the planes one workgroup of the stack kernel accumulates
+REFOCUS_STACK_KC = 8          # BE_REFOCUS_STACK_KC of the header: the planes one workgroup of a stack fold accumulates
 
 
 def rho_prime_list(rho_primes, name: str = "rho_primes"):
@@ -1093,46 +1092,17 @@ def rho_prime_list(rho_primes, name: str = "rho_primes"):
     return vals
 
 
-def fold_refocus_stack(opts, consts, records, rho_primes, H, W, hp=None, wp=None, stride=2, ys=None, xs=None):
-    """records [hp*wp,32] (render_full / render_full_grid at ANY rho_prime) + K optical powers -> [K,3,H,W]: plane k is the
-    `refoc` map of render_full*(rho_prime=rho_primes[k]) + fold_records*, bit for bit, from one launch that shares the record
-    fetch and the wedge distances between the planes.  ys / xs (both): origin tables as fold_records_grid takes them (hp / wp
-    then come from the tables); neither: the uniform grid hp x wp of `stride`.  rho_primes: floats or a float32 tensor."""
-    vals = rho_prime_list(rho_primes, "fold_refocus_stack(rho_primes)")
-    if (ys is None) != (xs is None):
-        raise ValueError("fold_refocus_stack: ys and xs must both be given (origin tables) or both be None (uniform grid)")
-    if not isinstance(records, torch.Tensor) or records.dim() != 2:
-        raise RuntimeError(f"fold_refocus_stack: records must be a [P,{RECORD_FLOATS}] tensor")
-    dev = records.device
-    if ys is not None:
-        ys = origin_table(ys, H, dev, "fold_refocus_stack(ys)", cover=True)
-        xs = origin_table(xs, W, dev, "fold_refocus_stack(xs)", cover=True)
-        if (hp is not None and hp != ys.numel()) or (wp is not None and wp != xs.numel()):
-            raise RuntimeError(f"fold_refocus_stack: hp / wp ({hp}, {wp}) do not match the tables ({ys.numel()}, {xs.numel()})")
-        hp, wp = ys.numel(), xs.numel()
-    elif hp is None or wp is None:
-        raise RuntimeError("fold_refocus_stack: the uniform grid needs hp and wp")
-    if tuple(records.shape) != (hp * wp, RECORD_FLOATS):
-        raise RuntimeError(f"fold_refocus_stack: records must be [{hp * wp},{RECORD_FLOATS}], got {tuple(records.shape)}")
-    records = records.contiguous()
-    dptr(records, "records", (torch.float32,))
+def _rho_tensor(rho_primes, vals, dev):
+    """The float32 [K] tensor on `dev` the stack entries read: rho_primes itself when it already is one, else built from
+    vals = rho_prime_list(rho_primes)."""
     if isinstance(rho_primes, torch.Tensor) and rho_primes.device == dev and rho_primes.dtype == torch.float32 and rho_primes.is_contiguous():
-        rho = rho_primes
-    else:
-        rho = torch.tensor(vals, dtype=torch.float32, device=dev)
-    o = ops()
-    if o is not None:
-        return o.fold_refocus_stack(struct_tensor(opts), struct_tensor(consts), records, rho, ys, xs, hp, wp, H, W, stride)
-    out = torch.empty(len(vals), 3, H, W, dtype=torch.float32, device=dev)
-    check(lib().be_fold_refocus_stack_f32(C.byref(opts), C.byref(consts), dptr(records, "records", (torch.float32,)), hp, wp, H, W,
-                                          stride, dptr(ys), dptr(xs), dptr(rho), len(vals), dptr(out), stream_ptr(dev)),
-          "be_fold_refocus_stack_f32")
-    return out
+        return rho_primes
+    return torch.tensor(vals, dtype=torch.float32, device=dev)
 
 
 def _record_grid(who, records, H, W, hp, wp, ys, xs):
-    """The host side the *_at and *_points wrappers share, before the library is touched: ys / xs both or neither, the tables
-    (origin_table, cover=True), the record shape, records on the GPU.  -> (records, ys, xs, hp, wp)."""
+    """The host side the wrappers over an optional-table grid share, before the library is touched: ys / xs both or neither, the
+    tables (origin_table, cover=True), the record shape, records on the GPU.  -> (records, ys, xs, hp, wp)."""
     if (ys is None) != (xs is None):
         raise ValueError(f"{who}: ys and xs must both be given (origin tables) or both be None (uniform grid)")
     if not isinstance(records, torch.Tensor) or records.dim() != 2:
@@ -1152,6 +1122,25 @@ def _record_grid(who, records, H, W, hp, wp, ys, xs):
     return records, ys, xs, hp, wp
 
 
+def fold_refocus_stack(opts, consts, records, rho_primes, H, W, hp=None, wp=None, stride=2, ys=None, xs=None):
+    """records [hp*wp,32] (render_full / render_full_grid at ANY rho_prime) + K optical powers -> [K,3,H,W]: plane k is the
+    `refoc` map of render_full*(rho_prime=rho_primes[k]) + fold_records*, bit for bit, from one launch that shares the record
+    fetch and the wedge distances between the planes.  ys / xs (both): origin tables as fold_records_grid takes them (hp / wp
+    then come from the tables); neither: the uniform grid hp x wp of `stride`.  rho_primes: floats or a float32 tensor."""
+    vals = rho_prime_list(rho_primes, "fold_refocus_stack(rho_primes)")
+    records, ys, xs, hp, wp = _record_grid("fold_refocus_stack", records, H, W, hp, wp, ys, xs)
+    dev = records.device
+    rho = _rho_tensor(rho_primes, vals, dev)
+    o = ops()
+    if o is not None:
+        return o.fold_refocus_stack(struct_tensor(opts), struct_tensor(consts), records, rho, ys, xs, hp, wp, H, W, stride)
+    out = torch.empty(len(vals), 3, H, W, dtype=torch.float32, device=dev)
+    check(lib().be_fold_refocus_stack_f32(C.byref(opts), C.byref(consts), dptr(records, "records", (torch.float32,)), hp, wp, H, W,
+                                          stride, dptr(ys), dptr(xs), dptr(rho), len(vals), dptr(out), stream_ptr(dev)),
+          "be_fold_refocus_stack_f32")
+    return out
+
+
 def _at_grid(who, records, H, W, scale, window, hp, wp, ys, xs):
     """The lattice (tiling.lattice), then _record_grid.  -> (lattice, records, ys, xs, hp, wp)."""
     from . import tiling
@@ -1166,19 +1155,14 @@ def fold_records_at(opts, records, H, W, scale=1, window=None, hp=None, wp=None,
     (iy, ix) sits at pixel position (top + iy / scale, left + ix / scale); out[..., ::scale, ::scale] equals the integer-pixel fold
     over the window bit for bit.  ys / xs (both): origin tables (hp / wp then come from them); neither: the uniform grid."""
     lat, records, ys, xs, hp, wp = _at_grid("fold_records_at", records, H, W, scale, window, hp, wp, ys, xs)
-    dev, (top, left, h, w), Ho, Wo = records.device, lat["window"], lat["Ho"], lat["Wo"]
-    o = ops()
-    if o is not None:
-        mask = sum(1 << i for i, k in enumerate(FOLD_MAPS) if k in want)
-        r = o.fold_records_at(struct_tensor(opts), records, ys, xs, hp, wp, H, W, stride, scale, top, left, h, w, bool(densify_w), mask)
-        return dict(zip([k for k in FOLD_MAPS if k in want], r))
-    shapes = dict(image=(2, 3, Ho, Wo), shpd=(3, Ho, Wo), refoc=(3, Ho, Wo), bndry=(Ho, Wo), depth=(Ho, Wo), conf=(Ho, Wo))
-    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in FOLD_MAPS if k in want}
-    g = lambda k: dptr(out.get(k))
-    check(lib().be_fold_records_at_f32(C.byref(opts), dptr(records, "records", (torch.float32,)), hp, wp, H, W, stride, dptr(ys), dptr(xs),
-                                       scale, top, left, h, w, int(bool(densify_w)), g("image"), g("shpd"), g("refoc"), g("bndry"),
-                                       g("depth"), g("conf"), stream_ptr(dev)), "be_fold_records_at_f32")
-    return out
+    dev, (top, left, h, w) = records.device, lat["window"]
+    return _fold_maps(
+        want, _map_shapes((lat["Ho"], lat["Wo"])), dev,
+        lambda mask: ops().fold_records_at(struct_tensor(opts), records, ys, xs, hp, wp, H, W, stride, scale, top, left, h, w,
+                                           bool(densify_w), mask),
+        lambda *maps: check(lib().be_fold_records_at_f32(C.byref(opts), dptr(records, "records", (torch.float32,)), hp, wp, H, W, stride,
+                                                         dptr(ys), dptr(xs), scale, top, left, h, w, int(bool(densify_w)), *maps,
+                                                         stream_ptr(dev)), "be_fold_records_at_f32"))
 
 
 def fold_refocus_stack_at(opts, consts, records, rho_primes, H, W, scale=1, window=None, hp=None, wp=None, stride=2, ys=None, xs=None):
@@ -1187,10 +1171,7 @@ def fold_refocus_stack_at(opts, consts, records, rho_primes, H, W, scale=1, wind
     vals = rho_prime_list(rho_primes, "fold_refocus_stack_at(rho_primes)")
     lat, records, ys, xs, hp, wp = _at_grid("fold_refocus_stack_at", records, H, W, scale, window, hp, wp, ys, xs)
     dev, (top, left, h, w) = records.device, lat["window"]
-    if isinstance(rho_primes, torch.Tensor) and rho_primes.device == dev and rho_primes.dtype == torch.float32 and rho_primes.is_contiguous():
-        rho = rho_primes
-    else:
-        rho = torch.tensor(vals, dtype=torch.float32, device=dev)
+    rho = _rho_tensor(rho_primes, vals, dev)
     o = ops()
     if o is not None:
         return o.fold_refocus_stack_at(struct_tensor(opts), struct_tensor(consts), records, rho, ys, xs, hp, wp, H, W, stride, scale, top,
@@ -1222,18 +1203,13 @@ def fold_records_points(opts, records, H, W, points, hp=None, wp=None, stride=2,
     records, ys, xs, hp, wp = _record_grid("fold_records_points", records, H, W, hp, wp, ys, xs)
     dev, N = records.device, pts.shape[0]
     dptr(pts, "points", (torch.float32,))
-    shapes = dict(image=(2, 3) + lead, shpd=(3,) + lead, refoc=(3,) + lead, bndry=lead, depth=lead, conf=lead)
-    o = ops()
-    if o is not None:
-        mask = sum(1 << i for i, k in enumerate(FOLD_MAPS) if k in want)
-        r = o.fold_records_points(struct_tensor(opts), records, ys, xs, hp, wp, H, W, stride, pts, bool(densify_w), mask)
-        return {k: v.view(shapes[k]) for k, v in zip([k for k in FOLD_MAPS if k in want], r)}
-    flat = dict(image=(6, N), shpd=(3, N), refoc=(3, N), bndry=(N,), depth=(N,), conf=(N,))
-    out = {k: torch.empty(flat[k], dtype=torch.float32, device=dev) for k in FOLD_MAPS if k in want}
-    g = lambda k: dptr(out.get(k))
-    check(lib().be_fold_records_points_f32(C.byref(opts), dptr(records, "records", (torch.float32,)), hp, wp, H, W, stride, dptr(ys), dptr(xs),
-                                           dptr(pts), N, int(bool(densify_w)), g("image"), g("shpd"), g("refoc"), g("bndry"), g("depth"),
-                                           g("conf"), stream_ptr(dev)), "be_fold_records_points_f32")
+    out = _fold_maps(                                                   # the kernels write channel-major over the points: [6,N], [3,N], [N]
+        want, _map_shapes((N,), image=(6,)), dev,
+        lambda mask: ops().fold_records_points(struct_tensor(opts), records, ys, xs, hp, wp, H, W, stride, pts, bool(densify_w), mask),
+        lambda *maps: check(lib().be_fold_records_points_f32(C.byref(opts), dptr(records, "records", (torch.float32,)), hp, wp, H, W, stride,
+                                                             dptr(ys), dptr(xs), dptr(pts), N, int(bool(densify_w)), *maps,
+                                                             stream_ptr(dev)), "be_fold_records_points_f32"))
+    shapes = _map_shapes(lead)
     return {k: v.view(shapes[k]) for k, v in out.items()}
 
 
@@ -1245,10 +1221,7 @@ def fold_refocus_stack_points(opts, consts, records, rho_primes, H, W, points, h
     records, ys, xs, hp, wp = _record_grid("fold_refocus_stack_points", records, H, W, hp, wp, ys, xs)
     dev, N = records.device, pts.shape[0]
     dptr(pts, "points", (torch.float32,))
-    if isinstance(rho_primes, torch.Tensor) and rho_primes.device == dev and rho_primes.dtype == torch.float32 and rho_primes.is_contiguous():
-        rho = rho_primes
-    else:
-        rho = torch.tensor(vals, dtype=torch.float32, device=dev)
+    rho = _rho_tensor(rho_primes, vals, dev)
     o = ops()
     if o is not None:
         out = o.fold_refocus_stack_points(struct_tensor(opts), struct_tensor(consts), records, rho, ys, xs, hp, wp, H, W, stride, pts)

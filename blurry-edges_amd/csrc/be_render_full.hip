@@ -2,22 +2,23 @@
 //
 // Replaces PostProcess.get_patches(colors_only=False) and the six nn.Fold aggregations of
 // blurry_edges_test.py:36-79,93-99 / utils/postprocessing_loss.py:151-173 (and the per-block patch-tensor
-// stitching of blurry_edges_test_big.py:166-189) with two kernels and NO per-patch tensors in HBM:
+// stitching of blurry_edges_test_big.py:166-189) with two steps and NO per-patch tensors in HBM:
 //
 //   k_render_records   one wavefront per patch position: both aperture images are read once (gather-on-read
 //                      through a strided patch view: an image pair, an unfolded tensor or flat patches),
 //                      the 882-row ridge system is reduced with wave shuffles, solved in fp64, the two
 //                      wedge depths come from etas2depth, the refocus radii from depth2sigma and a wave
 //                      ballot of the depth mask; result = one 128-byte record per patch.
-//   k_fold_records     one thread per output pixel ("owner computes"): walks the <= 11x11 patches that
-//                      cover the pixel in a fixed order, re-evaluates the wedges from the record for the four
-//                      blur sets (aperture 1, aperture 2, sharpened, refocused) and accumulates the six maps.
-//                      Deterministic (no atomics), divides by the analytic overlap count.
+//   the folds          one thread per output sample ("owner computes"): walks the <= 11x11 patches that cover the
+//                      sample in a fixed order and re-evaluates the wedges from the records.  Deterministic (no
+//                      atomics), divides by the number of patches visited.  A fold is a sampler (k_fold_pixels,
+//                      k_fold_lattice, k_fold_points: where the samples are) instantiated with an accumulator
+//                      (MapsAcc: the six maps of the four blur sets - aperture 1, aperture 2, sharpened, refocused -
+//                      boundary, depth and confidence; StackAcc: a focal stack); see the fold section.
 //
-// Both kernels are templated on how a patch's origin is obtained: UNIFORM (origin = stride * index, the grid of
+// Every kernel is templated on how a patch's origin is obtained: UNIFORM (origin = stride * index, the grid of
 // nn.Unfold) or ORIGIN TABLES ys[HP] / xs[WP] (a separable grid whose last line may sit flush with the image edge, so an
-// image of any size is covered; the fold then divides by the number of patches it visited).  The uniform instantiation
-// is the code path every existing entry point takes.
+// image of any size is covered).
 //
 // The reference materialises 26.5 KB per patch pair and folds it six times; here the per-patch state is
 // 128 B and every output byte is written once.
@@ -178,25 +179,35 @@ void k_render_records(be_render_opts o, be_depth_consts dc, FullArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ fold
-struct FoldArgs {
-    const float* records;    // [Hp*Wp,32]
+// Every fold is  sampler -> run -> visit -> accumulator, each written once:
+//
+//   sampler      where the output samples are.  k_fold_pixels (one thread per image pixel), k_fold_lattice (a lattice `scale`
+//                times finer, over a window), k_fold_points (a list of real-valued positions).  A sampler turns its sample into
+//                one Axis per image axis, picks the output index and says where the grid lines come from (*Lines, below).
+//   run          fold_run: the contiguous run of grid lines covering the sample on either axis, visited i outer, j inner,
+//                ascending; returns the number of patches visited.
+//   visit        visit_record: one record -> registers -> WedgeGeom -> wedge_dists -> accumulator.
+//   accumulator  what is summed per visit and how it is stored: MapsAcc (the six folded maps) or StackAcc (a chunk of
+//                focal-stack planes).
+//
+// The equalities the entry points promise (every scale-th lattice sample == the pixel fold; a point on a pixel centre == the
+// pixel fold; a dyadic point == the lattice fold; stack plane k == render + fold at rho_k) hold bit for bit because the
+// siblings run the SAME statements after the coordinate, not copies of them.  What decides bits:
+//   - `#pragma clang fp contract(off)` is lexically scoped and does not reach into a callee: each function below that needs
+//     it carries its own (lattice_coord, blend_add, MapsAcc::add, StackAcc::add); visit_record and wedge_dists are outside it.
+//   - the visiting order and the single division by (float)cnt in Acc::store.
+struct FoldGrid {            // the record grid a fold reads
+    const float* records;    // [hp*wp,32]
     int hp, wp, H, W, stride;
-    int densify_w;
-    float* image;            // [2,3,H,W] or null
-    float* shpd;             // [3,H,W] or null
-    float* refoc;            // [3,H,W] or null
-    float* bndry;            // [H,W] or null
-    float* depth;            // [H,W] or null
-    float* conf;             // [H,W] or null
-    int64_t rec_stride;      // batched form (grid.z = image): floats between the records / maps of consecutive images
-    const int32_t* ys;       // [hp] / [wp] patch origins, strictly increasing (k_fold_records<true> only)
+    const int32_t* ys;       // [hp] / [wp] patch origins, strictly increasing (TABLES instantiations only; stride is then 0)
     const int32_t* xs;
 };
 
-constexpr int FOLD_TILE = 16;                       // output pixels per workgroup and axis
+constexpr int FOLD_TILE = 16;                       // output samples per workgroup and axis (pixel and lattice samplers)
 constexpr int FOLD_LINES = FOLD_TILE + R - 1;       // strictly increasing integer origins: at most one grid line per pixel
                                                     // of [tile_first - (R-1), tile_last] can cover a pixel of the tile
 constexpr int LINE_NONE = 0x7fffffff;
+constexpr int FOLD_KC = BE_REFOCUS_STACK_KC;        // focal-stack planes per workgroup (the last chunk may be short)
 
 // first index in t[0..n) with t[i] >= v (t increasing)
 __device__ __forceinline__ int lower_bound(const int32_t* __restrict__ t, int n, int v) {
@@ -205,244 +216,174 @@ __device__ __forceinline__ int lower_bound(const int32_t* __restrict__ t, int n,
     return lo;
 }
 
-template <bool TABLES>
-__global__ __launch_bounds__(256)
-void k_fold_records(be_render_opts o, FoldArgs a) {
-    __shared__ float lin[R];
-    __shared__ int sy[TABLES ? FOLD_LINES : 1], sx[TABLES ? FOLD_LINES : 1];
-    if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
-    int i0 = 0, j0 = 0;                                         // grid line held by sy[0] / sx[0]
-    if constexpr (TABLES) {
-        // the grid lines that can cover this tile, staged once per workgroup; absent slots hold LINE_NONE
-        i0 = lower_bound(a.ys, a.hp, (int)blockIdx.y * FOLD_TILE - (R - 1));
-        j0 = lower_bound(a.xs, a.wp, (int)blockIdx.x * FOLD_TILE - (R - 1));
-        const int t = threadIdx.x;
-        if (t < FOLD_LINES) sy[t] = i0 + t < a.hp ? a.ys[i0 + t] : LINE_NONE;
-        else if (t >= 64 && t < 64 + FOLD_LINES) sx[t - 64] = j0 + t - 64 < a.wp ? a.xs[j0 + t - 64] : LINE_NONE;
-    }
-    __syncthreads();
-    const int x = blockIdx.x * FOLD_TILE + (threadIdx.x & 15);
-    const int y = blockIdx.y * FOLD_TILE + (threadIdx.x >> 4);
-    if (x >= a.W || y >= a.H) return;
-    if (blockIdx.z) {                                           // image blockIdx.z of a batch
-        const size_t b = blockIdx.z, hw = (size_t)a.H * a.W;
-        a.records += b * a.rec_stride;
-        if (a.image) a.image += b * 6 * hw;
-        if (a.shpd) a.shpd += b * 3 * hw;
-        if (a.refoc) a.refoc += b * 3 * hw;
-        if (a.bndry) a.bndry += b * hw;
-        if (a.depth) a.depth += b * hw;
-        if (a.conf) a.conf += b * hw;
-    }
-    // patches covering (y,x): origin(i) <= y <= origin(i) + 20, a contiguous run of grid lines on either axis
-    const int s = a.stride;
-    int i_lo, j_lo, i_hi, j_hi;
-    if constexpr (TABLES) {
-        i_lo = 0; while (i_lo < FOLD_LINES && sy[i_lo] < y - (R - 1)) ++i_lo;
-        j_lo = 0; while (j_lo < FOLD_LINES && sx[j_lo] < x - (R - 1)) ++j_lo;
-        i_hi = i_lo - 1; while (i_hi + 1 < FOLD_LINES && sy[i_hi + 1] <= y) ++i_hi;
-        j_hi = j_lo - 1; while (j_hi + 1 < FOLD_LINES && sx[j_hi + 1] <= x) ++j_hi;
-    } else {
-        i_lo = (y - (R - 1) + s - 1) / s; if (y - (R - 1) < 0) i_lo = 0;
-        j_lo = (x - (R - 1) + s - 1) / s; if (x - (R - 1) < 0) j_lo = 0;
-        i_hi = y / s; if (i_hi > a.hp - 1) i_hi = a.hp - 1;
-        j_hi = x / s; if (j_hi > a.wp - 1) j_hi = a.wp - 1;
-    }
-    float acc1[3] = {0, 0, 0}, acc2[3] = {0, 0, 0}, accs[3] = {0, 0, 0}, accf[3] = {0, 0, 0};
-    float accb = 0.f, accz = 0.f;
-    int cnt = 0, cntz = 0;
-    const float rs = be::kRoot2 * 1e-4f;
-    for (int i = i_lo; i <= i_hi; ++i) {
-        const float py = lin[y - (TABLES ? sy[i] : s * i)];
-        for (int j = j_lo; j <= j_hi; ++j) {
-            const float px = lin[x - (TABLES ? sx[j] : s * j)];
-            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)((i0 + i) * a.wp + (j0 + j)) * REC);
-            float r[REC];
-#pragma unroll
-            for (int k = 0; k < REC / 4; ++k) { const float4 t = rp[k]; r[4 * k] = t.x; r[4 * k + 1] = t.y; r[4 * k + 2] = t.z; r[4 * k + 3] = t.w; }
-            be::WedgeGeom g;
-            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
-            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
-            g.sg1 = r[12]; g.sg2 = r[13];
-            float d1, d2;
-            be::wedge_dists(g, px, py, o.w, d1, d2);
-            const float* col = r + R_COL;
-            float u0, u1, u2;
-            {
+// One colour accumulator.  A 3-vector, not float[3]: as a member of an accumulator struct a float[3] is split into scalars, the
+// compiler then packs fewer of the blends and of the indicator arithmetic into v_pk_* than it does for a kernel-local array,
+// and the map folds pay about ten more instructions per visited record.  With the vector the packing is the local array's.
+typedef float Rgb __attribute__((ext_vector_type(3)));
+
+// acc[c] += the three wedge colours of channel c blended by the indicators (no FMA: the bits of the reference's mul + add)
+__device__ __forceinline__ void blend_add(Rgb& acc, const float* col, float u0, float u1, float u2) {
 #pragma clang fp contract(off)
-                if (a.image) {
-                    be::indicators(d1, d2, r[R_RAD1], r[R_RAD1 + 1], u0, u1, u2);
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) acc1[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                    be::indicators(d1, d2, r[R_RAD2], r[R_RAD2 + 1], u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc2[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-                if (a.shpd) {
-                    be::indicators(d1, d2, rs, rs, u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) accs[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-                if (a.refoc) {
-                    be::indicators(d1, d2, r[R_RADF], r[R_RADF + 1], u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) accf[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-                if (a.bndry) accb += be::boundary_value(d1, d2, o.delta_sq);
-                if (a.depth || a.conf) {
-                    const int m = be::depth_mask(d1, d2, o.delta_sq, a.densify_w != 0);
-                    if (m == 1) { accz += r[R_DEPTH]; ++cntz; }
-                    else if (m == 2) { accz += r[R_DEPTH + 1]; ++cntz; }
-                }
-            }
-            ++cnt;
-        }
-    }
-    const size_t hw = (size_t)a.H * a.W, at = (size_t)y * a.W + x;
-    const float n = (float)cnt;                         // = nn.Fold(ones) at this pixel (>= 1): the patches visited
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (a.image) { a.image[c * hw + at] = acc1[c] / n; a.image[(3 + c) * hw + at] = acc2[c] / n; }
-        if (a.shpd) a.shpd[c * hw + at] = accs[c] / n;
-        if (a.refoc) a.refoc[c * hw + at] = accf[c] / n;
-    }
-    if (a.bndry) a.bndry[at] = accb / n;
-    if (a.depth) a.depth[at] = accz / (cntz > 0 ? (float)cntz : 1.0f);      // postprocessing_loss.py:170-172
-    if (a.conf) a.conf[at] = (float)cntz / n;
+    for (int c = 0; c < 3; ++c) acc[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
 }
 
-// ------------------------------------------------------------------------------------------------ focal stack
+// ---- accumulators.  Interface: Acc(o, a, z); add(r, d1, d2) per visited record; store(n, plane_stride, at) with n = (float)cnt;
+// store_zero(plane_stride, at) for a sample outside the domain - it writes exactly the outputs store writes.  `z` is the launch's
+// extra grid index: the plane chunk for StackAcc; MapsAcc has none (the pixel sampler alone uses it, to pick the image of a
+// batch).  Everything lives in registers: the kernels keep 0 bytes of scratch (check the compiler's resource report after a
+// change here: r[REC] and the accumulators pass through three inlined calls).
+struct FoldArgs {
+    FoldGrid g;
+    int densify_w;
+    float* image;            // [2,3,*] or null        (* = H,W | Ho,Wo | N: plane_stride elements)
+    float* shpd;             // [3,*] or null
+    float* refoc;            // [3,*] or null
+    float* bndry;            // [*] or null
+    float* depth;            // [*] or null
+    float* conf;             // [*] or null
+    int64_t rec_stride;      // batched form (pixel sampler only, grid.z = image): floats between the records of consecutive images
+    __device__ __forceinline__ void select_image(unsigned b) {  // image b of a batch; maps are [B,...,H,W]
+        if (!b) return;
+        const size_t hw = (size_t)g.H * g.W;
+        g.records += b * rec_stride;
+        if (image) image += b * 6 * hw;
+        if (shpd) shpd += b * 3 * hw;
+        if (refoc) refoc += b * 3 * hw;
+        if (bndry) bndry += b * hw;
+        if (depth) depth += b * hw;
+        if (conf) conf += b * hw;
+    }
+};
+
+struct MapsAcc {
+    using Args = FoldArgs;
+    static constexpr bool BATCHED = true;
+    const be_render_opts& o;
+    const FoldArgs& a;
+    Rgb acc1 = 0.f, acc2 = 0.f, accs = 0.f, accf = 0.f;
+    float accb = 0.f, accz = 0.f;
+    int cntz = 0;
+    __device__ __forceinline__ MapsAcc(const be_render_opts& o_, const FoldArgs& a_, unsigned) : o(o_), a(a_) {}
+
+    __device__ __forceinline__ void add(const float* r, float d1, float d2) {
+#pragma clang fp contract(off)
+        const float rs = be::kRoot2 * 1e-4f;                    // sharpened: eta = 1e-4 for both wedges
+        const float* col = r + R_COL;
+        float u0, u1, u2;
+        if (a.image) {
+            be::indicators(d1, d2, r[R_RAD1], r[R_RAD1 + 1], u0, u1, u2);
+            blend_add(acc1, col, u0, u1, u2);
+            be::indicators(d1, d2, r[R_RAD2], r[R_RAD2 + 1], u0, u1, u2);
+            blend_add(acc2, col, u0, u1, u2);
+        }
+        if (a.shpd) { be::indicators(d1, d2, rs, rs, u0, u1, u2); blend_add(accs, col, u0, u1, u2); }
+        if (a.refoc) { be::indicators(d1, d2, r[R_RADF], r[R_RADF + 1], u0, u1, u2); blend_add(accf, col, u0, u1, u2); }
+        if (a.bndry) accb += be::boundary_value(d1, d2, o.delta_sq);
+        if (a.depth || a.conf) {
+            const int m = be::depth_mask(d1, d2, o.delta_sq, a.densify_w != 0);
+            // m is 0, 1 or 2: the depth of wedge m joins the sum.  One arm, not `if (m == 1) .. else if (m == 2) ..`: inlined into
+            // the samplers the two arms were merged by the compiler anyway, into a dozen more exec-mask instructions per visit
+            if (m != 0) { accz += m == 1 ? r[R_DEPTH] : r[R_DEPTH + 1]; ++cntz; }
+        }
+    }
+    // n = nn.Fold(ones) at the sample: the patches visited (0 only where a uniform grid stops short of the edge)
+    template <bool ZERO = false>
+    __device__ __forceinline__ void store(float n, size_t hw, size_t at) const {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (a.image) { a.image[c * hw + at] = ZERO ? 0.f : acc1[c] / n; a.image[(3 + c) * hw + at] = ZERO ? 0.f : acc2[c] / n; }
+            if (a.shpd) a.shpd[c * hw + at] = ZERO ? 0.f : accs[c] / n;
+            if (a.refoc) a.refoc[c * hw + at] = ZERO ? 0.f : accf[c] / n;
+        }
+        if (a.bndry) a.bndry[at] = ZERO ? 0.f : accb / n;
+        if (a.depth) a.depth[at] = ZERO ? 0.f : accz / (cntz > 0 ? (float)cntz : 1.0f);       // postprocessing_loss.py:170-172
+        if (a.conf) a.conf[at] = ZERO ? 0.f : (float)cntz / n;
+    }
+    __device__ __forceinline__ void store_zero(size_t hw, size_t at) const { store<true>(0.f, hw, at); }
+};
+
 // K refocused images from ONE record grid: the refocus radius of a wedge is sqrt(2) * depth2sigma(z, rho') (or sqrt(2) * 1e-4
 // when the wedge owns no mask pixel), a function of the record's R_DEPTH / R_FLAGS and the plane's optical power alone, so the
-// record fetch, wedge_dists and the run search of k_fold_records are done once per covering patch and shared by the planes of a
-// chunk.  Plane k is k_render_records(rho_prime = rho_k) + k_fold_records(refoc) bit for bit: same radius expression, same
-// indicators / composite under contract(off), same visiting order, one division by the number of patches visited.
+// record visit and the run search are done once per covering patch and shared by the planes of a chunk.  Plane k is
+// k_render_records(rho_prime = rho_k) + the `refoc` map of MapsAcc bit for bit: same radius expression, same indicators /
+// blend_add under contract(off), same visiting order, one division by the number of patches visited.
 struct StackArgs {
-    const float* records;    // [hp*wp,32]
+    FoldGrid g;
+    be_depth_consts dc;
     const float* rho_primes; // [K] optical powers, device
-    float* out;              // [K,3,H,W]
-    int hp, wp, H, W, stride, K;
-    const int32_t* ys;       // [hp] / [wp] patch origins (k_fold_refocus_stack<true> only)
-    const int32_t* xs;
+    float* out;              // [K,3,*]
+    int K;
 };
 
-constexpr int FOLD_KC = BE_REFOCUS_STACK_KC;        // planes per workgroup (blockIdx.z = chunk; the last chunk may be short)
-
-template <bool TABLES>
-__global__ __launch_bounds__(256)
-void k_fold_refocus_stack(be_render_opts o, be_depth_consts dc, StackArgs a) {
-    __shared__ float lin[R];
-    __shared__ int sy[TABLES ? FOLD_LINES : 1], sx[TABLES ? FOLD_LINES : 1];
-    if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
-    int i0 = 0, j0 = 0;                                         // grid line held by sy[0] / sx[0]
-    if constexpr (TABLES) {
-        i0 = lower_bound(a.ys, a.hp, (int)blockIdx.y * FOLD_TILE - (R - 1));
-        j0 = lower_bound(a.xs, a.wp, (int)blockIdx.x * FOLD_TILE - (R - 1));
-        const int t = threadIdx.x;
-        if (t < FOLD_LINES) sy[t] = i0 + t < a.hp ? a.ys[i0 + t] : LINE_NONE;
-        else if (t >= 64 && t < 64 + FOLD_LINES) sx[t - 64] = j0 + t - 64 < a.wp ? a.xs[j0 + t - 64] : LINE_NONE;
-    }
-    __syncthreads();
-    const int x = blockIdx.x * FOLD_TILE + (threadIdx.x & 15);
-    const int y = blockIdx.y * FOLD_TILE + (threadIdx.x >> 4);
-    if (x >= a.W || y >= a.H) return;
-    const int k0 = blockIdx.z * FOLD_KC;
-    const int nk = min(FOLD_KC, a.K - k0);                      // planes of this chunk (uniform over the workgroup)
+struct StackAcc {
+    using Args = StackArgs;
+    static constexpr bool BATCHED = false;
+    const StackArgs& a;
+    const int k0, nk;                                           // first plane and planes of this chunk (uniform over the workgroup)
     float rho[FOLD_KC];
+    Rgb acc[FOLD_KC];
+    __device__ __forceinline__ StackAcc(const be_render_opts&, const StackArgs& a_, unsigned chunk)
+        : a(a_), k0((int)chunk * FOLD_KC), nk(min(FOLD_KC, a_.K - k0)) {
 #pragma unroll
-    for (int k = 0; k < FOLD_KC; ++k) rho[k] = a.rho_primes[k0 + min(k, nk - 1)];
-    const int s = a.stride;
-    int i_lo, j_lo, i_hi, j_hi;
-    if constexpr (TABLES) {
-        i_lo = 0; while (i_lo < FOLD_LINES && sy[i_lo] < y - (R - 1)) ++i_lo;
-        j_lo = 0; while (j_lo < FOLD_LINES && sx[j_lo] < x - (R - 1)) ++j_lo;
-        i_hi = i_lo - 1; while (i_hi + 1 < FOLD_LINES && sy[i_hi + 1] <= y) ++i_hi;
-        j_hi = j_lo - 1; while (j_hi + 1 < FOLD_LINES && sx[j_hi + 1] <= x) ++j_hi;
-    } else {
-        i_lo = (y - (R - 1) + s - 1) / s; if (y - (R - 1) < 0) i_lo = 0;
-        j_lo = (x - (R - 1) + s - 1) / s; if (x - (R - 1) < 0) j_lo = 0;
-        i_hi = y / s; if (i_hi > a.hp - 1) i_hi = a.hp - 1;
-        j_hi = x / s; if (j_hi > a.wp - 1) j_hi = a.wp - 1;
+        for (int k = 0; k < FOLD_KC; ++k) {
+            rho[k] = a.rho_primes[k0 + min(k, nk - 1)];
+            acc[k] = 0.f;
+        }
     }
-    float acc[FOLD_KC][3];
+    __device__ __forceinline__ void add(const float* r, float d1, float d2) {
+        const float* col = r + R_COL;
+        const float z1 = r[R_DEPTH], z2 = r[R_DEPTH + 1];
+        const int flags = (int)r[R_FLAGS];
+        const bool has1 = (flags & 1) != 0, has2 = (flags & 2) != 0;
 #pragma unroll
-    for (int k = 0; k < FOLD_KC; ++k) { acc[k][0] = 0.f; acc[k][1] = 0.f; acc[k][2] = 0.f; }
-    int cnt = 0;
-    for (int i = i_lo; i <= i_hi; ++i) {
-        const float py = lin[y - (TABLES ? sy[i] : s * i)];
-        for (int j = j_lo; j <= j_hi; ++j) {
-            const float px = lin[x - (TABLES ? sx[j] : s * j)];
-            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)((i0 + i) * a.wp + (j0 + j)) * REC);
-            float r[REC];
-#pragma unroll
-            for (int k = 0; k < REC / 4; ++k) { const float4 t = rp[k]; r[4 * k] = t.x; r[4 * k + 1] = t.y; r[4 * k + 2] = t.z; r[4 * k + 3] = t.w; }
-            be::WedgeGeom g;
-            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
-            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
-            g.sg1 = r[12]; g.sg2 = r[13];
-            float d1, d2;
-            be::wedge_dists(g, px, py, o.w, d1, d2);
-            const float* col = r + R_COL;
-            const float z1 = r[R_DEPTH], z2 = r[R_DEPTH + 1];
-            const int flags = (int)r[R_FLAGS];
-            const bool has1 = (flags & 1) != 0, has2 = (flags & 2) != 0;
-#pragma unroll
-            for (int k = 0; k < FOLD_KC; ++k) {
-                if (k < nk) {
+        for (int k = 0; k < FOLD_KC; ++k) {
+            if (k < nk) {
 #pragma clang fp contract(off)
-                    const float s1 = has1 ? be::depth2sigma(dc, z1, rho[k]) : 1e-4f;       // as k_render_records writes R_RADF
-                    const float s2 = has2 ? be::depth2sigma(dc, z2, rho[k]) : 1e-4f;
-                    float u0, u1, u2;
-                    be::indicators(d1, d2, be::kRoot2 * s1, be::kRoot2 * s2, u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc[k][c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
+                const float s1 = has1 ? be::depth2sigma(a.dc, z1, rho[k]) : 1e-4f;       // as k_render_records writes R_RADF
+                const float s2 = has2 ? be::depth2sigma(a.dc, z2, rho[k]) : 1e-4f;
+                float u0, u1, u2;
+                be::indicators(d1, d2, be::kRoot2 * s1, be::kRoot2 * s2, u0, u1, u2);
+                blend_add(acc[k], col, u0, u1, u2);
             }
-            ++cnt;
         }
     }
-    const size_t hw = (size_t)a.H * a.W, at = (size_t)y * a.W + x;
-    const float n = (float)cnt;
+    template <bool ZERO = false>
+    __device__ __forceinline__ void store(float n, size_t hw, size_t at) const {
 #pragma unroll
-    for (int k = 0; k < FOLD_KC; ++k) {
-        if (k < nk) {
+        for (int k = 0; k < FOLD_KC; ++k) {
+            if (k < nk) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) a.out[((size_t)(k0 + k) * 3 + c) * hw + at] = acc[k][c] / n;
+                for (int c = 0; c < 3; ++c) a.out[((size_t)(k0 + k) * 3 + c) * hw + at] = ZERO ? 0.f : acc[k][c] / n;
+            }
         }
     }
-}
-
-// ------------------------------------------------------------------------------------------------ the folds on a finer lattice
-// The record grid is a continuous description: wedge_dists, indicators, boundary_value and depth_mask take a real position.
-// The two kernels below are k_fold_records and k_fold_refocus_stack evaluated on a lattice `scale` (k) times finer, over a
-// window of the image: output sample (iy, ix) sits at Y = top * k + iy, X = left * k + ix in units of 1/k pixel.  With
-// Y = yq * k + yr (0 <= yr < k) a grid line of origin oy covers the sample iff oy * k <= Y <= (oy + 20) * k, i.e. iff
-// yq + (yr > 0) - 20 <= oy <= yq: integer arithmetic, a contiguous run of lines, and - the origins being whole pixels - the
-// remainder yr is the same for every covering line, so the one division by k is per thread and axis, not per patch.  The
-// patch-local coordinate is lin[q] (q = yq - oy, READ, not computed) when yr == 0 and lin[q] + (yr / k) * (lin[q+1] - lin[q])
-// otherwise (then q <= 19).  Everything after the coordinate is the body of the integer-pixel kernel, so every k-th sample
-// equals that kernel's pixel bit for bit.
-struct Lattice {
-    int scale;               // k, 1..16
-    int top, left;           // window origin, input pixels
-    int Ho, Wo;              // (h - 1) * k + 1, (w - 1) * k + 1
+    __device__ __forceinline__ void store_zero(size_t hw, size_t at) const { store<true>(0.f, hw, at); }
 };
 
-// the run of grid lines covering a sample at pq + pr / k: staged origins sl[0..FOLD_LINES) (TABLES) or stride * index
-template <bool TABLES>
-__device__ __forceinline__ void lattice_run(const int* sl, int s, int n, int pq, int pr, int& lo, int& hi) {
-    const int first = pq + (pr ? 1 : 0) - (R - 1);              // the smallest origin that still covers the sample
-    if constexpr (TABLES) {
-        lo = 0; while (lo < FOLD_LINES && sl[lo] < first) ++lo;
-        hi = lo - 1; while (hi + 1 < FOLD_LINES && sl[hi + 1] <= pq) ++hi;
-    } else {
-        lo = first > 0 ? (first + s - 1) / s : 0;
-        hi = pq / s; if (hi > n - 1) hi = n - 1;
-    }
+// ---- visit: one record at the patch-local position (px, py).  NOT under contract(off): wedge_dists never was.
+template <class Acc>
+__device__ __forceinline__ void visit_record(const float* rec, float px, float py, float w, Acc& acc) {
+    const float4* rp = reinterpret_cast<const float4*>(rec);
+    float r[REC];
+#pragma unroll
+    for (int k = 0; k < REC / 4; ++k) { const float4 t = rp[k]; r[4 * k] = t.x; r[4 * k + 1] = t.y; r[4 * k + 2] = t.z; r[4 * k + 3] = t.w; }
+    be::WedgeGeom g;
+    g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
+    g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
+    g.sg1 = r[12]; g.sg2 = r[13];
+    float d1, d2;
+    be::wedge_dists(g, px, py, w, d1, d2);
+    acc.add(r, d1, d2);
 }
 
-// first grid line a 16-sample tile starting at sample P0 (units of 1/k pixel) can be covered by
-__device__ __forceinline__ int lattice_tile_first(int P0, int k) { return P0 / k + (P0 % k ? 1 : 0) - (R - 1); }
+// ---- run.  The record grid is a continuous description: wedge_dists, indicators, boundary_value and depth_mask take a real
+// position.  A sample sits, per axis, at q + f pixels (Axis: q whole, 0 <= f < 1, r != 0 iff f > 0).  A grid line of origin oy
+// covers it iff oy <= q + f <= oy + 20, i.e. iff q + (r != 0) - 20 <= oy <= q: integer arithmetic and a contiguous run of lines.
+// The origins being whole pixels, r and f are the same for every covering line.  The patch-local coordinate is lin[q - oy]
+// (READ, not computed) when r == 0 and lin[q - oy] + f * (lin[q - oy + 1] - lin[q - oy]) otherwise (then q - oy <= 19); a
+// sample on a pixel therefore gets the pixel sampler's coordinate whatever sampler produced it.
+struct Axis { int q, r; float f; };
 
 __device__ __forceinline__ float lattice_coord(const float* lin, int q, int pr, float frac) {
 #pragma clang fp contract(off)
@@ -451,380 +392,168 @@ __device__ __forceinline__ float lattice_coord(const float* lin, int q, int pr, 
     return l0 + frac * (lin[q + 1] - l0);
 }
 
+// How a line index becomes an origin and a record row / column, and how the run [lo, hi] of lines with
+// first <= origin <= last is found (hi < lo: none).
+struct StagedLines {         // origin tables, the FOLD_LINES lines that can cover a tile staged in LDS; slot 0 is line `base`
+    const int* s; int base;
+    __device__ __forceinline__ int origin(int i) const { return s[i]; }
+    __device__ __forceinline__ int line(int i) const { return base + i; }
+    __device__ __forceinline__ void run(int first, int last, int& lo, int& hi) const {
+        lo = 0; while (lo < FOLD_LINES && s[lo] < first) ++lo;
+        hi = lo - 1; while (hi + 1 < FOLD_LINES && s[hi + 1] <= last) ++hi;
+    }
+};
+struct TableLines {          // origin tables t[0..n) searched in global memory (samples that are not tiled)
+    const int32_t* __restrict__ t; int n;
+    __device__ __forceinline__ int origin(int i) const { return t[i]; }
+    __device__ __forceinline__ int line(int i) const { return i; }
+    __device__ __forceinline__ void run(int first, int last, int& lo, int& hi) const {
+        lo = lower_bound(t, n, first);
+        hi = lo - 1; while (hi + 1 < n && t[hi + 1] <= last) ++hi;
+    }
+};
+struct StrideLines {         // the uniform grid of nn.Unfold: origin = stride * index, n lines
+    int s, n;
+    __device__ __forceinline__ int origin(int i) const { return s * i; }
+    __device__ __forceinline__ int line(int i) const { return i; }
+    __device__ __forceinline__ void run(int first, int last, int& lo, int& hi) const {
+        lo = first > 0 ? (first + s - 1) / s : 0;
+        hi = last / s; if (hi > n - 1) hi = n - 1;
+    }
+};
+
+// visits the patches covering the sample (y, x), i outer, j inner, ascending (the order is part of the result); returns how many
+template <class Lines, class Acc>
+__device__ __forceinline__ int fold_run(const float* lin, float w, const FoldGrid& g, const Lines& ly, const Lines& lx, const Axis& y,
+                                        const Axis& x, Acc& acc) {
+    int i_lo, j_lo, i_hi, j_hi;
+    ly.run(y.q + (y.r ? 1 : 0) - (R - 1), y.q, i_lo, i_hi);
+    lx.run(x.q + (x.r ? 1 : 0) - (R - 1), x.q, j_lo, j_hi);
+    int cnt = 0;
+    for (int i = i_lo; i <= i_hi; ++i) {
+        const float py = lattice_coord(lin, y.q - ly.origin(i), y.r, y.f);
+        for (int j = j_lo; j <= j_hi; ++j) {
+            const float px = lattice_coord(lin, x.q - lx.origin(j), x.r, x.f);
+            visit_record(g.records + (size_t)(ly.line(i) * g.wp + lx.line(j)) * REC, px, py, w, acc);
+            ++cnt;
+        }
+    }
+    return cnt;
+}
+
+// ---- samplers
+// What the two tiled samplers do before their threads part: lin -> LDS and, with origin tables, the grid lines that can cover
+// the tile (the first is the first with origin >= first_y / first_x) staged once per workgroup; absent slots hold LINE_NONE.
+// i0 / j0: the grid line held by sy[0] / sx[0].
 template <bool TABLES>
-__global__ __launch_bounds__(256)
-void k_fold_records_at(be_render_opts o, FoldArgs a, Lattice l) {
-    __shared__ float lin[R];
-    __shared__ int sy[TABLES ? FOLD_LINES : 1], sx[TABLES ? FOLD_LINES : 1];
-    if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
-    const int k = l.scale;
-    const int Y0 = l.top * k + (int)blockIdx.y * FOLD_TILE, X0 = l.left * k + (int)blockIdx.x * FOLD_TILE;
-    int i0 = 0, j0 = 0;                                         // grid line held by sy[0] / sx[0]
+__device__ __forceinline__ void stage_tile(const be_render_opts& o, const FoldGrid& g, int first_y, int first_x, float* lin, int* sy,
+                                           int* sx, int& i0, int& j0) {
+    const int t = threadIdx.x;
+    if (t < R) lin[t] = o.lin[t];
+    i0 = 0; j0 = 0;
     if constexpr (TABLES) {
-        // a tile spans at most 16 pixels, so at most FOLD_LINES distinct origins lie in [tile_first, (P0 + 15) / k]
-        i0 = lower_bound(a.ys, a.hp, lattice_tile_first(Y0, k));
-        j0 = lower_bound(a.xs, a.wp, lattice_tile_first(X0, k));
-        const int t = threadIdx.x;
-        if (t < FOLD_LINES) sy[t] = i0 + t < a.hp ? a.ys[i0 + t] : LINE_NONE;
-        else if (t >= 64 && t < 64 + FOLD_LINES) sx[t - 64] = j0 + t - 64 < a.wp ? a.xs[j0 + t - 64] : LINE_NONE;
+        i0 = lower_bound(g.ys, g.hp, first_y);
+        j0 = lower_bound(g.xs, g.wp, first_x);
+        if (t < FOLD_LINES) sy[t] = i0 + t < g.hp ? g.ys[i0 + t] : LINE_NONE;
+        else if (t >= 64 && t < 64 + FOLD_LINES) sx[t - 64] = j0 + t - 64 < g.wp ? g.xs[j0 + t - 64] : LINE_NONE;
     }
     __syncthreads();
+}
+
+// one tiled sample: fold the covering run into a fresh accumulator and store it
+template <class Acc, bool TABLES>
+__device__ __forceinline__ void fold_tile_sample(const be_render_opts& o, const typename Acc::Args& a, const float* lin, const int* sy,
+                                                 const int* sx, int i0, int j0, const Axis& y, const Axis& x, size_t hw, size_t at) {
+    Acc acc(o, a, blockIdx.z);
+    int cnt;
+    if constexpr (TABLES) cnt = fold_run(lin, o.w, a.g, StagedLines{sy, i0}, StagedLines{sx, j0}, y, x, acc);
+    else cnt = fold_run(lin, o.w, a.g, StrideLines{a.g.stride, a.g.hp}, StrideLines{a.g.stride, a.g.wp}, y, x, acc);
+    acc.store((float)cnt, hw, at);
+}
+
+// whole pixels: one thread per pixel of the H x W image ("owner computes": deterministic, no atomics).  blockIdx.z = image of
+// a batch (MapsAcc) / plane chunk (StackAcc).  r == 0: lattice_coord returns lin[q], no division anywhere.
+template <class Acc, bool TABLES>
+__global__ __launch_bounds__(256)
+void k_fold_pixels(be_render_opts o, typename Acc::Args a) {
+    __shared__ float lin[R];
+    __shared__ int sy[TABLES ? FOLD_LINES : 1], sx[TABLES ? FOLD_LINES : 1];
+    int i0, j0;
+    stage_tile<TABLES>(o, a.g, (int)blockIdx.y * FOLD_TILE - (R - 1), (int)blockIdx.x * FOLD_TILE - (R - 1), lin, sy, sx, i0, j0);
+    const int x = blockIdx.x * FOLD_TILE + (threadIdx.x & 15);
+    const int y = blockIdx.y * FOLD_TILE + (threadIdx.x >> 4);
+    if (x >= a.g.W || y >= a.g.H) return;
+    if constexpr (Acc::BATCHED) a.select_image(blockIdx.z);
+    fold_tile_sample<Acc, TABLES>(o, a, lin, sy, sx, i0, j0, Axis{y, 0, 0.f}, Axis{x, 0, 0.f}, (size_t)a.g.H * a.g.W, (size_t)y * a.g.W + x);
+}
+
+// a lattice `scale` (k) times finer, over a window of the image: output sample (iy, ix) sits at Y = top * k + iy,
+// X = left * k + ix in units of 1/k pixel; Y = yq * k + yr (0 <= yr < k) gives the Axis with f = yr / k - one division by k
+// per thread and axis, not per patch.  Every k-th sample has r == 0 and equals the pixel sampler's pixel bit for bit.
+struct Lattice {
+    int scale;               // k, 1..16
+    int top, left;           // window origin, input pixels
+    int Ho, Wo;              // (h - 1) * k + 1, (w - 1) * k + 1
+};
+
+// first grid line a 16-sample tile starting at sample P0 (units of 1/k pixel) can be covered by; a tile spans at most 16
+// pixels, so at most FOLD_LINES distinct origins lie in [tile_first, (P0 + 15) / k]
+__device__ __forceinline__ int lattice_tile_first(int P0, int k) { return P0 / k + (P0 % k ? 1 : 0) - (R - 1); }
+
+template <class Acc, bool TABLES>
+__global__ __launch_bounds__(256)
+void k_fold_lattice(be_render_opts o, typename Acc::Args a, Lattice l) {
+    __shared__ float lin[R];
+    __shared__ int sy[TABLES ? FOLD_LINES : 1], sx[TABLES ? FOLD_LINES : 1];
+    const int k = l.scale;
+    int i0, j0;
+    stage_tile<TABLES>(o, a.g, lattice_tile_first(l.top * k + (int)blockIdx.y * FOLD_TILE, k),
+                       lattice_tile_first(l.left * k + (int)blockIdx.x * FOLD_TILE, k), lin, sy, sx, i0, j0);
     const int ix = blockIdx.x * FOLD_TILE + (threadIdx.x & 15);
     const int iy = blockIdx.y * FOLD_TILE + (threadIdx.x >> 4);
     if (ix >= l.Wo || iy >= l.Ho) return;
     const int Y = l.top * k + iy, X = l.left * k + ix;
     const int yq = Y / k, yr = Y - yq * k, xq = X / k, xr = X - xq * k;
-    const float fy = (float)yr / (float)k, fx = (float)xr / (float)k;
-    const int s = a.stride;
-    int i_lo, j_lo, i_hi, j_hi;
-    lattice_run<TABLES>(sy, s, a.hp, yq, yr, i_lo, i_hi);
-    lattice_run<TABLES>(sx, s, a.wp, xq, xr, j_lo, j_hi);
-    float acc1[3] = {0, 0, 0}, acc2[3] = {0, 0, 0}, accs[3] = {0, 0, 0}, accf[3] = {0, 0, 0};
-    float accb = 0.f, accz = 0.f;
-    int cnt = 0, cntz = 0;
-    const float rs = be::kRoot2 * 1e-4f;
-    for (int i = i_lo; i <= i_hi; ++i) {
-        const float py = lattice_coord(lin, yq - (TABLES ? sy[i] : s * i), yr, fy);
-        for (int j = j_lo; j <= j_hi; ++j) {
-            const float px = lattice_coord(lin, xq - (TABLES ? sx[j] : s * j), xr, fx);
-            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)((i0 + i) * a.wp + (j0 + j)) * REC);
-            float r[REC];
-#pragma unroll
-            for (int q = 0; q < REC / 4; ++q) { const float4 t = rp[q]; r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w; }
-            be::WedgeGeom g;
-            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
-            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
-            g.sg1 = r[12]; g.sg2 = r[13];
-            float d1, d2;
-            be::wedge_dists(g, px, py, o.w, d1, d2);
-            const float* col = r + R_COL;
-            float u0, u1, u2;
-            {
-#pragma clang fp contract(off)
-                if (a.image) {
-                    be::indicators(d1, d2, r[R_RAD1], r[R_RAD1 + 1], u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc1[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                    be::indicators(d1, d2, r[R_RAD2], r[R_RAD2 + 1], u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc2[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-                if (a.shpd) {
-                    be::indicators(d1, d2, rs, rs, u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) accs[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-                if (a.refoc) {
-                    be::indicators(d1, d2, r[R_RADF], r[R_RADF + 1], u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) accf[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-                if (a.bndry) accb += be::boundary_value(d1, d2, o.delta_sq);
-                if (a.depth || a.conf) {
-                    const int m = be::depth_mask(d1, d2, o.delta_sq, a.densify_w != 0);
-                    if (m == 1) { accz += r[R_DEPTH]; ++cntz; }
-                    else if (m == 2) { accz += r[R_DEPTH + 1]; ++cntz; }
-                }
-            }
-            ++cnt;
-        }
-    }
-    const size_t hw = (size_t)l.Ho * l.Wo, at = (size_t)iy * l.Wo + ix;
-    const float n = (float)cnt;                         // the patches visited (0 only where a uniform grid stops short of the edge)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (a.image) { a.image[c * hw + at] = acc1[c] / n; a.image[(3 + c) * hw + at] = acc2[c] / n; }
-        if (a.shpd) a.shpd[c * hw + at] = accs[c] / n;
-        if (a.refoc) a.refoc[c * hw + at] = accf[c] / n;
-    }
-    if (a.bndry) a.bndry[at] = accb / n;
-    if (a.depth) a.depth[at] = accz / (cntz > 0 ? (float)cntz : 1.0f);
-    if (a.conf) a.conf[at] = (float)cntz / n;
+    fold_tile_sample<Acc, TABLES>(o, a, lin, sy, sx, i0, j0, Axis{yq, yr, (float)yr / (float)k}, Axis{xq, xr, (float)xr / (float)k},
+                                  (size_t)l.Ho * l.Wo, (size_t)iy * l.Wo + ix);
 }
 
-template <bool TABLES>
-__global__ __launch_bounds__(256)
-void k_fold_refocus_stack_at(be_render_opts o, be_depth_consts dc, StackArgs a, Lattice l) {
-    __shared__ float lin[R];
-    __shared__ int sy[TABLES ? FOLD_LINES : 1], sx[TABLES ? FOLD_LINES : 1];
-    if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
-    const int sc = l.scale;
-    const int Y0 = l.top * sc + (int)blockIdx.y * FOLD_TILE, X0 = l.left * sc + (int)blockIdx.x * FOLD_TILE;
-    int i0 = 0, j0 = 0;
-    if constexpr (TABLES) {
-        i0 = lower_bound(a.ys, a.hp, lattice_tile_first(Y0, sc));
-        j0 = lower_bound(a.xs, a.wp, lattice_tile_first(X0, sc));
-        const int t = threadIdx.x;
-        if (t < FOLD_LINES) sy[t] = i0 + t < a.hp ? a.ys[i0 + t] : LINE_NONE;
-        else if (t >= 64 && t < 64 + FOLD_LINES) sx[t - 64] = j0 + t - 64 < a.wp ? a.xs[j0 + t - 64] : LINE_NONE;
-    }
-    __syncthreads();
-    const int ix = blockIdx.x * FOLD_TILE + (threadIdx.x & 15);
-    const int iy = blockIdx.y * FOLD_TILE + (threadIdx.x >> 4);
-    if (ix >= l.Wo || iy >= l.Ho) return;
-    const int Y = l.top * sc + iy, X = l.left * sc + ix;
-    const int yq = Y / sc, yr = Y - yq * sc, xq = X / sc, xr = X - xq * sc;
-    const float fy = (float)yr / (float)sc, fx = (float)xr / (float)sc;
-    const int k0 = blockIdx.z * FOLD_KC;
-    const int nk = min(FOLD_KC, a.K - k0);                      // planes of this chunk (uniform over the workgroup)
-    float rho[FOLD_KC];
-#pragma unroll
-    for (int k = 0; k < FOLD_KC; ++k) rho[k] = a.rho_primes[k0 + min(k, nk - 1)];
-    const int s = a.stride;
-    int i_lo, j_lo, i_hi, j_hi;
-    lattice_run<TABLES>(sy, s, a.hp, yq, yr, i_lo, i_hi);
-    lattice_run<TABLES>(sx, s, a.wp, xq, xr, j_lo, j_hi);
-    float acc[FOLD_KC][3];
-#pragma unroll
-    for (int k = 0; k < FOLD_KC; ++k) { acc[k][0] = 0.f; acc[k][1] = 0.f; acc[k][2] = 0.f; }
-    int cnt = 0;
-    for (int i = i_lo; i <= i_hi; ++i) {
-        const float py = lattice_coord(lin, yq - (TABLES ? sy[i] : s * i), yr, fy);
-        for (int j = j_lo; j <= j_hi; ++j) {
-            const float px = lattice_coord(lin, xq - (TABLES ? sx[j] : s * j), xr, fx);
-            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)((i0 + i) * a.wp + (j0 + j)) * REC);
-            float r[REC];
-#pragma unroll
-            for (int q = 0; q < REC / 4; ++q) { const float4 t = rp[q]; r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w; }
-            be::WedgeGeom g;
-            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
-            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
-            g.sg1 = r[12]; g.sg2 = r[13];
-            float d1, d2;
-            be::wedge_dists(g, px, py, o.w, d1, d2);
-            const float* col = r + R_COL;
-            const float z1 = r[R_DEPTH], z2 = r[R_DEPTH + 1];
-            const int flags = (int)r[R_FLAGS];
-            const bool has1 = (flags & 1) != 0, has2 = (flags & 2) != 0;
-#pragma unroll
-            for (int k = 0; k < FOLD_KC; ++k) {
-                if (k < nk) {
-#pragma clang fp contract(off)
-                    const float s1 = has1 ? be::depth2sigma(dc, z1, rho[k]) : 1e-4f;       // as k_render_records writes R_RADF
-                    const float s2 = has2 ? be::depth2sigma(dc, z2, rho[k]) : 1e-4f;
-                    float u0, u1, u2;
-                    be::indicators(d1, d2, be::kRoot2 * s1, be::kRoot2 * s2, u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc[k][c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-            }
-            ++cnt;
-        }
-    }
-    const size_t hw = (size_t)l.Ho * l.Wo, at = (size_t)iy * l.Wo + ix;
-    const float n = (float)cnt;
-#pragma unroll
-    for (int k = 0; k < FOLD_KC; ++k) {
-        if (k < nk) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) a.out[((size_t)(k0 + k) * 3 + c) * hw + at] = acc[k][c] / n;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ the folds at arbitrary positions
-// The lattice kernels above sample on an axis-aligned lattice with an integer scale; nothing after the coordinate needs that.
-// The two kernels below take a list of N real-valued positions (y, x) in input-pixel coordinates (pixel centres at the integers,
-// the coordinate top + iy / k of the lattice), one thread per point.  Per axis yq = floor(y), fy = y - yq (exact in float32); a
-// grid line of origin oy covers the point iff oy <= y <= oy + 20, i.e. iff yq + (fy > 0) - 20 <= oy <= yq: the lattice rule
-// with `yr > 0` replaced by `fy > 0`.  The coordinate is lattice_coord, so a point with fy == fx == 0 equals the pixel kernels
-// bit for bit and a dyadic point equals the lattice kernels bit for bit.  Points are not tiled: origin tables are searched in
-// global memory (lower_bound, then a forward scan), not staged.  Outputs are channel-major over the points ([C,N]), so a point
-// grid [Ho,Wo] reshapes to the lattice layout without a transpose.  A point outside the closed domain [0, H-1] x [0, W-1]
-// (NaN included) gets 0 in every requested output.
+// a list of N real-valued positions (y, x) in input-pixel coordinates (pixel centres at the integers, the coordinate
+// top + iy / k of the lattice), one thread per point.  Per axis q = floor(y), f = y - q (exact in float32), r = (f > 0): a point
+// with fy == fx == 0 equals the pixel sampler bit for bit and a dyadic point equals the lattice sampler bit for bit.  Points are
+// not tiled: origin tables are searched in global memory (TableLines), not staged.  Outputs are channel-major over the points
+// ([C,N]), so a point grid [Ho,Wo] reshapes to the lattice layout without a transpose.  A point outside the closed domain
+// [0, H-1] x [0, W-1] (NaN included) gets 0 in every requested output.  blockIdx.y = plane chunk (StackAcc).
 struct Points {
     const float* pts;        // [N,2] (y, x), device
     int64_t N;
 };
 
-// the run of grid lines covering a position pq + f (0 <= f < 1): the global origin table t[0..n) (TABLES) or stride * index
-template <bool TABLES>
-__device__ __forceinline__ void point_run(const int32_t* __restrict__ t, int s, int n, int pq, bool frac, int& lo, int& hi) {
-    const int first = pq + (frac ? 1 : 0) - (R - 1);            // the smallest origin that still covers the position
-    if constexpr (TABLES) {
-        lo = lower_bound(t, n, first);
-        hi = lo - 1; while (hi + 1 < n && t[hi + 1] <= pq) ++hi;
-    } else {
-        lo = first > 0 ? (first + s - 1) / s : 0;
-        hi = pq / s; if (hi > n - 1) hi = n - 1;
-    }
-}
-
 // the point's position, split per axis; false (outside the closed domain, or not a number): the caller writes zeros
-__device__ __forceinline__ bool point_split(const float* __restrict__ pts, int64_t p, int H, int W, int& yq, int& xq, float& fy, float& fx) {
+__device__ __forceinline__ bool point_split(const float* __restrict__ pts, int64_t p, int H, int W, Axis& ay, Axis& ax) {
     const float y = pts[2 * p], x = pts[2 * p + 1];
     if (!(y >= 0.f && y <= (float)(H - 1) && x >= 0.f && x <= (float)(W - 1))) return false;
-    yq = (int)floorf(y); xq = (int)floorf(x);
-    fy = y - (float)yq; fx = x - (float)xq;
+    const int yq = (int)floorf(y), xq = (int)floorf(x);
+    const float fy = y - (float)yq, fx = x - (float)xq;
+    ay = Axis{yq, fy > 0.f, fy}; ax = Axis{xq, fx > 0.f, fx};
     return true;
 }
 
-template <bool TABLES>
+template <class Acc, bool TABLES>
 __global__ __launch_bounds__(256)
-void k_fold_records_points(be_render_opts o, FoldArgs a, Points l) {
+void k_fold_points(be_render_opts o, typename Acc::Args a, Points l) {
     __shared__ float lin[R];
     if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
     __syncthreads();
     const int64_t at = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (at >= l.N) return;
-    const size_t hw = (size_t)l.N;
-    int yq, xq;
-    float fy, fx;
-    if (!point_split(l.pts, at, a.H, a.W, yq, xq, fy, fx)) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            if (a.image) { a.image[c * hw + at] = 0.f; a.image[(3 + c) * hw + at] = 0.f; }
-            if (a.shpd) a.shpd[c * hw + at] = 0.f;
-            if (a.refoc) a.refoc[c * hw + at] = 0.f;
-        }
-        if (a.bndry) a.bndry[at] = 0.f;
-        if (a.depth) a.depth[at] = 0.f;
-        if (a.conf) a.conf[at] = 0.f;
-        return;
-    }
-    const int yr = fy > 0.f, xr = fx > 0.f;
-    const int s = a.stride;
-    int i_lo, j_lo, i_hi, j_hi;
-    point_run<TABLES>(a.ys, s, a.hp, yq, yr, i_lo, i_hi);
-    point_run<TABLES>(a.xs, s, a.wp, xq, xr, j_lo, j_hi);
-    float acc1[3] = {0, 0, 0}, acc2[3] = {0, 0, 0}, accs[3] = {0, 0, 0}, accf[3] = {0, 0, 0};
-    float accb = 0.f, accz = 0.f;
-    int cnt = 0, cntz = 0;
-    const float rs = be::kRoot2 * 1e-4f;
-    for (int i = i_lo; i <= i_hi; ++i) {
-        const float py = lattice_coord(lin, yq - (TABLES ? a.ys[i] : s * i), yr, fy);
-        for (int j = j_lo; j <= j_hi; ++j) {
-            const float px = lattice_coord(lin, xq - (TABLES ? a.xs[j] : s * j), xr, fx);
-            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)(i * a.wp + j) * REC);
-            float r[REC];
-#pragma unroll
-            for (int q = 0; q < REC / 4; ++q) { const float4 t = rp[q]; r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w; }
-            be::WedgeGeom g;
-            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
-            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
-            g.sg1 = r[12]; g.sg2 = r[13];
-            float d1, d2;
-            be::wedge_dists(g, px, py, o.w, d1, d2);
-            const float* col = r + R_COL;
-            float u0, u1, u2;
-            {
-#pragma clang fp contract(off)
-                if (a.image) {
-                    be::indicators(d1, d2, r[R_RAD1], r[R_RAD1 + 1], u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc1[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                    be::indicators(d1, d2, r[R_RAD2], r[R_RAD2 + 1], u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc2[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-                if (a.shpd) {
-                    be::indicators(d1, d2, rs, rs, u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) accs[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-                if (a.refoc) {
-                    be::indicators(d1, d2, r[R_RADF], r[R_RADF + 1], u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) accf[c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-                if (a.bndry) accb += be::boundary_value(d1, d2, o.delta_sq);
-                if (a.depth || a.conf) {
-                    const int m = be::depth_mask(d1, d2, o.delta_sq, a.densify_w != 0);
-                    if (m == 1) { accz += r[R_DEPTH]; ++cntz; }
-                    else if (m == 2) { accz += r[R_DEPTH + 1]; ++cntz; }
-                }
-            }
-            ++cnt;
-        }
-    }
-    const float n = (float)cnt;                         // the patches visited (0 only where a uniform grid stops short of the edge)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (a.image) { a.image[c * hw + at] = acc1[c] / n; a.image[(3 + c) * hw + at] = acc2[c] / n; }
-        if (a.shpd) a.shpd[c * hw + at] = accs[c] / n;
-        if (a.refoc) a.refoc[c * hw + at] = accf[c] / n;
-    }
-    if (a.bndry) a.bndry[at] = accb / n;
-    if (a.depth) a.depth[at] = accz / (cntz > 0 ? (float)cntz : 1.0f);
-    if (a.conf) a.conf[at] = (float)cntz / n;
-}
-
-template <bool TABLES>
-__global__ __launch_bounds__(256)
-void k_fold_refocus_stack_points(be_render_opts o, be_depth_consts dc, StackArgs a, Points l) {
-    __shared__ float lin[R];
-    if (threadIdx.x < R) lin[threadIdx.x] = o.lin[threadIdx.x];
-    __syncthreads();
-    const int64_t at = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (at >= l.N) return;
-    const size_t hw = (size_t)l.N;
-    const int k0 = blockIdx.y * FOLD_KC;
-    const int nk = min(FOLD_KC, a.K - k0);                      // planes of this chunk (uniform over the workgroup)
-    int yq, xq;
-    float fy, fx;
-    if (!point_split(l.pts, at, a.H, a.W, yq, xq, fy, fx)) {
-#pragma unroll
-        for (int k = 0; k < FOLD_KC; ++k) {
-            if (k < nk) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) a.out[((size_t)(k0 + k) * 3 + c) * hw + at] = 0.f;
-            }
-        }
-        return;
-    }
-    const int yr = fy > 0.f, xr = fx > 0.f;
-    float rho[FOLD_KC];
-#pragma unroll
-    for (int k = 0; k < FOLD_KC; ++k) rho[k] = a.rho_primes[k0 + min(k, nk - 1)];
-    const int s = a.stride;
-    int i_lo, j_lo, i_hi, j_hi;
-    point_run<TABLES>(a.ys, s, a.hp, yq, yr, i_lo, i_hi);
-    point_run<TABLES>(a.xs, s, a.wp, xq, xr, j_lo, j_hi);
-    float acc[FOLD_KC][3];
-#pragma unroll
-    for (int k = 0; k < FOLD_KC; ++k) { acc[k][0] = 0.f; acc[k][1] = 0.f; acc[k][2] = 0.f; }
-    int cnt = 0;
-    for (int i = i_lo; i <= i_hi; ++i) {
-        const float py = lattice_coord(lin, yq - (TABLES ? a.ys[i] : s * i), yr, fy);
-        for (int j = j_lo; j <= j_hi; ++j) {
-            const float px = lattice_coord(lin, xq - (TABLES ? a.xs[j] : s * j), xr, fx);
-            const float4* rp = reinterpret_cast<const float4*>(a.records + (size_t)(i * a.wp + j) * REC);
-            float r[REC];
-#pragma unroll
-            for (int q = 0; q < REC / 4; ++q) { const float4 t = rp[q]; r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w; }
-            be::WedgeGeom g;
-            g.x0 = r[0]; g.y0 = r[1]; g.x1 = r[2]; g.y1 = r[3];
-            g.s11 = r[4]; g.c11 = r[5]; g.s12 = r[6]; g.c12 = r[7]; g.s21 = r[8]; g.c21 = r[9]; g.s22 = r[10]; g.c22 = r[11];
-            g.sg1 = r[12]; g.sg2 = r[13];
-            float d1, d2;
-            be::wedge_dists(g, px, py, o.w, d1, d2);
-            const float* col = r + R_COL;
-            const float z1 = r[R_DEPTH], z2 = r[R_DEPTH + 1];
-            const int flags = (int)r[R_FLAGS];
-            const bool has1 = (flags & 1) != 0, has2 = (flags & 2) != 0;
-#pragma unroll
-            for (int k = 0; k < FOLD_KC; ++k) {
-                if (k < nk) {
-#pragma clang fp contract(off)
-                    const float s1 = has1 ? be::depth2sigma(dc, z1, rho[k]) : 1e-4f;       // as k_render_records writes R_RADF
-                    const float s2 = has2 ? be::depth2sigma(dc, z2, rho[k]) : 1e-4f;
-                    float u0, u1, u2;
-                    be::indicators(d1, d2, be::kRoot2 * s1, be::kRoot2 * s2, u0, u1, u2);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc[k][c] += u0 * col[3 * c] + u1 * col[3 * c + 1] + u2 * col[3 * c + 2];
-                }
-            }
-            ++cnt;
-        }
-    }
-    const float n = (float)cnt;
-#pragma unroll
-    for (int k = 0; k < FOLD_KC; ++k) {
-        if (k < nk) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) a.out[((size_t)(k0 + k) * 3 + c) * hw + at] = acc[k][c] / n;
-        }
-    }
+    Acc acc(o, a, blockIdx.y);
+    Axis y, x;
+    if (!point_split(l.pts, at, a.g.H, a.g.W, y, x)) { acc.store_zero((size_t)l.N, at); return; }
+    int cnt;
+    if constexpr (TABLES) cnt = fold_run(lin, o.w, a.g, TableLines{a.g.ys, a.g.hp}, TableLines{a.g.xs, a.g.wp}, y, x, acc);
+    else cnt = fold_run(lin, o.w, a.g, StrideLines{a.g.stride, a.g.hp}, StrideLines{a.g.stride, a.g.wp}, y, x, acc);
+    acc.store((float)cnt, (size_t)l.N, at);
 }
 
 // ------------------------------------------------------------------------------------------------ glue
@@ -895,28 +624,63 @@ extern "C" int be_render_full_f32(const be_render_opts* o, const be_depth_consts
     return be::check_launch("be_render_full_f32");
 }
 
+// ---- the fold entries.  Each checks its own arguments in its own order (BE_REQUIRE returns on the first failure, so the order
+// decides which message a doubly-wrong call gets); what they share is below.
+
+// the rule every fold entry ends its grid checks with: the grid lies in the image.  With origin tables the lines are distinct
+// pixels whose patches fit (HP <= H-20, WP <= W-20); without, stride > 0 and the last patch ends inside the image.
+static int check_fold_grid(const char* who, int HP, int WP, int H, int W, int stride, const int32_t* ys) {
+    if (ys) {
+        BE_REQUIRE(HP > 0 && WP > 0 && HP <= H - R + 1 && WP <= W - R + 1,
+                   "%s: HP / WP must be in [1, H-20] / [1, W-20] (origins are distinct pixels)", who);
+    } else {
+        BE_REQUIRE(stride > 0, "%s: bad sizes", who);
+        BE_REQUIRE((int64_t)stride * (HP - 1) + R <= H && (int64_t)stride * (WP - 1) + R <= W, "%s: patch grid exceeds the image", who);
+    }
+    return BE_OK;
+}
+
+static FoldGrid fold_grid(const float* records, int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs) {
+    return FoldGrid{records, HP, WP, H, W, ys ? 0 : stride, ys, xs};
+}
+
+static dim3 tile_grid(int Wo, int Ho, int z = 1) { return dim3((Wo + FOLD_TILE - 1) / FOLD_TILE, (Ho + FOLD_TILE - 1) / FOLD_TILE, z); }
+static int stack_chunks(int K) { return (K + FOLD_KC - 1) / FOLD_KC; }
+
+template <class... P, class... A>
+static int launch_fold(const char* who, void (*k)(P...), dim3 grid, void* stream, const A&... args) {
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, be::as_stream(stream), args...);
+    return be::check_launch(who);
+}
+// an entry that takes either grid: the instantiation that matches it, kt with origin tables, ku without (uniform)
+template <class... P, class... A>
+static int launch_fold(const char* who, bool tables, void (*kt)(P...), void (*ku)(P...), dim3 grid, void* stream, const A&... args) {
+    return launch_fold(who, tables ? kt : ku, grid, stream, args...);
+}
+
 extern "C" int be_fold_records_f32(const be_render_opts* o, const float* records, int hp, int wp, int H, int W,
                                    int stride, int densify_w, float* image, float* shpd, float* refoc, float* bndry,
                                    float* depth, float* conf, void* stream) {
-    BE_REQUIRE(o && records, "be_fold_records_f32: null pointer");
-    BE_REQUIRE(hp > 0 && wp > 0 && H > 0 && W > 0 && stride > 0, "be_fold_records_f32: bad sizes");
-    BE_REQUIRE(stride * (hp - 1) + R <= H && stride * (wp - 1) + R <= W, "be_fold_records_f32: patch grid exceeds the image");
-    BE_REQUIRE(be::aligned16(records), "be_fold_records_f32: records must be 16-byte aligned");
-    FoldArgs a{records, hp, wp, H, W, stride, densify_w, image, shpd, refoc, bndry, depth, conf, 0, nullptr, nullptr};
-    hipLaunchKernelGGL(k_fold_records<false>, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, be::as_stream(stream), *o, a);
-    return be::check_launch("be_fold_records_f32");
+    const char* who = "be_fold_records_f32";
+    BE_REQUIRE(o && records, "%s: null pointer", who);
+    BE_REQUIRE(hp > 0 && wp > 0 && H > 0 && W > 0, "%s: bad sizes", who);
+    if (const int rc = check_fold_grid(who, hp, wp, H, W, stride, nullptr)) return rc;
+    BE_REQUIRE(be::aligned16(records), "%s: records must be 16-byte aligned", who);
+    const FoldArgs a{fold_grid(records, hp, wp, H, W, stride, nullptr, nullptr), densify_w, image, shpd, refoc, bndry, depth, conf, 0};
+    return launch_fold(who, k_fold_pixels<MapsAcc, false>, tile_grid(W, H), stream, *o, a);
 }
 
 extern "C" int be_fold_records_batch_f32(const be_render_opts* o, const float* records, int B, int hp, int wp, int H, int W,
                                          int stride, int densify_w, float* image, float* shpd, float* refoc, float* bndry,
                                          float* depth, float* conf, void* stream) {
-    BE_REQUIRE(o && records, "be_fold_records_batch_f32: null pointer");
-    BE_REQUIRE(B > 0 && B <= 65535 && hp > 0 && wp > 0 && H > 0 && W > 0 && stride > 0, "be_fold_records_batch_f32: bad sizes");
-    BE_REQUIRE(stride * (hp - 1) + R <= H && stride * (wp - 1) + R <= W, "be_fold_records_batch_f32: patch grid exceeds the image");
-    BE_REQUIRE(be::aligned16(records), "be_fold_records_batch_f32: records must be 16-byte aligned");
-    FoldArgs a{records, hp, wp, H, W, stride, densify_w, image, shpd, refoc, bndry, depth, conf, (int64_t)hp * wp * REC, nullptr, nullptr};
-    hipLaunchKernelGGL(k_fold_records<false>, dim3((W + 15) / 16, (H + 15) / 16, B), dim3(256), 0, be::as_stream(stream), *o, a);
-    return be::check_launch("be_fold_records_batch_f32");
+    const char* who = "be_fold_records_batch_f32";
+    BE_REQUIRE(o && records, "%s: null pointer", who);
+    BE_REQUIRE(B > 0 && B <= 65535 && hp > 0 && wp > 0 && H > 0 && W > 0, "%s: bad sizes", who);
+    if (const int rc = check_fold_grid(who, hp, wp, H, W, stride, nullptr)) return rc;
+    BE_REQUIRE(be::aligned16(records), "%s: records must be 16-byte aligned", who);
+    const FoldArgs a{fold_grid(records, hp, wp, H, W, stride, nullptr, nullptr), densify_w, image, shpd, refoc, bndry, depth, conf,
+                     (int64_t)hp * wp * REC};
+    return launch_fold(who, k_fold_pixels<MapsAcc, false>, tile_grid(W, H, B), stream, *o, a);
 }
 
 extern "C" int be_render_full_grid_f32(const be_render_opts* o, const be_depth_consts* dc, float rho_prime, int densify_w,
@@ -941,16 +705,14 @@ extern "C" int be_render_full_grid_f32(const be_render_opts* o, const be_depth_c
 extern "C" int be_fold_records_grid_f32(const be_render_opts* o, const float* records, int HP, int WP, int H, int W,
                                         const int32_t* ys, const int32_t* xs, int densify_w, float* image, float* shpd,
                                         float* refoc, float* bndry, float* depth, float* conf, void* stream) {
-    BE_REQUIRE(o && records && ys && xs, "be_fold_records_grid_f32: null pointer");
-    BE_REQUIRE(H >= R && W >= R, "be_fold_records_grid_f32: the image is smaller than one patch");
-    BE_REQUIRE(HP > 0 && WP > 0 && HP <= H - R + 1 && WP <= W - R + 1,
-               "be_fold_records_grid_f32: HP / WP must be in [1, H-20] / [1, W-20] (origins are distinct pixels)");
-    BE_REQUIRE((H + FOLD_TILE - 1) / FOLD_TILE <= 65535 && (int64_t)HP * WP <= 0x7fffffff, "be_fold_records_grid_f32: image too large");
-    BE_REQUIRE(be::aligned16(records), "be_fold_records_grid_f32: records must be 16-byte aligned");
-    FoldArgs a{records, HP, WP, H, W, 0, densify_w, image, shpd, refoc, bndry, depth, conf, 0, ys, xs};
-    hipLaunchKernelGGL(k_fold_records<true>, dim3((W + FOLD_TILE - 1) / FOLD_TILE, (H + FOLD_TILE - 1) / FOLD_TILE), dim3(256), 0,
-                       be::as_stream(stream), *o, a);
-    return be::check_launch("be_fold_records_grid_f32");
+    const char* who = "be_fold_records_grid_f32";
+    BE_REQUIRE(o && records && ys && xs, "%s: null pointer", who);
+    BE_REQUIRE(H >= R && W >= R, "%s: the image is smaller than one patch", who);
+    if (const int rc = check_fold_grid(who, HP, WP, H, W, 0, ys)) return rc;
+    BE_REQUIRE((H + FOLD_TILE - 1) / FOLD_TILE <= 65535 && (int64_t)HP * WP <= 0x7fffffff, "%s: image too large", who);
+    BE_REQUIRE(be::aligned16(records), "%s: records must be 16-byte aligned", who);
+    const FoldArgs a{fold_grid(records, HP, WP, H, W, 0, ys, xs), densify_w, image, shpd, refoc, bndry, depth, conf, 0};
+    return launch_fold(who, k_fold_pixels<MapsAcc, true>, tile_grid(W, H), stream, *o, a);
 }
 
 extern "C" int be_refocus_stack_chunk(void) { return FOLD_KC; }
@@ -958,29 +720,20 @@ extern "C" int be_refocus_stack_chunk(void) { return FOLD_KC; }
 extern "C" int be_fold_refocus_stack_f32(const be_render_opts* o, const be_depth_consts* dc, const float* records, int HP, int WP,
                                          int H, int W, int stride, const int32_t* ys, const int32_t* xs, const float* rho_primes,
                                          int K, float* out, void* stream) {
-    BE_REQUIRE(o && dc && records && rho_primes && out, "be_fold_refocus_stack_f32: null pointer");
-    BE_REQUIRE((ys == nullptr) == (xs == nullptr), "be_fold_refocus_stack_f32: ys and xs must both be given (origin tables) or both be null (uniform grid)");
-    BE_REQUIRE(K >= 1 && (K + FOLD_KC - 1) / FOLD_KC <= 65535, "be_fold_refocus_stack_f32: K must be in [1, 65535 * BE_REFOCUS_STACK_KC]");
-    BE_REQUIRE(HP > 0 && WP > 0 && H >= R && W >= R, "be_fold_refocus_stack_f32: bad sizes");
-    BE_REQUIRE((H + FOLD_TILE - 1) / FOLD_TILE <= 65535 && (int64_t)HP * WP <= 0x7fffffff, "be_fold_refocus_stack_f32: image too large");
-    BE_REQUIRE(be::aligned16(records), "be_fold_refocus_stack_f32: records must be 16-byte aligned");
-    const dim3 grid((W + FOLD_TILE - 1) / FOLD_TILE, (H + FOLD_TILE - 1) / FOLD_TILE, (K + FOLD_KC - 1) / FOLD_KC);
-    if (ys) {
-        BE_REQUIRE(HP <= H - R + 1 && WP <= W - R + 1,
-                   "be_fold_refocus_stack_f32: HP / WP must be in [1, H-20] / [1, W-20] (origins are distinct pixels)");
-        StackArgs a{records, rho_primes, out, HP, WP, H, W, 0, K, ys, xs};
-        hipLaunchKernelGGL(k_fold_refocus_stack<true>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a);
-    } else {
-        BE_REQUIRE(stride > 0, "be_fold_refocus_stack_f32: bad sizes");
-        BE_REQUIRE((int64_t)stride * (HP - 1) + R <= H && (int64_t)stride * (WP - 1) + R <= W,
-                   "be_fold_refocus_stack_f32: patch grid exceeds the image");
-        StackArgs a{records, rho_primes, out, HP, WP, H, W, stride, K, nullptr, nullptr};
-        hipLaunchKernelGGL(k_fold_refocus_stack<false>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a);
-    }
-    return be::check_launch("be_fold_refocus_stack_f32");
+    const char* who = "be_fold_refocus_stack_f32";
+    BE_REQUIRE(o && dc && records && rho_primes && out, "%s: null pointer", who);
+    BE_REQUIRE((ys == nullptr) == (xs == nullptr), "%s: ys and xs must both be given (origin tables) or both be null (uniform grid)", who);
+    BE_REQUIRE(K >= 1 && stack_chunks(K) <= 65535, "%s: K must be in [1, 65535 * BE_REFOCUS_STACK_KC]", who);
+    BE_REQUIRE(HP > 0 && WP > 0 && H >= R && W >= R, "%s: bad sizes", who);
+    BE_REQUIRE((H + FOLD_TILE - 1) / FOLD_TILE <= 65535 && (int64_t)HP * WP <= 0x7fffffff, "%s: image too large", who);
+    BE_REQUIRE(be::aligned16(records), "%s: records must be 16-byte aligned", who);
+    if (const int rc = check_fold_grid(who, HP, WP, H, W, stride, ys)) return rc;
+    const StackArgs a{fold_grid(records, HP, WP, H, W, stride, ys, xs), *dc, rho_primes, out, K};
+    return launch_fold(who, ys != nullptr, k_fold_pixels<StackAcc, true>, k_fold_pixels<StackAcc, false>,
+                       tile_grid(W, H, stack_chunks(K)), stream, *o, a);
 }
 
-// the host checks the two *_at entries share: the grid (uniform or tables), the scale and the window -> the lattice
+// the host checks the two lattice entries share: the grid (uniform or tables), the scale and the window -> the lattice
 static int check_lattice(const char* who, int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs, int scale,
                          int top, int left, int h, int w, Lattice* l) {
     BE_REQUIRE((ys == nullptr) == (xs == nullptr), "%s: ys and xs must both be given (origin tables) or both be null (uniform grid)", who);
@@ -990,12 +743,7 @@ static int check_lattice(const char* who, int HP, int WP, int H, int W, int stri
                "%s: image too large (HP * WP, H * scale and W * scale must fit 31 bits)", who);
     BE_REQUIRE(top >= 0 && left >= 0 && h >= 1 && w >= 1 && (int64_t)top + h <= H && (int64_t)left + w <= W,
                "%s: window (%d, %d, %d, %d) leaves the %d x %d image", who, top, left, h, w, H, W);
-    if (ys) {
-        BE_REQUIRE(HP <= H - R + 1 && WP <= W - R + 1, "%s: HP / WP must be in [1, H-20] / [1, W-20] (origins are distinct pixels)", who);
-    } else {
-        BE_REQUIRE(stride > 0, "%s: bad sizes", who);
-        BE_REQUIRE((int64_t)stride * (HP - 1) + R <= H && (int64_t)stride * (WP - 1) + R <= W, "%s: patch grid exceeds the image", who);
-    }
+    if (const int rc = check_fold_grid(who, HP, WP, H, W, stride, ys)) return rc;
     const int64_t Ho = (int64_t)(h - 1) * scale + 1, Wo = (int64_t)(w - 1) * scale + 1;
     BE_REQUIRE(Ho * Wo <= 0x7fffffff && (Ho + FOLD_TILE - 1) / FOLD_TILE <= 65535,
                "%s: lattice %lld x %lld too large (Ho * Wo must fit 31 bits, Ho <= 16 * 65535)", who, (long long)Ho, (long long)Wo);
@@ -1007,33 +755,31 @@ extern "C" int be_fold_records_at_f32(const be_render_opts* o, const float* reco
                                       const int32_t* ys, const int32_t* xs, int scale, int top, int left, int h, int w,
                                       int densify_w, float* image, float* shpd, float* refoc, float* bndry, float* depth,
                                       float* conf, void* stream) {
-    BE_REQUIRE(o && records, "be_fold_records_at_f32: null pointer");
-    BE_REQUIRE(be::aligned16(records), "be_fold_records_at_f32: records must be 16-byte aligned");
+    const char* who = "be_fold_records_at_f32";
+    BE_REQUIRE(o && records, "%s: null pointer", who);
+    BE_REQUIRE(be::aligned16(records), "%s: records must be 16-byte aligned", who);
     Lattice l;
-    if (const int rc = check_lattice("be_fold_records_at_f32", HP, WP, H, W, stride, ys, xs, scale, top, left, h, w, &l)) return rc;
-    FoldArgs a{records, HP, WP, H, W, ys ? 0 : stride, densify_w, image, shpd, refoc, bndry, depth, conf, 0, ys, xs};
-    const dim3 grid((l.Wo + FOLD_TILE - 1) / FOLD_TILE, (l.Ho + FOLD_TILE - 1) / FOLD_TILE);
-    if (ys) hipLaunchKernelGGL(k_fold_records_at<true>, grid, dim3(256), 0, be::as_stream(stream), *o, a, l);
-    else hipLaunchKernelGGL(k_fold_records_at<false>, grid, dim3(256), 0, be::as_stream(stream), *o, a, l);
-    return be::check_launch("be_fold_records_at_f32");
+    if (const int rc = check_lattice(who, HP, WP, H, W, stride, ys, xs, scale, top, left, h, w, &l)) return rc;
+    const FoldArgs a{fold_grid(records, HP, WP, H, W, stride, ys, xs), densify_w, image, shpd, refoc, bndry, depth, conf, 0};
+    return launch_fold(who, ys != nullptr, k_fold_lattice<MapsAcc, true>, k_fold_lattice<MapsAcc, false>, tile_grid(l.Wo, l.Ho), stream,
+                       *o, a, l);
 }
 
 extern "C" int be_fold_refocus_stack_at_f32(const be_render_opts* o, const be_depth_consts* dc, const float* records, int HP, int WP,
                                             int H, int W, int stride, const int32_t* ys, const int32_t* xs, int scale, int top,
                                             int left, int h, int w, const float* rho_primes, int K, float* out, void* stream) {
-    BE_REQUIRE(o && dc && records && rho_primes && out, "be_fold_refocus_stack_at_f32: null pointer");
-    BE_REQUIRE(be::aligned16(records), "be_fold_refocus_stack_at_f32: records must be 16-byte aligned");
-    BE_REQUIRE(K >= 1 && (K + FOLD_KC - 1) / FOLD_KC <= 65535, "be_fold_refocus_stack_at_f32: K must be in [1, 65535 * BE_REFOCUS_STACK_KC]");
+    const char* who = "be_fold_refocus_stack_at_f32";
+    BE_REQUIRE(o && dc && records && rho_primes && out, "%s: null pointer", who);
+    BE_REQUIRE(be::aligned16(records), "%s: records must be 16-byte aligned", who);
+    BE_REQUIRE(K >= 1 && stack_chunks(K) <= 65535, "%s: K must be in [1, 65535 * BE_REFOCUS_STACK_KC]", who);
     Lattice l;
-    if (const int rc = check_lattice("be_fold_refocus_stack_at_f32", HP, WP, H, W, stride, ys, xs, scale, top, left, h, w, &l)) return rc;
-    StackArgs a{records, rho_primes, out, HP, WP, H, W, ys ? 0 : stride, K, ys, xs};
-    const dim3 grid((l.Wo + FOLD_TILE - 1) / FOLD_TILE, (l.Ho + FOLD_TILE - 1) / FOLD_TILE, (K + FOLD_KC - 1) / FOLD_KC);
-    if (ys) hipLaunchKernelGGL(k_fold_refocus_stack_at<true>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a, l);
-    else hipLaunchKernelGGL(k_fold_refocus_stack_at<false>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a, l);
-    return be::check_launch("be_fold_refocus_stack_at_f32");
+    if (const int rc = check_lattice(who, HP, WP, H, W, stride, ys, xs, scale, top, left, h, w, &l)) return rc;
+    const StackArgs a{fold_grid(records, HP, WP, H, W, stride, ys, xs), *dc, rho_primes, out, K};
+    return launch_fold(who, ys != nullptr, k_fold_lattice<StackAcc, true>, k_fold_lattice<StackAcc, false>,
+                       tile_grid(l.Wo, l.Ho, stack_chunks(K)), stream, *o, a, l);
 }
 
-// the host checks the two *_points entries share: the grid (uniform or tables), the point list and its launch
+// the host checks the two point entries share: the grid (uniform or tables) and the point list
 constexpr int64_t POINTS_MAX = (int64_t)0x00ffffff * 256;      // workgroups * 256 threads stay below 2^32
 
 static int check_points(const char* who, int HP, int WP, int H, int W, int stride, const int32_t* ys, const int32_t* xs,
@@ -1044,43 +790,33 @@ static int check_points(const char* who, int HP, int WP, int H, int W, int strid
     BE_REQUIRE((int64_t)HP * WP <= 0x7fffffff && H <= (1 << 24) && W <= (1 << 24),
                "%s: image too large (HP * WP must fit 31 bits, H and W 24 bits: positions are float32)", who);
     BE_REQUIRE(N >= 1 && N <= POINTS_MAX, "%s: N must be in [1, %lld], got %lld", who, (long long)POINTS_MAX, (long long)N);
-    if (ys) {
-        BE_REQUIRE(HP <= H - R + 1 && WP <= W - R + 1, "%s: HP / WP must be in [1, H-20] / [1, W-20] (origins are distinct pixels)", who);
-    } else {
-        BE_REQUIRE(stride > 0, "%s: bad sizes", who);
-        BE_REQUIRE((int64_t)stride * (HP - 1) + R <= H && (int64_t)stride * (WP - 1) + R <= W, "%s: patch grid exceeds the image", who);
-    }
-    return BE_OK;
+    return check_fold_grid(who, HP, WP, H, W, stride, ys);
 }
 
 extern "C" int be_fold_records_points_f32(const be_render_opts* o, const float* records, int HP, int WP, int H, int W, int stride,
                                           const int32_t* ys, const int32_t* xs, const float* points, int64_t N, int densify_w,
                                           float* image, float* shpd, float* refoc, float* bndry, float* depth, float* conf,
                                           void* stream) {
-    BE_REQUIRE(o && records, "be_fold_records_points_f32: null pointer");
-    BE_REQUIRE(be::aligned16(records), "be_fold_records_points_f32: records must be 16-byte aligned");
-    if (const int rc = check_points("be_fold_records_points_f32", HP, WP, H, W, stride, ys, xs, points, N)) return rc;
-    FoldArgs a{records, HP, WP, H, W, ys ? 0 : stride, densify_w, image, shpd, refoc, bndry, depth, conf, 0, ys, xs};
-    const Points l{points, N};
-    const dim3 grid((unsigned)((N + 255) / 256));
-    if (ys) hipLaunchKernelGGL(k_fold_records_points<true>, grid, dim3(256), 0, be::as_stream(stream), *o, a, l);
-    else hipLaunchKernelGGL(k_fold_records_points<false>, grid, dim3(256), 0, be::as_stream(stream), *o, a, l);
-    return be::check_launch("be_fold_records_points_f32");
+    const char* who = "be_fold_records_points_f32";
+    BE_REQUIRE(o && records, "%s: null pointer", who);
+    BE_REQUIRE(be::aligned16(records), "%s: records must be 16-byte aligned", who);
+    if (const int rc = check_points(who, HP, WP, H, W, stride, ys, xs, points, N)) return rc;
+    const FoldArgs a{fold_grid(records, HP, WP, H, W, stride, ys, xs), densify_w, image, shpd, refoc, bndry, depth, conf, 0};
+    return launch_fold(who, ys != nullptr, k_fold_points<MapsAcc, true>, k_fold_points<MapsAcc, false>, dim3((unsigned)((N + 255) / 256)),
+                       stream, *o, a, Points{points, N});
 }
 
 extern "C" int be_fold_refocus_stack_points_f32(const be_render_opts* o, const be_depth_consts* dc, const float* records, int HP, int WP,
                                                 int H, int W, int stride, const int32_t* ys, const int32_t* xs, const float* points,
                                                 int64_t N, const float* rho_primes, int K, float* out, void* stream) {
-    BE_REQUIRE(o && dc && records && rho_primes && out, "be_fold_refocus_stack_points_f32: null pointer");
-    BE_REQUIRE(be::aligned16(records), "be_fold_refocus_stack_points_f32: records must be 16-byte aligned");
-    BE_REQUIRE(K >= 1 && (K + FOLD_KC - 1) / FOLD_KC <= 65535, "be_fold_refocus_stack_points_f32: K must be in [1, 65535 * BE_REFOCUS_STACK_KC]");
-    if (const int rc = check_points("be_fold_refocus_stack_points_f32", HP, WP, H, W, stride, ys, xs, points, N)) return rc;
-    StackArgs a{records, rho_primes, out, HP, WP, H, W, ys ? 0 : stride, K, ys, xs};
-    const Points l{points, N};
-    const dim3 grid((unsigned)((N + 255) / 256), (K + FOLD_KC - 1) / FOLD_KC);
-    if (ys) hipLaunchKernelGGL(k_fold_refocus_stack_points<true>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a, l);
-    else hipLaunchKernelGGL(k_fold_refocus_stack_points<false>, grid, dim3(256), 0, be::as_stream(stream), *o, *dc, a, l);
-    return be::check_launch("be_fold_refocus_stack_points_f32");
+    const char* who = "be_fold_refocus_stack_points_f32";
+    BE_REQUIRE(o && dc && records && rho_primes && out, "%s: null pointer", who);
+    BE_REQUIRE(be::aligned16(records), "%s: records must be 16-byte aligned", who);
+    BE_REQUIRE(K >= 1 && stack_chunks(K) <= 65535, "%s: K must be in [1, 65535 * BE_REFOCUS_STACK_KC]", who);
+    if (const int rc = check_points(who, HP, WP, H, W, stride, ys, xs, points, N)) return rc;
+    const StackArgs a{fold_grid(records, HP, WP, H, W, stride, ys, xs), *dc, rho_primes, out, K};
+    return launch_fold(who, ys != nullptr, k_fold_points<StackAcc, true>, k_fold_points<StackAcc, false>,
+                       dim3((unsigned)((N + 255) / 256), stack_chunks(K)), stream, *o, a, Points{points, N});
 }
 
 extern "C" int be_unfold_patches_f32(const float* img, float* out, int B, int C, int H, int W, int stride, void* stream) {

@@ -393,7 +393,73 @@ std::vector<Tensor> render_full(const Tensor& opts, const Tensor& consts, double
     return r;
 }
 
-// records [P,32] or [B,P,32] -> the maps named by `want` (bit 0 image, 1 shpd, 2 refoc, 3 bndry, 4 depth, 5 conf), in that order
+// ---- the record folds.  What the operators share: the maps a `want` mask names, the optional origin tables and the checks of
+// records / rho_primes / points.  Every message starts with the operator's name (`who`).
+
+// the maps named by `want` (bit 0 image, 1 shpd, 2 refoc, 3 bndry, 4 depth, 5 conf): [batch.., channels.., tail..] with channels
+// {2,3} (image; {6} when `flat`), {3} (shpd, refoc) or none (bndry, depth, conf); the others stay undefined (a null pointer)
+struct FoldMaps {
+    Tensor t[6];
+    FoldMaps(int64_t want, const Tensor& like, const std::vector<int64_t>& batch, const std::vector<int64_t>& tail, bool flat = false) {
+        const std::vector<int64_t> channels[6] = {flat ? std::vector<int64_t>{6} : std::vector<int64_t>{2, 3}, {3}, {3}, {}, {}, {}};
+        for (int i = 0; i < 6; ++i) {
+            if (!(want & (1 << i))) continue;
+            std::vector<int64_t> s(batch);
+            s.insert(s.end(), channels[i].begin(), channels[i].end());
+            s.insert(s.end(), tail.begin(), tail.end());
+            t[i] = at::empty(s, like.options());
+        }
+    }
+    float* operator[](int i) const { return t[i].defined() ? t[i].data_ptr<float>() : nullptr; }
+    std::vector<Tensor> list() const {                          // the requested maps, in bit order
+        std::vector<Tensor> r;
+        for (int i = 0; i < 6; ++i) if (t[i].defined()) r.push_back(t[i]);
+        return r;
+    }
+};
+
+// a patch grid given by origin tables (ys [HP], xs [WP]: int32 on the GPU) instead of one stride
+static const int32_t* origin_table(const Tensor& t, const std::string& what) {
+    TORCH_CHECK(t.is_cuda(), what, ": expected the origin table on the GPU; the HIP path has no CPU fallback");
+    TORCH_CHECK(t.dim() == 1 && t.numel() > 0 && t.scalar_type() == at::kInt && t.is_contiguous(), what, ": a contiguous int32 vector");
+    return t.data_ptr<int32_t>();
+}
+
+// ys / xs both given = origin tables, both absent = the uniform grid of `stride` (null pointers)
+struct OriginTables { const int32_t* ys = nullptr; const int32_t* xs = nullptr; };
+static OriginTables optional_tables(const std::string& who, const optional<Tensor>& ys, const optional<Tensor>& xs, int64_t hp, int64_t wp) {
+    OriginTables g;
+    if (ys.has_value()) {
+        g.ys = origin_table(*ys, who + "(ys)");
+        g.xs = origin_table(*xs, who + "(xs)");
+        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, who, ": ys [hp], xs [wp]");
+    }
+    return g;
+}
+
+// what the operators over an optional-table grid check first: the table pair, then the records
+static void check_grid_records(const std::string& who, const optional<Tensor>& ys, const optional<Tensor>& xs, const Tensor& records, int64_t hp,
+                               int64_t wp) {
+    TORCH_CHECK(ys.has_value() == xs.has_value(), who, ": ys and xs must both be given (origin tables) or both be None");
+    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS, who, ": records [hp*wp,32]");
+}
+static void check_rho_primes(const std::string& who, const Tensor& rho_primes, const Tensor& records) {
+    TORCH_CHECK(rho_primes.dim() == 1 && rho_primes.numel() > 0, who, ": rho_primes [K], K >= 1");
+    TORCH_CHECK(rho_primes.device() == records.device(), who, ": rho_primes and records on one device");
+}
+static void check_points(const std::string& who, const Tensor& points, const Tensor& records) {
+    TORCH_CHECK(points.dim() == 2 && points.size(1) == 2 && points.size(0) > 0, who, ": points [N,2], N >= 1");
+    TORCH_CHECK(points.device() == records.device(), who, ": points and records on one device");
+}
+static void check_lattice(const std::string& who, int64_t scale, int64_t h, int64_t w, int64_t H, int64_t W) {
+    TORCH_CHECK(scale >= 1 && scale <= BE_RENDER_AT_MAX_SCALE && h >= 1 && w >= 1 && h <= H && w <= W, who, ": bad scale or window");
+}
+static const be_render_opts* fold_opts(const std::string& who, const Tensor& opts) { return host_struct<be_render_opts>(opts, (who + "(opts)").c_str()); }
+static const be_depth_consts* fold_consts(const std::string& who, const Tensor& consts) {
+    return host_struct<be_depth_consts>(consts, (who + "(consts)").c_str());
+}
+
+// records [P,32] or [B,P,32] -> the maps named by `want`, in bit order
 std::vector<Tensor> fold_records(const Tensor& opts, const Tensor& records, int64_t hp, int64_t wp, int64_t H, int64_t W, int64_t stride,
                                  bool densify_w, int64_t want) {
     fp(records, "records");
@@ -401,34 +467,18 @@ std::vector<Tensor> fold_records(const Tensor& opts, const Tensor& records, int6
     TORCH_CHECK((batched || records.dim() == 2) && records.size(-1) == BE_RECORD_FLOATS && records.size(-2) == hp * wp,
                 "fold_records: records [P,32] or [B,P,32] with P = hp * wp");
     const int64_t B = batched ? records.size(0) : 1;
-    auto o = records.options();
-    auto shape = [&](std::vector<int64_t> s) { if (batched) s.insert(s.begin(), B); return s; };
-    Tensor t[6];
-    if (want & 1) t[0] = at::empty(shape({2, 3, H, W}), o);
-    if (want & 2) t[1] = at::empty(shape({3, H, W}), o);
-    if (want & 4) t[2] = at::empty(shape({3, H, W}), o);
-    if (want & 8) t[3] = at::empty(shape({H, W}), o);
-    if (want & 16) t[4] = at::empty(shape({H, W}), o);
-    if (want & 32) t[5] = at::empty(shape({H, W}), o);
-    auto f = [&](int i) { return t[i].defined() ? t[i].data_ptr<float>() : nullptr; };
-    const be_render_opts* ro = host_struct<be_render_opts>(opts, "fold_records(opts)");
+    const FoldMaps m(want, records, batched ? std::vector<int64_t>{B} : std::vector<int64_t>{}, {H, W});
+    const be_render_opts* ro = fold_opts("fold_records", opts);
     if (batched)
-        check(be_fold_records_batch_f32(ro, records.data_ptr<float>(), (int)B, (int)hp, (int)wp, (int)H, (int)W, (int)stride, densify_w ? 1 : 0, f(0),
-                                        f(1), f(2), f(3), f(4), f(5), stream_of(records)), "be_fold_records_batch_f32");
+        check(be_fold_records_batch_f32(ro, records.data_ptr<float>(), (int)B, (int)hp, (int)wp, (int)H, (int)W, (int)stride, densify_w ? 1 : 0, m[0],
+                                        m[1], m[2], m[3], m[4], m[5], stream_of(records)), "be_fold_records_batch_f32");
     else
-        check(be_fold_records_f32(ro, records.data_ptr<float>(), (int)hp, (int)wp, (int)H, (int)W, (int)stride, densify_w ? 1 : 0, f(0), f(1), f(2),
-                                  f(3), f(4), f(5), stream_of(records)), "be_fold_records_f32");
-    std::vector<Tensor> r;
-    for (int i = 0; i < 6; ++i) if (t[i].defined()) r.push_back(t[i]);
-    return r;
+        check(be_fold_records_f32(ro, records.data_ptr<float>(), (int)hp, (int)wp, (int)H, (int)W, (int)stride, densify_w ? 1 : 0, m[0], m[1], m[2],
+                                  m[3], m[4], m[5], stream_of(records)), "be_fold_records_f32");
+    return m.list();
 }
 
-// the two passes over a patch grid given by origin tables (ys [HP], xs [WP]: int32 on the GPU) instead of one stride
-static const int32_t* origin_table(const Tensor& t, const char* what) {
-    TORCH_CHECK(t.is_cuda(), what, ": expected the origin table on the GPU; the HIP path has no CPU fallback");
-    TORCH_CHECK(t.dim() == 1 && t.numel() > 0 && t.scalar_type() == at::kInt && t.is_contiguous(), what, ": a contiguous int32 vector");
-    return t.data_ptr<int32_t>();
-}
+// the two passes over a patch grid given by origin tables
 Tensor render_full_grid(const Tensor& opts, const Tensor& consts, double rho_prime, bool densify_w, const Tensor& params12,
                         const Tensor& img, const Tensor& ys, const Tensor& xs) {
     TORCH_CHECK(img.dim() == 4 && img.size(0) == 2 && img.size(1) == 3, "render_full_grid: img [2,3,H,W]");
@@ -448,166 +498,95 @@ std::vector<Tensor> fold_records_grid(const Tensor& opts, const Tensor& records,
     TORCH_CHECK(records.dim() == 2 && records.size(0) == HP * WP && records.size(1) == BE_RECORD_FLOATS,
                 "fold_records_grid: records [HP*WP,32]");
     fp(records, "records");
-    auto o = records.options();
-    Tensor t[6];
-    if (want & 1) t[0] = at::empty({2, 3, H, W}, o);
-    if (want & 2) t[1] = at::empty({3, H, W}, o);
-    if (want & 4) t[2] = at::empty({3, H, W}, o);
-    if (want & 8) t[3] = at::empty({H, W}, o);
-    if (want & 16) t[4] = at::empty({H, W}, o);
-    if (want & 32) t[5] = at::empty({H, W}, o);
-    auto f = [&](int i) { return t[i].defined() ? t[i].data_ptr<float>() : nullptr; };
-    check(be_fold_records_grid_f32(host_struct<be_render_opts>(opts, "fold_records_grid(opts)"), records.data_ptr<float>(), (int)HP, (int)WP,
-                                   (int)H, (int)W, origin_table(ys, "fold_records_grid(ys)"), origin_table(xs, "fold_records_grid(xs)"),
-                                   densify_w ? 1 : 0, f(0), f(1), f(2), f(3), f(4), f(5), stream_of(records)), "be_fold_records_grid_f32");
-    std::vector<Tensor> r;
-    for (int i = 0; i < 6; ++i) if (t[i].defined()) r.push_back(t[i]);
-    return r;
+    const FoldMaps m(want, records, {}, {H, W});
+    check(be_fold_records_grid_f32(fold_opts("fold_records_grid", opts), records.data_ptr<float>(), (int)HP, (int)WP, (int)H, (int)W,
+                                   origin_table(ys, "fold_records_grid(ys)"), origin_table(xs, "fold_records_grid(xs)"), densify_w ? 1 : 0,
+                                   m[0], m[1], m[2], m[3], m[4], m[5], stream_of(records)), "be_fold_records_grid_f32");
+    return m.list();
 }
 
-// focal stack: records [hp*wp,32] + rho_primes [K] (fp32 on the GPU) -> [K,3,H,W]; ys / xs both given = origin tables, both
-// absent = the uniform grid of `stride`
+// focal stack: records [hp*wp,32] + rho_primes [K] (fp32 on the GPU) -> [K,3,H,W]
 Tensor fold_refocus_stack(const Tensor& opts, const Tensor& consts, const Tensor& records, const Tensor& rho_primes,
                           const c10::optional<Tensor>& ys, const c10::optional<Tensor>& xs, int64_t hp, int64_t wp, int64_t H, int64_t W,
                           int64_t stride) {
-    TORCH_CHECK(ys.has_value() == xs.has_value(), "fold_refocus_stack: ys and xs must both be given (origin tables) or both be None");
-    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS,
-                "fold_refocus_stack: records [hp*wp,32]");
-    TORCH_CHECK(rho_primes.dim() == 1 && rho_primes.numel() > 0, "fold_refocus_stack: rho_primes [K], K >= 1");
-    TORCH_CHECK(rho_primes.device() == records.device(), "fold_refocus_stack: rho_primes and records on one device");
-    const int32_t *py = nullptr, *px = nullptr;
-    if (ys.has_value()) {
-        py = origin_table(*ys, "fold_refocus_stack(ys)");
-        px = origin_table(*xs, "fold_refocus_stack(xs)");
-        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, "fold_refocus_stack: ys [hp], xs [wp]");
-    }
+    const char* who = "fold_refocus_stack";
+    check_grid_records(who, ys, xs, records, hp, wp);
+    check_rho_primes(who, rho_primes, records);
+    const OriginTables g = optional_tables(who, ys, xs, hp, wp);
     const int64_t K = rho_primes.numel();
     fp(records, "records");
     Tensor out = at::empty({K, 3, H, W}, records.options());
-    check(be_fold_refocus_stack_f32(host_struct<be_render_opts>(opts, "fold_refocus_stack(opts)"),
-                                    host_struct<be_depth_consts>(consts, "fold_refocus_stack(consts)"), records.data_ptr<float>(), (int)hp,
-                                    (int)wp, (int)H, (int)W, (int)stride, py, px, fp(rho_primes, "rho_primes"), (int)K,
-                                    out.data_ptr<float>(), stream_of(records)), "be_fold_refocus_stack_f32");
+    check(be_fold_refocus_stack_f32(fold_opts(who, opts), fold_consts(who, consts), records.data_ptr<float>(), (int)hp, (int)wp, (int)H, (int)W,
+                                    (int)stride, g.ys, g.xs, fp(rho_primes, "rho_primes"), (int)K, out.data_ptr<float>(), stream_of(records)),
+          "be_fold_refocus_stack_f32");
     return out;
 }
 
-// the folds on a lattice `scale` times finer over the window (top, left, h, w): ys / xs both given = origin tables, both absent =
-// the uniform grid of `stride`; maps [..,Ho,Wo] named by `want` as fold_records
+// the folds on a lattice `scale` times finer over the window (top, left, h, w); maps [..,Ho,Wo]
 std::vector<Tensor> fold_records_at(const Tensor& opts, const Tensor& records, const c10::optional<Tensor>& ys, const c10::optional<Tensor>& xs,
                                     int64_t hp, int64_t wp, int64_t H, int64_t W, int64_t stride, int64_t scale, int64_t top, int64_t left,
                                     int64_t h, int64_t w, bool densify_w, int64_t want) {
-    TORCH_CHECK(ys.has_value() == xs.has_value(), "fold_records_at: ys and xs must both be given (origin tables) or both be None");
-    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS, "fold_records_at: records [hp*wp,32]");
-    TORCH_CHECK(scale >= 1 && scale <= BE_RENDER_AT_MAX_SCALE && h >= 1 && w >= 1 && h <= H && w <= W, "fold_records_at: bad scale or window");
-    const int32_t *py = nullptr, *px = nullptr;
-    if (ys.has_value()) {
-        py = origin_table(*ys, "fold_records_at(ys)");
-        px = origin_table(*xs, "fold_records_at(xs)");
-        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, "fold_records_at: ys [hp], xs [wp]");
-    }
+    const char* who = "fold_records_at";
+    check_grid_records(who, ys, xs, records, hp, wp);
+    check_lattice(who, scale, h, w, H, W);
+    const OriginTables g = optional_tables(who, ys, xs, hp, wp);
     fp(records, "records");
-    const int64_t Ho = (h - 1) * scale + 1, Wo = (w - 1) * scale + 1;
-    auto o = records.options();
-    Tensor t[6];
-    if (want & 1) t[0] = at::empty({2, 3, Ho, Wo}, o);
-    if (want & 2) t[1] = at::empty({3, Ho, Wo}, o);
-    if (want & 4) t[2] = at::empty({3, Ho, Wo}, o);
-    if (want & 8) t[3] = at::empty({Ho, Wo}, o);
-    if (want & 16) t[4] = at::empty({Ho, Wo}, o);
-    if (want & 32) t[5] = at::empty({Ho, Wo}, o);
-    auto f = [&](int i) { return t[i].defined() ? t[i].data_ptr<float>() : nullptr; };
-    check(be_fold_records_at_f32(host_struct<be_render_opts>(opts, "fold_records_at(opts)"), records.data_ptr<float>(), (int)hp, (int)wp, (int)H,
-                                 (int)W, (int)stride, py, px, (int)scale, (int)top, (int)left, (int)h, (int)w, densify_w ? 1 : 0, f(0), f(1),
-                                 f(2), f(3), f(4), f(5), stream_of(records)), "be_fold_records_at_f32");
-    std::vector<Tensor> r;
-    for (int i = 0; i < 6; ++i) if (t[i].defined()) r.push_back(t[i]);
-    return r;
+    const FoldMaps m(want, records, {}, {(h - 1) * scale + 1, (w - 1) * scale + 1});
+    check(be_fold_records_at_f32(fold_opts(who, opts), records.data_ptr<float>(), (int)hp, (int)wp, (int)H, (int)W, (int)stride, g.ys, g.xs,
+                                 (int)scale, (int)top, (int)left, (int)h, (int)w, densify_w ? 1 : 0, m[0], m[1], m[2], m[3], m[4], m[5],
+                                 stream_of(records)), "be_fold_records_at_f32");
+    return m.list();
 }
 
 Tensor fold_refocus_stack_at(const Tensor& opts, const Tensor& consts, const Tensor& records, const Tensor& rho_primes,
                              const c10::optional<Tensor>& ys, const c10::optional<Tensor>& xs, int64_t hp, int64_t wp, int64_t H, int64_t W,
                              int64_t stride, int64_t scale, int64_t top, int64_t left, int64_t h, int64_t w) {
-    TORCH_CHECK(ys.has_value() == xs.has_value(), "fold_refocus_stack_at: ys and xs must both be given (origin tables) or both be None");
-    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS,
-                "fold_refocus_stack_at: records [hp*wp,32]");
-    TORCH_CHECK(rho_primes.dim() == 1 && rho_primes.numel() > 0, "fold_refocus_stack_at: rho_primes [K], K >= 1");
-    TORCH_CHECK(rho_primes.device() == records.device(), "fold_refocus_stack_at: rho_primes and records on one device");
-    TORCH_CHECK(scale >= 1 && scale <= BE_RENDER_AT_MAX_SCALE && h >= 1 && w >= 1 && h <= H && w <= W, "fold_refocus_stack_at: bad scale or window");
-    const int32_t *py = nullptr, *px = nullptr;
-    if (ys.has_value()) {
-        py = origin_table(*ys, "fold_refocus_stack_at(ys)");
-        px = origin_table(*xs, "fold_refocus_stack_at(xs)");
-        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, "fold_refocus_stack_at: ys [hp], xs [wp]");
-    }
+    const char* who = "fold_refocus_stack_at";
+    check_grid_records(who, ys, xs, records, hp, wp);
+    check_rho_primes(who, rho_primes, records);
+    check_lattice(who, scale, h, w, H, W);
+    const OriginTables g = optional_tables(who, ys, xs, hp, wp);
     const int64_t K = rho_primes.numel();
     fp(records, "records");
     Tensor out = at::empty({K, 3, (h - 1) * scale + 1, (w - 1) * scale + 1}, records.options());
-    check(be_fold_refocus_stack_at_f32(host_struct<be_render_opts>(opts, "fold_refocus_stack_at(opts)"),
-                                       host_struct<be_depth_consts>(consts, "fold_refocus_stack_at(consts)"), records.data_ptr<float>(), (int)hp,
-                                       (int)wp, (int)H, (int)W, (int)stride, py, px, (int)scale, (int)top, (int)left, (int)h, (int)w,
-                                       fp(rho_primes, "rho_primes"), (int)K, out.data_ptr<float>(), stream_of(records)),
-          "be_fold_refocus_stack_at_f32");
+    check(be_fold_refocus_stack_at_f32(fold_opts(who, opts), fold_consts(who, consts), records.data_ptr<float>(), (int)hp, (int)wp, (int)H, (int)W,
+                                       (int)stride, g.ys, g.xs, (int)scale, (int)top, (int)left, (int)h, (int)w, fp(rho_primes, "rho_primes"),
+                                       (int)K, out.data_ptr<float>(), stream_of(records)), "be_fold_refocus_stack_at_f32");
     return out;
 }
 
 // the folds at arbitrary positions: points [N,2] (y, x) float32 on the records' device; maps channel-major over the points
-// ([6,N], [3,N], [N]) named by `want` as fold_records
+// ([6,N], [3,N], [N])
 std::vector<Tensor> fold_records_points(const Tensor& opts, const Tensor& records, const c10::optional<Tensor>& ys, const c10::optional<Tensor>& xs,
                                         int64_t hp, int64_t wp, int64_t H, int64_t W, int64_t stride, const Tensor& points, bool densify_w,
                                         int64_t want) {
-    TORCH_CHECK(ys.has_value() == xs.has_value(), "fold_records_points: ys and xs must both be given (origin tables) or both be None");
-    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS, "fold_records_points: records [hp*wp,32]");
-    TORCH_CHECK(points.dim() == 2 && points.size(1) == 2 && points.size(0) > 0, "fold_records_points: points [N,2], N >= 1");
-    TORCH_CHECK(points.device() == records.device(), "fold_records_points: points and records on one device");
-    const int32_t *py = nullptr, *px = nullptr;
-    if (ys.has_value()) {
-        py = origin_table(*ys, "fold_records_points(ys)");
-        px = origin_table(*xs, "fold_records_points(xs)");
-        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, "fold_records_points: ys [hp], xs [wp]");
-    }
+    const char* who = "fold_records_points";
+    check_grid_records(who, ys, xs, records, hp, wp);
+    check_points(who, points, records);
+    const OriginTables g = optional_tables(who, ys, xs, hp, wp);
     fp(records, "records");
     const int64_t N = points.size(0);
-    auto o = records.options();
-    Tensor t[6];
-    if (want & 1) t[0] = at::empty({6, N}, o);
-    if (want & 2) t[1] = at::empty({3, N}, o);
-    if (want & 4) t[2] = at::empty({3, N}, o);
-    if (want & 8) t[3] = at::empty({N}, o);
-    if (want & 16) t[4] = at::empty({N}, o);
-    if (want & 32) t[5] = at::empty({N}, o);
-    auto f = [&](int i) { return t[i].defined() ? t[i].data_ptr<float>() : nullptr; };
-    check(be_fold_records_points_f32(host_struct<be_render_opts>(opts, "fold_records_points(opts)"), records.data_ptr<float>(), (int)hp, (int)wp,
-                                     (int)H, (int)W, (int)stride, py, px, fp(points, "points"), N, densify_w ? 1 : 0, f(0), f(1), f(2), f(3),
-                                     f(4), f(5), stream_of(records)), "be_fold_records_points_f32");
-    std::vector<Tensor> r;
-    for (int i = 0; i < 6; ++i) if (t[i].defined()) r.push_back(t[i]);
-    return r;
+    const FoldMaps m(want, records, {}, {N}, true);
+    check(be_fold_records_points_f32(fold_opts(who, opts), records.data_ptr<float>(), (int)hp, (int)wp, (int)H, (int)W, (int)stride, g.ys, g.xs,
+                                     fp(points, "points"), N, densify_w ? 1 : 0, m[0], m[1], m[2], m[3], m[4], m[5], stream_of(records)),
+          "be_fold_records_points_f32");
+    return m.list();
 }
 
 Tensor fold_refocus_stack_points(const Tensor& opts, const Tensor& consts, const Tensor& records, const Tensor& rho_primes,
                                  const c10::optional<Tensor>& ys, const c10::optional<Tensor>& xs, int64_t hp, int64_t wp, int64_t H, int64_t W,
                                  int64_t stride, const Tensor& points) {
-    TORCH_CHECK(ys.has_value() == xs.has_value(), "fold_refocus_stack_points: ys and xs must both be given (origin tables) or both be None");
-    TORCH_CHECK(records.dim() == 2 && records.size(0) == hp * wp && records.size(1) == BE_RECORD_FLOATS,
-                "fold_refocus_stack_points: records [hp*wp,32]");
-    TORCH_CHECK(rho_primes.dim() == 1 && rho_primes.numel() > 0, "fold_refocus_stack_points: rho_primes [K], K >= 1");
-    TORCH_CHECK(rho_primes.device() == records.device(), "fold_refocus_stack_points: rho_primes and records on one device");
-    TORCH_CHECK(points.dim() == 2 && points.size(1) == 2 && points.size(0) > 0, "fold_refocus_stack_points: points [N,2], N >= 1");
-    TORCH_CHECK(points.device() == records.device(), "fold_refocus_stack_points: points and records on one device");
-    const int32_t *py = nullptr, *px = nullptr;
-    if (ys.has_value()) {
-        py = origin_table(*ys, "fold_refocus_stack_points(ys)");
-        px = origin_table(*xs, "fold_refocus_stack_points(xs)");
-        TORCH_CHECK(ys->numel() == hp && xs->numel() == wp, "fold_refocus_stack_points: ys [hp], xs [wp]");
-    }
+    const char* who = "fold_refocus_stack_points";
+    check_grid_records(who, ys, xs, records, hp, wp);
+    check_rho_primes(who, rho_primes, records);
+    check_points(who, points, records);
+    const OriginTables g = optional_tables(who, ys, xs, hp, wp);
     const int64_t K = rho_primes.numel(), N = points.size(0);
     fp(records, "records");
     Tensor out = at::empty({K, 3, N}, records.options());
-    check(be_fold_refocus_stack_points_f32(host_struct<be_render_opts>(opts, "fold_refocus_stack_points(opts)"),
-                                           host_struct<be_depth_consts>(consts, "fold_refocus_stack_points(consts)"), records.data_ptr<float>(),
-                                           (int)hp, (int)wp, (int)H, (int)W, (int)stride, py, px, fp(points, "points"), N,
-                                           fp(rho_primes, "rho_primes"), (int)K, out.data_ptr<float>(), stream_of(records)),
-          "be_fold_refocus_stack_points_f32");
+    check(be_fold_refocus_stack_points_f32(fold_opts(who, opts), fold_consts(who, consts), records.data_ptr<float>(), (int)hp, (int)wp, (int)H,
+                                           (int)W, (int)stride, g.ys, g.xs, fp(points, "points"), N, fp(rho_primes, "rho_primes"), (int)K,
+                                           out.data_ptr<float>(), stream_of(records)), "be_fold_refocus_stack_points_f32");
     return out;
 }
 

@@ -36,13 +36,13 @@ def test_lattice_sizes_and_checks():
 
 
 def _pixel_run_uniform(y, s, n):
-    """k_fold_records<false>: the run of grid lines covering integer pixel y."""
+    """The pixel fold on a uniform grid (k_fold_pixels<.., false>): the run of grid lines covering integer pixel y."""
     lo = (y - (R - 1) + s - 1) // s if y - (R - 1) >= 0 else 0
     return lo, min(y // s, n - 1)
 
 
 def _pixel_run_tables(y, lines):
-    """k_fold_records<true>: the same from an origin table."""
+    """The pixel fold with origin tables (k_fold_pixels<.., true>): the same from an origin table."""
     lo = 0
     while lo < len(lines) and lines[lo] < y - (R - 1):
         lo += 1

@@ -177,6 +177,34 @@ def test_windows_are_slices_of_the_full_lattice(env, binding, kind):
             assert _same_bits(_stack_at(env, sc, RHO[:3], k, (t, l, h, w)), full_stack[sl]), (k, (t, l, h, w))
 
 
+def test_lattice_sample_under_no_patch_is_zero_over_zero(env, binding):
+    """A uniform grid that stops short of the edge: 150 x 150 under the 64 x 64 stride-2 grid, which ends at pixel 146.  A lattice
+    sample in (146, 149] is inside the window and under no patch - the pixel fold's 0/0 - and every k-th sample of a window that
+    reaches the edge is still the pixel fold's, NaN bits included; the six maps and the stack (K = 9: a short last chunk)."""
+    n = env["native"]
+    sc = _scene(env, "g6", None)
+    opts, consts, rec, uni = sc["opts"], env["dcal"].consts, sc["rec"], dict(hp=64, wp=64, stride=2)
+    ref = n.fold_records(opts, rec, 64, 64, 150, 150, 2, False)
+    ref_stack = n.fold_refocus_stack(opts, consts, rec, RHO[:9], 150, 150, **uni)
+    assert torch.isnan(ref["bndry"][147:]).all() and torch.isnan(ref_stack[..., 147:, :]).all()
+    assert torch.isfinite(ref["bndry"][:147, :147]).all() and torch.isfinite(ref_stack[..., :147, :147]).all()
+    top, left, h, w = 131, 127, 19, 23
+    sl = (Ellipsis, slice(top, top + h), slice(left, left + w))
+    for k in (1, 3):
+        got = n.fold_records_at(opts, rec, 150, 150, scale=k, window=(top, left, h, w), **uni)
+        st = n.fold_refocus_stack_at(opts, consts, rec, RHO[:9], 150, 150, scale=k, window=(top, left, h, w), **uni)
+        for m in MAPS:
+            assert _same_bits(got[m][..., ::k, ::k], ref[m][sl]), (k, m)
+        assert _same_bits(st[..., ::k, ::k], ref_stack[sl]), k
+        ey, ex = (146 - top) * k, (146 - left) * k                      # the samples on pixel 146: the last ones under a patch
+        for m in ("image", "shpd", "refoc", "bndry", "conf"):
+            assert torch.isnan(got[m][..., ey + 1:, :]).all() and torch.isnan(got[m][..., :, ex + 1:]).all(), (k, m)
+            assert torch.isfinite(got[m][..., :ey + 1, :ex + 1]).all(), (k, m)
+        assert (got["depth"][ey + 1:] == 0).all() and (got["depth"][:, ex + 1:] == 0).all()     # depth divides by max(cntz, 1)
+        assert torch.isnan(st[..., ey + 1:, :]).all() and torch.isnan(st[..., :, ex + 1:]).all(), k
+        assert torch.isfinite(st[..., :ey + 1, :ex + 1]).all(), k
+
+
 # ------------------------------------------------------------------------------------------ 4. against float64
 @pytest.mark.parametrize("densify", [None, "w"])
 @pytest.mark.parametrize("kind,k", [("g6", 3), ("flush", 2)])

@@ -159,6 +159,20 @@ def test_point_under_no_patch_is_zero_over_zero(env, binding):
     assert (got["depth"][1:] == 0).all()                                # depth divides by max(cntz, 1)
 
 
+def test_stack_point_under_no_patch_is_zero_over_zero(env, binding):
+    """The same grid and points through the stack: a short last chunk (K = 9), the covered point equals the pixel stack bit for
+    bit, the points under no patch are its 0/0 - NaN bits included where the point is a pixel."""
+    n = env["native"]
+    sc = _scene(env, "g6", None)
+    pts = P(np.array([[146.0, 146.0], [146.5, 30.0], [30.0, 149.0], [149.0, 149.0]], np.float32))
+    st = n.fold_refocus_stack_points(sc["opts"], env["dcal"].consts, sc["rec"], RHO[:9], 150, 150, pts, hp=64, wp=64, stride=2)
+    ref = n.fold_refocus_stack(sc["opts"], env["dcal"].consts, sc["rec"], RHO[:9], 150, 150, hp=64, wp=64, stride=2)
+    assert st.shape == (9, 3, 4)
+    assert _same_bits(st[..., 0], ref[..., 146, 146]) and torch.isfinite(st[..., 0]).all()
+    assert torch.isnan(st[..., 1:]).all()
+    assert _same_bits(st[..., 2], ref[..., 30, 149]) and _same_bits(st[..., 3], ref[..., 149, 149])
+
+
 # ------------------------------------------------------------------------------------------ 5. stack consistency
 @pytest.mark.parametrize("kind", ["g6", "flush"])
 def test_stack_plane_equals_the_point_fold_of_records_rendered_at_that_power(env, binding, kind):
