@@ -111,6 +111,13 @@ _SIGNATURES = {
     "be_wino_conv3x3_pair_chain_6x6_f32": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int,
                                                      _P, C.c_size_t, _P, C.c_int, C.c_int]),
     "be_maxpool_wino_in_11x11_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "be_wino_ds_positions": (C.c_int, []),
+    "be_wino_ds_packed_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "be_wino_ds_pack_f32": (C.c_int, [_P] * 6 + [C.c_float, C.c_int, C.c_int, _P, _P, _P]),
+    "be_wino_pair_ds_workspace_floats": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "be_wino_conv3x3_pair_ds_6x6_f32": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                                  _P, C.c_size_t, _P, C.c_int, C.c_int]),
+    "be_wino_gemms_ext_f32": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "be_conv_fused2_packed_floats": (C.c_size_t, [C.c_int] * 4),
     "be_conv_pack_fused2_f32": (C.c_int, [_P] * 12 + [C.c_float] + [C.c_int] * 4 + [_P, _P, _P]),
     "be_conv_nhwc_fused2_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
@@ -849,6 +856,51 @@ def wino_conv3x3_pair_chain(x, pw1, pb1, cmid, pw2, pb2, cout, workspace, act1=1
     return y
 
 
+def wino_ds_pack(weight, bias=None, bn=None, eps=1e-5, with_bias=True):
+    """A block's 1x1 downsample weight [Cout,Cin] (or [Cout,Cin,1,1]; + bias, + eval BatchNorm) in the form conv2's Winograd GEMMs take
+    as their second K segment -> (packed_ds: U_ds [positions', cout_pad, cin] fp32, then its bf16 planes; folded bias [cout_pad])."""
+    cout, cin = weight.shape[0], weight.shape[1]
+    nfl = lib().be_wino_ds_packed_floats(cout, cin)
+    if nfl == 0 or weight.numel() != cout * cin:
+        raise RuntimeError(f"wino_ds_pack: unsupported shape {tuple(weight.shape)}")
+    dev = weight.device
+    pd = torch.empty(nfl, dtype=torch.float32, device=dev)
+    pb = torch.zeros((cout + 31) // 32 * 32, dtype=torch.float32, device=dev) if with_bias else None
+    g = bn if bn is not None else (None, None, None, None)
+    check(lib().be_wino_ds_pack_f32(dptr(weight.contiguous(), "weight"), dptr(bias), dptr(g[0]), dptr(g[1]), dptr(g[2]), dptr(g[3]), eps,
+                                    cout, cin, dptr(pd), dptr(pb), stream_ptr(dev)), "be_wino_ds_pack_f32")
+    return pd, pb
+
+
+def wino_conv3x3_pair_ds(x, pw1, pb1, cmid, pw2, pb2, pds, cout, act1=1, act2=1, workspace=None, x_in_v=False, next_cmid=0, cin=None,
+                         n=None, store_y=True):
+    """wino_conv3x3_pair_chain with the block's 1x1 downsample (pds: wino_ds_pack; its bias already in pb2) inside conv2's GEMMs instead
+    of a residual tensor.  x may be None with x_in_v (pass cin and n), and store_y=False with next_cmid leaves y unwritten (None).
+    -> (y, workspace)"""
+    if x is not None:
+        n, _, _, cin = x.shape
+    dev = pw1.device
+    need = lib().be_wino_pair_ds_workspace_floats(n, cin, cmid, cout)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=dev)
+    y = torch.empty(n, 6, 6, cout, dtype=torch.float32, device=dev) if store_y else None
+    check(lib().be_wino_conv3x3_pair_ds_6x6_f32(dptr(x), dptr(pw1), dptr(pb1), int(act1), dptr(pw2), dptr(pb2), dptr(pds), int(act2),
+                                                dptr(y), n, cin, cmid, cout, dptr(workspace), workspace.numel(), stream_ptr(dev),
+                                                int(bool(x_in_v)), int(next_cmid)), "be_wino_conv3x3_pair_ds_6x6_f32")
+    return y, workspace
+
+
+def wino_gemms_ext(v, pw, n, cin, cout, vx=None, pds=None, cin_ext=0, tile_major=False):
+    """The transform-domain GEMMs of one Winograd layer alone: v [positions, tiles, cin] (tile_major: [tiles, positions, cin]) ->
+    M likewise with cout channels; with vx / pds (wino_ds_pack) the second K segment over vx at pds's positions."""
+    npos = 5 * (lib().be_wino_tile_rows() + 2)
+    tiles = 12 // lib().be_wino_tile_rows() * n
+    m = torch.empty((tiles, npos, cout) if tile_major else (npos, tiles, cout), dtype=torch.float32, device=v.device)
+    check(lib().be_wino_gemms_ext_f32(dptr(v, "v"), dptr(pw), dptr(m), n, cin, cout, dptr(vx), dptr(pds), int(cin_ext), int(bool(tile_major)),
+                                      stream_ptr(v.device)), "be_wino_gemms_ext_f32")
+    return m
+
+
 def maxpool_wino_in(x, next_cmid, workspace):
     """x [N,11,11,C] NHWC -> its 3/2/1 max-pool [N,6,6,C] (maxpool_nhwc's bits); the pooled map's Winograd input transform for a block
     whose conv1 has next_cmid outputs is left at the start of `workspace` (head of a wino_conv3x3_pair_chain)."""
@@ -879,8 +931,8 @@ def local_stage_forward_view(packed, view, patches_per_image: int, n: int, devic
 KERNEL_NAMES = {0: "k_conv_igemm<2,2,2,2,TAPS> (128x128)", 1: "k_conv_igemm<4,1,1,3,TAPS> (128x96)",
                 2: "k_conv_igemm<4,1,1,2,TAPS> (128x64)", 3: "k_conv_igemm<4,1,1,1,TAPS> (128x32)",
                 4: "k_conv_igemm<4,1,1,2,ROW8> (conv1)", 5: "k_conv_igemm small-M tiles (64x64 / 128x32)",
-                6: "k_wino_gemm<0, 1> (128x128 tiles, the Winograd transform-domain GEMMs of a layer - one per position: 40 for the 8x5 tiles - per launch, in split-bf16 arithmetic: six v_mfma_f32_32x32x16_bf16 per product, FLOPs counted as fp32 products; BE_WINO_F32=1: the fp32 k_wino_gemm_ws / k_wino_gemm / batched k_conv_igemm)",
-                7: "row GEMMs: k_wino_gemm_ps<EPI> on pre-split weights (split-bf16 arithmetic, FLOPs counted as fp32 products: LocalStage's 1x1 downsamples and fc.1; BE_ROWS_F32=1 / BE_WINO_F32=1: fp32) and the fp32 k_wino_gemm<1> / k_wino_gemm_ws<.., 1> (1x1 convolutions / linears of large batches)",
+                6: "k_wino_gemm<0, 1> (128x128 tiles, the Winograd transform-domain GEMMs of a layer - one per position: 40 for the 8x5 tiles - per launch, in split-bf16 arithmetic: six v_mfma_f32_32x32x16_bf16 per product, FLOPs counted as fp32 products; in LocalStage conv2's launches carry the block's 1x1 downsample as a second K segment at 18 of the 40 positions, k_wino_gemm_ps<0, 0, 1>, unless BE_WINO_DS_GEMM=1; BE_WINO_F32=1: the fp32 k_wino_gemm_ws / k_wino_gemm / batched k_conv_igemm)",
+                7: "row GEMMs: k_wino_gemm_ps<EPI> on pre-split weights (split-bf16 arithmetic, FLOPs counted as fp32 products: fc.1, and LocalStage's 1x1 downsamples under BE_WINO_DS_GEMM=1; BE_ROWS_F32=1 / BE_WINO_F32=1: fp32) and the fp32 k_wino_gemm<1> / k_wino_gemm_ws<.., 1> (1x1 convolutions / linears of large batches)",
                 8: "k_wino_in / k_wino_out_in / k_wino_out / k_wino_out_pool2 / k_wino_out_res_in / k_pool_wino_in (Winograd transforms; the chained LocalStage runs k_pool_wino_in - the 3/2/1 max-pool with layer1's input transform - three k_wino_out_in, two k_wino_out_res_in and k_wino_out_pool2; BE_WINO_NO_CHAIN=1: k_maxpool_nhwc and a k_wino_in and k_wino_out per block)",
                 9: "k_maxpool_nhwc",
                 10: "k_render_colors (pass A)", 11: "conv1 input staging",

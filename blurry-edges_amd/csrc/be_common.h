@@ -102,7 +102,14 @@ bool c1_bf6_enabled();
 // next_cmid > 0: y's input transform for a following block (conv1 with next_cmid outputs) is left there (not with pool2)
 int wino_pair(const float* x, const float* packed_w1, const float* packed_bias1, int act1, const float* packed_w2,
               const float* packed_bias2, const float* residual, int act2, float* y, int64_t n, int cin, int cmid, int cout,
-              float* workspace, size_t workspace_floats, void* stream, int pool2, int x_in_v = 0, int next_cmid = 0);
+              float* workspace, size_t workspace_floats, void* stream, int pool2, int x_in_v = 0, int next_cmid = 0,
+              const float* packed_ds = nullptr);
+// packed_ds (be_wino_ds_pack_f32): the block's 1x1 downsample runs as a second K segment of conv2's GEMMs, no residual
+// tensor, three workspace regions (be_wino_pair_ds_workspace_floats); y may then be null with next_cmid > 0 (not stored).
+// wino_ds_fold_enabled(): LocalStage takes that form - false under BE_WINO_DS_GEMM=1, BE_WINO_F32=1, BE_WINO_BF6_R7=1, BE_ROWS_F32=1
+// (read once per process).  pool_wino_in: be_maxpool_wino_in_11x11_f32; pooled may be null (the pooled map is then not stored)
+bool wino_ds_fold_enabled();
+int pool_wino_in(const float* x, float* pooled, int64_t n, int c, int next_cmid, float* workspace, size_t workspace_floats, void* stream);
 // be_conv.hip: convolution / linear of a training unit (small M).  With scratch the K loop may be split: then the S raw slices
 // are LEFT in scratch as [S][M][ldp] (S > 1 reported, nothing written to y, bias / res not applied) for the caller's kernel to sum;
 // S == 1: y = conv + bias (+ res).

@@ -3,9 +3,12 @@
 //   384->256 @6^2 -> maxpool(2,2) -> flatten -> Linear 2304->1024 + BN1d + Smish -> Linear 1024->10
 // Activations are NHWC in a caller-provided workspace; the batch is walked in sub-batches (default 8192 patches,
 // measured best) so the workspace stays bounded whatever N is.  Per sub-batch: staging, conv1, 2-3 pools, layer0 as two direct
-// launches (conv1; conv2 with the downsample fused in), the second pool with layer1's input transform in it, layers 1-3 each as a
-// 1x1 downsample launch + the chained Winograd pair (40 GEMMs, output+input transform, 40 GEMMs, output transform - layers 1
-// and 2's with the next layer's input transform in it, layer3's with the 2x2 max-pool in it; be_wino.hip), fc.1, fc.4.
+// launches (conv1; conv2 with the downsample fused in), the second pool with layer1's input transform in it, layers 1-3 each as
+// the chained Winograd pair (40 GEMMs, output+input transform, 40 GEMMs - the 1x1 downsample a second K segment of 18 of them, over
+// the block's own input transform -, output transform - layers 1 and 2's with the next layer's input transform in it, layer3's with
+// the 2x2 max-pool in it; be_wino.hip), fc.1, fc.4: 21 launches.  BE_WINO_DS_GEMM=1 (read once per process; also BE_ROWS_F32=1,
+// BE_WINO_F32=1, BE_WINO_BF6_R7=1): the downsample as its own 1x1 launch in front of each pair, joined behind conv2's output transform
+// (24 launches; round 13's bits).
 // BE_WINO_NO_CHAIN=1 (read once per process): the unchained launches - k_maxpool_nhwc, and every layer from k_wino_in to
 // k_wino_out - with the same bits.  Sub-batches of 512 patches and more take the LDS-DMA kernels (be_conv_pm.hip for conv1 on a
 // row-padded staging and for layer0, the row GEMM of be_wino.hip for the 1x1s and fc.1); smaller ones k_conv_igemm - same
@@ -69,10 +72,15 @@ struct PackedLayout {
         for (int i : {1, 2}) {             // layer0's two pixel-major 3x3 matrices (conv2's with the downsample's columns) likewise
             sw_off[i] = o; o += be_conv3x3_pm_bf6_packed_floats(kLayers[i].cout, kLayers[i].cin, i == 2 ? kLayers[3].cin : 0);
         }
+        for (int i = 0; i < 15; ++i) xw_off[i] = 0;
+        for (int i : {6, 9, 12}) {         // the downsamples of layers 1-3 as conv2's second K segment (be_wino_ds_pack_f32; behind all else)
+            xw_off[i] = o; o += be_wino_ds_packed_floats(kLayers[i].cout, kLayers[i].cin);
+        }
         total = o;
     }
     size_t zero_off;
     size_t sw_off[15];
+    size_t xw_off[15];
 };
 const PackedLayout& layout() { static PackedLayout l; return l; }
 
@@ -81,7 +89,8 @@ const PackedLayout& layout() { static PackedLayout l; return l; }
 constexpr size_t RA = 28224, RB = 13824, RC = 13824;
 // Winograd path: RW = transform-domain input + output of the widest layer (room for 100 values per channel: 25 positions x 4 tiles; the 8x5 tiles use 80,
 // 384 + 384 channels), RR = the block's downsample branch [6,6,384]
-constexpr size_t RW = 100 * (384 + 384), RR = 13824;
+// (round 14: a block that folds its downsample into conv2's GEMMs keeps three transform-domain buffers, be_wino_pair_ds_workspace_floats)
+constexpr size_t RW = 100 * (384 + 384 + 384), RR = 13824;
 constexpr size_t WS_FLOATS_PER_PATCH = RA + RB + RC + RW + RR;
 constexpr int kDefaultChunk = 8192;   // measured: 8192 > 4096 > 2048 (fewer partial rounds of the 512 resident blocks)
 inline int chunk_of(int chunk) { return chunk > 0 ? chunk : kDefaultChunk; }
@@ -145,6 +154,11 @@ extern "C" int be_local_stage_pack_f32(const float* const* t, float bn_eps, floa
         const float* src = packed + (i == 13 ? L.w_off[13] : L.dw_off[i]);
         if ((rc = be_gemm_rows_bf6_pack_f32(src, kLayers[i].cout, kLayers[i].cin, packed + L.sw_off[i], stream))) return rc;
     }
+    for (int i : {6, 9, 12}) {                        // the same downsamples in the transform domain: conv2's second K segment
+        const float* const* e = t + 6 * i;
+        if ((rc = be_wino_ds_pack_f32(e[0], e[1], e[2], e[3], e[4], e[5], bn_eps, kLayers[i].cout, kLayers[i].cin, packed + L.xw_off[i],
+                                      nullptr, stream))) return rc;
+    }
     for (int i : {1, 2}) {                            // layer0: K order of the packed matrices = the pixel-major K walk
         if ((rc = be_conv3x3_pm_bf6_pack_f32(packed + L.w_off[i], kLayers[i].cout, kLayers[i].cin, i == 2 ? kLayers[3].cin : 0,
                                              packed + L.sw_off[i], stream))) return rc;
@@ -189,11 +203,21 @@ int block_l0_bf6(const float* packed, const float* x, float* t, float* o, int n,
 // The same block on a 6x6 map with both 3x3 convolutions in Winograd F(3x3,3x3) form (be_wino.hip): 2.56x fewer multiplies
 // than the direct form; the 1x1 downsample runs as its own convolution into `r` and joins in the output transform of conv2.
 // x_in_v / next_cmid: the block as a link of the chain (be::wino_pair): x's transform is already in `w` / the next block's is left there
+// Default (round 14, be::wino_ds_fold_enabled): no `r` at all - the downsample is a second K segment of conv2's GEMMs over x's
+// transform (be::wino_pair's ds_planes).  x may then be null with x_in_v and o with next_cmid (a chained block reads and writes
+// transforms only).  BE_WINO_DS_GEMM=1 and the fp32 / round-7 arms keep the separate launch below.
 int block_wino(const float* packed, int l0, const float* x, float* t, float* o, float* r, float* w, int n, void* stream, int pool2 = 0,
                int x_in_v = 0, int next_cmid = 0) {
     const PackedLayout& L = layout();
     const int c = kLayers[l0].cout;
     (void)t;                                          // conv1's 6x6 result only ever exists in registers (k_wino_out_in)
+    if (be::wino_ds_fold_enabled()) {
+        const bool bare = x_in_v && next_cmid > 0;    // nothing reads the block's output map
+        return be::wino_pair(x_in_v ? nullptr : x, packed + L.uw_off[l0], packed + L.ub_off[l0], 1, packed + L.uw_off[l0 + 1],
+                             packed + L.ub_off[l0 + 1], nullptr, 1, bare ? nullptr : o, n, kLayers[l0].cin, c, c, w, (size_t)n * RW, stream,
+                             pool2, x_in_v, next_cmid,
+                             packed + L.xw_off[l0 + 2]);
+    }
     // the 1x1 downsample, bias-free (its bias sits in conv2's, see be_local_stage_pack_f32), raw accumulators: the split-bf16 row
     // GEMM at every batch size.  fp32 arm (BE_ROWS_F32=1 / BE_WINO_F32=1): large sub-batches on the weight-stationary GEMM
     // (128 TFLOP/s where the row GEMM does 92-119), others on the general kernel with a zero bias
@@ -284,11 +308,14 @@ int forward_impl(const float* packed, const float* x, const be_patch_view* view,
         float* p2 = rb;                                   // nb*3456
         // Winograd path, at every sub-batch size: the blocks are chained through the start of RW.  The pool leaves layer1's input
         // transform there, layers 1 and 2 end in the kernel that also writes the next layer's, so no block reads its input map a
-        // second time (the 1x1 downsample still does, hence the maps are written as before).  Lifetimes in RW: a block's V and M are
-        // dead once its last GEMMs ran, except M, which the boundary kernel reads while it writes the next V below M's start.
+        // second time.  Lifetimes in RW: a block's V and M are
+        // dead once its last GEMMs ran, except M, which the boundary kernel reads while it writes the next V below M's start.  With the
+        // downsamples folded into conv2's GEMMs (the default) x's transform stays alive beside conv1's (three regions) and nothing
+        // reads the maps themselves; under BE_WINO_DS_GEMM=1 the 1x1 downsample launch reads them, and they are written.
         static const bool no_chain = getenv("BE_WINO_NO_CHAIN") != nullptr && atoi(getenv("BE_WINO_NO_CHAIN")) != 0;   // A/B knob
         const int chain = wino && !no_chain;
-        if (chain) rc = be_maxpool_wino_in_11x11_f32(rc_, p2, nb, 96, kLayers[4].cout, rw, (size_t)nb * RW, stream);
+        // (with the downsamples folded into conv2's GEMMs nothing reads the pooled map or the maps between the blocks: not stored)
+        if (chain) rc = be::pool_wino_in(rc_, be::wino_ds_fold_enabled() ? nullptr : p2, nb, 96, kLayers[4].cout, rw, (size_t)nb * RW, stream);
         else rc = be_maxpool_nhwc_f32(rc_, p2, nb, 11, 11, 96, 3, 2, 1, stream);
         if (rc) return rc;
         // layer1: in RB, t RA, out RC

@@ -31,6 +31,12 @@
 //   written by whatever produced its input map, out of the registers that hold the map, so no block reads its input a second time:
 //   k_wino_out_res_in  k_wino_out (+ bias, residual, activation, y stored) + the NEXT block's input transform
 //   k_pool_wino_in     max-pool 3/2/1 of [N,11,11,C] (k_maxpool_nhwc's bits) + the input transform of the pooled map
+//   The downsample folded (round 14; be::wino_pair's packed_ds, be_wino_conv3x3_pair_ds_6x6_f32): a block's 1x1 downsample is a 3x3
+//   with only the centre tap, whose kernel transform is non-zero at (NR - 2) x 3 = 18 of the 40 positions; there conv2's GEMMs run a
+//   second K segment over the block's own input transform (k_wino_gemm_ps<0, 0, 1>: M2 = V_h U2^T + V_x U_ds^T - the direct 1x1's
+//   multiply count), so the residual tensor [N,6,6,Cout] is neither computed by a row GEMM, nor written, nor read back behind the
+//   output transform, and in a chain neither the maps between the blocks nor the pooled map are stored (STORE_Y / STORE_P = 0).
+//   k_wino_pack<1> + k_wino_pack_split   the 1x1 kernel through the 3x3 pack's arithmetic: U_ds at its 18 positions, and its planes
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -51,6 +57,22 @@ inline unsigned grid_cap(int64_t total, int block, int64_t limit = 65535) {
     return (unsigned)(g < 1 ? 1 : (g > limit ? limit : g));
 }
 
+// A 1x1 convolution is a 3x3 with only the centre tap, and the middle column of G is zero at the points 0 and inf: its kernel
+// transform lives on the (NR - 2) x 3 positions z = 5 zr + zc with 0 < zr < NR - 1, 0 < zc < 4 (18 of the 40) - the positions at
+// which conv2's GEMMs take a block's 1x1 downsample as a second K segment (round 14).  Live position z is number wino_ds_index(z).
+constexpr int NLIVE = (NR - 2) * 3;
+constexpr bool wino_ds_live(int z) { return z / 5 > 0 && z / 5 < NR - 1 && z % 5 > 0 && z % 5 < 4; }
+constexpr int wino_ds_index(int z) { return 3 * (z / 5 - 1) + z % 5 - 1; }
+constexpr uint64_t wino_ds_mask() {
+    uint64_t m = 0;
+    for (int z = 0; z < NPOS; ++z)
+        if (wino_ds_live(z)) m |= (uint64_t)1 << z;
+    return m;
+}
+
+// DS = 1: w is a 1x1 kernel [Cout,Cin], taken as the centre tap of a 3x3 through the same arithmetic (the dead positions come out
+// as exact zeros and are not stored): U [NLIVE][Cout_pad][Cin]
+template <int DS>
 __global__ void k_wino_pack(const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ gamma,
                             const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ var,
                             float eps, int cout, int cin, int cout_pad, float* __restrict__ U, float* __restrict__ bias) {
@@ -61,12 +83,13 @@ __global__ void k_wino_pack(const float* __restrict__ w, const float* __restrict
         float u[NR][5];
         if (co < cout) {
             const float scale = gamma ? gamma[co] / sqrtf(var[co] + eps) : 1.0f;
-            const float* g = w + ((size_t)co * cin + ci) * 9;
+            const float* g = w + ((size_t)co * cin + ci) * (DS ? 1 : 9);
             float t[NR][3];                                 // G_rows g: the kernel's three rows -> NR transform rows, column by column
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 float col[NR];
-                be::wino_g_rows(g[c] * scale, g[3 + c] * scale, g[6 + c] * scale, col);
+                if constexpr (DS) be::wino_g_rows(0.0f, c == 1 ? g[0] * scale : 0.0f, 0.0f, col);     // the centre tap alone
+                else be::wino_g_rows(g[c] * scale, g[3 + c] * scale, g[6 + c] * scale, col);
 #pragma unroll
                 for (int r = 0; r < NR; ++r) t[r][c] = col[r];
             }
@@ -81,8 +104,15 @@ __global__ void k_wino_pack(const float* __restrict__ w, const float* __restrict
 #pragma unroll
         for (int r = 0; r < NR; ++r)
 #pragma unroll
-            for (int c = 0; c < 5; ++c) U[(size_t)(5 * r + c) * total + idx] = u[r][c];
+            for (int c = 0; c < 5; ++c) {
+                if constexpr (DS) {
+                    if (wino_ds_live(5 * r + c)) U[(size_t)wino_ds_index(5 * r + c) * total + idx] = u[r][c];
+                } else {
+                    U[(size_t)(5 * r + c) * total + idx] = u[r][c];
+                }
+            }
     }
+    if (DS && !bias) return;                                // (the folded bias of a block's downsample is kept elsewhere)
     for (int64_t co = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; co < cout_pad; co += gs) {
         float v = 0.0f;
         if (co < cout) {
@@ -260,7 +290,8 @@ void k_wino_out_in(const float* __restrict__ M, const float* __restrict__ bias, 
 // Compiler report (gfx950, NT = 1, hipcc -Rpass-analysis=kernel-resource-usage): 205 VGPRs, 0 AGPRs, scratch 0, no VGPR spills,
 // 189 SGPR spills (to VGPR lanes: the addresses), two waves per SIMD - as k_wino_out_pool2 (256 VGPRs, 274 SGPR spills, two waves)
 // and k_wino_out_in (172 VGPRs, 622 SGPR spills, two waves).
-template <int NT, int VW = VW_OUT>
+// STORE_Y = 0 (round 14, a chained block whose successor folds its downsample into conv2's GEMMs): nothing reads y, it is not stored.
+template <int NT, int VW = VW_OUT, int STORE_Y = 1>
 __global__ __launch_bounds__(256, VW_OUT == 2 ? 2 : 1)
 void k_wino_out_res_in(const float* __restrict__ M, const float* __restrict__ bias, const float* __restrict__ res,
                        float* __restrict__ y, float* __restrict__ V, int64_t n, int c4, int act, int tm_in, int tm_out) {
@@ -298,7 +329,8 @@ void k_wino_out_res_in(const float* __restrict__ M, const float* __restrict__ bi
                         if (res) w += rv[3 * r + c];
                         w = wino_act(w, act);
                         v[TH * ty + r][3 * tx + c] = w;
-                        st_s<NT>(reinterpret_cast<vec*>(y) + ((size_t)img * 36 + (TH * ty + r) * 6 + 3 * tx + c) * c4 + cq, w);
+                        if constexpr (STORE_Y)
+                            st_s<NT>(reinterpret_cast<vec*>(y) + ((size_t)img * 36 + (TH * ty + r) * 6 + 3 * tx + c) * c4 + cq, w);
                     }
             }
         wino_in_map<NT>(v, reinterpret_cast<vec*>(V) + img * TPI * ts_o + cq, ts_o, plane_o);
@@ -312,7 +344,8 @@ void k_wino_out_res_in(const float* __restrict__ M, const float* __restrict__ bi
 // a tap outside the map replaced by the nearest one inside (taken twice) - so signed zeros, infinities and dropped NaNs come out
 // as there.  Every input byte is read once, so the loads stream (NT) like the other transforms'.
 // Compiler report (gfx950, NT = 1): 126 VGPRs, 0 AGPRs, scratch 0, no VGPR spills, 90 SGPR spills, four waves per SIMD.
-template <int NT, int VW = VW_OUT>
+// STORE_P = 0 (round 14): the pooled map is not stored (layer1 folds its downsample into conv2's GEMMs: nothing reads it).
+template <int NT, int VW = VW_OUT, int STORE_P = 1>
 __global__ __launch_bounds__(256, VW_OUT == 2 ? 2 : 1)
 void k_pool_wino_in(const float* __restrict__ x, float* __restrict__ pooled, float* __restrict__ V, int64_t n, int c4, int tm_out) {
     typedef typename VecOf<VW>::type vec;
@@ -345,7 +378,7 @@ void k_pool_wino_in(const float* __restrict__ x, float* __restrict__ pooled, flo
                         for (int k = 0; k < VW; ++k) m[k] = fmaxf(m[k], row[dy][xx][k]);
                     }
                 p[oy][ox] = m;
-                st_s<NT>(reinterpret_cast<vec*>(pooled) + ((size_t)img * 36 + oy * 6 + ox) * c4 + cq, m);
+                if constexpr (STORE_P) st_s<NT>(reinterpret_cast<vec*>(pooled) + ((size_t)img * 36 + oy * 6 + ox) * c4 + cq, m);
             }
         }
         wino_in_map<NT>(p, reinterpret_cast<vec*>(V) + img * TPI * ts_o + cq, ts_o, plane_o);
@@ -441,6 +474,14 @@ struct GemmArgs {
     int act;
     int zgroups;          // BF6: problem groups (one workgroup per M tile x N tile x group)
     int npad;             // BF6: rows of w that exist (Npad; B rows past it load row 0 of the tile and are never stored)
+    // k_wino_gemm_ps<0, 0, 1> (round 14): a second K segment at the positions of the mask zext - problem z accumulates x[z] w[z]^T
+    // over K and then, where bit z is set, x2[z] w2[e]^T over 16 kext more (e: the number of set bits below z), into one accumulator.
+    const float* x2;      // rows [M][16 kext] at x2 + z * xb2, lda2 floats between rows
+    const float* w2;      // the planes of the extended positions only, wb2 floats per position
+    int64_t xb2, wb2;
+    int lda2, kext;
+    uint64_t zext;
+    uint64_t ztab[4];     // the walk: group g takes the positions number g zper .. of this table, 6 bits each, ten to a word
 };
 
 // ---- split-bf16 operands (BF6 = 1) --------------------------------------------------------------------------------------------
@@ -702,7 +743,20 @@ void k_wino_gemm(GemmArgs a) {
 //   <0, 1>  210 VGPRs [140], 0 AGPRs, scratch 0, no VGPR spills,  15 SGPR spills [71],  15.3 KB [10.9]
 //   <1, 1>  the one-set loop: 182 VGPRs [150], 0 AGPRs, scratch 0, no VGPR spills, 26 SGPR spills [84], 41.7 KB [43.8].  With the
 //           two-set loop and the boundary block (Smish epilogue) behind both bodies it was 222 VGPRs and 80.0 KB, and slower.
-template <int EPI, int ROWS = 0>
+// Round 14, EXT = 1 (<0, 0, 1>): a second K segment.  A problem whose position is in GemmArgs::zext runs kext chunks more, A from
+// x2 (the transform of the block's input), B from w2 (the planes of the 1x1 downsample's kernel transform), into the same
+// accumulators: the block's residual branch inside conv2's GEMMs.  Only the DMA's source addresses and the chunk count a problem
+// ends at change (scalar work); a chunk is 2 A + 3 B pieces per wave whichever segment it is from, so the ring, the counted waits
+// ("all but the newest chunk have landed"), the two register sets and the boundary block are the ones above, across the seam and
+// across problems of unequal length.  K order per output element: x's chunks ascending, then x2's, from a zero accumulator - bits
+// depend on neither batch, group count nor stream.  The groups' problems come from a walk table (GemmArgs::ztab) in which the host
+// deals the dearer positions evenly.  A template parameter and not a run-time branch: the three instantiations without it are the
+// parent's instruction for instruction (hipcc -S compared).  Emitted loop of <0, 0, 1>: per body the same 24 MFMAs, 10 ds_read_b128 and
+// 5 global_load_lds_dwordx4 with the same gaps (no gap between two MFMAs of a chunk longer than 12 instructions, as <0, 0>); the
+// additions are scalar (5 s_bcnt1_i32_b64, the table look-ups) in the DMA block and the boundary block.
+//   <0, 0, 1>  180 VGPRs, 0 AGPRs, scratch 0, no VGPR spills, 94 SGPR spills, 21.5 KB of code, two workgroups per CU
+//              (with the segment chosen by selects per piece instead of one branch: 181 VGPRs and 12 B of scratch - not kept)
+template <int EPI, int ROWS = 0, int EXT = 0>
 __global__ __launch_bounds__(256, 2)
 void k_wino_gemm_ps(GemmArgs a) {
     constexpr int BM = 128, BKT = 16;
@@ -717,7 +771,21 @@ void k_wino_gemm_ps(GemmArgs a) {
     const int zg = m_tile % a.zgroups, zper = (a.nb + a.zgroups - 1) / a.zgroups;
     m_tile /= a.zgroups;
     if (m_tile >= a.m_tiles || zg * zper >= a.nb) return;
-    const int nb = min(zper, a.nb - zg * zper), kchunks = a.K / BKT, total = kchunks * nb;
+    const int nb = min(zper, a.nb - zg * zper), kchunks = a.K / BKT, total0 = kchunks * nb;
+    // EXT: the group's problems are entries zg zper .. of the walk table, and a problem in the mask runs kext chunks more
+    [[maybe_unused]] const int zbase = zg * zper;
+    [[maybe_unused]] auto zpos = [&](int i) -> int {
+        const int q = i / 10;
+        const uint64_t t = q == 0 ? a.ztab[0] : q == 1 ? a.ztab[1] : q == 2 ? a.ztab[2] : a.ztab[3];
+        return (int)((t >> (6 * (i - 10 * q))) & 63);
+    };
+    [[maybe_unused]] auto zchunks = [&](int pos) -> int { return kchunks + ((a.zext >> pos) & 1 ? a.kext : 0); };
+    [[maybe_unused]] auto ext_chunks = [&]() -> int {
+        int t = 0;
+        for (int i = 0; i < nb; ++i) t += zchunks(zpos(zbase + i)) - kchunks;
+        return t;
+    };
+    const int total = EXT ? total0 + ext_chunks() : total0;
     const int n0 = n_tile * 128, row_base = m_tile * (ROWS ? a.mrows : BM);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -731,10 +799,23 @@ void k_wino_gemm_ps(GemmArgs a) {
         const int r = (2 * wave + p) * 16 + srow;
         a_off[p] = (unsigned)((row_base + r < a.M ? r : 0) * a.lda + 4 * sq) * 4u;     // rows past M load a valid row, never stored
     }
-    const char* xt = reinterpret_cast<const char*>(a.x + (int64_t)zg * zper * a.xb + (int64_t)row_base * a.lda);
+    const char* xt = reinterpret_cast<const char*>(a.x + (EXT ? (int64_t)0 : (int64_t)zg * zper * a.xb) + (int64_t)row_base * a.lda);   // (EXT: positions from the table)
     // B: pieces 3w .. 3w+2 of the chunk's 12-KB block, which is already the LDS image (lane-linear: this lane's 16 B)
-    const char* wt = reinterpret_cast<const char*>(a.w + (int64_t)zg * zper * a.wb) + (int64_t)n_tile * kchunks * BBYTES + lane * 16;
-    float* const yg = a.y + (int64_t)zg * zper * a.yb;
+    const char* wt = reinterpret_cast<const char*>(a.w + (EXT ? (int64_t)0 : (int64_t)zg * zper * a.wb)) + (int64_t)n_tile * kchunks * BBYTES + lane * 16;
+    float* const yg = a.y + (EXT ? (int64_t)0 : (int64_t)zg * zper * a.yb);
+    // EXT: the second segment's operands - A rows of x2 (its own row stride), B blocks of w2
+    [[maybe_unused]] unsigned a_off2[2] = {0u, 0u};
+    [[maybe_unused]] const char* x2t = nullptr;
+    [[maybe_unused]] const char* w2t = nullptr;
+    if constexpr (EXT) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int r = (2 * wave + p) * 16 + srow;
+            a_off2[p] = (unsigned)((row_base + r < a.M ? r : 0) * a.lda2 + 4 * sq) * 4u;
+        }
+        x2t = reinterpret_cast<const char*>(a.x2 + (int64_t)row_base * a.lda2);
+        w2t = reinterpret_cast<const char*>(a.w2) + (int64_t)n_tile * a.kext * BBYTES + lane * 16;
+    }
     // fragment reads: A row 64 wm + 32 i + li, quads 2 lh, 2 lh + 1 (swizzled as stored); B plane p, row 64 wn + 32 j + li, half lh
     const int fsw = (li >> 2) & 3;
     const int a_fr0 = ((wm * 64 + li) * BKT + 4 * ((2 * lh) ^ fsw)) * 4;
@@ -748,17 +829,45 @@ void k_wino_gemm_ps(GemmArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
     int lz = 0, lk = 0, l_buf = 0;                     // (problem, chunk) of the next DMA and its ring slot
+    // EXT: that problem's position and chunk count; chunks kchunks .. are the second segment's.  Every chunk is still 2 A + 3 B
+    // pieces per wave, so the counted waits below hold across the seam and across problems of unequal length.
+    [[maybe_unused]] int lpos = 0, lkz = 0;
+    if constexpr (EXT) { lpos = zpos(zbase); lkz = zchunks(lpos); }
 #define PS_DMA()                                                                                                \
     do {                                                                                                        \
-        const char* xs_ = xt + ((int64_t)lz * a.xb + lk * BKT) * 4;                                             \
-        const char* ws_ = wt + (int64_t)lz * a.wb * 4 + lk * BBYTES;                                            \
-        char* st_ = lds + l_buf * STAGE;                                                                        \
-        _Pragma("unroll") for (int p_ = 0; p_ < 2; ++p_)                                                        \
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(xs_ + a_off[p_]), (lds_ptr_t)(st_ + (2 * wave + p_) * 1024), 16, 0, 0); \
-        _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                        \
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(ws_ + (3 * wave + p_) * 1024),                         \
-                                             (lds_ptr_t)(st_ + ABYTES + (3 * wave + p_) * 1024), 16, 0, 0);     \
-        if (lk + 1 < kchunks) ++lk; else if (lz + 1 < nb) { lk = 0; ++lz; }   /* past the end: the last chunk again */ \
+        if constexpr (EXT) {                                                                                    \
+            const char* xs_ = xt + ((int64_t)lpos * a.xb + lk * BKT) * 4;                                       \
+            const char* ws_ = wt + (int64_t)lpos * a.wb * 4 + lk * BBYTES;                                      \
+            unsigned ao_[2] = {a_off[0], a_off[1]};                                                             \
+            if (lk >= kchunks) {                       /* the second segment: A from x2, B from w2 */           \
+                const int e_ = __builtin_popcountll(a.zext & (((uint64_t)1 << lpos) - 1));                      \
+                xs_ = x2t + ((int64_t)lpos * a.xb2 + (lk - kchunks) * BKT) * 4;                                 \
+                ws_ = w2t + (int64_t)e_ * a.wb2 * 4 + (lk - kchunks) * BBYTES;                                  \
+                ao_[0] = a_off2[0];                                                                             \
+                ao_[1] = a_off2[1];                                                                             \
+            }                                                                                                   \
+            char* st_ = lds + l_buf * STAGE;                                                                    \
+            _Pragma("unroll") for (int p_ = 0; p_ < 2; ++p_)                                                    \
+                __builtin_amdgcn_global_load_lds((glb_ptr_t)(xs_ + ao_[p_]), (lds_ptr_t)(st_ + (2 * wave + p_) * 1024), 16, 0, 0); \
+            _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                    \
+                __builtin_amdgcn_global_load_lds((glb_ptr_t)(ws_ + (3 * wave + p_) * 1024),                     \
+                                                 (lds_ptr_t)(st_ + ABYTES + (3 * wave + p_) * 1024), 16, 0, 0); \
+        } else {                                                                                                \
+            const char* xs_ = xt + ((int64_t)lz * a.xb + lk * BKT) * 4;                                         \
+            const char* ws_ = wt + (int64_t)lz * a.wb * 4 + lk * BBYTES;                                        \
+            char* st_ = lds + l_buf * STAGE;                                                                    \
+            _Pragma("unroll") for (int p_ = 0; p_ < 2; ++p_)                                                    \
+                __builtin_amdgcn_global_load_lds((glb_ptr_t)(xs_ + a_off[p_]), (lds_ptr_t)(st_ + (2 * wave + p_) * 1024), 16, 0, 0); \
+            _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                    \
+                __builtin_amdgcn_global_load_lds((glb_ptr_t)(ws_ + (3 * wave + p_) * 1024),                     \
+                                                 (lds_ptr_t)(st_ + ABYTES + (3 * wave + p_) * 1024), 16, 0, 0); \
+        }                                                                                                       \
+        if constexpr (EXT) {                                                                                    \
+            if (lk + 1 < lkz) ++lk;                                                                             \
+            else if (lz + 1 < nb) { lk = 0; ++lz; lpos = zpos(zbase + lz); lkz = zchunks(lpos); }               \
+        } else {                                                                                                \
+            if (lk + 1 < kchunks) ++lk; else if (lz + 1 < nb) { lk = 0; ++lz; }   /* past the end: the last chunk again */ \
+        }                                                                                                       \
         l_buf = (l_buf + 1) % NS;                                                                               \
     } while (0)
     const unsigned y_off = (unsigned)((wm * 64 + 4 * lh) * a.ldy + wn * 64 + li) * 4u;
@@ -846,6 +955,8 @@ void k_wino_gemm_ps(GemmArgs a) {
     PS_FRAGS0(0);                                      // chunk 0's pieces
     r_buf = 1;
     int cz = 0, ck = 0;
+    [[maybe_unused]] int cpos = 0, ckz = 0;            // EXT: position and chunk count of problem cz
+    if constexpr (EXT) { cpos = zpos(zbase); ckz = zchunks(cpos); }
     bool landed = true;                                // the NEXT chunk's DMA is known to be in LDS
     // The loop walks two chunks per trip, body 0 then body 1, each followed by the problem-boundary block; an odd total ends behind
     // body 0.  (One shared boundary block - body by parity, or set 1 moved / read again into set 0 behind an odd problem - was tried:
@@ -860,13 +971,13 @@ void k_wino_gemm_ps(GemmArgs a) {
         __builtin_amdgcn_sched_barrier(0);                                                                      \
     } while (0)
     auto boundary = [&](int kc) __attribute__((always_inline)) {   // behind chunk kc
-        if (++ck == kchunks) {                          // problem cz is complete: store, clear
+        if (++ck == (EXT ? ckz : kchunks)) {            // problem cz is complete: store, clear
             if (kc + 1 < total) __builtin_amdgcn_s_waitcnt(0x0F75);                    // chunk + 2 has landed
             else __builtin_amdgcn_s_waitcnt(0x0F70);                                   // nothing left in flight
             landed = true;
             __builtin_amdgcn_sched_barrier(0);
             const int zrow = ROWS ? row_base + cz * a.zrows : row_base;
-            char* yt = reinterpret_cast<char*>(yg + (int64_t)cz * a.yb + (int64_t)row_base * a.ldy + n0);             // uniform
+            char* yt = reinterpret_cast<char*>(yg + (int64_t)(EXT ? cpos : cz) * a.yb + (int64_t)row_base * a.ldy + n0);   // uniform
             const char* rt = EPI && a.res ? reinterpret_cast<const char*>(a.res) + (yt - reinterpret_cast<char*>(a.y)) : nullptr;
 #define PS_VALUE(J)                                                                                             \
             float v_ = acc[i][J][r];                                                                            \
@@ -909,6 +1020,8 @@ void k_wino_gemm_ps(GemmArgs a) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
             ck = 0; ++cz;
+            if constexpr (EXT)
+                if (cz < nb) { cpos = zpos(zbase + cz); ckz = zchunks(cpos); }
         }
     };
     if constexpr (EPI) {
@@ -1164,7 +1277,7 @@ extern "C" int be_wino_pack_f32(const float* w, const float* b, const float* gam
     BE_REQUIRE((gamma == nullptr) == (beta == nullptr) && (gamma == nullptr) == (mean == nullptr) && (gamma == nullptr) == (var == nullptr),
                "be_wino_pack_f32: BatchNorm tensors must be all set or all null");
     const int cp = (cout + 31) / 32 * 32;
-    hipLaunchKernelGGL(k_wino_pack, dim3(grid_cap((int64_t)cp * cin, 256, 4096)), dim3(256), 0, be::as_stream(stream), w, b, gamma,
+    hipLaunchKernelGGL(k_wino_pack<0>, dim3(grid_cap((int64_t)cp * cin, 256, 4096)), dim3(256), 0, be::as_stream(stream), w, b, gamma,
                        beta, mean, var, eps, cout, cin, cp, packed_w, packed_bias);
     if (int rc = be::check_launch("be_wino_pack_f32")) return rc;
     const int n_tiles = (cout + 127) / 128;
@@ -1172,6 +1285,35 @@ extern "C" int be_wino_pack_f32(const float* w, const float* b, const float* gam
                        be::as_stream(stream), packed_w, NPOS, cp, cin, n_tiles,
                        reinterpret_cast<__bf16*>(packed_w + wino_u_floats(cout, cin)));
     return be::check_launch("be_wino_pack_f32(split)");
+}
+
+// A block's 1x1 downsample in the form conv2's GEMMs take as their second K segment (round 14): the transform of the kernel as a
+// centre-tap 3x3 at its NLIVE non-zero positions, U_ds [NLIVE][cout_pad32][cin] fp32 (position 5 zr + zc is number 3 (zr - 1) + zc - 1),
+// then its hi / mid / lo planes in the GEMM's block layout
+static size_t wino_ds_u_floats(int cout, int cin) { return (size_t)NLIVE * ((cout + 31) / 32 * 32) * cin; }
+
+extern "C" int be_wino_ds_positions(void) { return NLIVE; }
+
+extern "C" size_t be_wino_ds_packed_floats(int cout, int cin) {
+    if (cout <= 0 || cin <= 0 || cin % 16) return 0;
+    return wino_ds_u_floats(cout, cin) + (size_t)NLIVE * ((cout + 127) / 128 * 128) * cin * 3 / 2;
+}
+
+extern "C" int be_wino_ds_pack_f32(const float* w, const float* b, const float* gamma, const float* beta, const float* mean,
+                                   const float* var, float eps, int cout, int cin, float* packed_ds, float* packed_bias, void* stream) {
+    BE_REQUIRE(w && packed_ds, "be_wino_ds_pack_f32: null pointer");
+    BE_REQUIRE(cout > 0 && cin > 0 && cin % 16 == 0, "be_wino_ds_pack_f32: cin must be a multiple of 16 (got %d)", cin);
+    BE_REQUIRE((gamma == nullptr) == (beta == nullptr) && (gamma == nullptr) == (mean == nullptr) && (gamma == nullptr) == (var == nullptr),
+               "be_wino_ds_pack_f32: BatchNorm tensors must be all set or all null");
+    BE_REQUIRE(be::aligned16(packed_ds), "be_wino_ds_pack_f32: packed_ds must be 16-byte aligned");
+    const int cp = (cout + 31) / 32 * 32, n_tiles = (cout + 127) / 128;
+    hipLaunchKernelGGL(k_wino_pack<1>, dim3(grid_cap((int64_t)cp * cin, 256, 4096)), dim3(256), 0, be::as_stream(stream), w, b, gamma,
+                       beta, mean, var, eps, cout, cin, cp, packed_ds, packed_bias);
+    if (int rc = be::check_launch("be_wino_ds_pack_f32")) return rc;
+    hipLaunchKernelGGL(k_wino_pack_split, dim3(grid_cap((int64_t)NLIVE * 128 * n_tiles * (cin / 8), 256, 4096)), dim3(256), 0,
+                       be::as_stream(stream), packed_ds, NLIVE, cp, cin, n_tiles,
+                       reinterpret_cast<__bf16*>(packed_ds + wino_ds_u_floats(cout, cin)));
+    return be::check_launch("be_wino_ds_pack_f32(split)");
 }
 
 extern "C" size_t be_wino_workspace_floats(int64_t n, int cin, int cout) {
@@ -1228,13 +1370,21 @@ int wino_gemms_bf6(const float* V, const float* packed_w, float* M, int64_t n, i
 }
 
 // The same GEMMs on k_wino_gemm_ps: A (V) split in the loop, B from the pre-split planes behind U.  Bit-identical to wino_gemms_bf6.
-int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s) {
+// Round 14, Vx != nullptr: at the NLIVE positions of a 1x1 kernel's transform M[z] = V[z] U[z]^T + Vx[z] Uds[z]^T, K order V's chunks
+// ascending, then Vx's, from a zero accumulator (k_wino_gemm_ps<0, 0, 1>) - a block's downsample inside conv2's GEMMs.  Vx: the
+// transform of the block's input (cin_ext channels) in V's layout; ds_planes: the planes of be_wino_ds_pack_f32.  tm_force >= 0
+// picks the layout (tile-major 1 / plane-major 0) whatever the batch size.
+int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s,
+                  const float* Vx = nullptr, const float* ds_planes = nullptr, int cin_ext = 0, int tm_force = -1) {
     constexpr size_t lds = (size_t)PS_STAGES * (128 * 16 * 4 + PS_BLOCK * 2);    // stages of 8 KB A + 12 KB B
-    static be::DeviceFlags attr_set{};                          // dynamic-LDS cap raised once per device (thread-safe)
+    static be::DeviceFlags attr_set{}, attr_set_ext{};          // dynamic-LDS cap raised once per device (thread-safe)
     if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm_ps<0, 0>), lds, attr_set)) return rc_;
+    if (Vx)
+        if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm_ps<0, 0, 1>), lds, attr_set_ext)) return rc_;
     const int64_t rows = (int64_t)TPI * n;
-    const bool tm = wino_large(n, cout);
+    const bool tm = tm_force >= 0 ? tm_force != 0 : wino_large(n, cout);
     const int m_tiles = (int)((rows + 127) / 128), n_tiles = (cout + 127) / 128, kchunks = cin / 16;
+    const int kext = Vx ? cin_ext / 16 : 0;
     // problem groups: two workgroups fit on a CU, and a CU with one runs no faster than with two, so a launch costs rounds of two
     // workgroups per CU times a workgroup's problems x K chunks + ~2 chunks of prologue and turnover; the fewest groups of least cost
     static const int zg_env = getenv("BE_WINO_ZGROUPS") ? atoi(getenv("BE_WINO_ZGROUPS")) : 0;   // A/B knob
@@ -1243,11 +1393,13 @@ int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, in
     if (zg_env > 0 && zg_env <= NPOS) {
         zgroups = zg_env;
     } else {
+        // (with the second segment a workgroup is priced by its real chunks: the extended positions are dealt evenly, so the
+        // dearest group has ceil(NLIVE / zg) of them)
         int64_t best = INT64_MAX;
         for (int zg = 1; zg <= NPOS; ++zg) {
             if (NPOS % zg) continue;
             const int64_t wgs = (int64_t)m_tiles * zg * n_tiles, rounds = ((wgs + cus - 1) / cus + 1) / 2;
-            const int64_t cost = rounds * ((NPOS / zg) * kchunks + 2);
+            const int64_t cost = rounds * ((NPOS / zg) * kchunks + (kext ? (NLIVE + zg - 1) / zg * kext : 0) + 2);
             if (cost < best) { best = cost; zgroups = zg; }
         }
     }
@@ -1256,7 +1408,32 @@ int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, in
                tm ? (int64_t)cin : rows * cin, (int64_t)n_tiles * kchunks * (PS_BLOCK / 2), tm ? (int64_t)cout : rows * cout,
                tm ? NPOS * cin : cin, 128, 0, nullptr, nullptr, 0, zgroups, n_tiles * 128};
     const unsigned grid = (unsigned)(8 * ((m_tiles * zgroups + 7) / 8) * n_tiles);
-    {
+    if (Vx) {
+        g.x2 = Vx;
+        g.w2 = ds_planes;
+        g.xb2 = tm ? (int64_t)cin_ext : rows * cin_ext;
+        g.wb2 = (int64_t)n_tiles * kext * (PS_BLOCK / 2);
+        g.lda2 = tm ? NPOS * cin_ext : cin_ext;
+        g.kext = kext;
+        g.zext = wino_ds_mask();
+        // the walk: the extended positions first, dealt one at a time round the groups that still have room, then the others - the
+        // groups' chunk counts are as equal as the group count allows.  (Which group computes a position changes no bit of it.)
+        const int zper = (NPOS + zgroups - 1) / zgroups;
+        int fill[NPOS] = {0}, order[NPOS] = {0}, grp = 0;
+        for (int live = 1; live >= 0; --live)
+            for (int z = 0; z < NPOS; ++z) {
+                if ((int)wino_ds_live(z) != live) continue;
+                while (fill[grp] >= std::min(zper, NPOS - grp * zper)) grp = (grp + 1) % zgroups;
+                order[grp * zper + fill[grp]++] = z;
+                grp = (grp + 1) % zgroups;
+            }
+        for (int i = 0; i < NPOS; ++i) g.ztab[i / 10] |= (uint64_t)order[i] << (6 * (i % 10));
+        const double ext = (double)NLIVE;
+        be::ProfileScope prof(s, BE_KERNEL_WINO_GEMM, 2.0 * rows * cout * ((double)NPOS * cin + ext * cin_ext),
+                              4.0 * rows * ((double)NPOS * (cin + cout) + ext * cin_ext) + 6.0 * n_tiles * 128 * ((double)NPOS * cin + ext * cin_ext),
+                              2.0 * m_tiles * n_tiles * 128.0 * 128.0 * ((double)NPOS * cin + ext * cin_ext));
+        hipLaunchKernelGGL((k_wino_gemm_ps<0, 0, 1>), dim3(grid), dim3(256), lds, s, g);
+    } else {
         // (FLOPs in fp32-equivalent products, as wino_gemms_bf6)
         be::ProfileScope prof(s, BE_KERNEL_WINO_GEMM, (double)NPOS * 2.0 * rows * cin * cout,
                               (double)NPOS * 4.0 * ((double)rows * cin + (double)rows * cout) + (double)NPOS * 6.0 * cin * n_tiles * 128,
@@ -1266,7 +1443,16 @@ int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, in
     return be::check_launch("be_wino_conv3x3_6x6_f32(gemm, split bf16, pre-split weights)");
 }
 
-int wino_gemms(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s, void* stream) {
+bool wino_knob(const char* name) { return getenv(name) != nullptr && atoi(getenv(name)) != 0; }
+
+int wino_gemms(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s, void* stream,
+               const float* Vx = nullptr, const float* ds_planes = nullptr, int cin_ext = 0) {
+    if (Vx) {
+        // only the GEMMs on pre-split weights have the second K segment
+        static const bool other_arm = wino_knob("BE_WINO_F32") || wino_knob("BE_WINO_BF6_R7");
+        BE_REQUIRE(!other_arm, "be_wino_conv3x3_pair_ds_6x6_f32: no folded downsample under BE_WINO_F32=1 / BE_WINO_BF6_R7=1");
+        return wino_gemms_ps(V, packed_w, M, n, cin, cout, s, Vx, ds_planes, cin_ext);
+    }
     // A/B knobs: BE_WINO_F32=1 restores the fp32-MFMA GEMMs of all three batch regimes (weight-stationary, walked 128x128, and
     // the batched k_conv_igemm of small batches); BE_WINO_BF6_R7=1 the split-bf16 GEMMs that split B in the loop too (round 7:
     // the same bits as the default)
@@ -1454,6 +1640,16 @@ static int wino_nt() { static const int v = getenv("BE_WINO_NT") ? atoi(getenv("
             default: hipLaunchKernelGGL(K<0>, GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                    \
         }                                                                                                       \
     } while (0)
+// the kernels with a third template flag (k_wino_out_res_in's STORE_Y, k_pool_wino_in's STORE_P)
+#define BE_WINO_LAUNCH_FLAG(K, F, GRID, BLOCK, LDS, STREAM, ...)                                                \
+    do {                                                                                                        \
+        switch (wino_nt()) {                                                                                    \
+            case 1: hipLaunchKernelGGL((K<1, VW_OUT, F>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;        \
+            case 2: hipLaunchKernelGGL((K<2, VW_OUT, F>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;        \
+            case 3: hipLaunchKernelGGL((K<3, VW_OUT, F>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;        \
+            default: hipLaunchKernelGGL((K<0, VW_OUT, F>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;       \
+        }                                                                                                       \
+    } while (0)
 
 extern "C" int be_wino_conv3x3_6x6_f32(const float* x, const float* packed_w, const float* packed_bias, const float* residual,
                                        float* y, int64_t n, int cin, int cout, int act, float* workspace,
@@ -1481,31 +1677,52 @@ extern "C" size_t be_wino_pair_workspace_floats(int64_t n, int cin, int cmid, in
     return (size_t)100 * n * (big + out);                       // V (cin, then cmid) + M (cmid, then cout)
 }
 
+// The pair with the downsample folded into conv2's GEMMs keeps x's transform alive beside conv1's: three regions, V_x (cin; a
+// following block's transform, cout channels, is written there once conv2's GEMMs have run), M (cmid, then cout) and V_h (cmid)
+extern "C" size_t be_wino_pair_ds_workspace_floats(int64_t n, int cin, int cmid, int cout) {
+    if (n <= 0) return 0;
+    const size_t first = (size_t)(cin > cout ? cin : cout), out = (size_t)(cmid > cout ? cmid : cout);
+    return (size_t)100 * n * (first + out + (size_t)cmid);
+}
+
 // pool2 = 1: y is [n,3,3,cout], the 2x2 max-pool of the block's output (k_wino_out_pool2)
 // x_in_v = 1: the start of the workspace already holds x's input transform in this block's layout (left there by the block or the
 // pool kernel in front: k_wino_in is skipped).  next_cmid > 0: the last launch is k_wino_out_res_in, which writes y and, at the
 // start of the workspace, y's input transform for a following block whose conv1 has next_cmid outputs.
+// packed_ds != nullptr (round 14; be_wino_conv3x3_pair_ds_6x6_f32): the block's 1x1 downsample (be_wino_ds_pack_f32) runs inside
+// conv2's GEMMs as a second K segment over x's transform; there is no residual tensor, the workspace has three regions
+// (be_wino_pair_ds_workspace_floats: x's transform outlives k_wino_out_in), x may be null with x_in_v and y with next_cmid > 0
+// (the map is then not stored: nothing reads it).
 int be::wino_pair(const float* x, const float* packed_w1, const float* packed_bias1, int act1, const float* packed_w2,
                   const float* packed_bias2, const float* residual, int act2, float* y, int64_t n, int cin, int cmid, int cout,
-                  float* workspace, size_t workspace_floats, void* stream, int pool2, int x_in_v, int next_cmid) {
-    BE_REQUIRE(x && packed_w1 && packed_bias1 && packed_w2 && packed_bias2 && y && workspace,
+                  float* workspace, size_t workspace_floats, void* stream, int pool2, int x_in_v, int next_cmid, const float* packed_ds) {
+    const bool ds = packed_ds != nullptr;
+    const float* ds_planes = ds ? packed_ds + wino_ds_u_floats(cout, cin) : nullptr;
+    BE_REQUIRE((x || (ds && x_in_v)) && packed_w1 && packed_bias1 && packed_w2 && packed_bias2 && (y || (ds && next_cmid > 0)) && workspace,
                "be_wino_conv3x3_pair_6x6_f32: null pointer");
     if (int rc = wino_args_ok("be_wino_conv3x3_pair_6x6_f32", n, cin, cmid)) return rc;
     if (int rc = wino_args_ok("be_wino_conv3x3_pair_6x6_f32", n, cmid, cout)) return rc;
-    BE_REQUIRE(workspace_floats >= be_wino_pair_workspace_floats(n, cin, cmid, cout), "be_wino_conv3x3_pair_6x6_f32: workspace too small");
-    BE_REQUIRE(be::aligned16(x) && be::aligned16(y) && be::aligned16(workspace) && be::aligned16(packed_w1) && be::aligned16(packed_w2),
-               "be_wino_conv3x3_pair_6x6_f32: 16-byte alignment");
+    BE_REQUIRE(workspace_floats >= (ds ? be_wino_pair_ds_workspace_floats(n, cin, cmid, cout) : be_wino_pair_workspace_floats(n, cin, cmid, cout)),
+               "be_wino_conv3x3_pair_6x6_f32: workspace too small");
+    BE_REQUIRE(be::aligned16(x) && be::aligned16(y) && be::aligned16(workspace) && be::aligned16(packed_w1) && be::aligned16(packed_w2) &&
+               be::aligned16(packed_ds), "be_wino_conv3x3_pair_6x6_f32: 16-byte alignment");
     hipStream_t s = be::as_stream(stream);
-    const size_t big = (size_t)(cin > cmid ? cin : cmid);
-    float* V = workspace;
+    const size_t big = ds ? (size_t)(cin > cout ? cin : cout) : (size_t)(cin > cmid ? cin : cmid);
+    float* V = workspace;                                       // x's transform; without ds then also conv1's result's
     float* M = workspace + (size_t)100 * n * big;
+    float* Vh = ds ? M + (size_t)100 * n * (size_t)(cmid > cout ? cmid : cout) : V;
     const int tm1 = wino_large(n, cmid), tm2 = wino_large(n, cout);
     BE_REQUIRE(next_cmid >= 0 && !(next_cmid > 0 && pool2), "be_wino_conv3x3_pair_6x6_f32: next_cmid cannot be combined with pool2");
+    if (ds) {
+        BE_REQUIRE(!residual, "be_wino_conv3x3_pair_ds_6x6_f32: the folded downsample replaces the residual tensor");
+        BE_REQUIRE(tm1 == tm2, "be_wino_conv3x3_pair_ds_6x6_f32: x's transform and conv1's must share a layout (cmid %d, cout %d)", cmid, cout);
+    }
     if (next_cmid > 0) {
         if (int rc = wino_args_ok("be_wino_conv3x3_pair_6x6_f32", n, cout, next_cmid)) return rc;
         // the boundary kernel writes V' while it reads M: V' must end where M starts at the latest
         BE_REQUIRE((size_t)(NPOS * TPI) * n * cout <= (size_t)100 * n * big,
-                   "be_wino_conv3x3_pair_6x6_f32: the next block's transform (cout %d) would reach M (max(cin, cmid) = %d)", cout, (int)big);
+                   "be_wino_conv3x3_pair_6x6_f32: the next block's transform (cout %d) would reach M (%s = %d)", cout,
+                   ds ? "max(cin, cout)" : "max(cin, cmid)", (int)big);
     }
     if (!x_in_v) {
         be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * cin * (36.0 + (double)(NPOS * TPI)), 0.0);
@@ -1515,15 +1732,19 @@ int be::wino_pair(const float* x, const float* packed_w1, const float* packed_bi
     if (int rc = wino_gemms(V, packed_w1, M, n, cin, cmid, s, stream)) return rc;
     {
         be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * cmid * (2.0 * NPOS * TPI), 0.0);
-        BE_WINO_LAUNCH(k_wino_out_in, dim3(grid_cap(n * (cmid / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias1, V, n, cmid / VW_OUT, act1,
+        BE_WINO_LAUNCH(k_wino_out_in, dim3(grid_cap(n * (cmid / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias1, Vh, n, cmid / VW_OUT, act1,
                            tm1, tm2);
     }
     if (int rc = be::check_launch("be_wino_conv3x3_pair_6x6_f32(out_in)")) return rc;
-    if (int rc = wino_gemms(V, packed_w2, M, n, cmid, cout, s, stream)) return rc;
+    if (int rc = wino_gemms(Vh, packed_w2, M, n, cmid, cout, s, stream, ds ? V : nullptr, ds_planes, cin)) return rc;
     {
-        be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * cout * ((double)(NPOS * TPI) + (residual ? 36.0 : 0.0) + (pool2 ? 9.0 : 36.0) +
+        be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * cout * ((double)(NPOS * TPI) + (residual ? 36.0 : 0.0) +
+                                                                                   (pool2 ? 9.0 : y ? 36.0 : 0.0) +
                                                                                    (next_cmid > 0 ? (double)(NPOS * TPI) : 0.0)), 0.0);
-        if (next_cmid > 0)
+        if (next_cmid > 0 && !y)
+            BE_WINO_LAUNCH_FLAG(k_wino_out_res_in, 0, dim3(grid_cap(n * (cout / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias2, residual, y, V,
+                                n, cout / VW_OUT, act2, tm2, (int)wino_large(n, next_cmid));
+        else if (next_cmid > 0)
             BE_WINO_LAUNCH(k_wino_out_res_in, dim3(grid_cap(n * (cout / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias2, residual, y, V, n,
                                cout / VW_OUT, act2, tm2, (int)wino_large(n, next_cmid));
         else if (pool2)
@@ -1552,17 +1773,58 @@ extern "C" int be_wino_conv3x3_pair_chain_6x6_f32(const float* x, const float* p
                          workspace_floats, stream, 0, x_in_v, next_cmid);
 }
 
-extern "C" int be_maxpool_wino_in_11x11_f32(const float* x, float* pooled, int64_t n, int c, int next_cmid, float* workspace,
-                                            size_t workspace_floats, void* stream) {
-    BE_REQUIRE(x && pooled && workspace, "be_maxpool_wino_in_11x11_f32: null pointer");
+// The folded pair (round 14): be_wino_conv3x3_pair_chain_6x6_f32 with the block's 1x1 downsample inside conv2's GEMMs
+// (packed_ds: be_wino_ds_pack_f32; its bias belongs in packed_bias2) instead of a residual tensor
+extern "C" int be_wino_conv3x3_pair_ds_6x6_f32(const float* x, const float* packed_w1, const float* packed_bias1, int act1,
+                                               const float* packed_w2, const float* packed_bias2, const float* packed_ds, int act2,
+                                               float* y, int64_t n, int cin, int cmid, int cout, float* workspace,
+                                               size_t workspace_floats, void* stream, int x_in_v, int next_cmid) {
+    BE_REQUIRE(packed_ds, "be_wino_conv3x3_pair_ds_6x6_f32: null pointer");
+    return be::wino_pair(x, packed_w1, packed_bias1, act1, packed_w2, packed_bias2, nullptr, act2, y, n, cin, cmid, cout, workspace,
+                         workspace_floats, stream, 0, x_in_v, next_cmid, packed_ds);
+}
+
+// The transform-domain GEMMs alone on k_wino_gemm_ps: M[z] = V[z] U[z]^T and, with Vx, + Vx[z] U_ds[z]^T at U_ds's positions.
+// V [positions][tiles][cin] (tile_major = 0) or [tiles][positions][cin] (1), tiles = (12 / be_wino_tile_rows()) n; Vx and M likewise
+extern "C" int be_wino_gemms_ext_f32(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, const float* Vx,
+                                     const float* packed_ds, int cin_ext, int tile_major, void* stream) {
+    BE_REQUIRE(V && packed_w && M && (Vx == nullptr) == (packed_ds == nullptr), "be_wino_gemms_ext_f32: null pointer");
+    BE_REQUIRE(n > 0 && 4 * n < ((int64_t)1 << 31) / 128, "be_wino_gemms_ext_f32: batch out of range");
+    BE_REQUIRE(cin > 0 && cin % 16 == 0 && cout > 0 && cout % 4 == 0, "be_wino_gemms_ext_f32: cin %% 16, cout %% 4 required");
+    BE_REQUIRE(!Vx || (cin_ext > 0 && cin_ext % 16 == 0), "be_wino_gemms_ext_f32: cin_ext must be a multiple of 16 (got %d)", cin_ext);
+    BE_REQUIRE((int64_t)NPOS * TPI * n * (int64_t)std::max(std::max(cin, cout), cin_ext) < ((int64_t)1 << 31), "be_wino_gemms_ext_f32: batch out of range");
+    BE_REQUIRE(be::aligned16(V) && be::aligned16(packed_w) && be::aligned16(M) && be::aligned16(Vx) && be::aligned16(packed_ds),
+               "be_wino_gemms_ext_f32: 16-byte alignment");
+    return wino_gemms_ps(V, packed_w, M, n, cin, cout, be::as_stream(stream), Vx, Vx ? packed_ds + wino_ds_u_floats(cout, cin_ext) : nullptr,
+                         cin_ext, tile_major != 0);
+}
+
+bool be::wino_ds_fold_enabled() {
+    // A/B knob BE_WINO_DS_GEMM=1: the blocks' downsamples stay separate row GEMMs; so they do in the arms without the second K segment
+    static const bool on = be::rows_bf6_enabled() && !wino_knob("BE_WINO_BF6_R7") && !wino_knob("BE_WINO_DS_GEMM");
+    return on;
+}
+
+int be::pool_wino_in(const float* x, float* pooled, int64_t n, int c, int next_cmid, float* workspace, size_t workspace_floats, void* stream) {
+    BE_REQUIRE(x && workspace, "be_maxpool_wino_in_11x11_f32: null pointer");
     if (int rc = wino_args_ok("be_maxpool_wino_in_11x11_f32", n, c, next_cmid)) return rc;
     BE_REQUIRE(workspace_floats >= (size_t)(NPOS * TPI) * n * c, "be_maxpool_wino_in_11x11_f32: workspace too small");
     BE_REQUIRE(be::aligned16(x) && be::aligned16(pooled) && be::aligned16(workspace), "be_maxpool_wino_in_11x11_f32: 16-byte alignment");
     hipStream_t s = be::as_stream(stream);
     {
-        be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * c * (121.0 + 36.0 + (double)(NPOS * TPI)), 0.0);
-        BE_WINO_LAUNCH(k_pool_wino_in, dim3(grid_cap(n * (c / VW_OUT), 256)), dim3(256), 0, s, x, pooled, workspace, n, c / VW_OUT,
-                           (int)wino_large(n, next_cmid));
+        be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * c * (121.0 + (pooled ? 36.0 : 0.0) + (double)(NPOS * TPI)), 0.0);
+        if (pooled)
+            BE_WINO_LAUNCH(k_pool_wino_in, dim3(grid_cap(n * (c / VW_OUT), 256)), dim3(256), 0, s, x, pooled, workspace, n, c / VW_OUT,
+                               (int)wino_large(n, next_cmid));
+        else
+            BE_WINO_LAUNCH_FLAG(k_pool_wino_in, 0, dim3(grid_cap(n * (c / VW_OUT), 256)), dim3(256), 0, s, x, pooled, workspace, n, c / VW_OUT,
+                                (int)wino_large(n, next_cmid));
     }
     return be::check_launch("be_maxpool_wino_in_11x11_f32");
+}
+
+extern "C" int be_maxpool_wino_in_11x11_f32(const float* x, float* pooled, int64_t n, int c, int next_cmid, float* workspace,
+                                            size_t workspace_floats, void* stream) {
+    BE_REQUIRE(pooled, "be_maxpool_wino_in_11x11_f32: null pointer");
+    return be::pool_wino_in(x, pooled, n, c, next_cmid, workspace, workspace_floats, stream);
 }

@@ -575,6 +575,33 @@ int be_wino_conv3x3_pair_chain_6x6_f32(const float* x, const float* packed_w1, c
 int be_maxpool_wino_in_11x11_f32(const float* x, float* pooled, int64_t n, int c, int next_cmid, float* workspace,
                                  size_t workspace_floats, void* stream);
 
+/* A residual block's 1x1 downsample inside conv2's transform-domain GEMMs (round 14).  A 1x1 kernel is a 3x3 with only the centre
+ * tap; its kernel transform is non-zero at be_wino_ds_positions() of the positions (18 of the 40 with the 8x5 tiles: 5 zr + zc with
+ * zr neither first nor last, zc in 1..3), and there conv2's GEMMs run on over the transform of the block's INPUT, into the same
+ * accumulator: M[z] = V_h[z] U2[z]^T + V_x[z] U_ds[z]^T, K order V_h ascending, then V_x ascending.  No residual tensor is written or
+ * read; the downsample's rounding is that of a Winograd layer instead of a row GEMM's.
+ * be_wino_ds_pack_f32: w [cout,cin] (+ bias, + eval BatchNorm, folded as be_wino_pack_f32 does) -> packed_ds = U_ds
+ * [positions'][cout_pad32][cin] fp32 (be_wino_pack_f32's arithmetic on the centre-tap kernel, live position 5 zr + zc at number
+ * 3 (zr - 1) + zc - 1) followed by its hi / mid / lo bf16 planes in the GEMM's block layout (be_wino_ds_packed_floats; cin %% 16 == 0);
+ * the folded bias [cout_pad32] goes to packed_bias unless that is NULL (the caller adds it to conv2's).
+ * be_wino_conv3x3_pair_ds_6x6_f32: be_wino_conv3x3_pair_chain_6x6_f32 with packed_ds in place of the residual.  The workspace has
+ * three regions (x's transform, M, conv1's transform: be_wino_pair_ds_workspace_floats); x may be NULL with x_in_v, and y with
+ * next_cmid > 0 (the map is then not stored).  Requires the two transforms in one layout (always so when cmid == cout); refused under
+ * BE_WINO_F32=1 / BE_WINO_BF6_R7=1.  Bits depend on neither the batch nor BE_WINO_ZGROUPS.
+ * be_wino_gemms_ext_f32: the GEMMs alone.  V [positions][tiles][cin] (tile_major 0) or [tiles][positions][cin] (1), tiles =
+ * (12 / be_wino_tile_rows()) n; M and Vx (cin_ext channels, NULL: no second segment) likewise; packed_w of be_wino_pack_f32. */
+int be_wino_ds_positions(void);
+size_t be_wino_ds_packed_floats(int cout, int cin);
+int be_wino_ds_pack_f32(const float* w_oi, const float* bias, const float* bn_gamma, const float* bn_beta, const float* bn_mean,
+                        const float* bn_var, float bn_eps, int cout, int cin, float* packed_ds, float* packed_bias, void* stream);
+size_t be_wino_pair_ds_workspace_floats(int64_t n, int cin, int cmid, int cout);
+int be_wino_conv3x3_pair_ds_6x6_f32(const float* x, const float* packed_w1, const float* packed_bias1, int act1,
+                                    const float* packed_w2, const float* packed_bias2, const float* packed_ds, int act2, float* y,
+                                    int64_t n, int cin, int cmid, int cout, float* workspace, size_t workspace_floats, void* stream,
+                                    int x_in_v, int next_cmid);
+int be_wino_gemms_ext_f32(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, const float* Vx,
+                          const float* packed_ds, int cin_ext, int tile_major, void* stream);
+
 /* Row GEMM in the same split-bf16 arithmetic (bf16x6): y[m][ldy] = act(x[m][k] w^T + bias (+ residual)), act 0 none / 1 Smish / 2 ReLU,
  * residual with y's row stride; bias and residual may be NULL.  LocalStage's 1x1 downsamples of layers 1-3 and fc.1 run on it wherever
  * the Winograd path runs; environment BE_ROWS_F32=1 (read once per process) sends those four back to the fp32 kernels (BE_WINO_F32=1 does
@@ -910,8 +937,8 @@ int be_datagen_test_render_f64(const double* bkgd, const double* frgd, const dou
 #define BE_KERNEL_CONV_128x32       3   /* fc.4                                                                */
 #define BE_KERNEL_CONV_ROW8_128x64  4   /* conv1 (7x7 row-gather)                                              */
 #define BE_KERNEL_CONV_SMALL        5   /* 64x64 / 128x32 tiles for small M (training batches)                 */
-#define BE_KERNEL_WINO_GEMM         6   /* k_wino_gemm<0, 1> (split bf16; fp32: k_wino_gemm_ws / k_wino_gemm): the transform-domain GEMMs (one per position) of a Winograd layer; FLOPs as fp32 products */
-#define BE_KERNEL_GEMM_ROWS         7   /* row GEMMs: k_wino_gemm_ps<EPI> on pre-split weights (split bf16: LocalStage's 1x1 downsamples and fc.1; FLOPs as fp32 products); fp32: k_wino_gemm<1> / k_wino_gemm_ws<.., 1> (1x1 convolutions / linears, large batches) */
+#define BE_KERNEL_WINO_GEMM         6   /* k_wino_gemm<0, 1> (split bf16; fp32: k_wino_gemm_ws / k_wino_gemm): the transform-domain GEMMs (one per position) of a Winograd layer, with a block's 1x1 downsample as a second K segment where it is folded in (k_wino_gemm_ps<0, 0, 1>); FLOPs as fp32 products */
+#define BE_KERNEL_GEMM_ROWS         7   /* row GEMMs: k_wino_gemm_ps<EPI> on pre-split weights (split bf16: fc.1, and LocalStage's 1x1 downsamples under BE_WINO_DS_GEMM=1; FLOPs as fp32 products); fp32: k_wino_gemm<1> / k_wino_gemm_ws<.., 1> (1x1 convolutions / linears, large batches) */
 /* HBM-bound kernels: `bytes` = the algorithmic bytes the launch has to move, `flops` = 0 */
 #define BE_KERNEL_WINO_TRANSFORM    8   /* k_wino_in / k_wino_out / k_wino_out_in / k_wino_out_pool2 */
 #define BE_KERNEL_MAXPOOL           9   /* k_maxpool_nhwc */
