@@ -14,7 +14,8 @@
 // row-padded staging and for layer0, the row GEMM of be_wino.hip for the 1x1s and fc.1); smaller ones k_conv_igemm - same
 // results bit for bit.  On the Winograd path the 1x1 downsamples of layers 1-3 and fc.1 run in split-bf16 arithmetic on ONE kernel for
 // every sub-batch size (be::gemm_rows_bf6; BE_ROWS_F32=1 / BE_WINO_F32=1: the fp32 kernels just named), and so does layer0
-// (be::conv3x3_pm_bf6, be_conv_pm_bf6.hip; BE_L0_F32=1 / BE_WINO_F32=1: the fp32 kernels), and so do conv1 + the first pool
+// (be::conv3x3_pm_bf6, be_conv_pm_bf6.hip; BE_L0_F32=1 / BE_WINO_F32=1: the fp32 kernels; its LDS ring is 42 KB, three workgroups
+// per CU - BE_BF6_RING4=1, read once per process: the 80-KB ring at two per CU, the same bits), and so do conv1 + the first pool
 // (be_conv1_pool_bf6.hip on the row-padded staging; BE_C1_F32=1 / BE_WINO_F32=1: the fp32 routing by sub-batch size).  No allocation, no
 // synchronisation, no process-wide state: graph-capturable, re-entrant.  opts->winograd = 0 runs layers 1-3 as direct launches
 // like layer0, all in fp32.
