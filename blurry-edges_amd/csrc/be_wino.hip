@@ -27,6 +27,9 @@
 //   k_wino_out     M -> y [N,6,6,Cout] + bias (+ residual) (+ Smish)
 //   k_wino_out_in  conv1 -> conv2 of a residual block: output transform + Smish + input transform, the map stays in registers
 //   k_wino_out_pool2   the last block's output transform with the 2x2 max-pool that follows it
+//   All transform kernels are one tile loop per side - wino_out_tiles: M's NPOS values (+ the residual's) -> be::wino_out ->
+//   act(o + bias (+ res)) -> the caller's sink; wino_in_tiles: window from the caller's getter -> be::wino_in -> NPOS stores - over
+//   one tile (k_wino_in, k_wino_out) or the TPI tiles of a map kept in registers (the others), with wino_strides for both layouts
 //   Chained blocks (round 13; be::wino_pair's x_in_v / next_cmid, be_wino_conv3x3_pair_chain_6x6_f32): a block's input transform is
 //   written by whatever produced its input map, out of the registers that hold the map, so no block reads its input a second time:
 //   k_wino_out_res_in  k_wino_out (+ bias, residual, activation, y stored) + the NEXT block's input transform
@@ -50,7 +53,7 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // tile shape (be_wino_math.h): TH x 3 outputs per tile from an NR x 5 window; TPI tiles per 6x6 map; NPOS positions = GEMMs
-constexpr int TH = be::WINO_TH, NR = be::WINO_NR, TY = be::WINO_TY, TPI = be::WINO_TPI, NPOS = be::WINO_NPOS, NOUT = be::WINO_OUT;
+constexpr int TH = be::WINO_TH, NR = be::WINO_NR, TPI = be::WINO_TPI, NPOS = be::WINO_NPOS, NOUT = be::WINO_OUT;
 
 inline unsigned grid_cap(int64_t total, int block, int64_t limit = 65535) {
     int64_t g = (total + block - 1) / block;
@@ -123,13 +126,11 @@ __global__ void k_wino_pack(const float* __restrict__ w, const float* __restrict
     }
 }
 
-// streaming accesses of the transform kernels: NT bit 0 = non-temporal loads, bit 1 = non-temporal stores (A/B: BE_WINO_NT)
-template <int NT, class V> __device__ __forceinline__ V ld_s(const V* p) {
-    if constexpr (NT & 1) return __builtin_nontemporal_load(p); else return *p;
-}
-template <int NT, class V> __device__ __forceinline__ void st_s(V* p, V v) {
-    if constexpr (NT & 2) __builtin_nontemporal_store(v, p); else *p = v;
-}
+// streaming load of the transform kernels, which read every byte once: non-temporal loads move 5.42-5.46 TB/s where plain loads
+// move 5.24-5.28 (2.65 -> 2.56 ms of transforms per step).  Their stores are plain: non-temporal stores had no effect, and the
+// max-pool, whose windows overlap, loses a third with them.
+template <class V> __device__ __forceinline__ V ld_s(const V* p) { return __builtin_nontemporal_load(p); }
+
 // channels per thread of the output-side transform kernels: with the 8x5 tiles a thread holding a channel QUAD needs 40 + 18 + 18
 // float4 values live (304 registers: the compiler parked 64-130 of them in AGPRs and the kernels fell to 4.9 TB/s); a channel
 // PAIR per thread needs half and runs two waves per SIMD.  Per-channel arithmetic: the width changes no bit.
@@ -139,201 +140,202 @@ template <int W> struct VecOf;
 template <> struct VecOf<4> { typedef f32x4 type; };
 template <> struct VecOf<2> { typedef f32x2 type; };
 
-// one thread = one tile (patch, ty, tx) x one channel quad; arithmetic: be_wino_math.h
-template <int NT>
-__global__ __launch_bounds__(256)
-void k_wino_in(const float* __restrict__ x, float* __restrict__ V, int64_t n, int c4, int tm) {
-    const int64_t total = n * TPI * c4;
-    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    // float4 elements between transform positions / between tiles: plane-major V [NPOS][TPI n][C] (small batches) or
-    // tile-major V [TPI n][NPOS][C] (large batches: a tile's NPOS x C block is one contiguous piece of HBM for this kernel)
-    const int64_t plane = tm ? c4 : n * TPI * c4, ts = tm ? NPOS * c4 : c4;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
-        const int cq = (int)(idx % c4);
-        const int64_t tile = idx / c4;
-        const int64_t img = tile / TPI;
-        const int tt = (int)(tile - img * TPI), ty = tt >> 1, tx = tt & 1;
-        const f32x4* src = reinterpret_cast<const f32x4*>(x) + img * 36 * c4 + cq;
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        f32x4 d[NR][5], v[NPOS];
+// The two layouts of a transform-domain buffer (V or M) of n maps x c channels: plane-major [NPOS][TPI n][c] for small batches,
+// tile-major [TPI n][NPOS][c] for large ones (a tile's NPOS x c block is one contiguous piece of HBM for the transform kernels).
+// plane / ts: elements between the positions of a tile / between tiles.  The kernels count in channel vectors (c = c4), the host,
+// for the GEMMs' arguments, in floats.
+struct WinoStrides { int64_t plane, ts; };
+__host__ __device__ __forceinline__ WinoStrides wino_strides(int tm, int64_t n, int c) {
+    return {tm ? c : n * TPI * c, tm ? NPOS * c : c};
+}
+
+// channel vector cq of pixel (row, col) of map img in [N,6,6,C]: where the residual is read and y is written
+__device__ __forceinline__ size_t map_at(int64_t img, int row, int col, int c4, int cq) {
+    return ((size_t)img * 36 + row * 6 + col) * c4 + cq;
+}
+
+// the activation of a tile's N values under ONE test of `act` (per value, the test and its branches cost the chained kernels a
+// reload of the spilled kernel arguments at every pixel)
+template <class V, int N>
+__device__ __forceinline__ void wino_act(V (&v)[N], int act) {
+    constexpr int W = (int)(sizeof(V) / sizeof(float));
+    if (act == 1) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+#pragma unroll
+            for (int k = 0; k < W; ++k) v[i][k] = be::smish(v[i][k]);
+    } else if (act == 2) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+#pragma unroll
+            for (int k = 0; k < W; ++k) v[i][k] = fmaxf(v[i][k], 0.f);
+    }
+}
+
+// The tile loop of the input side: NTILES tiles of a 6x6 map from its tile t0 on (tile t is (ty, tx) = (t >> 1, t & 1)).  Per tile the
+// NR x 5 window with one pixel of zero padding (get(yy, xx): the map's pixel, asked for inside the map only), be::wino_in
+// (be_wino_math.h), and the NPOS stores from dst() on: tile t0's first position, this thread's channel vector - asked for once the
+// values are there, so that a kernel which forms that address for the call does not hold it across the transform (k_wino_in needs
+// every one of its 256 registers for two waves per SIMD).
+template <int NTILES, class V, class Get, class Dst>
+__device__ __forceinline__ void wino_in_tiles(int t0, WinoStrides so, Get get, Dst dst) {
+    const V zero = V(0.f);
+#pragma unroll
+    for (int t = 0; t < NTILES; ++t) {
+        const int ty = (t0 + t) >> 1, tx = (t0 + t) & 1;
+        V d[NR][5], v[NPOS];
 #pragma unroll
         for (int r = 0; r < NR; ++r)
 #pragma unroll
             for (int c = 0; c < 5; ++c) {
                 const int yy = TH * ty - 1 + r, xx = 3 * tx - 1 + c;
-                d[r][c] = ((unsigned)xx < 6u && (unsigned)yy < 6u) ? ld_s<NT>(src + (size_t)(yy * 6 + xx) * c4) : zero;
+                d[r][c] = ((unsigned)xx < 6u && (unsigned)yy < 6u) ? get(yy, xx) : zero;
             }
         be::wino_in(d, v);
-        f32x4* dst = reinterpret_cast<f32x4*>(V) + tile * ts + cq;
 #pragma unroll
-        for (int z = 0; z < NPOS; ++z) st_s<NT>(dst + (size_t)z * plane, v[z]);
+        for (int z = 0; z < NPOS; ++z) *(dst() + t * so.ts + (size_t)z * so.plane) = v[z];
     }
 }
 
+// input transform of map img held in registers (the kernels below that keep one): the TPI x NPOS values of its tiles go to channel
+// vector cq of the image's tiles in the buffer Vb
 template <class V>
-__device__ __forceinline__ V wino_act(V v, int act) {
-    constexpr int W = (int)(sizeof(V) / sizeof(float));
-    if (act == 1) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) v[k] = be::smish(v[k]);
-    } else if (act == 2) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) v[k] = fmaxf(v[k], 0.f);
-    }
-    return v;
+__device__ __forceinline__ void wino_in_map(const V y[6][6], V* Vb, int64_t img, int cq, WinoStrides so) {
+    V* dst = Vb + img * TPI * so.ts + cq;
+    wino_in_tiles<TPI, V>(0, so, [&](int yy, int xx) { return y[yy][xx]; }, [&] { return dst; });
 }
 
-// input transform of a 6x6 map held in registers (the kernels below that keep one): the TPI x NPOS values of its tiles go to dst (the
-// image's first tile, this thread's channel vector; ts_o / plane_o: vectors between tiles / positions).  k_wino_in's arithmetic.
-template <int NT, class V>
-__device__ __forceinline__ void wino_in_map(const V y[6][6], V* dst, int64_t ts_o, int64_t plane_o) {
-    const V zero = V(0.f);
+// The tile loop of the output side: NTILES tiles of map img from its tile t0 on.  Per tile the NPOS transform-domain values of M,
+// be::wino_out, act(o + bias (+ res)) for the tile's TH x 3 pixels - the bias, the residual and the activation each in one pass over
+// the tile, so `res` and `act` are tested once per tile - and sink(row, col, value) for each of them.  That operation order is
+// what every kernel below computes: a block's y and the transform of it carry the same bits whichever of them writes them
+// (tests/test_wino_chain.py).  The residual's values are fetched with the tile's transform-domain ones (inside the output loop
+// each was a round trip of its own: k_wino_out sat 58 % of its wave cycles in s_waitcnt).
+template <int NTILES, class vec, class Sink>
+__device__ __forceinline__ void wino_out_tiles(int t0, const vec* M, WinoStrides sm, vec bv, const vec* res, int64_t img, int c4, int cq,
+                                               int act, Sink sink) {
 #pragma unroll
-    for (int ty = 0; ty < TY; ++ty)
+    for (int t = 0; t < NTILES; ++t) {
+        const int ty = (t0 + t) >> 1, tx = (t0 + t) & 1;
+        const vec* src = M + (img * TPI + t0 + t) * sm.ts + cq;
+        vec m[NPOS], o[NOUT], rv[NOUT];
 #pragma unroll
-        for (int tx = 0; tx < 2; ++tx) {
-            V d[NR][5], v[NPOS];
+        for (int z = 0; z < NPOS; ++z) m[z] = ld_s(src + (size_t)z * sm.plane);
+        if (res) {
 #pragma unroll
-            for (int r = 0; r < NR; ++r)
+            for (int r = 0; r < TH; ++r)
 #pragma unroll
-                for (int c = 0; c < 5; ++c) {
-                    const int yy = TH * ty - 1 + r, xx = 3 * tx - 1 + c;
-                    d[r][c] = (xx >= 0 && xx < 6 && yy >= 0 && yy < 6) ? y[yy < 0 ? 0 : (yy > 5 ? 5 : yy)][xx < 0 ? 0 : (xx > 5 ? 5 : xx)] : zero;
-                }
-            be::wino_in(d, v);
-#pragma unroll
-            for (int z = 0; z < NPOS; ++z) st_s<NT>(dst + (ty * 2 + tx) * ts_o + (size_t)z * plane_o, v[z]);
+                for (int c = 0; c < 3; ++c) rv[3 * r + c] = ld_s(res + map_at(img, TH * ty + r, 3 * tx + c, c4, cq));
         }
+        be::wino_out(m, o);
+#pragma unroll
+        for (int k = 0; k < NOUT; ++k) o[k] = o[k] + bv;
+        if (res) {
+#pragma unroll
+            for (int k = 0; k < NOUT; ++k) o[k] += rv[k];
+        }
+        wino_act(o, act);
+#pragma unroll
+        for (int r = 0; r < TH; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sink(TH * ty + r, 3 * tx + c, o[3 * r + c]);
+    }
 }
 
-template <int NT, int VW = VW_OUT>
+// the 6x6 map of image img out of its TPI tiles of M, into registers (one thread = one image x one channel vector), and with
+// STORE_Y also to y [N,6,6,C]
+template <int STORE_Y, class vec>
+__device__ __forceinline__ void wino_out_map(const vec* M, WinoStrides sm, vec bv, const vec* res, vec* y, int64_t img, int c4, int cq,
+                                             int act, vec v[6][6]) {
+    wino_out_tiles<TPI>(0, M, sm, bv, res, img, c4, cq, act, [&](int row, int col, vec w) {
+        v[row][col] = w;
+        if constexpr (STORE_Y) *(y + map_at(img, row, col, c4, cq)) = w;
+    });
+}
+
+// one thread = one tile (patch, ty, tx) x one channel quad
+// Compiler report (gfx950, hipcc -Rpass-analysis=kernel-resource-usage; in all six kernels 0 AGPRs, scratch 0, no VGPR spills, the
+// SGPR spills go to VGPR lanes: the addresses): 254 VGPRs, 15 SGPR spills, two waves per SIMD.
+__global__ __launch_bounds__(256)
+void k_wino_in(const float* __restrict__ x, float* __restrict__ V, int64_t n, int c4, int tm) {
+    const int64_t total = n * TPI * c4;
+    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
+    const WinoStrides sv = wino_strides(tm, n, c4);
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
+        const int cq = (int)(idx % c4);
+        const int64_t tile = idx / c4;
+        const int64_t img = tile / TPI;
+        const int tt = (int)(tile - img * TPI);
+        const f32x4* src = reinterpret_cast<const f32x4*>(x) + img * 36 * c4 + cq;
+        wino_in_tiles<1, f32x4>(tt, sv, [&](int yy, int xx) { return ld_s(src + (size_t)(yy * 6 + xx) * c4); },
+                                [&] { return reinterpret_cast<f32x4*>(V) + tile * sv.ts + cq; });
+    }
+}
+
+// one thread = one tile x one channel vector
+// Compiler report: 163 VGPRs, 32 SGPR spills, three waves per SIMD.
+template <int VW = VW_OUT>
 __global__ __launch_bounds__(256)
 void k_wino_out(const float* __restrict__ M, const float* __restrict__ bias, const float* __restrict__ res,
                 float* __restrict__ y, int64_t n, int c4, int act, int tm) {
     typedef typename VecOf<VW>::type vec;
     const int64_t total = n * TPI * c4;
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    const int64_t plane = tm ? c4 : n * TPI * c4, ts = tm ? NPOS * c4 : c4;
+    const WinoStrides sm = wino_strides(tm, n, c4);
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
         const int cq = (int)(idx % c4);
         const int64_t tile = idx / c4;
         const int64_t img = tile / TPI;
-        const int tt = (int)(tile - img * TPI), ty = tt >> 1, tx = tt & 1;
-        const vec* src = reinterpret_cast<const vec*>(M) + tile * ts + cq;
-        vec m[NPOS], o[NOUT], rv[NOUT];
-#pragma unroll
-        for (int z = 0; z < NPOS; ++z) m[z] = ld_s<NT>(src + (size_t)z * plane);
-        // the residual's values are fetched with the transform-domain ones (inside the store loop each was a round trip of
-        // its own: the kernel sat 58 % of its wave cycles in s_waitcnt)
-        if (res) {
-#pragma unroll
-            for (int r = 0; r < TH; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    rv[3 * r + c] = ld_s<NT>(reinterpret_cast<const vec*>(res) + ((size_t)img * 36 + (TH * ty + r) * 6 + 3 * tx + c) * c4 + cq);
-        }
-        be::wino_out(m, o);
-        const vec bv = reinterpret_cast<const vec*>(bias)[cq];
-#pragma unroll
-        for (int r = 0; r < TH; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const size_t e = ((size_t)img * 36 + (TH * ty + r) * 6 + 3 * tx + c) * c4 + cq;
-                vec v = o[3 * r + c] + bv;
-                if (res) v += rv[3 * r + c];
-                st_s<NT>(reinterpret_cast<vec*>(y) + e, wino_act(v, act));
-            }
+        const int tt = (int)(tile - img * TPI);
+        wino_out_tiles<1>(tt, reinterpret_cast<const vec*>(M), sm, reinterpret_cast<const vec*>(bias)[cq], reinterpret_cast<const vec*>(res),
+                          img, c4, cq, act, [&](int row, int col, vec w) { *(reinterpret_cast<vec*>(y) + map_at(img, row, col, c4, cq)) = w; });
     }
 }
 
-// conv1 -> conv2 of a residual block without the intermediate map in HBM: one thread = one image x one channel quad reads the
+// conv1 -> conv2 of a residual block without the intermediate map in HBM: one thread = one image x one channel vector reads the
 // TPI x NPOS transform-domain values of conv1's result, forms the 6x6 map (+ bias, Smish) in registers and writes the TPI x NPOS
 // transform-domain values conv2's GEMMs read.  Saves the 36 values written and re-read (tile overlap) per channel.
-template <int NT, int VW = VW_OUT>
+// M as conv1's GEMMs wrote it (tm_in), V as conv2's GEMMs read it (tm_out).
+// Compiler report: 173 VGPRs, 634 SGPR spills, two waves per SIMD.
+template <int VW = VW_OUT>
 __global__ __launch_bounds__(256, VW_OUT == 2 ? 2 : 1)
 void k_wino_out_in(const float* __restrict__ M, const float* __restrict__ bias, float* __restrict__ V, int64_t n, int c4, int act,
                    int tm_in, int tm_out) {
     typedef typename VecOf<VW>::type vec;
     const int64_t total = n * c4;
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    const int64_t plane = tm_in ? c4 : n * TPI * c4, ts = tm_in ? NPOS * c4 : c4;          // M as conv1's GEMMs wrote it
-    const int64_t plane_o = tm_out ? c4 : n * TPI * c4, ts_o = tm_out ? NPOS * c4 : c4;    // V as conv2's GEMMs read it
+    const WinoStrides sm = wino_strides(tm_in, n, c4), sv = wino_strides(tm_out, n, c4);
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
         const int cq = (int)(idx % c4);
         const int64_t img = idx / c4;
-        const vec bv = reinterpret_cast<const vec*>(bias)[cq];
-        vec y[6][6];
-#pragma unroll
-        for (int ty = 0; ty < TY; ++ty)
-#pragma unroll
-            for (int tx = 0; tx < 2; ++tx) {
-                const vec* src = reinterpret_cast<const vec*>(M) + (img * TPI + ty * 2 + tx) * ts + cq;
-                vec m[NPOS], o[NOUT];
-#pragma unroll
-                for (int z = 0; z < NPOS; ++z) m[z] = ld_s<NT>(src + (size_t)z * plane);
-                be::wino_out(m, o);
-#pragma unroll
-                for (int r = 0; r < TH; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) y[TH * ty + r][3 * tx + c] = wino_act(o[3 * r + c] + bv, act);
-            }
-        wino_in_map<NT>(y, reinterpret_cast<vec*>(V) + img * TPI * ts_o + cq, ts_o, plane_o);
+        vec v[6][6];
+        wino_out_map<0>(reinterpret_cast<const vec*>(M), sm, reinterpret_cast<const vec*>(bias)[cq], (const vec*)nullptr, (vec*)nullptr,
+                        img, c4, cq, act, v);
+        wino_in_map(v, reinterpret_cast<vec*>(V), img, cq, sv);
     }
 }
 
 // Block boundary (round 13): conv2's output transform + bias + residual + activation, the store of y [N,6,6,C] (the next block's
 // 1x1 downsample reads it) AND the next block's input transform of that map out of the same registers - k_wino_out followed by
-// k_wino_in without k_wino_in's read of y (36 values per channel and map) and without its launch.  k_wino_out_pool2's register shape:
-// one thread = one image x one channel vector, M and the residual fetched together per tile; operation order as k_wino_out
-// (o + bias, + res, activation), so y and V carry that pair's bits.  M in the layout conv2's GEMMs wrote (tm_in), V in the one the
-// next block's conv1 GEMMs read (tm_out).
-// Compiler report (gfx950, NT = 1, hipcc -Rpass-analysis=kernel-resource-usage): 205 VGPRs, 0 AGPRs, scratch 0, no VGPR spills,
-// 189 SGPR spills (to VGPR lanes: the addresses), two waves per SIMD - as k_wino_out_pool2 (256 VGPRs, 274 SGPR spills, two waves)
-// and k_wino_out_in (172 VGPRs, 622 SGPR spills, two waves).
+// k_wino_in without k_wino_in's read of y (36 values per channel and map) and without its launch.  M in the layout conv2's GEMMs
+// wrote (tm_in), V in the one the next block's conv1 GEMMs read (tm_out).
 // STORE_Y = 0 (round 14, a chained block whose successor folds its downsample into conv2's GEMMs): nothing reads y, it is not stored.
-template <int NT, int VW = VW_OUT, int STORE_Y = 1>
+// Compiler report: STORE_Y = 1: 189 VGPRs, 187 SGPR spills; STORE_Y = 0: 244 VGPRs, 642 SGPR spills; two waves per SIMD both.
+template <int VW = VW_OUT, int STORE_Y = 1>
 __global__ __launch_bounds__(256, VW_OUT == 2 ? 2 : 1)
 void k_wino_out_res_in(const float* __restrict__ M, const float* __restrict__ bias, const float* __restrict__ res,
                        float* __restrict__ y, float* __restrict__ V, int64_t n, int c4, int act, int tm_in, int tm_out) {
     typedef typename VecOf<VW>::type vec;
     const int64_t total = n * c4;
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    const int64_t plane = tm_in ? c4 : n * TPI * c4, ts = tm_in ? NPOS * c4 : c4;
-    const int64_t plane_o = tm_out ? c4 : n * TPI * c4, ts_o = tm_out ? NPOS * c4 : c4;
+    const WinoStrides sm = wino_strides(tm_in, n, c4), sv = wino_strides(tm_out, n, c4);
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
         const int cq = (int)(idx % c4);
         const int64_t img = idx / c4;
-        const vec bv = reinterpret_cast<const vec*>(bias)[cq];
         vec v[6][6];
-#pragma unroll
-        for (int ty = 0; ty < TY; ++ty)
-#pragma unroll
-            for (int tx = 0; tx < 2; ++tx) {
-                const vec* src = reinterpret_cast<const vec*>(M) + (img * TPI + ty * 2 + tx) * ts + cq;
-                vec m[NPOS], o[NOUT], rv[NOUT];
-#pragma unroll
-                for (int z = 0; z < NPOS; ++z) m[z] = ld_s<NT>(src + (size_t)z * plane);
-                if (res) {
-#pragma unroll
-                    for (int r = 0; r < TH; ++r)
-#pragma unroll
-                        for (int c = 0; c < 3; ++c)
-                            rv[3 * r + c] = ld_s<NT>(reinterpret_cast<const vec*>(res) + ((size_t)img * 36 + (TH * ty + r) * 6 + 3 * tx + c) * c4 + cq);
-                }
-                be::wino_out(m, o);
-#pragma unroll
-                for (int r = 0; r < TH; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        vec w = o[3 * r + c] + bv;
-                        if (res) w += rv[3 * r + c];
-                        w = wino_act(w, act);
-                        v[TH * ty + r][3 * tx + c] = w;
-                        if constexpr (STORE_Y)
-                            st_s<NT>(reinterpret_cast<vec*>(y) + ((size_t)img * 36 + (TH * ty + r) * 6 + 3 * tx + c) * c4 + cq, w);
-                    }
-            }
-        wino_in_map<NT>(v, reinterpret_cast<vec*>(V) + img * TPI * ts_o + cq, ts_o, plane_o);
+        wino_out_map<STORE_Y>(reinterpret_cast<const vec*>(M), sm, reinterpret_cast<const vec*>(bias)[cq], reinterpret_cast<const vec*>(res),
+                              reinterpret_cast<vec*>(y), img, c4, cq, act, v);
+        wino_in_map(v, reinterpret_cast<vec*>(V), img, cq, sv);
     }
 }
 
@@ -342,16 +344,16 @@ void k_wino_out_res_in(const float* __restrict__ M, const float* __restrict__ bi
 // output row's first), writes the pooled [N,6,6,C] (layer1's 1x1 downsample reads it) and the TPI x NPOS transform-domain values of
 // that map.  The pooled values are k_maxpool_nhwc's bit for bit: its fold - from -inf over the nine taps, rows outer, columns inner,
 // a tap outside the map replaced by the nearest one inside (taken twice) - so signed zeros, infinities and dropped NaNs come out
-// as there.  Every input byte is read once, so the loads stream (NT) like the other transforms'.
-// Compiler report (gfx950, NT = 1): 126 VGPRs, 0 AGPRs, scratch 0, no VGPR spills, 90 SGPR spills, four waves per SIMD.
+// as there.  Every input byte is read once, so the loads stream like the other transforms'.
 // STORE_P = 0 (round 14): the pooled map is not stored (layer1 folds its downsample into conv2's GEMMs: nothing reads it).
-template <int NT, int VW = VW_OUT, int STORE_P = 1>
+// Compiler report: STORE_P = 1: 126 VGPRs, 90 SGPR spills, four waves per SIMD; STORE_P = 0: 162 VGPRs, 88 SGPR spills, three.
+template <int VW = VW_OUT, int STORE_P = 1>
 __global__ __launch_bounds__(256, VW_OUT == 2 ? 2 : 1)
 void k_pool_wino_in(const float* __restrict__ x, float* __restrict__ pooled, float* __restrict__ V, int64_t n, int c4, int tm_out) {
     typedef typename VecOf<VW>::type vec;
     const int64_t total = n * c4;
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    const int64_t plane_o = tm_out ? c4 : n * TPI * c4, ts_o = tm_out ? NPOS * c4 : c4;
+    const WinoStrides sv = wino_strides(tm_out, n, c4);
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
         const int cq = (int)(idx % c4);
         const int64_t img = idx / c4;
@@ -361,11 +363,11 @@ void k_pool_wino_in(const float* __restrict__ x, float* __restrict__ pooled, flo
         for (int oy = 0; oy < 6; ++oy) {
 #pragma unroll
             for (int c = 0; c < 11; ++c) {
-                row[0][c] = oy ? row[2][c] : ld_s<NT>(src + (size_t)c * c4);
-                row[1][c] = oy ? ld_s<NT>(src + (size_t)(22 * oy + c) * c4) : row[0][c];
+                row[0][c] = oy ? row[2][c] : ld_s(src + (size_t)c * c4);
+                row[1][c] = oy ? ld_s(src + (size_t)(22 * oy + c) * c4) : row[0][c];
             }
 #pragma unroll
-            for (int c = 0; c < 11; ++c) row[2][c] = oy < 5 ? ld_s<NT>(src + (size_t)(22 * oy + 11 + c) * c4) : row[1][c];
+            for (int c = 0; c < 11; ++c) row[2][c] = oy < 5 ? ld_s(src + (size_t)(22 * oy + 11 + c) * c4) : row[1][c];
 #pragma unroll
             for (int ox = 0; ox < 6; ++ox) {
                 vec m = vec(-INFINITY);
@@ -378,54 +380,31 @@ void k_pool_wino_in(const float* __restrict__ x, float* __restrict__ pooled, flo
                         for (int k = 0; k < VW; ++k) m[k] = fmaxf(m[k], row[dy][xx][k]);
                     }
                 p[oy][ox] = m;
-                if constexpr (STORE_P) st_s<NT>(reinterpret_cast<vec*>(pooled) + ((size_t)img * 36 + oy * 6 + ox) * c4 + cq, m);
+                if constexpr (STORE_P) *(reinterpret_cast<vec*>(pooled) + map_at(img, oy, ox, c4, cq)) = m;
             }
         }
-        wino_in_map<NT>(p, reinterpret_cast<vec*>(V) + img * TPI * ts_o + cq, ts_o, plane_o);
+        wino_in_map(p, reinterpret_cast<vec*>(V), img, cq, sv);
     }
 }
 
 // Last block of LocalStage: output transform + bias + residual + activation + the 2x2 max-pool that follows it
-// (models/local_stage.py:42,67: maxpool after layer3), one thread per image and channel quad: the 6x6 map exists only in
+// (models/local_stage.py:42,67: maxpool after layer3), one thread per image and channel vector: the 6x6 map exists only in
 // registers, [N,3,3,C] is written (saves the map's round trip through HBM and the pooling launch).
-template <int NT, int VW = VW_OUT>
+// Compiler report: 241 VGPRs, 265 SGPR spills, two waves per SIMD.
+template <int VW = VW_OUT>
 __global__ __launch_bounds__(256, VW_OUT == 2 ? 2 : 1)
 void k_wino_out_pool2(const float* __restrict__ M, const float* __restrict__ bias, const float* __restrict__ res,
                       float* __restrict__ y, int64_t n, int c4, int act, int tm) {
     typedef typename VecOf<VW>::type vec;
     const int64_t total = n * c4;
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    const int64_t plane = tm ? c4 : n * TPI * c4, ts = tm ? NPOS * c4 : c4;
+    const WinoStrides sm = wino_strides(tm, n, c4);
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
         const int cq = (int)(idx % c4);
         const int64_t img = idx / c4;
-        const vec bv = reinterpret_cast<const vec*>(bias)[cq];
         vec v[6][6];
-#pragma unroll
-        for (int ty = 0; ty < TY; ++ty)
-#pragma unroll
-            for (int tx = 0; tx < 2; ++tx) {
-                const vec* src = reinterpret_cast<const vec*>(M) + (img * TPI + ty * 2 + tx) * ts + cq;
-                vec m[NPOS], o[NOUT], rv[NOUT];
-#pragma unroll
-                for (int z = 0; z < NPOS; ++z) m[z] = ld_s<NT>(src + (size_t)z * plane);
-                if (res) {                                   // with the tile's loads, not one by one behind the transform
-#pragma unroll
-                    for (int r = 0; r < TH; ++r)
-#pragma unroll
-                        for (int c = 0; c < 3; ++c)
-                            rv[3 * r + c] = ld_s<NT>(reinterpret_cast<const vec*>(res) + ((size_t)img * 36 + (TH * ty + r) * 6 + 3 * tx + c) * c4 + cq);
-                }
-                be::wino_out(m, o);
-#pragma unroll
-                for (int r = 0; r < TH; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        vec w = o[3 * r + c] + bv;
-                        if (res) w += rv[3 * r + c];
-                        v[TH * ty + r][3 * tx + c] = wino_act(w, act);
-                    }
-            }
+        wino_out_map<0>(reinterpret_cast<const vec*>(M), sm, reinterpret_cast<const vec*>(bias)[cq], reinterpret_cast<const vec*>(res),
+                        (vec*)nullptr, img, c4, cq, act, v);
 #pragma unroll
         for (int py = 0; py < 3; ++py)
 #pragma unroll
@@ -434,7 +413,7 @@ void k_wino_out_pool2(const float* __restrict__ M, const float* __restrict__ bia
 #pragma unroll
                 for (int k = 0; k < VW; ++k)
                     m[k] = fmaxf(fmaxf(v[2 * py][2 * px][k], v[2 * py][2 * px + 1][k]), fmaxf(v[2 * py + 1][2 * px][k], v[2 * py + 1][2 * px + 1][k]));
-                st_s<NT>(reinterpret_cast<vec*>(y) + ((size_t)img * 9 + py * 3 + px) * c4 + cq, m);
+                *(reinterpret_cast<vec*>(y) + ((size_t)img * 9 + py * 3 + px) * c4 + cq) = m;
             }
     }
 }
@@ -1355,9 +1334,9 @@ int wino_gemms_bf6(const float* V, const float* packed_w, float* M, int64_t n, i
             if (cost < best) { best = cost; zgroups = zg; }
         }
     }
-    GemmArgs g{V, packed_w, M, (int)rows, cin, cout, tm ? NPOS * cout : cout, NPOS, m_tiles, n_tiles,
-               tm ? (int64_t)cin : rows * cin, (int64_t)cp * cin, tm ? (int64_t)cout : rows * cout, tm ? NPOS * cin : cin, 128, 0,
-               nullptr, nullptr, 0, zgroups, cp};
+    const WinoStrides sv = wino_strides(tm, n, cin), sm = wino_strides(tm, n, cout);           // in floats
+    GemmArgs g{V, packed_w, M, (int)rows, cin, cout, (int)sm.ts, NPOS, m_tiles, n_tiles, sv.plane, (int64_t)cp * cin, sm.plane, (int)sv.ts,
+               128, 0, nullptr, nullptr, 0, zgroups, cp};
     const unsigned grid = (unsigned)(8 * ((m_tiles * zgroups + 7) / 8) * n_tiles);
     {
         // (FLOPs in fp32-equivalent products: what the layer computes, not the six bf16 products the matrix pipe issues)
@@ -1404,16 +1383,17 @@ int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, in
         }
     }
     // (w: the planes; wb = floats per position of them)
-    GemmArgs g{V, packed_w + wino_u_floats(cout, cin), M, (int)rows, cin, cout, tm ? NPOS * cout : cout, NPOS, m_tiles, n_tiles,
-               tm ? (int64_t)cin : rows * cin, (int64_t)n_tiles * kchunks * (PS_BLOCK / 2), tm ? (int64_t)cout : rows * cout,
-               tm ? NPOS * cin : cin, 128, 0, nullptr, nullptr, 0, zgroups, n_tiles * 128};
+    const WinoStrides sv = wino_strides(tm, n, cin), sm = wino_strides(tm, n, cout);           // in floats
+    GemmArgs g{V, packed_w + wino_u_floats(cout, cin), M, (int)rows, cin, cout, (int)sm.ts, NPOS, m_tiles, n_tiles, sv.plane,
+               (int64_t)n_tiles * kchunks * (PS_BLOCK / 2), sm.plane, (int)sv.ts, 128, 0, nullptr, nullptr, 0, zgroups, n_tiles * 128};
     const unsigned grid = (unsigned)(8 * ((m_tiles * zgroups + 7) / 8) * n_tiles);
     if (Vx) {
+        const WinoStrides sx = wino_strides(tm, n, cin_ext);
         g.x2 = Vx;
         g.w2 = ds_planes;
-        g.xb2 = tm ? (int64_t)cin_ext : rows * cin_ext;
+        g.xb2 = sx.plane;
         g.wb2 = (int64_t)n_tiles * kext * (PS_BLOCK / 2);
-        g.lda2 = tm ? NPOS * cin_ext : cin_ext;
+        g.lda2 = (int)sx.ts;
         g.kext = kext;
         g.zext = wino_ds_mask();
         // the walk: the extended positions first, dealt one at a time round the groups that still have room, then the others - the
@@ -1627,29 +1607,11 @@ extern "C" int be_gemm_rows_bf6_f32(const float* x, int64_t m, int k, const floa
     return be::gemm_rows_bf6(x, m, k, planes, n, bias, residual, act, y, ldy, stream);
 }
 
-// The transform kernels read every byte once: non-temporal loads (default) move 5.42-5.46 TB/s where plain loads move 5.24-5.28
-// (2.65 -> 2.56 ms of transforms per step; stores: no effect; the max-pool, whose windows overlap, loses a third with them).
-// A/B knob: BE_WINO_NT = 0 plain | 1 non-temporal loads (default) | 2 non-temporal stores | 3 both
-static int wino_nt() { static const int v = getenv("BE_WINO_NT") ? atoi(getenv("BE_WINO_NT")) & 3 : 1; return v; }
-#define BE_WINO_LAUNCH(K, GRID, BLOCK, LDS, STREAM, ...)                                                        \
-    do {                                                                                                        \
-        switch (wino_nt()) {                                                                                    \
-            case 1: hipLaunchKernelGGL(K<1>, GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                     \
-            case 2: hipLaunchKernelGGL(K<2>, GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                     \
-            case 3: hipLaunchKernelGGL(K<3>, GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                     \
-            default: hipLaunchKernelGGL(K<0>, GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                    \
-        }                                                                                                       \
-    } while (0)
-// the kernels with a third template flag (k_wino_out_res_in's STORE_Y, k_pool_wino_in's STORE_P)
-#define BE_WINO_LAUNCH_FLAG(K, F, GRID, BLOCK, LDS, STREAM, ...)                                                \
-    do {                                                                                                        \
-        switch (wino_nt()) {                                                                                    \
-            case 1: hipLaunchKernelGGL((K<1, VW_OUT, F>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;        \
-            case 2: hipLaunchKernelGGL((K<2, VW_OUT, F>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;        \
-            case 3: hipLaunchKernelGGL((K<3, VW_OUT, F>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;        \
-            default: hipLaunchKernelGGL((K<0, VW_OUT, F>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;       \
-        }                                                                                                       \
-    } while (0)
+// a transform kernel over `threads` threads of its grid-stride loop, 256 to a workgroup
+template <class... P, class... A>
+static void launch_transform(void (*kernel)(P...), int64_t threads, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_cap(threads, 256)), dim3(256), 0, s, static_cast<P>(args)...);
+}
 
 extern "C" int be_wino_conv3x3_6x6_f32(const float* x, const float* packed_w, const float* packed_bias, const float* residual,
                                        float* y, int64_t n, int cin, int cout, int act, float* workspace,
@@ -1663,11 +1625,10 @@ extern "C" int be_wino_conv3x3_6x6_f32(const float* x, const float* packed_w, co
     float* V = workspace;
     float* M = workspace + (size_t)100 * n * cin;
     const int tm = wino_large(n, cout);
-    BE_WINO_LAUNCH(k_wino_in, dim3(grid_cap(n * TPI * (cin / 4), 256)), dim3(256), 0, s, x, V, n, cin / 4, tm);
+    launch_transform(k_wino_in, n * TPI * (cin / 4), s, x, V, n, cin / 4, tm);
     if (int rc = be::check_launch("be_wino_conv3x3_6x6_f32(in)")) return rc;
     if (int rc = wino_gemms(V, packed_w, M, n, cin, cout, s, stream)) return rc;
-    BE_WINO_LAUNCH(k_wino_out, dim3(grid_cap(n * TPI * (cout / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias, residual, y, n, cout / VW_OUT,
-                       act, tm);
+    launch_transform(k_wino_out<>, n * TPI * (cout / VW_OUT), s, M, packed_bias, residual, y, n, cout / VW_OUT, act, tm);
     return be::check_launch("be_wino_conv3x3_6x6_f32(out)");
 }
 
@@ -1726,14 +1687,13 @@ int be::wino_pair(const float* x, const float* packed_w1, const float* packed_bi
     }
     if (!x_in_v) {
         be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * cin * (36.0 + (double)(NPOS * TPI)), 0.0);
-        BE_WINO_LAUNCH(k_wino_in, dim3(grid_cap(n * TPI * (cin / 4), 256)), dim3(256), 0, s, x, V, n, cin / 4, tm1);
+        launch_transform(k_wino_in, n * TPI * (cin / 4), s, x, V, n, cin / 4, tm1);
     }
     if (int rc = be::check_launch("be_wino_conv3x3_pair_6x6_f32(in)")) return rc;
     if (int rc = wino_gemms(V, packed_w1, M, n, cin, cmid, s, stream)) return rc;
     {
         be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * cmid * (2.0 * NPOS * TPI), 0.0);
-        BE_WINO_LAUNCH(k_wino_out_in, dim3(grid_cap(n * (cmid / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias1, Vh, n, cmid / VW_OUT, act1,
-                           tm1, tm2);
+        launch_transform(k_wino_out_in<>, n * (cmid / VW_OUT), s, M, packed_bias1, Vh, n, cmid / VW_OUT, act1, tm1, tm2);
     }
     if (int rc = be::check_launch("be_wino_conv3x3_pair_6x6_f32(out_in)")) return rc;
     if (int rc = wino_gemms(Vh, packed_w2, M, n, cmid, cout, s, stream, ds ? V : nullptr, ds_planes, cin)) return rc;
@@ -1741,18 +1701,15 @@ int be::wino_pair(const float* x, const float* packed_w1, const float* packed_bi
         be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * cout * ((double)(NPOS * TPI) + (residual ? 36.0 : 0.0) +
                                                                                    (pool2 ? 9.0 : y ? 36.0 : 0.0) +
                                                                                    (next_cmid > 0 ? (double)(NPOS * TPI) : 0.0)), 0.0);
+        const int c4 = cout / VW_OUT, tm_next = next_cmid > 0 ? (int)wino_large(n, next_cmid) : 0;
         if (next_cmid > 0 && !y)
-            BE_WINO_LAUNCH_FLAG(k_wino_out_res_in, 0, dim3(grid_cap(n * (cout / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias2, residual, y, V,
-                                n, cout / VW_OUT, act2, tm2, (int)wino_large(n, next_cmid));
+            launch_transform(k_wino_out_res_in<VW_OUT, 0>, n * c4, s, M, packed_bias2, residual, y, V, n, c4, act2, tm2, tm_next);
         else if (next_cmid > 0)
-            BE_WINO_LAUNCH(k_wino_out_res_in, dim3(grid_cap(n * (cout / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias2, residual, y, V, n,
-                               cout / VW_OUT, act2, tm2, (int)wino_large(n, next_cmid));
+            launch_transform(k_wino_out_res_in<>, n * c4, s, M, packed_bias2, residual, y, V, n, c4, act2, tm2, tm_next);
         else if (pool2)
-            BE_WINO_LAUNCH(k_wino_out_pool2, dim3(grid_cap(n * (cout / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias2, residual, y, n,
-                               cout / VW_OUT, act2, tm2);
+            launch_transform(k_wino_out_pool2<>, n * c4, s, M, packed_bias2, residual, y, n, c4, act2, tm2);
         else
-            BE_WINO_LAUNCH(k_wino_out, dim3(grid_cap(n * TPI * (cout / VW_OUT), 256)), dim3(256), 0, s, M, packed_bias2, residual, y, n,
-                               cout / VW_OUT, act2, tm2);
+            launch_transform(k_wino_out<>, n * TPI * c4, s, M, packed_bias2, residual, y, n, c4, act2, tm2);
     }
     return be::check_launch("be_wino_conv3x3_pair_6x6_f32(out)");
 }
@@ -1813,12 +1770,11 @@ int be::pool_wino_in(const float* x, float* pooled, int64_t n, int c, int next_c
     hipStream_t s = be::as_stream(stream);
     {
         be::ProfileScope prof(s, BE_KERNEL_WINO_TRANSFORM, 0.0, 4.0 * n * c * (121.0 + (pooled ? 36.0 : 0.0) + (double)(NPOS * TPI)), 0.0);
+        const int c4 = c / VW_OUT, tm_next = (int)wino_large(n, next_cmid);
         if (pooled)
-            BE_WINO_LAUNCH(k_pool_wino_in, dim3(grid_cap(n * (c / VW_OUT), 256)), dim3(256), 0, s, x, pooled, workspace, n, c / VW_OUT,
-                               (int)wino_large(n, next_cmid));
+            launch_transform(k_pool_wino_in<>, n * c4, s, x, pooled, workspace, n, c4, tm_next);
         else
-            BE_WINO_LAUNCH_FLAG(k_pool_wino_in, 0, dim3(grid_cap(n * (c / VW_OUT), 256)), dim3(256), 0, s, x, pooled, workspace, n, c / VW_OUT,
-                                (int)wino_large(n, next_cmid));
+            launch_transform(k_pool_wino_in<VW_OUT, 0>, n * c4, s, x, pooled, workspace, n, c4, tm_next);
     }
     return be::check_launch("be_maxpool_wino_in_11x11_f32");
 }
