@@ -176,6 +176,11 @@ _SIGNATURES = {
     "be_fuse_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "be_fuse_views_f32": (C.c_int, [C.c_int, _P, _P, _P, C.c_int] + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_float)] * 3
                           + [C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [_P] * 7 + [_P]),
+    "be_tsdf_integrate_f32": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [C.POINTER(C.c_float)] * 2 + [C.c_float, C.POINTER(C.c_int)]
+                              + [C.POINTER(C.c_float)] * 2 + [C.c_float, _P, _P, _P, _P]),
+    "be_tsdf_mean_f32": (C.c_int, [C.POINTER(C.c_int), C.c_int] + [_P] * 6 + [_P]),
+    "be_tsdf_raycast_f32": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int)] + [C.POINTER(C.c_float)] * 4
+                            + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [_P] * 3 + [_P]),
     "be_depth_normals_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.c_int, C.c_float, _P, _P]),
     "be_icp_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "be_icp_linearize_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [C.POINTER(C.c_float), _P, _P, _P, C.c_int, C.c_int]
@@ -1382,6 +1387,40 @@ def reproject(depth, cam_src, cam_dst, pose, size, feat=None, near=1e-3, scale=1
 FUSE_VIEW_KEYS = ("depth", "weight", "feat", "cam_src", "pose", "scale", "window_origin")
 
 
+def _fuse_view(who, v, dev, whose):
+    """One view dict of fuse_views / tsdf_integrate, validated -> (depth [Hs,Ws], weight [Hs,Ws] or None, feat [C,Hs*Ws] or None,
+    camera float32 [4], pose float32 [12], scale, top, left), every tensor contiguous on `dev` (None: the depth's own device)."""
+    if not isinstance(v, dict) or "depth" not in v or "cam_src" not in v:
+        raise ValueError(f"{who}: a view is a dict with the keys {FUSE_VIEW_KEYS} (depth and cam_src at least)")
+    unknown = [k for k in v if k not in FUSE_VIEW_KEYS]
+    if unknown:
+        raise ValueError(f"{who}: unknown keys {unknown}; a view holds {FUSE_VIEW_KEYS}")
+    depth, (cs,), p12, top, left = _reproject_args(who, v["depth"], [("cam_src", v["cam_src"])], v.get("pose"), v.get("scale", 1),
+                                                   v.get("window_origin", (0, 0)))
+    Hs, Ws = depth.shape
+    dev = depth.device if dev is None else dev
+    if depth.device != dev:
+        raise ValueError(f"{who}: depth is on {depth.device}, {whose} on {dev}")
+    w = v.get("weight")
+    if w is not None:
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != (Hs, Ws):
+            raise ValueError(f"{who}: weight must be a float32 tensor [{Hs},{Ws}], got "
+                             f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}")
+        if w.device != dev:
+            raise ValueError(f"{who}: weight is on {w.device}, depth on {dev}")
+        w = w.contiguous()
+    f = v.get("feat")
+    if f is not None:
+        if (not isinstance(f, torch.Tensor) or f.dtype != torch.float32 or f.dim() not in (2, 3)
+                or tuple(f.shape[1:]) not in ((Hs, Ws), (Hs * Ws,))):
+            raise ValueError(f"{who}: feat must be a float32 tensor [C,{Hs},{Ws}] or [C,{Hs * Ws}], got "
+                             f"{getattr(f, 'dtype', type(f).__name__)} {tuple(getattr(f, 'shape', ()))}")
+        if f.device != dev:
+            raise ValueError(f"{who}: feat is on {f.device}, depth on {dev}")
+        f = f.reshape(f.shape[0], Hs * Ws).contiguous()
+    return depth, w, f, cs, p12, v.get("scale", 1), top, left
+
+
 def fuse_views(views, cam_dst, size, tau=0.05, min_views=1, recentre=True, peel=0, near=1e-3):
     """The depth of several views merged in one camera.  views: a list of 1..32 dicts with the keys depth [Hs,Ws] (float32 on the
     GPU, the samples of reproject), weight [Hs,Ws] or None (1 everywhere), feat [C,Hs,Ws] / [C,Hs*Ws] or None (the same C in
@@ -1423,37 +1462,10 @@ def fuse_views(views, cam_dst, size, tau=0.05, min_views=1, recentre=True, peel=
     depths, weights, feats, cams, poses, scales, tops, lefts = [], [], [], [], [], [], [], []
     dev = None
     for i, v in enumerate(views):
-        who = f"fuse_views(views[{i}])"
-        if not isinstance(v, dict) or "depth" not in v or "cam_src" not in v:
-            raise ValueError(f"{who}: a view is a dict with the keys {FUSE_VIEW_KEYS} (depth and cam_src at least)")
-        unknown = [k for k in v if k not in FUSE_VIEW_KEYS]
-        if unknown:
-            raise ValueError(f"{who}: unknown keys {unknown}; a view holds {FUSE_VIEW_KEYS}")
-        depth, (cs,), p12, top, left = _reproject_args(who, v["depth"], [("cam_src", v["cam_src"])], v.get("pose"), v.get("scale", 1),
-                                                       v.get("window_origin", (0, 0)))
-        Hs, Ws = depth.shape
-        dev = depth.device if dev is None else dev
-        if depth.device != dev:
-            raise ValueError(f"{who}: depth is on {depth.device}, the first view's on {dev}")
-        w = v.get("weight")
-        if w is not None:
-            if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != (Hs, Ws):
-                raise ValueError(f"{who}: weight must be a float32 tensor [{Hs},{Ws}], got "
-                                 f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}")
-            if w.device != dev:
-                raise ValueError(f"{who}: weight is on {w.device}, depth on {dev}")
-            w = w.contiguous()
-        f = v.get("feat")
-        if f is not None:
-            if (not isinstance(f, torch.Tensor) or f.dtype != torch.float32 or f.dim() not in (2, 3)
-                    or tuple(f.shape[1:]) not in ((Hs, Ws), (Hs * Ws,))):
-                raise ValueError(f"{who}: feat must be a float32 tensor [C,{Hs},{Ws}] or [C,{Hs * Ws}], got "
-                                 f"{getattr(f, 'dtype', type(f).__name__)} {tuple(getattr(f, 'shape', ()))}")
-            if f.device != dev:
-                raise ValueError(f"{who}: feat is on {f.device}, depth on {dev}")
-            f = f.reshape(f.shape[0], Hs * Ws).contiguous()
+        depth, w, f, cs, p12, scale, top, left = _fuse_view(f"fuse_views(views[{i}])", v, dev, "the first view's")
+        dev = depth.device
         depths.append(depth); weights.append(w); feats.append(f); cams.append(cs); poses.append(p12)
-        scales.append(v.get("scale", 1)); tops.append(top); lefts.append(left)
+        scales.append(scale); tops.append(top); lefts.append(left)
     Cs = sorted({0 if f is None else f.shape[0] for f in feats})
     if len(Cs) != 1:
         raise ValueError(f"fuse_views: every view must carry the same number of feat channels (or none), got {Cs}")
@@ -1483,6 +1495,143 @@ def fuse_views(views, cam_dst, size, tau=0.05, min_views=1, recentre=True, peel=
                                       dptr(scratch, "scratch", (torch.int64,)), dptr(d), dptr(wsum), dptr(nviews), dptr(count), dptr(layer),
                                       dptr(f if C_ else None), stream_ptr(dev)), "be_fuse_views_f32")
     return dict(depth=d, valid=layer >= 0, weight=wsum, views=nviews, count=count, layer=layer, feat=f if C_ else None)
+
+
+def tsdf_volume(dims, origin, voxel, trunc, C=0, device="cuda"):
+    """An empty truncated signed distance volume on the GPU -> volume.Volume: dims = (Nz, Ny, Nx) voxels (each in 1..1024, product
+    < 2^31), origin = (X0, Y0, Z0) the centre of voxel (0, 0, 0), voxel = (sX, sY, sZ) the spacing per axis (the pipeline's own
+    camera sees 3 cm across at 1 m with centimetres of depth noise: cubes are useless to it), trunc the truncation distance, all
+    in metres; C channels ride along.  Its sums sw int32 [Nz,Ny,Nx], swd int64 [Nz,Ny,Nx] and swf int64 [C,Nz,Ny,Nx] start at zero."""
+    from . import volume
+    dims, origin, voxel, trunc, C_ = volume.check_params("tsdf_volume", dims, origin, voxel, trunc, C)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("tsdf_volume: the volume lives on the GPU; nothing here computes on the CPU (volume.Volume is the host statement)")
+    return volume.Volume(dims, origin, voxel, trunc, C_, torch.zeros(dims, dtype=torch.int32, device=dev),
+                         torch.zeros(dims, dtype=torch.int64, device=dev), torch.zeros((C_,) + dims, dtype=torch.int64, device=dev))
+
+
+def _tsdf_state(who, vol):
+    """The volume's description as the host arrays the entries take, its sums checked -> (dims int32 [3], origin, voxel float32 [3])."""
+    from . import volume
+    import numpy as np
+    if not isinstance(vol, volume.Volume):
+        raise ValueError(f"{who}: volume must be a volume.Volume (native.tsdf_volume makes one), got {type(vol).__name__}")
+    dims, origin, voxel, trunc, C_ = volume.check_params(who, vol.dims, vol.origin, vol.voxel, vol.trunc, vol.C)
+    for name, t, dt, shape in (("sw", vol.sw, torch.int32, dims), ("swd", vol.swd, torch.int64, dims), ("swf", vol.swf, torch.int64, (C_,) + dims)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{who}: volume.{name} must be a contiguous {dt} tensor {shape} on the GPU (volume.integrate is the host "
+                             f"statement), got {getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+        if t.device != vol.sw.device:
+            raise ValueError(f"{who}: volume.{name} is on {t.device}, volume.sw on {vol.sw.device}")
+    return np.array(dims, np.int32), np.array(origin, np.float32), np.array(voxel, np.float32)
+
+
+def _iptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def tsdf_integrate(volume, views, near=1e-3):
+    """views: fuse_views' view dicts (depth, weight, feat, cam_src, pose = the view's frame -> the volume's, scale,
+    window_origin), each integrated into `volume` (native.tsdf_volume) in place, one launch per view -> volume.  A voxel takes the
+    sample its centre projects to (the nearest of the view's lattice) when that sample's depth is a finite number > 0, its weight
+    > 0 and the voxel lies no further than trunc behind it; it adds the weight, the weighted signed distance clamped to trunc and
+    the weighted channels to its integer sums (weights in 2^-8, clamped to 16; distances in trunc * 2^-15; channels in 2^-16,
+    clamped to +-2048).  Every view must carry the volume's C channels.  Each voxel is owned by one thread: no atomics, and the
+    sums depend neither on the order of the views nor on how they are grouped into calls; exact below 2^19 views.  Nothing
+    synchronises with the host.  volume.integrate is the host statement, bit for bit."""
+    dims, origin, voxel = _tsdf_state("tsdf_integrate", volume)
+    try:
+        views = list(views)
+    except TypeError:
+        raise ValueError(f"tsdf_integrate: views must be a list of dicts with the keys {FUSE_VIEW_KEYS}, got {type(views).__name__}") from None
+    try:
+        near = float(near)
+    except (TypeError, ValueError):
+        near = -1.0
+    if not 0 <= near < float("inf"):
+        raise ValueError("tsdf_integrate: near must be a finite number >= 0")
+    dev = volume.sw.device
+    checked = []
+    for i, v in enumerate(views):
+        who = f"tsdf_integrate(views[{i}])"
+        item = _fuse_view(who, v, dev, "the volume")
+        if (0 if item[2] is None else item[2].shape[0]) != volume.C:
+            raise ValueError(f"{who}: feat holds {0 if item[2] is None else item[2].shape[0]} channels, the volume {volume.C}")
+        checked.append(item)
+    o = ops()
+    for depth, w, f, cs, p12, scale, top, left in checked:
+        Hs, Ws = depth.shape
+        if o is not None:
+            o.tsdf_integrate(depth, w, f, torch.from_numpy(cs), torch.from_numpy(p12), near, scale, top, left, torch.from_numpy(origin),
+                             torch.from_numpy(voxel), volume.trunc, volume.sw, volume.swd, volume.swf)
+        else:
+            check(lib().be_tsdf_integrate_f32(dptr(depth, "depth", (torch.float32,)), dptr(w), dptr(f), volume.C, Hs, Ws, scale, top, left,
+                                              _fptr(cs), _fptr(p12), near, _iptr(dims), _fptr(origin), _fptr(voxel), volume.trunc,
+                                              dptr(volume.sw, "sw", (torch.int32,)), dptr(volume.swd, "swd", (torch.int64,)),
+                                              dptr(volume.swf if volume.C else None, "swf", (torch.int64,)), stream_ptr(dev)),
+                  "be_tsdf_integrate_f32")
+    return volume
+
+
+def tsdf_mean(volume):
+    """The means of a volume's sums -> (D [Nz,Ny,Nx] = the signed distance in units of trunc, in [-1, 1], W [Nz,Ny,Nx] = the sum
+    of the weights, Fm [C,Nz,Ny,Nx] = the weighted mean channels); D and Fm +0 where the voxel holds nothing (W == 0).
+    volume.mean is the host statement, bit for bit."""
+    dims, _, _ = _tsdf_state("tsdf_mean", volume)
+    o = ops()
+    if o is not None:
+        return tuple(o.tsdf_mean(volume.sw, volume.swd, volume.swf))
+    dev = volume.sw.device
+    D = torch.empty(volume.dims, dtype=torch.float32, device=dev)
+    W = torch.empty(volume.dims, dtype=torch.float32, device=dev)
+    Fm = torch.empty((volume.C,) + volume.dims, dtype=torch.float32, device=dev)
+    check(lib().be_tsdf_mean_f32(_iptr(dims), volume.C, dptr(volume.sw, "sw", (torch.int32,)), dptr(volume.swd, "swd", (torch.int64,)),
+                                 dptr(volume.swf if volume.C else None, "swf", (torch.int64,)), dptr(D), dptr(W),
+                                 dptr(Fm if volume.C else None), stream_ptr(dev)), "be_tsdf_mean_f32")
+    return D, W, Fm
+
+
+def tsdf_raycast(volume, cam_dst, pose, size, z_range, step=None, normals=False, normals_kw=None):
+    """The volume as the camera cam_dst sees it from `pose` (camera.pose: the camera's frame -> the volume's; None: the identity),
+    size = (Ho, Wo): every pixel's ray is sampled at z = z_near + i * step (z_range = (z_near, z_far) in metres along the optical
+    axis, 0 < z_near; step None: trunc / 4; at most 4096 samples), the signed distance is interpolated trilinearly where all 8
+    voxels about the sample hold data, and the first crossing from in front (> 0) to behind (<= 0) between two consecutive valid
+    samples is the surface, placed by linear interpolation.  -> dict(depth [Ho,Wo] = Z in the camera's frame, valid (depth > 0;
+    on the device, no sync), weight [Ho,Wo] = the interpolated sum of weights, feat [C,Ho,Wo] or None); +0 / False where no ray
+    hit.  normals=True: also normal [3,Ho,Wo] and normal_valid, depth_normals(depth, cam_dst, **normals_kw).  Runs tsdf_mean,
+    then the ray cast; nothing synchronises with the host.  volume.raycast is the host statement, bit for bit."""
+    from . import camera, volume as volume_
+    dims, origin, voxel = _tsdf_state("tsdf_raycast", volume)
+    try:
+        Ho, Wo = size
+        ok = all(not isinstance(v, bool) and int(v) == v and 1 <= v <= 1 << 24 for v in (Ho, Wo)) and Ho * Wo <= 0x7fffffff
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"tsdf_raycast: size must be (Ho, Wo), integers >= 1 with Ho * Wo < 2^31, got {size!r}")
+    Ho, Wo = int(Ho), int(Wo)
+    z_near, _, step, n = volume_.check_raycast("tsdf_raycast", z_range, step, volume.trunc)
+    cd = camera.as_pinhole(cam_dst, "tsdf_raycast(cam_dst)").f32()
+    p12 = camera.as_pose(pose, "tsdf_raycast(pose)")
+    D, W, Fm = tsdf_mean(volume)
+    dev = D.device
+    o = ops()
+    if o is not None:
+        d, w, f = o.tsdf_raycast(D, W, Fm, torch.from_numpy(origin), torch.from_numpy(voxel), torch.from_numpy(cd), torch.from_numpy(p12),
+                                 Ho, Wo, z_near, step, n)
+    else:
+        d = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
+        w = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
+        f = torch.empty(volume.C, Ho, Wo, dtype=torch.float32, device=dev)
+        check(lib().be_tsdf_raycast_f32(dptr(D), dptr(W), dptr(Fm if volume.C else None), volume.C, _iptr(dims), _fptr(origin), _fptr(voxel),
+                                        _fptr(cd), _fptr(p12), Ho, Wo, z_near, step, n, dptr(d), dptr(w), dptr(f if volume.C else None),
+                                        stream_ptr(dev)), "be_tsdf_raycast_f32")
+    out = dict(depth=d, valid=d > 0, weight=w, feat=f if volume.C else None)
+    if normals:
+        nrm = depth_normals(d, cam_dst, **dict(normals_kw or {}))
+        out.update(normal=nrm["normal"], normal_valid=nrm["valid"])
+    return out
 
 
 def depth_normals(depth, cam, step=3, max_jump=0.05, scale=1, window_origin=(0, 0)):

@@ -489,6 +489,92 @@ class DepthPipeline:
         return res
 
 
+    # ---- TSDF volumes: views integrated one at a time into a voxel grid, any camera ray-cast out of it -----------------------
+    @torch.no_grad()
+    def integrate(self, views, volume=None, dims=None, origin=None, voxel=None, trunc=0.05, want=("shpd",), source="depth_map",
+                  near=1e-3, complete_kw=None):
+        """views: a list of (maps, pose) as fuse takes them - what __call__, run_big or run_any returned for one pair, and the pose
+        of that pair's camera into the volume's frame (camera.pose; None: the identity) - integrated into a truncated signed
+        distance volume -> the volume (volume.Volume, its sums on the GPU).  volume=None makes a new one from dims = (Nz, Ny, Nx),
+        origin = (X0, Y0, Z0), voxel = (sX, sY, sZ) and trunc (native.tsdf_volume; metres; the camera sees 3 cm across at 1 m with
+        centimetres of depth noise, so the voxels want to be much longer along Z than across); passing a volume adds to it, and
+        its own `want` holds.  Samples, weights (conf) and the `want`ed maps out of native.FOLD_MAPS are taken exactly as fuse
+        takes them, each view in the camera dcal.intrinsics(H, W) of its own size; source="complete" integrates
+        complete(maps, **complete_kw)["depth_dense"] instead of depth_map.  Views may come one at a time, in any order and any
+        grouping: the sums are the same bits.  raycast renders the result."""
+        want = tuple(want)
+        if source not in ("depth_map", "complete"):
+            raise ValueError(f"integrate: source must be 'depth_map' or 'complete', got {source!r}")
+        if complete_kw and source != "complete":
+            raise ValueError(f"integrate: {sorted(complete_kw)} are keywords of complete; they need source='complete'")
+        try:
+            views = list(views)
+        except TypeError:
+            raise ValueError(f"integrate: views must be a list of (maps, pose), got {type(views).__name__}") from None
+        if not views:
+            raise ValueError("integrate: views must hold at least one (maps, pose)")
+        if volume is not None:
+            if dims is not None or origin is not None or voxel is not None:
+                raise ValueError("integrate: pass either a volume or dims, origin and voxel, not both")
+            want = tuple(volume.meta.get("want", want))
+        elif dims is None or origin is None or voxel is None:
+            raise ValueError("integrate: without a volume, dims = (Nz, Ny, Nx), origin = (X0, Y0, Z0) and voxel = (sX, sY, sZ) are needed")
+        vs, layout = [], None
+        for i, item in enumerate(views):
+            try:
+                maps, pose = item
+            except (TypeError, ValueError):
+                raise ValueError(f"integrate: views[{i}] must be (maps, pose)") from None
+            src, lat = self._depth_samples(f"integrate(views[{i}])", maps, 1, None, want + ("conf",), None)
+            g = maps["grid"]
+            cam = self.dcal.intrinsics(g["H"], g["W"])
+            z = src["depth_map"] if source == "depth_map" else self.complete(maps, **dict(complete_kw or {}))["depth_dense"]
+            Ns = z.numel()
+            feat = torch.cat([src[k].reshape(-1, Ns) for k in want]) if want else None
+            if layout is None:
+                layout = dict(want=want, channels=[(k, tuple(src[k].shape[:-2]), src[k].numel() // Ns) for k in want], camera=cam,
+                              size=(g["H"], g["W"]))
+            vs.append(dict(depth=z, weight=src["conf"].reshape(z.shape).to(torch.float32), feat=feat, cam_src=cam, pose=pose,
+                           scale=lat["scale"], window_origin=lat["window"][:2]))
+        if volume is None:
+            volume = native.tsdf_volume(dims, origin, voxel, trunc, C=sum(n for _, _, n in layout["channels"]), device=vs[0]["depth"].device)
+            volume.meta.update(layout)
+        elif "want" not in volume.meta:
+            volume.meta.update(layout)
+        return native.tsdf_integrate(volume, vs, near=near)
+
+    @torch.no_grad()
+    def raycast(self, volume, cam_dst=None, pose=None, size=None, z_range=None, step=None, normals=False, normals_kw=None):
+        """volume: what integrate returned -> the camera cam_dst at `pose` (camera.pose: the camera's frame -> the volume's; None:
+        the identity), size = (Ho, Wo), rendered out of it (native.tsdf_raycast): depth [Ho,Wo] along cam_dst's axis, valid,
+        weight (the interpolated sum of conf) and the maps the volume was integrated with, with the channel counts fuse gives
+        them; with normals=True also normal [3,Ho,Wo] and normal_valid (native.depth_normals on depth, **normals_kw).  +0 / False
+        where no ray met a surface.  Defaults: the camera and size of the first view integrated, the identity pose, z_range = the
+        extent of the volume's corners along the camera's axis under `pose`, step = trunc / 4 (at most 4096 samples: pass a
+        narrower z_range or a longer step otherwise).  The rendered view is what register takes as a frame-to-model target."""
+        meta = getattr(volume, "meta", None) or {}
+        cam_dst = meta.get("camera") if cam_dst is None else cam_dst
+        size = meta.get("size") if size is None else size
+        if cam_dst is None or size is None:
+            raise ValueError("raycast: this volume was not made by integrate: pass cam_dst and size")
+        if z_range is None:
+            import numpy as np
+            from . import volume as volume_
+            q = volume_.inverse_pose(pose).astype(np.float64)
+            ends = [(o, o + (n - 1) * s) for o, s, n in zip(volume.origin, volume.voxel, volume.dims[::-1])]
+            zs = [q[6] * x + q[7] * y + q[8] * z + q[11] for x in ends[0] for y in ends[1] for z in ends[2]]
+            z_range = (max(min(zs), min(volume.voxel)), max(zs))
+        out = native.tsdf_raycast(volume, cam_dst, pose, size, z_range, step=step, normals=normals, normals_kw=normals_kw)
+        res = {k: out[k] for k in ("depth", "valid", "weight")}
+        c = 0
+        for k, lead, n in meta.get("channels", ()):
+            res[k] = out["feat"][c:c + n].reshape(lead + tuple(out["depth"].shape))
+            c += n
+        if normals:
+            res.update(normal=out["normal"], normal_valid=out["normal_valid"])
+        return res
+
+
     # ---- registration: surface normals of a depth map, and the pose between two pairs from their depth ---------------------
     def _depth_view(self, who, maps, source, weights, complete_kw):
         """One pair as a view of native.register_depth: its depth (depth_map, or complete()'s dense depth), its weights and its

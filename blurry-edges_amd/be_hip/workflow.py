@@ -14,6 +14,7 @@ formats (argument names and defaults = utils/args.py of the reference):
     ... eval --point_cloud [--out_path DIR]                also write every pair's depth map as points in space
     ... eval --reproject CAM.npz [--out_path DIR]          also write every pair's depth and colours as the camera of CAM sees them
     ... eval --fuse FILE.npz [--out_path DIR]              also merge every V consecutive pairs, with the poses of FILE, in one camera
+                                                           (with tsdf_dims / tsdf_origin / tsdf_voxel in FILE: also in a TSDF volume)
     ... eval --normals [--out_path DIR]                    also write every pair's surface normals (of its completed depth)
     ... eval --complete [--out_path DIR]                   also write and score every pair's depth map completed to a dense one
     ... eval --complete --complete_method diffuse          ... by edge-aware diffusion instead of the nearest sample's depth
@@ -358,6 +359,17 @@ def load_fusion(path):
             if int(n) != n or not 0 <= n <= 1000:
                 raise ValueError(f"--fuse: register must be an integer number of iterations in [0, 1000], got {f['register']!r}")
             cfg["register"] = int(n)
+        if any(k in f for k in ("tsdf_dims", "tsdf_origin", "tsdf_voxel", "tsdf_trunc")):   # absent: the dict holds what it held before
+            from . import volume
+            missing = [k for k in ("tsdf_dims", "tsdf_origin", "tsdf_voxel") if k not in f]
+            if missing:
+                raise ValueError(f"--fuse: a TSDF volume needs tsdf_dims = (Nz, Ny, Nx), tsdf_origin = (X0, Y0, Z0) and tsdf_voxel = "
+                                 f"(sX, sY, sZ) (tsdf_trunc is optional: 0.05); {path} lacks {missing}")
+            dims, origin, voxel, trunc, _ = volume.check_params("--fuse(tsdf)", np.asarray(f["tsdf_dims"]).reshape(-1).tolist(),
+                                                                np.asarray(f["tsdf_origin"]).reshape(-1).tolist(),
+                                                                np.asarray(f["tsdf_voxel"]).reshape(-1).tolist(),
+                                                                one("tsdf_trunc", float) if "tsdf_trunc" in f else 0.05)
+            cfg["tsdf"] = dict(dims=dims, origin=origin, voxel=voxel, trunc=trunc)
         return cfg
 
 
@@ -406,7 +418,10 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     DepthPipeline.fuse, goes to {args.out_path}/fused_{g:04d}.npz (depth, valid, weight, views, count, layer, shpd), outside the
     timed region; a remainder of fewer than V pairs is skipped, with a printed note.  With an integer `register` > 0 in the settings
     file every view's pose is first refined against view 0 (refine_poses, that many iterations of DepthPipeline.register), and the
-    npz also holds poses_refined [V,12] and register_rms [V]; without the key the file holds what it held before.
+    npz also holds poses_refined [V,12] and register_rms [V]; without the key the file holds what it held before.  With tsdf_dims
+    = (Nz, Ny, Nx), tsdf_origin = (X0, Y0, Z0) and tsdf_voxel = (sX, sY, sZ) (and optionally tsdf_trunc, 0.05) in the settings file
+    each group is also integrated into a TSDF volume of that description, DepthPipeline.integrate, and ray-cast into view 0's
+    camera, DepthPipeline.raycast: {args.out_path}/tsdf_{g:04d}.npz (depth, valid, weight, normal, shpd), outside the timed region.
     args.normals (not in the reference): every pair's surface normals, DepthPipeline.normals(source="complete"), go to
     {args.out_path}/normals_{j:04d}.npz (normal [3,H,W], valid), outside the timed region."""
     import data, models, utils
@@ -507,6 +522,11 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
                                   depth_thres=fine_thres if fcfg["scale"] > 1 else None, **fcfg["kw"])
                 np.savez(os.path.join(args.out_path, f"fused_{j // len(group):04d}.npz"), **{k: v.cpu().numpy() for k, v in fused.items()},
                          **extra)
+                if "tsdf" in fcfg:
+                    vol = pipe.integrate(list(zip(group, gposes)), want=("shpd",), **fcfg["tsdf"])
+                    cast = pipe.raycast(vol, pose=gposes[0], normals=True)           # view 0's camera, where view 0 stands
+                    np.savez(os.path.join(args.out_path, f"tsdf_{j // len(group):04d}.npz"),
+                             **{k: cast[k].cpu().numpy() for k in ("depth", "valid", "weight", "normal", "shpd")})
                 group = []
         depth = maps["depth_map"][None]
         m = np.array(utils.eval_depth(depth, gt[None].to(depth.dtype), depth, crop=args.crop))

@@ -685,6 +685,80 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fuse_views(at::Tensor
     return {dout, wout, views, count, layer, fout};
 }
 
+// TSDF volumes: the sums sw int32 [Nz,Ny,Nx], swd int64 [Nz,Ny,Nx], swf int64 [C,Nz,Ny,Nx] on the GPU; origin, voxel [3], cam [4]
+// and pose [12] CPU float32 tensors.  tsdf_integrate adds one view to the sums in place.
+static void tsdf_dims(const Tensor& a, const char* what, int dims[3]) {
+    TORCH_CHECK(a.dim() == 3 && a.is_cuda() && a.is_contiguous(), what, ": expected a contiguous tensor [Nz,Ny,Nx] on the GPU");
+    for (int i = 0; i < 3; ++i) {
+        TORCH_CHECK(a.size(i) >= 1 && a.size(i) <= BE_TSDF_MAX_DIM, what, ": each of (Nz, Ny, Nx) must be in [1, ", BE_TSDF_MAX_DIM, "]");
+        dims[i] = (int)a.size(i);
+    }
+}
+
+static int64_t tsdf_sums(const Tensor& sw, const Tensor& swd, const Tensor& swf, const char* what, int dims[3]) {
+    tsdf_dims(sw, what, dims);
+    TORCH_CHECK(sw.scalar_type() == at::kInt && swd.scalar_type() == at::kLong && swf.scalar_type() == at::kLong, what,
+                ": sw must be int32, swd and swf int64");
+    TORCH_CHECK(swd.sizes() == sw.sizes() && swd.device() == sw.device() && swd.is_contiguous(), what, ": swd [Nz,Ny,Nx] on sw's device");
+    TORCH_CHECK(swf.dim() == 4 && swf.sizes().slice(1) == sw.sizes() && swf.device() == sw.device() && swf.is_contiguous(), what,
+                ": swf [C,Nz,Ny,Nx] on sw's device");
+    return swf.size(0);
+}
+
+void tsdf_integrate(const Tensor& depth, const c10::optional<Tensor>& weight, const c10::optional<Tensor>& feat, const Tensor& cam_src,
+                    const Tensor& pose, double near, int64_t scale, int64_t top, int64_t left, const Tensor& origin, const Tensor& voxel,
+                    double trunc, Tensor& sw, Tensor& swd, Tensor& swf) {
+    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "tsdf_integrate: depth [Hs,Ws], 1 .. 2^31 - 1 samples");
+    fp(depth, "depth");
+    int dims[3];
+    const int64_t C = tsdf_sums(sw, swd, swf, "tsdf_integrate", dims);
+    TORCH_CHECK(sw.device() == depth.device(), "tsdf_integrate: the volume and depth on one device");
+    if (weight.has_value() && weight->defined())
+        TORCH_CHECK(weight->sizes() == depth.sizes() && weight->device() == depth.device(), "tsdf_integrate: weight [Hs,Ws] on depth's device");
+    const bool has_feat = feat.has_value() && feat->defined();
+    TORCH_CHECK((has_feat ? feat->size(0) : 0) == C, "tsdf_integrate: feat must hold the volume's ", C, " channels");
+    if (has_feat)
+        TORCH_CHECK(feat->dim() == 2 && feat->size(1) == depth.numel() && feat->device() == depth.device(), "tsdf_integrate: feat [C,Hs*Ws] on depth's device");
+    check(be_tsdf_integrate_f32(depth.data_ptr<float>(), fpo(weight, "weight"), C > 0 ? fp(*feat, "feat") : nullptr, (int)C, (int)depth.size(0),
+                                (int)depth.size(1), (int)scale, (int)top, (int)left, host_floats(cam_src, 4, "tsdf_integrate(cam_src)"),
+                                host_floats(pose, 12, "tsdf_integrate(pose)"), (float)near, dims, host_floats(origin, 3, "tsdf_integrate(origin)"),
+                                host_floats(voxel, 3, "tsdf_integrate(voxel)"), (float)trunc, sw.data_ptr<int32_t>(), swd.data_ptr<int64_t>(),
+                                C > 0 ? swf.data_ptr<int64_t>() : nullptr, stream_of(depth)), "be_tsdf_integrate_f32");
+}
+
+// -> (D, W [Nz,Ny,Nx], Fm [C,Nz,Ny,Nx]) float32
+std::tuple<Tensor, Tensor, Tensor> tsdf_mean(const Tensor& sw, const Tensor& swd, const Tensor& swf) {
+    int dims[3];
+    const int64_t C = tsdf_sums(sw, swd, swf, "tsdf_mean", dims);
+    auto o = sw.options().dtype(at::kFloat);
+    Tensor D = at::empty(sw.sizes(), o), W = at::empty(sw.sizes(), o), Fm = at::empty(swf.sizes(), o);
+    check(be_tsdf_mean_f32(dims, (int)C, sw.data_ptr<int32_t>(), swd.data_ptr<int64_t>(), C > 0 ? swf.data_ptr<int64_t>() : nullptr,
+                           D.data_ptr<float>(), W.data_ptr<float>(), C > 0 ? Fm.data_ptr<float>() : nullptr, stream_of(sw)), "be_tsdf_mean_f32");
+    return {D, W, Fm};
+}
+
+// D, W [Nz,Ny,Nx], Fm [C,Nz,Ny,Nx] as tsdf_mean returns them -> (depth, weight [Ho,Wo], feat [C,Ho,Wo])
+std::tuple<Tensor, Tensor, Tensor> tsdf_raycast(const Tensor& D, const Tensor& W, const Tensor& Fm, const Tensor& origin, const Tensor& voxel,
+                                                const Tensor& cam_dst, const Tensor& pose, int64_t Ho, int64_t Wo, double z_near, double step,
+                                                int64_t n) {
+    int dims[3];
+    tsdf_dims(D, "tsdf_raycast", dims);
+    fp(D, "D");
+    fp(W, "W");
+    TORCH_CHECK(W.sizes() == D.sizes() && W.device() == D.device(), "tsdf_raycast: W [Nz,Ny,Nx] on D's device");
+    TORCH_CHECK(Fm.dim() == 4 && Fm.sizes().slice(1) == D.sizes() && Fm.device() == D.device(), "tsdf_raycast: Fm [C,Nz,Ny,Nx] on D's device");
+    TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= (1 << 24) && Wo <= (1 << 24) && Ho * Wo <= 0x7fffffff, "tsdf_raycast: bad target size");
+    TORCH_CHECK(n >= 1 && n <= BE_TSDF_MAX_STEPS, "tsdf_raycast: n must be in [1, ", BE_TSDF_MAX_STEPS, "]");
+    const int64_t C = Fm.size(0);
+    Tensor dout = at::empty({Ho, Wo}, D.options()), wout = at::empty({Ho, Wo}, D.options()), fout = at::empty({C, Ho, Wo}, D.options());
+    check(be_tsdf_raycast_f32(D.data_ptr<float>(), W.data_ptr<float>(), C > 0 ? fp(Fm, "Fm") : nullptr, (int)C, dims,
+                              host_floats(origin, 3, "tsdf_raycast(origin)"), host_floats(voxel, 3, "tsdf_raycast(voxel)"),
+                              host_floats(cam_dst, 4, "tsdf_raycast(cam_dst)"), host_floats(pose, 12, "tsdf_raycast(pose)"), (int)Ho, (int)Wo,
+                              (float)z_near, (float)step, (int)n, dout.data_ptr<float>(), wout.data_ptr<float>(),
+                              C > 0 ? fout.data_ptr<float>() : nullptr, stream_of(D)), "be_tsdf_raycast_f32");
+    return {dout, wout, fout};
+}
+
 // depth registration: normal [3,H,W] of depth [H,W]; cam [4] a CPU float32 tensor as for unproject
 Tensor depth_normals(const Tensor& depth, const Tensor& cam, int64_t step, double max_jump, int64_t scale, int64_t top, int64_t left) {
     TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "depth_normals: depth [H,W], 1 .. 2^31 - 1 samples");
@@ -900,6 +974,11 @@ TORCH_LIBRARY(be, m) {
     m.def("reproject(Tensor depth, Tensor cam_src, Tensor cam_dst, Tensor pose, float near, int Ho, int Wo, Tensor? feat, int scale, int top, int left) -> (Tensor, Tensor, Tensor)");
     m.def("fuse_views(Tensor[] depth, Tensor[] weight, Tensor[] feat, Tensor cam_src, Tensor pose, Tensor cam_dst, float near, int Ho, int Wo, "
           "int[] scale, int[] top, int[] left, float tau, int min_views, bool recentre, int peel) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("tsdf_integrate(Tensor depth, Tensor? weight, Tensor? feat, Tensor cam_src, Tensor pose, float near, int scale, int top, int left, "
+          "Tensor origin, Tensor voxel, float trunc, Tensor(a!) sw, Tensor(b!) swd, Tensor(c!) swf) -> ()");
+    m.def("tsdf_mean(Tensor sw, Tensor swd, Tensor swf) -> (Tensor, Tensor, Tensor)");
+    m.def("tsdf_raycast(Tensor D, Tensor W, Tensor Fm, Tensor origin, Tensor voxel, Tensor cam_dst, Tensor pose, int Ho, int Wo, float z_near, "
+          "float step, int n) -> (Tensor, Tensor, Tensor)");
     m.def("depth_normals(Tensor depth, Tensor cam, int step, float max_jump, int scale, int top, int left) -> Tensor");
     m.def("icp_linearize(Tensor depth_s, Tensor? weight_s, Tensor cam_src, int scale, int top, int left, Tensor depth_d, Tensor normal_d, "
           "Tensor? weight_d, Tensor cam_dst, Tensor pose, float near, float max_dist, float huber, bool rows) -> (Tensor, Tensor)");
@@ -966,6 +1045,9 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("unproject", unproject);
     m.impl("reproject", reproject);
     m.impl("fuse_views", fuse_views);
+    m.impl("tsdf_integrate", tsdf_integrate);
+    m.impl("tsdf_mean", tsdf_mean);
+    m.impl("tsdf_raycast", tsdf_raycast);
     m.impl("depth_normals", depth_normals);
     m.impl("icp_linearize", icp_linearize);
     m.impl("fill_nearest", fill_nearest);

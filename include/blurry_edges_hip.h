@@ -276,6 +276,55 @@ int be_fuse_views_f32(int V, const float* const* depth, const float* const* weig
                       void* scratch, float* depth_out, float* weight_out, int32_t* views_out, int32_t* count_out, int32_t* layer_out,
                       float* feat_out, void* stream);
 
+/* Truncated signed distance volumes: posed depth views integrated one at a time into a regular voxel grid, and any pinhole camera
+ * ray-cast out of it.  dims: 3 host ints (Nz, Ny, Nx), each in 1..BE_TSDF_MAX_DIM, product < 2^31; every volume tensor is
+ * [Nz,Ny,Nx] on the device, x fastest.  origin: 3 host floats (X0, Y0, Z0), the centre of voxel (0, 0, 0); voxel: 3 host floats
+ * (sX, sY, sZ) > 0, the spacing per axis; 0 < trunc <= 4; all in metres in the volume's frame.  The state is three sums, zero at
+ * the start and owned by the caller: sw int32 [Nz,Ny,Nx], swd int64 [Nz,Ny,Nx], swf int64 [C,Nz,Ny,Nx] (0 <= C <=
+ * BE_FUSE_MAX_CHANNELS; may be NULL when C == 0).  All float arithmetic is fp32, one rounding per operation, in the order written.
+ *
+ * be_tsdf_integrate_f32: one view into the sums.  depth [Hs,Ws], weight of the same shape or NULL (1 everywhere), feat [C,Hs*Ws] or
+ * NULL, the lattice (scale, top, left) and cam_src as for be_reproject_f32; pose: the view's frame -> the volume's frame.  On the
+ * host q = (R^T, -R^T t) is formed in double, each component of R^T t summed left to right, and rounded to 12 floats.  Per voxel
+ * (iz, iy, ix), one thread each:
+ *   x = X0 + (float) ix * sX, y = Y0 + (float) iy * sY, z = Z0 + (float) iz * sZ;
+ *   X = ((q0 x + q1 y) + q2 z) + q9, Y = ((q3 x + q4 y) + q5 z) + q10, Z = ((q6 x + q7 y) + q8 z) + q11;
+ *   u = (fx X) / Z + cx, v = (fy Y) / Z + cy;  su = floorf((u - left) * scale + 0.5f), sv = floorf((v - top) * scale + 0.5f).
+ * The voxel takes part iff Z > near; 0 <= su < Ws and 0 <= sv < Hs (tested in fp32 before any conversion; NaN fails);
+ * Zq = depth[sv * Ws + su] is a finite number > 0; w = weight[sv * Ws + su] > 0 (NaN fails; NULL: 1); sdf = Zq - Z >= -trunc; and
+ * wq = floorf(fminf(w, 16) * 256 + 0.5f) != 0.  It then adds, with dq = floorf(fminf(sdf, trunc) / trunc * 32768 + 0.5f):
+ *   sw += wq;  swd += wq * dq;  swf[c] += wq * fq[c], fq = floorf(min(max(f, -2048), 2048) * 65536 + 0.5f) (a NaN f counts as 0).
+ * A voxel that does not take part is neither read nor written.  No atomics: the sums depend neither on the order of the views nor on
+ * how they are grouped into calls, and are exact below 2^19 views (not checked).
+ *
+ * be_tsdf_mean_f32: D = (float)((double) swd / (double) sw * 2^-15) (in [-1, 1], units of trunc), W = (float)((double) sw * 2^-8),
+ * Fm[c] = (float)((double) swf[c] / (double) sw * 2^-16); D and Fm are +0 where sw == 0.  D, W [Nz,Ny,Nx], Fm [C,Nz,Ny,Nx] float32.
+ *
+ * be_tsdf_raycast_f32: D, W, Fm as be_tsdf_mean_f32 left them, seen by camera cam_dst (fy, fx, cy, cx) of Ho x Wo pixels under
+ * pose (camera frame -> volume frame).  Per pixel (v, u), one thread each:
+ *   xn = ((float) u - cx) / fx, yn = ((float) v - cy) / fy;  for i = 0 .. n - 1: z = z_near + (float) i * step;
+ *   X = xn * z, Y = yn * z;  Px = ((r0 X + r1 Y) + r2 z) + t0 (Py, Pz likewise);
+ *   gx = (Px - X0) / sX, ix = floorf(gx), fx = gx - ix (y, z likewise).
+ * The sample is valid iff 0 <= ix <= Nx - 2, 0 <= iy <= Ny - 2, 0 <= iz <= Nz - 2 (in fp32; NaN fails) and W > 0 at all 8 corners
+ * (iz + dz, iy + dy, ix + dx); an invalid sample gathers nothing further.  F is the trilinear value of D: along x
+ * c = a0 + fx * (a1 - a0) for the four corner pairs, then along y, then along z in the same form; Wt and the channels likewise.
+ * The first i whose sample and the one before are both valid with F_prev > 0 and F <= 0 is the hit, where the loop ends:
+ *   a = F_prev / (F_prev - F), depth_out = z_prev + (z - z_prev) * a, weight_out = Wt_prev + a * (Wt - Wt_prev),
+ *   feat_out[c] = Fc_prev + a * (Fc - Fc_prev).  An invalid sample resets the bracket; a crossing from behind (F_prev <= 0 < F) is
+ * walked through.  No hit: +0 in every output.  z_near > 0, so depth_out > 0 exactly on the hit pixels.  depth_out, weight_out
+ * [Ho,Wo], feat_out [C,Ho*Wo]; every output element is written exactly once.  step > 0; 1 <= n <= BE_TSDF_MAX_STEPS.
+ * Nothing synchronises with the host; everything runs on `stream`. */
+#define BE_TSDF_MAX_DIM 1024
+#define BE_TSDF_MAX_STEPS 4096
+int be_tsdf_integrate_f32(const float* depth, const float* weight, const float* feat, int C, int Hs, int Ws, int scale, int top, int left,
+                          const float* cam_src, const float* pose, float near, const int* dims, const float* origin, const float* voxel,
+                          float trunc, int32_t* sw, int64_t* swd, int64_t* swf, void* stream);
+int be_tsdf_mean_f32(const int* dims, int C, const int32_t* sw, const int64_t* swd, const int64_t* swf, float* D, float* W, float* Fm,
+                     void* stream);
+int be_tsdf_raycast_f32(const float* D, const float* W, const float* Fm, int C, const int* dims, const float* origin, const float* voxel,
+                        const float* cam_dst, const float* pose, int Ho, int Wo, float z_near, float step, int n, float* depth_out,
+                        float* weight_out, float* feat_out, void* stream);
+
 /* Depth registration: the two kernels of a point-to-plane ICP on depth maps; the loop around them is be_hip/registration.py.
  * Lattice, camera and pose arguments are be_reproject_f32's; all per-sample arithmetic is fp32, one rounding per operation.
  *
