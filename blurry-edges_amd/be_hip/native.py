@@ -936,7 +936,7 @@ def local_stage_forward_view(packed, view, patches_per_image: int, n: int, devic
 KERNEL_NAMES = {0: "k_conv_igemm<2,2,2,2,TAPS> (128x128)", 1: "k_conv_igemm<4,1,1,3,TAPS> (128x96)",
                 2: "k_conv_igemm<4,1,1,2,TAPS> (128x64)", 3: "k_conv_igemm<4,1,1,1,TAPS> (128x32)",
                 4: "k_conv_igemm<4,1,1,2,ROW8> (conv1)", 5: "k_conv_igemm small-M tiles (64x64 / 128x32)",
-                6: "k_wino_gemm<0, 1> (128x128 tiles, the Winograd transform-domain GEMMs of a layer - one per position: 40 for the 8x5 tiles - per launch, in split-bf16 arithmetic: six v_mfma_f32_32x32x16_bf16 per product, FLOPs counted as fp32 products; in LocalStage conv2's launches carry the block's 1x1 downsample as a second K segment at 18 of the 40 positions, k_wino_gemm_ps<0, 0, 1>, unless BE_WINO_DS_GEMM=1; BE_WINO_F32=1: the fp32 k_wino_gemm_ws / k_wino_gemm / batched k_conv_igemm)",
+                6: "k_wino_gemm_ps<0, 0> (128x128 tiles, the Winograd transform-domain GEMMs of a layer - one per position: 40 for the 8x5 tiles - per launch, in split-bf16 arithmetic: six v_mfma_f32_32x32x16_bf16 per product, FLOPs counted as fp32 products; in LocalStage conv2's launches carry the block's 1x1 downsample as a second K segment at 18 of the 40 positions, k_wino_gemm_ps<0, 0, 1>, unless BE_WINO_DS_GEMM=1; BE_WINO_F32=1: the fp32 k_wino_gemm_ws / k_wino_gemm / batched k_conv_igemm)",
                 7: "row GEMMs: k_wino_gemm_ps<EPI> on pre-split weights (split-bf16 arithmetic, FLOPs counted as fp32 products: fc.1, and LocalStage's 1x1 downsamples under BE_WINO_DS_GEMM=1; BE_ROWS_F32=1 / BE_WINO_F32=1: fp32) and the fp32 k_wino_gemm<1> / k_wino_gemm_ws<.., 1> (1x1 convolutions / linears of large batches)",
                 8: "k_wino_in / k_wino_out_in / k_wino_out / k_wino_out_pool2 / k_wino_out_res_in / k_pool_wino_in (Winograd transforms; the chained LocalStage runs k_pool_wino_in - the 3/2/1 max-pool with layer1's input transform - three k_wino_out_in, two k_wino_out_res_in and k_wino_out_pool2; BE_WINO_NO_CHAIN=1: k_maxpool_nhwc and a k_wino_in and k_wino_out per block)",
                 9: "k_maxpool_nhwc",

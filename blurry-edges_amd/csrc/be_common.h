@@ -4,6 +4,7 @@
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include "../../include/blurry_edges_hip.h"
 
 namespace be {
@@ -59,6 +60,12 @@ inline int device_cu_count() {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// an A/B knob of the environment: set and not 0.  Callers keep the answer in a `static const`: a knob is read once per process
+inline bool knob_on(const char* name) {
+    const char* v = getenv(name);
+    return v != nullptr && atoi(v) != 0;
+}
+
 // Opt-in per-launch timing (be_profile_* in the C ABI): when enabled, every conv launch is bracketed by two
 // pre-created hipEvents recorded on the launch stream (asynchronous; read back later).
 struct ProfileScope {
@@ -106,7 +113,7 @@ int wino_pair(const float* x, const float* packed_w1, const float* packed_bias1,
               const float* packed_ds = nullptr);
 // packed_ds (be_wino_ds_pack_f32): the block's 1x1 downsample runs as a second K segment of conv2's GEMMs, no residual
 // tensor, three workspace regions (be_wino_pair_ds_workspace_floats); y may then be null with next_cmid > 0 (not stored).
-// wino_ds_fold_enabled(): LocalStage takes that form - false under BE_WINO_DS_GEMM=1, BE_WINO_F32=1, BE_WINO_BF6_R7=1, BE_ROWS_F32=1
+// wino_ds_fold_enabled(): LocalStage takes that form - false under BE_WINO_DS_GEMM=1, BE_WINO_F32=1, BE_ROWS_F32=1
 // (read once per process).  pool_wino_in: be_maxpool_wino_in_11x11_f32; pooled may be null (the pooled map is then not stored)
 bool wino_ds_fold_enabled();
 int pool_wino_in(const float* x, float* pooled, int64_t n, int c, int next_cmid, float* workspace, size_t workspace_floats, void* stream);

@@ -215,8 +215,7 @@ void k_conv1_pool_bf6(const float* __restrict__ x4p, const float* __restrict__ w
 
 bool be::c1_bf6_enabled() {
     // A/B knobs: BE_C1_F32=1 sends only conv1 + pool back to the fp32 routing; BE_WINO_F32=1 restores fp32 everywhere
-    static const bool f32 = (getenv("BE_C1_F32") != nullptr && atoi(getenv("BE_C1_F32")) != 0) ||
-                            (getenv("BE_WINO_F32") != nullptr && atoi(getenv("BE_WINO_F32")) != 0);
+    static const bool f32 = be::knob_on("BE_C1_F32") || be::knob_on("BE_WINO_F32");
     return !f32;
 }
 

@@ -17,30 +17,23 @@
 // 18 MFMAs for 2 + 9 fragment reads, one split8 and its DMA pieces - the SAME pieces in the tap segment and in the x2 segment,
 // which is what the counted waits rely on.  Past the end of the walk the last chunk is fetched again (into slots nobody reads any
 // more), so the counts never change; the last wait drains everything: no DMA into LDS outlives the workgroup.
-// The LDS ring, two forms (template parameter RING3; no result bit depends on it):
-//   <1>, the default (round 15): three 8-KB A slots and two 9-KB B slots, 42 KB: three workgroups per CU.  The two register sets
-//        free the slot of chunk c a chunk before its MFMAs, so a ring of N slots gives a lead of N - 1 chunks: A (from HBM, or L2
-//        behind a sibling tile) keeps a lead of two chunk times, B (0.4-0.7 MB of planes shared by every tile: L2 hits) gets one.
-//        A B slot holds the 9 real pieces only - rows 96-127 of each plane, one 1-KB piece in four, are padding that no fragment
-//        read touches and are not fetched.  Per chunk the 8 A pieces go two to a wave and the 9 B pieces 3 / 2 / 2 / 2 (wave 0
-//        takes the odd one); at the top of chunk c a wave issues B(c + 2), then A(c + 3), and the wait at the top of c + 1 is
-//        "vmcnt(2)": all but the two A pieces just issued - the same count for every wave.  The invariant is written out at the
-//        prologue below.
-//   <0>, BE_BF6_RING4=1 (read once per process): rounds 10-14's ring of four 20-KB stages (80 KB: two workgroups per CU) with the
-//        DMA three chunks ahead, 5 pieces per wave and chunk (2 A + 3 B), "vmcnt(5)" = all but the newest chunk have landed.
+// The LDS ring (no result bit depends on it): three 8-KB A slots and two 9-KB B slots, 42 KB: three workgroups per CU.  The two
+// register sets free the slot of chunk c a chunk before its MFMAs, so a ring of N slots gives a lead of N - 1 chunks: A (from HBM,
+// or L2 behind a sibling tile) keeps a lead of two chunk times, B (0.4-0.7 MB of planes shared by every tile: L2 hits) gets one.
+// A B slot holds the 9 real pieces only - rows 96-127 of each plane, one 1-KB piece in four, are padding that no fragment read
+// touches and are not fetched.  Per chunk the 8 A pieces go two to a wave and the 9 B pieces 3 / 2 / 2 / 2 (wave 0 takes the odd
+// one); at the top of chunk c a wave issues B(c + 2), then A(c + 3), and the wait at the top of c + 1 is "vmcnt(2)": all but the
+// two A pieces just issued - the same count for every wave.  The invariant is written out at the prologue below.
 // The pieces live in two register sets; the next chunk's reads and split sit between this chunk's MFMAs, every gap closed by
 // __builtin_amdgcn_sched_barrier(0) (L0_CHUNK; k_wino_gemm_ps's scheme and the reasons for it: be_wino.hip).  No result bit depends
-// on it.  The emitted loop (hipcc -S, gfx950, read by hand; hipcc rotates the loop into four bodies, all alike; <0> is the parent's
-// kernel instruction for instruction):
-//   <0>  [vmcnt(5)] s_barrier, the walker's scalar arithmetic, 5 global_load_lds_dwordx4
-//   <1>  vmcnt(2) lgkmcnt(0), s_barrier, 2 global_load_lds_dwordx4 of B (a third behind a branch on the wave), the walker's scalar
-//        arithmetic, 2 global_load_lds_dwordx4 of A;  then, both alike:
+// on it.  The emitted loop (hipcc -S, gfx950, read by hand; hipcc rotates the loop into four bodies, all alike):
+//   top         vmcnt(2) lgkmcnt(0), s_barrier, 2 global_load_lds_dwordx4 of B (a third behind a branch on the wave), the walker's
+//               scalar arithmetic, 2 global_load_lds_dwordx4 of A
 //   gaps 0-4    MFMA, 2 ds_read_b128 each;  gap 5  MFMA, 1 ds_read_b128;  gaps 6-9  MFMA alone
 //   gap 10      MFMA, s_waitcnt lgkmcnt(0) (the youngest read is four MFMAs old), half A: 6 VALU + 1 s_nop
 //   gaps 11-17  MFMA, half B (5 VALU + s_nop) and half A (6 VALU + s_nop) in turn
 //   consecutive MFMAs write different accumulators (v[32:47] v[16:31] v[0:15] in turn); no v_pk_* f32 instruction, no scratch.
-// Compiler report (gfx950): <0> 166 VGPRs (one set: 123), 0 AGPRs, scratch 0, no spills, 34.2 KB of code (32.2); LDS 80 KB: two
-// workgroups per CU.  <1> 164 VGPRs (168 allocated: three waves per SIMD), 0 AGPRs, scratch 0, no VGPR or SGPR spills; LDS 42 KB:
+// Compiler report (gfx950): 164 VGPRs (168 allocated: three waves per SIMD), 0 AGPRs, scratch 0, no VGPR or SGPR spills; LDS 42 KB:
 // three workgroups per CU.
 // One body for every batch size: an output element sees the same chain of operations whatever the batch, the position in it or
 // the tile it falls in.
@@ -61,11 +54,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
-constexpr int L0_BM = 128, L0_BKT = 16, L0_STAGES = 4;
-constexpr int L0_ABYTES = L0_BM * L0_BKT * 4, L0_BBYTES = PS_BLOCK * 2, L0_STAGE = L0_ABYTES + L0_BBYTES;   // 8 KB + 12 KB
-// RING3 (the default): three A slots, then two B slots of the 9 real pieces - rows 0-95 of each plane, 3 KB a plane
+constexpr int L0_BM = 128, L0_BKT = 16;
+constexpr int L0_ABYTES = L0_BM * L0_BKT * 4, L0_BBYTES = PS_BLOCK * 2;      // an A slot: 8 KB; a chunk's block of planes in HBM: 12 KB
+// the ring: three A slots, then two B slots of the 9 real pieces - rows 0-95 of each plane, 3 KB a plane
 constexpr int L0_ASLOTS = 3, L0_BSLOTS = 2, L0_BPLANE3 = 96 * 32, L0_BBYTES3 = 3 * L0_BPLANE3;
-constexpr int L0_LDS4 = L0_STAGES * L0_STAGE, L0_LDS3 = L0_ASLOTS * L0_ABYTES + L0_BSLOTS * L0_BBYTES3;       // 80 KB, 42 KB
+constexpr int L0_LDS3 = L0_ASLOTS * L0_ABYTES + L0_BSLOTS * L0_BBYTES3;      // 42 KB
 
 struct PmBf6Args {
     const float* x;       // NHWC [N,H,W,Cin]
@@ -77,11 +70,10 @@ struct PmBf6Args {
     int64_t istride, istride2;      // floats per image in x / x2
 };
 
-template <int RING3>
-__global__ __launch_bounds__(256, RING3 ? 3 : 2)
+__global__ __launch_bounds__(256, 3)
 void k_conv_pm_bf6(PmBf6Args a) {
-    constexpr int BM = L0_BM, BKT = L0_BKT, NS = L0_STAGES, ABYTES = L0_ABYTES, BBYTES = L0_BBYTES, STAGE = L0_STAGE;
-    constexpr int BBASE3 = L0_ASLOTS * ABYTES, BBYTES3 = L0_BBYTES3, BPLANE = RING3 ? L0_BPLANE3 : 4096;
+    constexpr int BM = L0_BM, BKT = L0_BKT, ABYTES = L0_ABYTES, BBYTES = L0_BBYTES;
+    constexpr int BBASE3 = L0_ASLOTS * ABYTES, BBYTES3 = L0_BBYTES3, BPLANE = L0_BPLANE3;
     extern __shared__ __attribute__((aligned(16))) float smem_l0[];
     char* const lds = reinterpret_cast<char*>(smem_l0);
 
@@ -133,49 +125,18 @@ void k_conv_pm_bf6(PmBf6Args a) {
     }
     const float* xpix = a.x + (int64_t)img0 * a.istride + (py * a.W + px) * a.Cin;
     const float* x2pix = a.x2 ? a.x2 + (int64_t)img0 * a.istride2 + (py * a.W + px) * a.Cin2 : nullptr;
-    // B: pieces 3w .. 3w+2 of the chunk's 12-KB block, which is already the LDS image (lane-linear: this lane's 16 B)
+    // B: 1-KB pieces of the chunk's 12-KB block, whose rows 0-95 of each plane are already the LDS image (lane-linear: this lane's 16 B)
     const char* wt = reinterpret_cast<const char*>(a.planes) + lane * 16;
 
     // ---- K walk: main part (cc, valid tap j, half), then the 1x1 on x2 (16-float chunks)
     const int n_main = a.ncc * ntap * 2;
     const int total = n_main + (a.x2 ? a.Cin2 / BKT : 0);
-    int w_cc = 0, w_j = 0, w_sub = 0, w_k = 0, l_buf = 0;      // walker state of the next chunk to load and its ring slot
-#define L0_DMA()                                                                                                \
-    do {                                                                                                        \
-        char* st_ = lds + l_buf * STAGE;                                                                        \
-        const char* xs_;                                                                                        \
-        int chunk_;                                                                                             \
-        unsigned o0_, o1_;                                                                                      \
-        if (w_k < n_main) {                                                                                     \
-            const int tap_ = (int)((tap_list >> (4 * w_j)) & 15ull);                                            \
-            const int ty_ = (tap_ * 11) >> 5, tx_ = tap_ - 3 * ty_;                    /* tap / 3, tap % 3 */     \
-            xs_ = reinterpret_cast<const char*>(xpix + ((ty_ - 1) * a.W + tx_ - 1) * a.Cin + w_cc * 32 + w_sub * BKT); \
-            chunk_ = (w_cc * 9 + tap_) * 2 + w_sub;                                                             \
-            o0_ = a_off[0]; o1_ = a_off[1];                                                                     \
-        } else {                                                                                                \
-            const int k2_ = w_k - n_main;                                                                       \
-            xs_ = reinterpret_cast<const char*>(x2pix + k2_ * BKT);                                             \
-            chunk_ = a.ncc * 18 + k2_;                                                                          \
-            o0_ = a_off2[0]; o1_ = a_off2[1];                                                                   \
-        }                                                                                                       \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t)(xs_ + o0_), (lds_ptr_t)(st_ + (2 * wave) * 1024), 16, 0, 0);     \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t)(xs_ + o1_), (lds_ptr_t)(st_ + (2 * wave + 1) * 1024), 16, 0, 0); \
-        const char* ws_ = wt + (int64_t)chunk_ * BBYTES;                                                        \
-        _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                        \
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(ws_ + (3 * wave + p_) * 1024),                         \
-                                             (lds_ptr_t)(st_ + ABYTES + (3 * wave + p_) * 1024), 16, 0, 0);     \
-        if (w_k + 1 < total) {                         /* past the end: the last chunk again */                  \
-            ++w_k;                                                                                              \
-            if (++w_sub == 2) { w_sub = 0; if (++w_j == ntap) { w_j = 0; ++w_cc; } }                            \
-        }                                                                                                       \
-        l_buf = (l_buf + 1) % NS;                                                                               \
-    } while (0)
-
-    // RING3: A and B are fetched apart - B(c + 2), then A(c + 3).  The walker belongs to A; B's block is the walker's chunk one A
+    int w_cc = 0, w_j = 0, w_sub = 0, w_k = 0;         // walker state of the next chunk to load
+    // A and B are fetched apart - B(c + 2), then A(c + 3).  The walker belongs to A; B's block is the walker's chunk one A
     // fetch ago (b_chunk).  A: pieces 2w, 2w+1 as above.  B: the 9 real pieces b = 3 plane + (32-row piece) dealt b = w, w + 4 and
     // b = 8 to wave 0 - 3 pieces for wave 0, 2 for the others; piece b is piece 4 (b / 3) + b % 3 of the block (every fourth is the
     // padding rows 96-127, which no fragment read touches: not fetched).
-    [[maybe_unused]] int b_chunk = 0, l_a = 0, l_b = 0;
+    int b_chunk = 0, l_a = 0, l_b = 0;                 // ... and the ring slots the next A and B fetches fill
 #define L0_DMA_A()                                                                                              \
     do {                                                                                                        \
         char* st_ = lds + l_a * ABYTES;                                                                         \
@@ -218,7 +179,7 @@ void k_conv_pm_bf6(PmBf6Args a) {
     const int fsw = (li >> 2) & 3;
     const int a_fr0 = ((wave * 32 + li) * BKT + 4 * ((2 * lh) ^ fsw)) * 4;
     const int a_fr1 = ((wave * 32 + li) * BKT + 4 * ((2 * lh + 1) ^ fsw)) * 4;
-    const int b_fr = (RING3 ? 0 : ABYTES) + li * 32 + ps_slot(li, lh) * 16;
+    const int b_fr = li * 32 + ps_slot(li, lh) * 16;
     f32x16 acc[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j)
@@ -230,8 +191,7 @@ void k_conv_pm_bf6(PmBf6Args a) {
     // behind body 0.
     u32x4 ap[2][3];                                    // [set][hi, mid, lo], one dword per pair unit
     bf16x8 bp[2][3][3];                                // [set][hi, mid, lo][j]
-    int r_buf = 0;                                     // ring slot whose fragments are read next (RING3: A's slot)
-    [[maybe_unused]] int r_b = 0;                      // RING3: B's slot
+    int r_buf = 0, r_b = 0;                            // the A slot and the B slot whose fragments are read next
     // One chunk: 18 groups, each closed by a sched_barrier(0) (nothing crosses it, so the order below is the emitted order).
     // Group g issues MFMA g - product p = g / 3 (lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi), accumulator j = g % 3: consecutive
     // MFMAs never share an accumulator - and, for chunk + 1 out of ring slot r_buf into set S ^ 1:
@@ -243,8 +203,8 @@ void k_conv_pm_bf6(PmBf6Args a) {
 #define L0_CHUNK(S)                                                                                             \
     do {                                                                                                        \
         constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};                                   \
-        const char* sb_ = lds + r_buf * (RING3 ? ABYTES : STAGE);                                               \
-        const char* sw_ = RING3 ? lds + BBASE3 + r_b * BBYTES3 : sb_;                                           \
+        const char* sb_ = lds + r_buf * ABYTES;                                                                 \
+        const char* sw_ = lds + BBASE3 + r_b * BBYTES3;                                                         \
         f32x4 af_[2];                                  /* [quad] */                                             \
         float r0_[4], r1_[4];                                                                                   \
         _Pragma("unroll") for (int g_ = 0; g_ < 18; ++g_) {                                                     \
@@ -273,31 +233,24 @@ void k_conv_pm_bf6(PmBf6Args a) {
             }                                                                                                   \
             __builtin_amdgcn_sched_barrier(0);                                                                  \
         }                                                                                                       \
-        if constexpr (RING3) { r_buf = r_buf == L0_ASLOTS - 1 ? 0 : r_buf + 1; r_b ^= 1; }                      \
-        else r_buf = (r_buf + 1) % NS;                                                                          \
+        r_buf = r_buf == L0_ASLOTS - 1 ? 0 : r_buf + 1;                                                         \
+        r_b ^= 1;                                                                                               \
     } while (0)
 
     __builtin_amdgcn_sched_barrier(0);                 // (the bias loads are older than every DMA: no count below depends on them)
-    if constexpr (RING3) {
-        // The ring invariant.  A wave's DMA pieces in issue order (nB = 3 for wave 0, 2 for the others; nA = 2):
-        //   A(0) B(0) A(1) B(1) A(2) | B(2) A(3) | B(3) A(4) | ... : the prologue, then "B(c + 2) A(c + 3)" at the top of chunk c.
-        // vmcnt counts a wave's own pieces, oldest first, so "vmcnt(2)" = all but the A pieces just issued have landed:
-        //   here           in flight A(2);      landed: chunks 0 and 1
-        //   top of c + 1   in flight A(c + 3);  landed: B(c + 2), A(c + 2) and everything older - chunk c + 2, whose fragments
-        //                  are read during chunk c + 1.  Nothing less would do: B(c + 2) is the youngest piece that must be in LDS.
-        // Slots: A(c + 3) goes to A slot c % 3 and B(c + 2) to B slot c % 2, the slots of chunk c, whose fragments every wave read
-        // during chunk c - 1 (two register sets) and holds in registers before it passes the barrier at the top of c (lgkmcnt(0)
-        // there).  Chunk c + 1, read during chunk c, sits in A slot (c + 1) % 3 and B slot (c + 1) % 2: neither is written then.
-        L0_DMA_A(); L0_DMA_B();                        // chunk 0
-        L0_DMA_A(); L0_DMA_B();                        // chunk 1
-        L0_DMA_A();                                    // A of chunk 2
-        __builtin_amdgcn_s_waitcnt(0x0F72);            // vmcnt(2): chunks 0 and 1 have landed
-    } else {
-        L0_DMA();                                      // chunk 0
-        L0_DMA();                                      // chunk 1
-        L0_DMA();                                      // chunk 2
-        __builtin_amdgcn_s_waitcnt(0x0F75);            // vmcnt(5): chunks 0 and 1 have landed
-    }
+    // The ring invariant.  A wave's DMA pieces in issue order (nB = 3 for wave 0, 2 for the others; nA = 2):
+    //   A(0) B(0) A(1) B(1) A(2) | B(2) A(3) | B(3) A(4) | ... : the prologue, then "B(c + 2) A(c + 3)" at the top of chunk c.
+    // vmcnt counts a wave's own pieces, oldest first, so "vmcnt(2)" = all but the A pieces just issued have landed:
+    //   here           in flight A(2);      landed: chunks 0 and 1
+    //   top of c + 1   in flight A(c + 3);  landed: B(c + 2), A(c + 2) and everything older - chunk c + 2, whose fragments
+    //                  are read during chunk c + 1.  Nothing less would do: B(c + 2) is the youngest piece that must be in LDS.
+    // Slots: A(c + 3) goes to A slot c % 3 and B(c + 2) to B slot c % 2, the slots of chunk c, whose fragments every wave read
+    // during chunk c - 1 (two register sets) and holds in registers before it passes the barrier at the top of c (lgkmcnt(0)
+    // there).  Chunk c + 1, read during chunk c, sits in A slot (c + 1) % 3 and B slot (c + 1) % 2: neither is written then.
+    L0_DMA_A(); L0_DMA_B();                            // chunk 0
+    L0_DMA_A(); L0_DMA_B();                            // chunk 1
+    L0_DMA_A();                                        // A of chunk 2
+    __builtin_amdgcn_s_waitcnt(0x0F72);                // vmcnt(2): chunks 0 and 1 have landed
     __builtin_amdgcn_s_barrier();                      // ... every wave's
     {                                                  // chunk 0's pieces into set 0, in one piece
         const f32x4 af0_ = *reinterpret_cast<const f32x4*>(lds + a_fr0);
@@ -306,7 +259,7 @@ void k_conv_pm_bf6(PmBf6Args a) {
         for (int p = 0; p < 3; ++p)
 #pragma unroll
             for (int j = 0; j < 3; ++j)
-                bp[0][p][j] = *reinterpret_cast<const bf16x8*>(lds + (RING3 ? BBASE3 : 0) + b_fr + p * BPLANE + j * 32 * 32);
+                bp[0][p][j] = *reinterpret_cast<const bf16x8*>(lds + BBASE3 + b_fr + p * BPLANE + j * 32 * 32);
         bf16x8 h, m, l;
         split8(af0_, af1_, h, m, l);
         ap[0][0] = __builtin_bit_cast(u32x4, h);
@@ -318,19 +271,12 @@ void k_conv_pm_bf6(PmBf6Args a) {
     bool landed = true;                                // the NEXT chunk's DMA is known to be in LDS
 #define L0_TOP()                                                                                                \
     do {                                                                                                        \
-        if constexpr (RING3) {                                                                                  \
-            if (!landed) __builtin_amdgcn_s_waitcnt(0x0072);   /* vmcnt(2): all but A(chunk + 2): chunk + 1 has landed; lgkmcnt(0) */ \
-            else __builtin_amdgcn_s_waitcnt(0xC07F);           /* lgkmcnt(0): this chunk's fragments are in registers */ \
-            landed = false;                                                                                     \
-            __builtin_amdgcn_s_barrier();              /* ... every wave's; everyone holds this chunk's fragments */ \
-            L0_DMA_B();                                /* B of chunk + 2, into this chunk's B slot */           \
-            L0_DMA_A();                                /* A of chunk + 3, into this chunk's A slot */           \
-        } else {                                                                                                \
-            if (!landed) __builtin_amdgcn_s_waitcnt(0x0F75);                           /* vmcnt(5): chunk + 1 has landed */ \
-            landed = false;                                                                                     \
-            __builtin_amdgcn_s_barrier();              /* ... every wave's; everyone has read the slot of chunk - 1 (a chunk ago) */ \
-            L0_DMA();                                  /* chunk + 3, into that slot */                          \
-        }                                                                                                       \
+        if (!landed) __builtin_amdgcn_s_waitcnt(0x0072);   /* vmcnt(2): all but A(chunk + 2): chunk + 1 has landed; lgkmcnt(0) */ \
+        else __builtin_amdgcn_s_waitcnt(0xC07F);           /* lgkmcnt(0): this chunk's fragments are in registers */ \
+        landed = false;                                                                                         \
+        __builtin_amdgcn_s_barrier();                  /* ... every wave's; everyone holds this chunk's fragments */ \
+        L0_DMA_B();                                    /* B of chunk + 2, into this chunk's B slot */           \
+        L0_DMA_A();                                    /* A of chunk + 3, into this chunk's A slot */           \
         __builtin_amdgcn_sched_barrier(0);                                                                      \
     } while (0)
     for (int kc = 0; kc < total; kc += 2) {
@@ -344,7 +290,6 @@ void k_conv_pm_bf6(PmBf6Args a) {
         }
     }
 #undef L0_TOP
-#undef L0_DMA
 #undef L0_DMA_A
 #undef L0_DMA_B
 #undef L0_CHUNK
@@ -392,8 +337,7 @@ inline bool shape_ok(int cout, int cin, int cin2) {
 
 bool be::l0_bf6_enabled() {
     // A/B knobs: BE_L0_F32=1 sends only layer0 back to the fp32 kernels; BE_WINO_F32=1 restores fp32 everywhere
-    static const bool f32 = (getenv("BE_L0_F32") != nullptr && atoi(getenv("BE_L0_F32")) != 0) ||
-                            (getenv("BE_WINO_F32") != nullptr && atoi(getenv("BE_WINO_F32")) != 0);
+    static const bool f32 = be::knob_on("BE_L0_F32") || be::knob_on("BE_WINO_F32");
     return !f32;
 }
 
@@ -437,12 +381,9 @@ int be::conv3x3_pm_bf6(const be_conv_desc* d, const float* x, const float* x2, i
     const int64_t grid = (int64_t)8 * ((a.groups + 7) / 8) * a.HW;
     BE_REQUIRE(grid < ((int64_t)1 << 31), "be_conv3x3_pm_bf6_f32: too many tiles (n %d, %d x %d)", d->n, d->h, d->w);
     hipStream_t s = be::as_stream(stream);
-    // A/B knob BE_BF6_RING4=1 (read once per process): the four-stage ring, two workgroups per CU.  No result bit depends on it.
-    static const bool ring4 = getenv("BE_BF6_RING4") != nullptr && atoi(getenv("BE_BF6_RING4")) != 0;
-    const size_t lds = ring4 ? (size_t)L0_LDS4 : (size_t)L0_LDS3;
-    static be::DeviceFlags attr_set{}, attr_set4{};         // dynamic-LDS cap raised once per device (thread-safe)
-    if (int rc_ = ring4 ? be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_conv_pm_bf6<0>), lds, attr_set4)
-                        : be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_conv_pm_bf6<1>), lds, attr_set)) return rc_;
+    const size_t lds = L0_LDS3;
+    static be::DeviceFlags attr_set{};                      // dynamic-LDS cap raised once per device (thread-safe)
+    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_conv_pm_bf6), lds, attr_set)) return rc_;
     {   // algorithmic work: 2*M*K*Cout with the real K, in fp32-equivalent products; executed: the chunks the tiles visit x 2*BM*96*16
         const double M = (double)a.Nimg * a.HW, k_real = 9.0 * a.Cin, k2 = (double)a.Cin2;
         double chunks = 0.0;
@@ -456,8 +397,7 @@ int be::conv3x3_pm_bf6(const be_conv_desc* d, const float* x, const float* x2, i
         be::ProfileScope prof(s, BE_KERNEL_CONV_128x96, 2.0 * M * (k_real + k2) * a.Cout,
                               4.0 * (M * (a.Cin + k2) + M * a.Cout) + 6.0 * (k_real + k2) * 128,
                               chunks * 2.0 * L0_BM * 96 * 16);
-        if (ring4) hipLaunchKernelGGL(k_conv_pm_bf6<0>, dim3((unsigned)grid), dim3(256), lds, s, a);
-        else hipLaunchKernelGGL(k_conv_pm_bf6<1>, dim3((unsigned)grid), dim3(256), lds, s, a);
+        hipLaunchKernelGGL(k_conv_pm_bf6, dim3((unsigned)grid), dim3(256), lds, s, a);
     }
     return be::check_launch("be_conv3x3_pm_bf6_f32");
 }

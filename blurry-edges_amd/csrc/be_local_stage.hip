@@ -7,7 +7,7 @@
 // the chained Winograd pair (40 GEMMs, output+input transform, 40 GEMMs - the 1x1 downsample a second K segment of 18 of them, over
 // the block's own input transform -, output transform - layers 1 and 2's with the next layer's input transform in it, layer3's with
 // the 2x2 max-pool in it; be_wino.hip), fc.1, fc.4: 21 launches.  BE_WINO_DS_GEMM=1 (read once per process; also BE_ROWS_F32=1,
-// BE_WINO_F32=1, BE_WINO_BF6_R7=1): the downsample as its own 1x1 launch in front of each pair, joined behind conv2's output transform
+// BE_WINO_F32=1): the downsample as its own 1x1 launch in front of each pair, joined behind conv2's output transform
 // (24 launches; round 13's bits).
 // BE_WINO_NO_CHAIN=1 (read once per process): the unchained launches - k_maxpool_nhwc, and every layer from k_wino_in to
 // k_wino_out - with the same bits.  Sub-batches of 512 patches and more take the LDS-DMA kernels (be_conv_pm.hip for conv1 on a
@@ -15,7 +15,7 @@
 // results bit for bit.  On the Winograd path the 1x1 downsamples of layers 1-3 and fc.1 run in split-bf16 arithmetic on ONE kernel for
 // every sub-batch size (be::gemm_rows_bf6; BE_ROWS_F32=1 / BE_WINO_F32=1: the fp32 kernels just named), and so does layer0
 // (be::conv3x3_pm_bf6, be_conv_pm_bf6.hip; BE_L0_F32=1 / BE_WINO_F32=1: the fp32 kernels; its LDS ring is 42 KB, three workgroups
-// per CU - BE_BF6_RING4=1, read once per process: the 80-KB ring at two per CU, the same bits), and so do conv1 + the first pool
+// per CU), and so do conv1 + the first pool
 // (be_conv1_pool_bf6.hip on the row-padded staging; BE_C1_F32=1 / BE_WINO_F32=1: the fp32 routing by sub-batch size).  No allocation, no
 // synchronisation, no process-wide state: graph-capturable, re-entrant.  opts->winograd = 0 runs layers 1-3 as direct launches
 // like layer0, all in fp32.

@@ -1,10 +1,16 @@
 // Split-bf16 (bf16x6) operand helpers shared by the kernels that multiply fp32 operands on v_mfma_f32_32x32x16_bf16
-// (be_wino.hip: k_wino_gemm<., 1>, k_wino_gemm_ps; be_conv_pm_bf6.hip: k_conv_pm_bf6; be_conv1_pool_bf6.hip: k_conv1_pool_bf6).
+// (be_wino.hip: k_wino_gemm_ps; be_conv_pm_bf6.hip: k_conv_pm_bf6; be_conv1_pool_bf6.hip: k_conv1_pool_bf6).
 //
 // x = hi + mid + lo exactly, each a bf16 rounded to nearest-even from what is left: |mid| <= 2^-8 |x|, |lo| <= 2^-16 |x| (finite x
 // whose lo stays a bf16 normal, |x| >= ~2^-110; below that lo loses bits to the bf16 subnormal grid, an absolute error < 2^-133).
 // A product of two split operands is the six bf16 MFMAs of all pieces but mid.lo, lo.mid, lo.lo (<= 3 x 2^-24 relative), in fp32
-// accumulation.  Inf / NaN: hi keeps them, x - hi is NaN, so the products stay non-finite.  The residuals are formed with plain
+// accumulation.  The arithmetic every kernel above keeps, bit for bit (a = the A operand's pieces, b = B's):
+//   - per 16-deep K chunk and accumulator the six products in the order a_lo.b_hi, a_hi.b_lo, a_mid.b_mid, a_mid.b_hi, a_hi.b_mid,
+//     a_hi.b_hi - the small ones first - each one v_mfma_f32_32x32x16_bf16 into the same fp32 accumulator;
+//   - the MFMA's operand map: lane (li = lane & 31, lh = lane >> 5) holds row li's values k = 8 lh .. 8 lh + 7 of the chunk, so a
+//     fragment is the two fp32 quads 2 lh and 2 lh + 1 of the row, split by split8 (B: at pack time, k_wino_pack_split);
+//   - the K chunks ascending, from a zero accumulator per output tile (a second K segment follows the first).
+// Inf / NaN: hi keeps them, x - hi is NaN, so the products stay non-finite.  The residuals are formed with plain
 // v_sub_f32: hipcc's SLP pass otherwise packs them into v_pk_add_f32, which beside MFMAs costs more issue than two scalar ops.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -15,14 +15,13 @@
 //   k_wino_pack_split  U -> its hi / mid / lo bf16 planes behind it, in k_wino_gemm_ps's LDS image (round 8)
 //   k_wino_in      x [N,6,6,C] NHWC -> V: tile-major [TPI N][NPOS][C] for large batches, plane-major [NPOS][TPI N][C] for small ones
 //                  (HBM-bound: reads 36, writes TPI * NPOS = 80 values per channel)
-//   k_wino_gemm    M[xi] = V[xi] U[xi]^T for the NPOS positions xi: one workgroup per 128x128 tile walks a group of them.
-//                  <0, 1>: split-bf16, every batch size (tile-major buffers for large batches, plane-major for small ones), both
-//                  operands split in the loop (round 7; BE_WINO_BF6_R7=1)
-//   k_wino_gemm_ps the same GEMMs and bits with B's pieces read ready from the planes, a 3-stage ring, counted waits (the default)
+//   k_wino_gemm_ps M[xi] = V[xi] U[xi]^T for the NPOS positions xi in split-bf16, every batch size (tile-major buffers for large
+//                  batches, plane-major for small ones): one workgroup per 128x128 tile walks a group of the positions; A split in
+//                  the loop, B's pieces read ready from the planes, a ring of four stages, counted waits
 //                  <EPI, 1> (round 9): the same loop as a plain row GEMM on pre-split planes of a packed matrix - LocalStage's 1x1
 //                  downsamples (raw accumulators) and fc.1 (bias + Smish), every batch size; BE_ROWS_F32=1: the fp32 kernels
-//                  fp32 (BE_WINO_F32=1): <0, 0> for large batches, all positions per workgroup; small ones go through
-//                  be_conv_nhwc_batched_f32 on k_conv_igemm, same arithmetic per output element
+//   k_wino_gemm    fp32 (BE_WINO_F32=1): <0> the same GEMMs for large batches, all positions per workgroup; small ones go through
+//                  be_conv_nhwc_batched_f32 on k_conv_igemm, same arithmetic per output element.  <1>: be::gemm_rows
 //   k_wino_gemm_ws the fp32 GEMMs weight-stationary (B tile in registers, A streamed through LDS by DMA): batches of >= 4096 maps
 //   k_wino_out     M -> y [N,6,6,Cout] + bias (+ residual) (+ Smish)
 //   k_wino_out_in  conv1 -> conv2 of a residual block: output transform + Smish + input transform, the map stays in registers
@@ -451,8 +450,9 @@ struct GemmArgs {
     const float* bias;    // EPI = 1: y = act(acc + bias[col] (+ res[row][col]))
     const float* res;     //          same row stride as y
     int act;
-    int zgroups;          // BF6: problem groups (one workgroup per M tile x N tile x group)
-    int npad;             // BF6: rows of w that exist (Npad; B rows past it load row 0 of the tile and are never stored)
+    int zgroups;          // k_wino_gemm_ps: problem groups (one workgroup per M tile x N tile x group walks ceil(nb / zgroups) problems;
+                          // every output element sees the same K loop, so the group count changes no bit)
+    int npad;             // k_wino_gemm_ps: rows of w's planes, 128 n_tiles (zero past Npad): every B piece a tile fetches exists
     // k_wino_gemm_ps<0, 0, 1> (round 14): a second K segment at the positions of the mask zext - problem z accumulates x[z] w[z]^T
     // over K and then, where bit z is set, x2[z] w2[e]^T over 16 kext more (e: the number of set bits below z), into one accumulator.
     const float* x2;      // rows [M][16 kext] at x2 + z * xb2, lda2 floats between rows
@@ -463,7 +463,7 @@ struct GemmArgs {
     uint64_t ztab[4];     // the walk: group g takes the positions number g zper .. of this table, 6 bits each, ten to a word
 };
 
-// ---- split-bf16 operands (BF6 = 1) --------------------------------------------------------------------------------------------
+// ---- split-bf16 operands --------------------------------------------------------------------------------------------------------
 // x = hi + mid + lo, the six products per K chunk and split8: be_split_bf16.h (shared with be_conv_pm_bf6.hip)
 using be::bf6::bf16x8;
 using be::bf6::u32x4;
@@ -472,7 +472,7 @@ using be::bf6::PS_BLOCK;
 using be::bf6::ps_slot;
 
 // ---- the weights pre-split (round 8) -------------------------------------------------------------------------------------------
-// k_wino_pack_split writes the hi / mid / lo pieces of U behind it, formed by split8 - the very pieces k_wino_gemm<0, 1> forms in
+// k_wino_pack_split writes the hi / mid / lo pieces of U behind it, formed by split8 - as k_wino_gemm_ps forms A's in
 // registers - in the image k_wino_gemm_ps's LDS stage holds: per (position, 128-row N tile, 16-deep K chunk) one contiguous 12-KB
 // block [plane hi, mid, lo][128 rows][2 x 16 B], the 16-B half h of a row (k = 8 h .. 8 h + 7) at slot h ^ ((row >> 3) & 1).  With
 // the swap a ds_read_b128 of one half for 32 rows puts each 16-lane group (rows 0-3, 12-15, 20-27 / 4-11, 16-19, 28-31) on 16
@@ -503,12 +503,8 @@ __global__ void k_wino_pack_split(const float* __restrict__ U, int npos, int cou
     }
 }
 
-// EPI: 0 = raw Winograd problems, 1 = row GEMM with bias / residual / activation (fp32 only).
-// BF6 = 1: the split-bf16 arithmetic of the Winograd GEMMs (v_mfma_f32_32x32x16_bf16, six products per 16-deep K chunk, in the
-// fixed order lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi), fp32 operands in memory and LDS, split after the fragment read.
-// The workgroup walks a group of problems rather than all of them (a.zgroups groups: the 40 problems of a 4096-patch layer are
-// only 64 x 2-3 tiles otherwise); every output element still sees the same K loop, so the group count changes no bit.
-template <int EPI, int BF6 = 0>
+// EPI: 0 = raw Winograd problems, 1 = row GEMM with bias / residual / activation.
+template <int EPI>
 __global__ __launch_bounds__(256, 3)
 void k_wino_gemm(GemmArgs a) {
     constexpr int BM = 128, BN = 128, BKT = 16;
@@ -517,16 +513,7 @@ void k_wino_gemm(GemmArgs a) {
     const int bid = blockIdx.x;
     const int xcd = bid & 7, slot = bid >> 3;          // all N tiles of an M tile on one XCD
     const int n_tile = slot % a.n_tiles;
-    int m_tile = (slot / a.n_tiles) * 8 + xcd;
-    if constexpr (BF6) {                               // unit -> (M tile, problem group): the groups of an M tile on one XCD too
-        const int zg = m_tile % a.zgroups, zper = (a.nb + a.zgroups - 1) / a.zgroups;
-        m_tile /= a.zgroups;
-        if (m_tile >= a.m_tiles || zg * zper >= a.nb) return;
-        a.x += (int64_t)zg * zper * a.xb;
-        a.w += (int64_t)zg * zper * a.wb;
-        a.y += (int64_t)zg * zper * a.yb;
-        a.nb = min(zper, a.nb - zg * zper);
-    }
+    const int m_tile = (slot / a.n_tiles) * 8 + xcd;
     if (m_tile >= a.m_tiles) return;
     const int n0 = n_tile * BN, row_base = m_tile * a.mrows;
     const int tid = threadIdx.x;
@@ -543,15 +530,13 @@ void k_wino_gemm(GemmArgs a) {
         // (walked tiles, zrows > 0, are launched only when every tile is full: M % (128 nb) == 0)
         a_off[p] = (unsigned)((row_base + r < a.M ? r : 0) * a.lda + 4 * sq) * 4u;
         b_off[p] = (unsigned)(r * a.K + 4 * sq) * 4u;  // rows up to Npad exist (zero rows past N)
-        if (BF6 && n0 + r >= a.npad) b_off[p] = (unsigned)(4 * sq) * 4u;   // (small layers: Npad need not be a multiple of 128)
     }
     const float* xt = a.x + (int64_t)row_base * a.lda; // uniform
     const float* wt = a.w + (int64_t)n0 * a.K;
     const int kchunks = a.K / BKT, total = kchunks * a.nb;
     // fragment reads: row = 64 wm + 32 i + li, quad (lh + 2 g) ^ ((li >> 2) & 3)
-    // (BF6: k = 8 lh .. 8 lh + 7, the quads 2 lh and 2 lh + 1 - the bf16 operand map; conflict-free for the same reason)
     const int fsw = (li >> 2) & 3;
-    const int q0 = BF6 ? 2 * lh : lh, q1 = BF6 ? 2 * lh + 1 : lh + 2;
+    const int q0 = lh, q1 = lh + 2;
     const int a_fr0 = (wm * 64 + li) * BKT + 4 * (q0 ^ fsw);
     const int a_fr1 = (wm * 64 + li) * BKT + 4 * (q1 ^ fsw);
     const int b_fr0 = BM * BKT + (wn * 64 + li) * BKT + 4 * (q0 ^ fsw);
@@ -604,22 +589,6 @@ void k_wino_gemm(GemmArgs a) {
                 af[1][i] = *reinterpret_cast<const f32x4*>(sb + a_fr1 + i * 32 * BKT);
                 bf[1][i] = *reinterpret_cast<const f32x4*>(sb + b_fr1 + i * 32 * BKT);
             }
-            if constexpr (BF6) {
-                bf16x8 ap[3][2], bp[3][2];             // [hi, mid, lo][i or j]
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    split8(af[0][i], af[1][i], ap[0][i], ap[1][i], ap[2][i]);
-                    split8(bf[0][i], bf[1][i], bp[0][i], bp[1][i], bp[2][i]);
-                }
-                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi
-#pragma unroll
-                for (int p = 0; p < 6; ++p)
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[PA[p]][i], bp[PB[p]][j], acc[i][j], 0, 0, 0);
-            } else {
 #pragma unroll
             for (int g = 0; g < 2; ++g)
 #pragma unroll
@@ -631,7 +600,6 @@ void k_wino_gemm(GemmArgs a) {
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g][i].z, bf[g][j].z, acc[i][j], 0, 0, 0);
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g][i].w, bf[g][j].w, acc[i][j], 0, 0, 0);
                     }
-            }
         }
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
@@ -688,10 +656,12 @@ void k_wino_gemm(GemmArgs a) {
 }
 
 // ---- split-bf16 GEMMs on the pre-split weights (round 8, the default) ---------------------------------------------------------------
-// k_wino_gemm<0, 1>'s arithmetic - the same pieces (split8, for B at pack time), the same v_mfma_f32_32x32x16_bf16 with the same lane ->
-// k map (k = 8 lh .. 8 lh + 7), the same six products per chunk in the same order, K ascending from a zero accumulator per problem:
-// bit-identical - with B's pieces read ready from LDS (k_wino_pack_split's blocks), so that only A (fp32 in HBM and LDS, as before)
-// is split in the loop: half the split instructions.  The stage grows to 8 KB A + 12 KB B; the K loop runs over a ring of four
+// The arithmetic (be_split_bf16.h; the bits of round 7's kernel, which split both operands in the loop: tests/test_wino_presplit.py):
+// both operands' hi / mid / lo pieces by split8 (B's at pack time), v_mfma_f32_32x32x16_bf16 with lane (li, lh) holding row li's
+// k = 8 lh .. 8 lh + 7 of a 16-deep chunk, per chunk and accumulator the six products in the order lo.hi, hi.lo, mid.mid, mid.hi,
+// hi.mid, hi.hi (A's piece first), fp32 accumulation, K ascending from a zero accumulator per problem.  B's pieces are read ready
+// from LDS (k_wino_pack_split's blocks), so that only A (fp32 in HBM and LDS) is split in the loop: half the split instructions of
+// splitting both.  A stage is 8 KB A + 12 KB B; the K loop runs over a ring of four
 // stages (80 KB: two workgroups per CU) with the DMA three chunks ahead, explicit counted vmcnt waits and one raw s_barrier per chunk
 // (the idiom of k_wino_gemm_ws: no full drain of the DMA in front of every barrier), and the next chunk's fragments are read and
 // split right behind the current chunk's MFMAs (the read -> split chain no longer sits in front of every chunk's MFMAs).
@@ -1308,47 +1278,9 @@ bool wino_large(int64_t n, int cout) {
     return ((cout + 31) / 32 * 32) % 128 == 0 && n >= 1024 && !no_persist && (int64_t)NPOS * TPI * n * (int64_t)cout < ((int64_t)1 << 31);
 }
 
-// The split-bf16 GEMMs (k_wino_gemm<0, 1>) for every batch size: tile-major buffers for large batches, plane-major for small ones
-// (only the strides differ), so one patch gets the same bits in any batch.
-int wino_gemms_bf6(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s) {
-    constexpr size_t lds = (size_t)2 * (128 + 128) * 16 * sizeof(float);
-    static be::DeviceFlags attr_set{};                          // dynamic-LDS cap raised once per device (thread-safe)
-    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm<0, 1>), lds, attr_set)) return rc_;
-    const int cp = (cout + 31) / 32 * 32;
-    const int64_t rows = (int64_t)TPI * n;
-    const bool tm = wino_large(n, cout);
-    const int m_tiles = (int)((rows + 127) / 128), n_tiles = (cp + 127) / 128, kchunks = cin / 16;
-    // problem groups: the fewest that give every CU >= 2 workgroups of the least work per CU (a workgroup costs its problems x K
-    // chunks + ~2 chunks of prologue and turnover; 3 fit on a CU, and a CU with fewer runs no faster than with 2 - one wave per SIMD)
-    static const int zg_env = getenv("BE_WINO_ZGROUPS") ? atoi(getenv("BE_WINO_ZGROUPS")) : 0;   // A/B knob
-    const int cus = be::device_cu_count();
-    int zgroups = 1;
-    if (zg_env > 0 && zg_env <= NPOS) {
-        zgroups = zg_env;
-    } else {
-        int64_t best = INT64_MAX;
-        for (int zg = 1; zg <= NPOS; ++zg) {
-            if (NPOS % zg) continue;
-            const int64_t wgs = (int64_t)m_tiles * zg * n_tiles, per_cu = std::max<int64_t>(2, (wgs + cus - 1) / cus);
-            const int64_t cost = per_cu * ((NPOS / zg) * kchunks + 2);
-            if (cost < best) { best = cost; zgroups = zg; }
-        }
-    }
-    const WinoStrides sv = wino_strides(tm, n, cin), sm = wino_strides(tm, n, cout);           // in floats
-    GemmArgs g{V, packed_w, M, (int)rows, cin, cout, (int)sm.ts, NPOS, m_tiles, n_tiles, sv.plane, (int64_t)cp * cin, sm.plane, (int)sv.ts,
-               128, 0, nullptr, nullptr, 0, zgroups, cp};
-    const unsigned grid = (unsigned)(8 * ((m_tiles * zgroups + 7) / 8) * n_tiles);
-    {
-        // (FLOPs in fp32-equivalent products: what the layer computes, not the six bf16 products the matrix pipe issues)
-        be::ProfileScope prof(s, BE_KERNEL_WINO_GEMM, (double)NPOS * 2.0 * rows * cin * cout,
-                              (double)NPOS * 4.0 * ((double)rows * cin + (double)cin * cout + (double)rows * cout),
-                              (double)NPOS * 2.0 * m_tiles * n_tiles * 128.0 * 128.0 * cin);
-        hipLaunchKernelGGL((k_wino_gemm<0, 1>), dim3(grid), dim3(256), lds, s, g);
-    }
-    return be::check_launch("be_wino_conv3x3_6x6_f32(gemm, split bf16)");
-}
-
-// The same GEMMs on k_wino_gemm_ps: A (V) split in the loop, B from the pre-split planes behind U.  Bit-identical to wino_gemms_bf6.
+// The split-bf16 GEMMs (k_wino_gemm_ps) for every batch size: A (V) split in the loop, B from the pre-split planes behind U;
+// tile-major buffers for large batches, plane-major for small ones (only the strides differ), so one patch gets the same bits in
+// any batch.
 // Round 14, Vx != nullptr: at the NLIVE positions of a 1x1 kernel's transform M[z] = V[z] U[z]^T + Vx[z] Uds[z]^T, K order V's chunks
 // ascending, then Vx's, from a zero accumulator (k_wino_gemm_ps<0, 0, 1>) - a block's downsample inside conv2's GEMMs.  Vx: the
 // transform of the block's input (cin_ext channels) in V's layout; ds_planes: the planes of be_wino_ds_pack_f32.  tm_force >= 0
@@ -1414,7 +1346,7 @@ int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, in
                               2.0 * m_tiles * n_tiles * 128.0 * 128.0 * ((double)NPOS * cin + ext * cin_ext));
         hipLaunchKernelGGL((k_wino_gemm_ps<0, 0, 1>), dim3(grid), dim3(256), lds, s, g);
     } else {
-        // (FLOPs in fp32-equivalent products, as wino_gemms_bf6)
+        // (FLOPs in fp32-equivalent products: what the layer computes, not the six bf16 products the matrix pipe issues)
         be::ProfileScope prof(s, BE_KERNEL_WINO_GEMM, (double)NPOS * 2.0 * rows * cin * cout,
                               (double)NPOS * 4.0 * ((double)rows * cin + (double)rows * cout) + (double)NPOS * 6.0 * cin * n_tiles * 128,
                               (double)NPOS * 2.0 * m_tiles * n_tiles * 128.0 * 128.0 * cin);
@@ -1423,22 +1355,18 @@ int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, in
     return be::check_launch("be_wino_conv3x3_6x6_f32(gemm, split bf16, pre-split weights)");
 }
 
-bool wino_knob(const char* name) { return getenv(name) != nullptr && atoi(getenv(name)) != 0; }
-
 int wino_gemms(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s, void* stream,
                const float* Vx = nullptr, const float* ds_planes = nullptr, int cin_ext = 0) {
     if (Vx) {
         // only the GEMMs on pre-split weights have the second K segment
-        static const bool other_arm = wino_knob("BE_WINO_F32") || wino_knob("BE_WINO_BF6_R7");
-        BE_REQUIRE(!other_arm, "be_wino_conv3x3_pair_ds_6x6_f32: no folded downsample under BE_WINO_F32=1 / BE_WINO_BF6_R7=1");
+        static const bool other_arm = be::knob_on("BE_WINO_F32");
+        BE_REQUIRE(!other_arm, "be_wino_conv3x3_pair_ds_6x6_f32: no folded downsample under BE_WINO_F32=1");
         return wino_gemms_ps(V, packed_w, M, n, cin, cout, s, Vx, ds_planes, cin_ext);
     }
-    // A/B knobs: BE_WINO_F32=1 restores the fp32-MFMA GEMMs of all three batch regimes (weight-stationary, walked 128x128, and
-    // the batched k_conv_igemm of small batches); BE_WINO_BF6_R7=1 the split-bf16 GEMMs that split B in the loop too (round 7:
-    // the same bits as the default)
-    static const bool f32 = getenv("BE_WINO_F32") != nullptr && atoi(getenv("BE_WINO_F32")) != 0;
-    static const bool r7 = getenv("BE_WINO_BF6_R7") != nullptr && atoi(getenv("BE_WINO_BF6_R7")) != 0;
-    if (!f32) return r7 ? wino_gemms_bf6(V, packed_w, M, n, cin, cout, s) : wino_gemms_ps(V, packed_w, M, n, cin, cout, s);
+    // A/B knob: BE_WINO_F32=1 restores the fp32-MFMA GEMMs of all three batch regimes (weight-stationary, walked 128x128, and
+    // the batched k_conv_igemm of small batches)
+    static const bool f32 = be::knob_on("BE_WINO_F32");
+    if (!f32) return wino_gemms_ps(V, packed_w, M, n, cin, cout, s);
     const int cp = (cout + 31) / 32 * 32;
     if (wino_large(n, cout)) {
         // large batches: one workgroup per (M tile, N tile) walks the 25 problems back to back
@@ -1543,8 +1471,7 @@ extern "C" int be_gemm_rows_bf6_pack_f32(const float* packed_w, int cout, int ci
 
 bool be::rows_bf6_enabled() {
     // A/B knobs: BE_ROWS_F32=1 sends only these row GEMMs back to the fp32 kernels; BE_WINO_F32=1 restores fp32 everywhere
-    static const bool f32 = (getenv("BE_ROWS_F32") != nullptr && atoi(getenv("BE_ROWS_F32")) != 0) ||
-                            (getenv("BE_WINO_F32") != nullptr && atoi(getenv("BE_WINO_F32")) != 0);
+    static const bool f32 = be::knob_on("BE_ROWS_F32") || be::knob_on("BE_WINO_F32");
     return !f32;
 }
 
@@ -1758,7 +1685,7 @@ extern "C" int be_wino_gemms_ext_f32(const float* V, const float* packed_w, floa
 
 bool be::wino_ds_fold_enabled() {
     // A/B knob BE_WINO_DS_GEMM=1: the blocks' downsamples stay separate row GEMMs; so they do in the arms without the second K segment
-    static const bool on = be::rows_bf6_enabled() && !wino_knob("BE_WINO_BF6_R7") && !wino_knob("BE_WINO_DS_GEMM");
+    static const bool on = be::rows_bf6_enabled() && !be::knob_on("BE_WINO_DS_GEMM");
     return on;
 }
 

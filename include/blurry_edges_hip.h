@@ -587,8 +587,7 @@ int be_conv_nhwc_batched_f32(const be_conv_desc* d, const float* x, const float*
 /* Winograd form of the 3x3 'same' convolutions on 6x6 maps (LocalStage layers 1-3): fewer multiplies than the direct form, the
  * transforms in fp32, the transform-domain products in split-bf16 (each fp32 operand split exactly into three bf16 pieces, six bf16
  * MFMAs per product, fp32 accumulation; per-GEMM error at or below the fp32 products'; the same bits at every batch size).
- * Environment BE_WINO_F32=1 (read once per process) restores exact fp32 products and accumulation; BE_WINO_BF6_R7=1 the round-7 split-bf16
- * GEMMs that split the fp32 U in the loop (same bits as the default).  Tile shape (compile-time, be_wino_tile_rows()): 6 = F(6,3) along the rows x F(3,3) along
+ * Environment BE_WINO_F32=1 (read once per process) restores exact fp32 products and accumulation.  Tile shape (compile-time, be_wino_tile_rows()): 6 = F(6,3) along the rows x F(3,3) along
  * the columns - two 8x5 tiles per map, 40 transform positions, 80 multiplies per map and channel pair instead of 324 (the default
  * since round 4); 3 = F(3,3) x F(3,3) - four 5x5 tiles, 25 positions, 100 multiplies (rounds 1-3).  be_wino_pack_f32 folds an
  * optional eval BatchNorm like be_conv_pack_f32 and writes U [positions][cout_pad32][cin] + bias [cout_pad32]; behind U in the same buffer
@@ -636,7 +635,7 @@ int be_maxpool_wino_in_11x11_f32(const float* x, float* pooled, int64_t n, int c
  * be_wino_conv3x3_pair_ds_6x6_f32: be_wino_conv3x3_pair_chain_6x6_f32 with packed_ds in place of the residual.  The workspace has
  * three regions (x's transform, M, conv1's transform: be_wino_pair_ds_workspace_floats); x may be NULL with x_in_v, and y with
  * next_cmid > 0 (the map is then not stored).  Requires the two transforms in one layout (always so when cmid == cout); refused under
- * BE_WINO_F32=1 / BE_WINO_BF6_R7=1.  Bits depend on neither the batch nor BE_WINO_ZGROUPS.
+ * BE_WINO_F32=1.  Bits depend on neither the batch nor BE_WINO_ZGROUPS.
  * be_wino_gemms_ext_f32: the GEMMs alone.  V [positions][tiles][cin] (tile_major 0) or [tiles][positions][cin] (1), tiles =
  * (12 / be_wino_tile_rows()) n; M and Vx (cin_ext channels, NULL: no second segment) likewise; packed_w of be_wino_pack_f32. */
 int be_wino_ds_positions(void);
@@ -986,7 +985,7 @@ int be_datagen_test_render_f64(const double* bkgd, const double* frgd, const dou
 #define BE_KERNEL_CONV_128x32       3   /* fc.4                                                                */
 #define BE_KERNEL_CONV_ROW8_128x64  4   /* conv1 (7x7 row-gather)                                              */
 #define BE_KERNEL_CONV_SMALL        5   /* 64x64 / 128x32 tiles for small M (training batches)                 */
-#define BE_KERNEL_WINO_GEMM         6   /* k_wino_gemm<0, 1> (split bf16; fp32: k_wino_gemm_ws / k_wino_gemm): the transform-domain GEMMs (one per position) of a Winograd layer, with a block's 1x1 downsample as a second K segment where it is folded in (k_wino_gemm_ps<0, 0, 1>); FLOPs as fp32 products */
+#define BE_KERNEL_WINO_GEMM         6   /* k_wino_gemm_ps<0, 0> (split bf16; fp32: k_wino_gemm_ws / k_wino_gemm): the transform-domain GEMMs (one per position) of a Winograd layer, with a block's 1x1 downsample as a second K segment where it is folded in (k_wino_gemm_ps<0, 0, 1>); FLOPs as fp32 products */
 #define BE_KERNEL_GEMM_ROWS         7   /* row GEMMs: k_wino_gemm_ps<EPI> on pre-split weights (split bf16: fc.1, and LocalStage's 1x1 downsamples under BE_WINO_DS_GEMM=1; FLOPs as fp32 products); fp32: k_wino_gemm<1> / k_wino_gemm_ws<.., 1> (1x1 convolutions / linears, large batches) */
 /* HBM-bound kernels: `bytes` = the algorithmic bytes the launch has to move, `flops` = 0 */
 #define BE_KERNEL_WINO_TRANSFORM    8   /* k_wino_in / k_wino_out / k_wino_out_in / k_wino_out_pool2 */

@@ -1,5 +1,5 @@
 """Accuracy of split-bf16 (bf16x6) products in the Winograd transform-domain GEMMs, emulated on the CPU (numpy; nothing in the
-product uses it).  The go / no-go of the bf16x6 GEMMs (be_wino.hip, k_wino_gemm<0, 1>).
+product uses it).  The go / no-go of the bf16x6 GEMMs (be_wino.hip, k_wino_gemm_ps).
 
 Each fp32 operand is split x = hi + mid + lo (bf16 pieces, round-to-nearest-even from what is left: exact for finite x whose lo stays
 a bf16 normal); a product is the six bf16 MFMAs lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi per 16-deep K chunk, each MFMA adding the

@@ -1,6 +1,13 @@
-"""The asymmetric LDS ring of layer0's split-bf16 loop (be_conv_pm_bf6.hip: k_conv_pm_bf6<1>): three A slots and two B slots of the 9
-real pieces, B(c + 2) then A(c + 3) fetched at the top of chunk c, three workgroups per CU - against the ring of four whole stages
-(k_conv_pm_bf6<0>, BE_BF6_RING4=1: read once per process, hence the one child process of this module).
+"""The asymmetric LDS ring of layer0's split-bf16 loop (be_conv_pm_bf6.hip: k_conv_pm_bf6): three A slots and two B slots of the 9
+real pieces, B(c + 2) then A(c + 3) fetched at the top of chunk c, three workgroups per CU - against the recorded bits of the ring of
+four whole stages that it replaced.  That ring left the library; its bits are tests/golden/l0_ring_bits.json, the "y" digests of
+run_cases(False) recorded with the library of commit d45619f (the last one that held it) under its knob BE_BF6_RING4=1, read once per
+process:
+
+    BE_BF6_RING4=1 BE_LIB_DIR=<directory with that commit's libblurry_edges_hip.so> python tests/test_bf6_ring3.py --record
+
+(without BE_LIB_DIR it records the library in the tree: do that only for a change that is meant to move bits, and say so).  Every
+operand comes from numpy's default_rng or be_hip.synth on the CPU.
 
 What such a ring can get wrong, at the smallest shapes that reach it: a slot overwritten before its fragments were read or read before
 its DMA landed, A and B of different chunks paired, a B piece dealt to no wave or to the wrong place in the 9-KB slot, a padding piece
@@ -14,9 +21,7 @@ read touches and the new ring does not fetch - are NaN in a second copy of the p
 import hashlib
 import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -26,6 +31,7 @@ from test_layer0_split_bf16 import COUT, _pack
 from test_split_bf16_interleave import _exact_f32, _l0_ref, _sparse_rows, _three_piece
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "l0_ring_bits.json")
 DEV = "cuda:0"
 CONFIGS = [(64, 0), (96, 64)]                          # layer0's two launches: 64 -> 96, and 96 -> 96 with the fused 1x1 over 64
 MAPS = [(3, 3), (11, 11)]                              # every pixel but one on the border; the real map
@@ -110,19 +116,6 @@ def run_cases(check_exact):
     return out
 
 
-_CHILD = r'''
-import json, os, sys
-sys.path[:0] = [os.environ["BE_ROOT"], os.path.join(os.environ["BE_ROOT"], "blurry-edges_amd"), os.path.join(os.environ["BE_ROOT"], "tests")]
-import test_bf6_ring3 as t
-json.dump(t.run_cases(False), open(os.environ["BE_OUT"], "w"))
-'''
-
-
-def _ring4_here():
-    v = os.environ.get("BE_BF6_RING4")
-    return bool(v) and v.lstrip("+-").isdigit() and int(v) != 0
-
-
 @pytest.fixture(scope="module")
 def native():
     if not torch.cuda.is_available():
@@ -138,35 +131,31 @@ def this_arm(native):
 
 
 @pytest.fixture(scope="module")
-def other_arm():
-    """The same cases on the other ring: BE_BF6_RING4=1 in a child process (=0 if this process itself runs under the knob)."""
-    with tempfile.TemporaryDirectory() as d:
-        env = dict(os.environ, BE_ROOT=ROOT, BE_OUT=os.path.join(d, "other.json"), BE_BF6_RING4="0" if _ring4_here() else "1")
-        r = subprocess.run([sys.executable, "-c", _CHILD], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return json.load(open(os.path.join(d, "other.json")))
+def golden():
+    """{case: digest of y} of the same cases on the ring of four whole stages"""
+    with open(GOLDEN) as f:
+        return json.load(f)["digests"]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin,cin2,h,w,kind", CASES, ids=[_key(*c, 0)[:-3] for c in CASES])
-def test_layer0_bits_on_either_ring_with_nan_in_the_padding_rows(this_arm, other_arm, cin, cin2, h, w, kind):
+def test_layer0_bits_on_either_ring_with_nan_in_the_padding_rows(this_arm, golden, cin, cin2, h, w, kind):
     for n in NS:
         k = _key(cin, cin2, h, w, kind, n)
-        a, b = this_arm[k], other_arm[k]
-        assert a["finite"] and b["finite"], k
+        a = this_arm[k]
+        assert a["finite"], k
         if kind != "normal":
             assert a["wrong"] == 0, (k, a["wrong"])                  # the float64 convolution, bit for bit
         assert a["y_poisoned_planes"] == a["y"], k                   # rows 96-127 of the planes reach no output
-        assert b["y_poisoned_planes"] == b["y"], k
-        assert a["y"] == b["y"], k                                   # the two rings: the same bits
+        assert a["y"] == golden[k], k                                # the two rings: the same bits
 
 
 @pytest.mark.gpu
-def test_local_stage_logits_are_bit_equal_on_either_ring(this_arm, other_arm):
+def test_local_stage_logits_are_bit_equal_on_either_ring(this_arm, golden):
     for n in STAGE_NS:
-        a, b = this_arm[f"stage_n{n}"], other_arm[f"stage_n{n}"]
-        assert a["finite"] and b["finite"]
-        assert a["y"] == b["y"], n
+        a = this_arm[f"stage_n{n}"]
+        assert a["finite"]
+        assert a["y"] == golden[f"stage_n{n}"], n
 
 
 def _normal_on_device(native, cin, cin2, h, w):
@@ -202,3 +191,20 @@ def test_nonfinite_values_of_one_image_stay_in_that_image(native):
     assert not np.isfinite(y[rows]).any()
     keep = np.setdiff1d(np.arange(max(NS)), rows)
     assert np.array_equal(y[keep], clean[keep])
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] != ["--record"]:
+        sys.exit("usage: [BE_LIB_DIR=<directory of the library to record>] python tests/test_bf6_ring3.py --record")
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "blurry-edges_amd"), os.path.join(ROOT, "tests")]
+    from be_hip import native as n
+    n.lib()
+    cases = run_cases(False)
+    assert all(v["finite"] for v in cases.values())
+    with open(os.path.join(os.path.dirname(n.LIB_PATH), "BUILD_INFO.json")) as f:       # written by build() next to the library
+        built = json.load(f)
+    with open(GOLDEN, "w") as f:
+        json.dump({"library_git_head": built.get("git_head"), "library_dirty": built.get("dirty"),
+                   "digests": {k: v["y"] for k, v in cases.items()}}, f, indent=1)
+        f.write("\n")
+    print(f"recorded {len(cases)} digests of {n.LIB_PATH} in {GOLDEN}")

@@ -150,7 +150,7 @@ def test_bad_arguments_are_refused_before_any_launch(native, ops):
 
 BATCHES = (3, 300, 700)
 CHUNKS = (0, 256)
-KNOBS = ("BE_WINO_F32", "BE_WINO_BF6_R7", "BE_ROWS_F32", "BE_L0_F32", "BE_C1_F32", "BE_NO_CONV_PM", "BE_NO_CONV1_POOL")
+KNOBS = ("BE_WINO_F32", "BE_ROWS_F32", "BE_L0_F32", "BE_C1_F32", "BE_NO_CONV_PM", "BE_NO_CONV1_POOL")
 
 
 def _logits():

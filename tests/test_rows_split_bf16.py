@@ -170,7 +170,7 @@ np.savez(os.environ["BE_OUT"], **t._logits())
 def test_local_stage_logits_per_arm_are_batch_and_chunk_independent_and_the_arms_agree(native):
     def arm(d, name, **knobs):
         env = dict(os.environ, BE_ROOT=ROOT, BE_OUT=os.path.join(d, name + ".npz"))
-        for k in ("BE_WINO_F32", "BE_WINO_BF6_R7", "BE_ROWS_F32"):
+        for k in ("BE_WINO_F32", "BE_ROWS_F32"):
             env.pop(k, None)
         env.update(knobs)
         r = subprocess.run([sys.executable, "-c", _CHILD], env=env, capture_output=True, text=True, timeout=900)

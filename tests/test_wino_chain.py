@@ -186,7 +186,7 @@ def test_pool_kernel_equals_the_max_pool_and_feeds_the_next_block(native, c, n):
 
 # ---------------------------------------------------------------------------------------------------- whole LocalStage
 LS_BATCHES = (1, 65, 1100)                                  # 1100 crosses the tile-major threshold (1024 maps)
-KNOBS = ("BE_WINO_NO_CHAIN", "BE_WINO_F32", "BE_WINO_BF6_R7", "BE_ROWS_F32", "BE_L0_F32", "BE_C1_F32", "BE_NO_CONV_PM", "BE_NO_CONV1_POOL",
+KNOBS = ("BE_WINO_NO_CHAIN", "BE_WINO_F32", "BE_ROWS_F32", "BE_L0_F32", "BE_C1_F32", "BE_NO_CONV_PM", "BE_NO_CONV1_POOL",
          "BE_WINO_NO_PERSIST", "BE_WINOGRAD")
 
 

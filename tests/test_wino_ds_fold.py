@@ -29,7 +29,7 @@ LIVE = [5 * r + c for r in range(1, 7) for c in range(1, 4)]
 BLOCKS = [(32, 64, 164), (64, 96, 100), (96, 256, 256), (32, 64, 96)]
 NS = (1, 3, 65)                                             # 65 maps = 130 tiles: a partial second M tile
 LAYER_TOL = 1.5e-5                                          # the Winograd layer bound of test_hip_parity.py / test_wino_split_bf16.py
-KNOBS = ("BE_WINO_DS_GEMM", "BE_WINO_ZGROUPS", "BE_WINO_NO_CHAIN", "BE_WINO_F32", "BE_WINO_BF6_R7", "BE_ROWS_F32", "BE_L0_F32", "BE_C1_F32",
+KNOBS = ("BE_WINO_DS_GEMM", "BE_WINO_ZGROUPS", "BE_WINO_NO_CHAIN", "BE_WINO_F32", "BE_ROWS_F32", "BE_L0_F32", "BE_C1_F32",
          "BE_NO_CONV_PM", "BE_NO_CONV1_POOL", "BE_WINO_NO_PERSIST", "BE_WINOGRAD")
 
 

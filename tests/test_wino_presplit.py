@@ -1,14 +1,19 @@
 """The pre-split Winograd weights (be_wino.hip: k_wino_pack_split) and the split-bf16 GEMM that reads them (k_wino_gemm_ps).
 
 CPU: the packed size (fp32 U, then three bf16 planes of U with cout padded to 128).  GPU: the planes are a round-to-nearest-even split
-of the packed fp32 U in the GEMM's block layout; the GEMM gives the bits of the round-7 kernel that splits both operands in the loop
-(BE_WINO_BF6_R7=1, in a child process: the knob is read once per process) for the six LocalStage layer shapes at every batch regime,
-padded channel counts and non-finite inputs."""
+of the packed fp32 U in the GEMM's block layout; the GEMM gives the bits of the round-7 kernel that split both operands in the loop,
+for the six LocalStage layer shapes at every batch regime, padded channel counts and non-finite inputs.  That kernel left the library
+when k_wino_gemm_ps had replaced it; its bits are tests/golden/wino_presplit_bits.json, the sha256 digests of _outputs() recorded with
+the library of commit d45619f (the last one that held it) under its knob BE_WINO_BF6_R7=1, read once per process:
+
+    BE_WINO_BF6_R7=1 BE_LIB_DIR=<directory with that commit's libblurry_edges_hip.so> python tests/test_wino_presplit.py --record
+
+(that commit's default arm gave the same digests in the same recording run).  Without BE_LIB_DIR it records the library in the tree:
+do that only for a change that is meant to move bits, and say so.  The inputs are seeded on the CPU."""
 import hashlib
+import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -17,6 +22,7 @@ import torch
 from test_wino_split_bf16 import LAYERS, split3
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "wino_presplit_bits.json")
 DEV = "cuda:0"
 BATCHES = (3, 700, 1501, 4096)          # plane-major, plane-major, tile-major with a partial row tile, tile-major full tiles
 ODD = [(64, 100), (32, 164)]             # cout_pad32 = 128 / 192: N tiles past cout_pad (zero rows of the planes)
@@ -52,7 +58,7 @@ def _weights(cin, cout, seed):
 
 
 def _outputs():
-    """Digests of the Winograd layer outputs on fixed inputs under this process's GEMMs (plus one small array for diagnostics)."""
+    """-> {case: sha256 of the Winograd layer's output} on fixed inputs under this process's GEMMs"""
     from be_hip import native
     out = {}
 
@@ -60,31 +66,20 @@ def _outputs():
         w, b = _weights(cin, cout, seed)
         uw, ub = native.wino_pack(w.to(DEV), b.to(DEV))
         y, _ = native.wino_conv3x3(x, uw, ub, cout, act=1)
-        y = y.cpu().numpy()
-        out[name] = np.frombuffer(hashlib.sha256(y.tobytes()).digest(), dtype=np.uint8)
-        out[name + "_head"] = y.reshape(-1)[:4096].copy()
+        out[name] = hashlib.sha256(y.cpu().numpy().tobytes()).hexdigest()
 
     for i, (cin, cout) in enumerate(LAYERS + ODD):
-        g = torch.Generator(device=DEV).manual_seed(1000 + i)
-        x4 = torch.randn(max(BATCHES), 6, 6, cin, device=DEV, generator=g)
+        g = torch.Generator().manual_seed(1000 + i)
+        x4 = torch.randn(max(BATCHES), 6, 6, cin, generator=g).to(DEV)
         for n in BATCHES:
             run(f"l{i}_n{n}", x4[:n].contiguous(), cin, cout, 200 + i)
-    g = torch.Generator(device=DEV).manual_seed(7)
-    x = torch.randn(64, 6, 6, 256, device=DEV, generator=g)
+    g = torch.Generator().manual_seed(7)
+    x = torch.randn(64, 6, 6, 256, generator=g)
     x[3, 2, 2, 5] = float("inf")
     x[9, 0, 4, 17] = float("-inf")
     x[20, 5, 5, 100] = float("nan")
-    run("nonfinite", x, 256, 256, 7)
+    run("nonfinite", x.to(DEV), 256, 256, 7)
     return out
-
-
-_CHILD = r'''
-import os, sys
-import numpy as np
-sys.path[:0] = [os.environ["BE_ROOT"], os.path.join(os.environ["BE_ROOT"], "blurry-edges_amd"), os.path.join(os.environ["BE_ROOT"], "tests")]
-import test_wino_presplit as t
-np.savez(os.environ["BE_OUT"], **t._outputs())
-'''
 
 
 @pytest.fixture(scope="module")
@@ -121,21 +116,28 @@ def test_planes_are_the_rne_split_of_u_in_block_layout(native):
 
 @pytest.mark.gpu
 def test_presplit_gemm_gives_the_round7_kernels_bits(native):
-    """Default GEMM (B from the planes) against BE_WINO_BF6_R7=1 (both operands split in the loop) in a fresh child process: the six
-    layer shapes and two padded ones at 3 / 700 / 1501 / 4096 patches, and a batch with inf / NaN inputs - bit for bit.  Both arms run
-    in child processes whose knobs are set here, whatever the suite's environment holds."""
-    def arm(d, name, **knobs):
-        env = dict(os.environ, BE_ROOT=ROOT, BE_OUT=os.path.join(d, name + ".npz"))
-        for k in ("BE_WINO_F32", "BE_WINO_BF6_R7"):
-            env.pop(k, None)
-        env.update(knobs)
-        r = subprocess.run([sys.executable, "-c", _CHILD], env=env, capture_output=True, text=True, timeout=900)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return dict(np.load(os.path.join(d, name + ".npz")))
-
-    with tempfile.TemporaryDirectory() as d:
-        new = arm(d, "default")
-        old = arm(d, "r7", BE_WINO_BF6_R7="1")
+    """Default GEMM (B from the planes) against the recorded bits of the round-7 kernel (both operands split in the loop): the six
+    layer shapes and two padded ones at 3 / 700 / 1501 / 4096 patches, and a batch with inf / NaN inputs - bit for bit."""
+    assert os.environ.get("BE_WINO_F32") in (None, "", "0"), \
+        "BE_WINO_F32 is set in this environment: the fp32 GEMMs would run, not the split-bf16 GEMM whose bits are pinned here"
+    with open(GOLDEN) as f:
+        old = json.load(f)["digests"]
+    new = _outputs()
     assert sorted(old) == sorted(new)
-    bad = [k for k in new if new[k].tobytes() != old[k].tobytes()]
+    bad = [k for k in new if new[k] != old[k]]
     assert not bad, bad
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] != ["--record"]:
+        sys.exit("usage: [BE_LIB_DIR=<directory of the library to record>] python tests/test_wino_presplit.py --record")
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "blurry-edges_amd"), os.path.join(ROOT, "tests")]
+    from be_hip import native as n
+    n.lib()
+    digests = _outputs()
+    with open(os.path.join(os.path.dirname(n.LIB_PATH), "BUILD_INFO.json")) as f:       # written by build() next to the library
+        built = json.load(f)
+    with open(GOLDEN, "w") as f:
+        json.dump({"library_git_head": built.get("git_head"), "library_dirty": built.get("dirty"), "digests": digests}, f, indent=1)
+        f.write("\n")
+    print(f"recorded {len(digests)} digests of {n.LIB_PATH} in {GOLDEN}")

@@ -1,4 +1,4 @@
-"""The split-bf16 (bf16x6) arithmetic of the Winograd transform-domain GEMMs (be_wino.hip, k_wino_gemm<0, 1>).
+"""The split-bf16 (bf16x6) arithmetic of the Winograd transform-domain GEMMs (be_wino.hip, k_wino_gemm_ps).
 
 CPU: the three-piece split x = hi + mid + lo (each piece a bf16 rounded to nearest-even from what is left) is exact, on the same
 operation sequence as the kernel's split8.  GPU: the six LocalStage Winograd layer shapes against float64 and against the fp32 GEMMs
