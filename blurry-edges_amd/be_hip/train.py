@@ -230,7 +230,8 @@ def _unit_bwd(xin, dout, saved, gamma, dg_pack, dx_add, ks, chw_hw, dgamma, dbet
 def _unit_pair_fwd(xin, packs, ua, ub):
     """Two units on the same input that produce the same [n,h,w,cout] - a residual block's 3x3 convolution and its 1x1 downsample -
     with every launch shared (be_train_unit_pair_fwd_f32).  ua / ub = (wi, cout, ks, gamma, beta, run_mean, run_var, act).
-    Returns ((out_a, saved_a), (out_b, saved_b)) as two _unit_fwd calls would, bit for bit."""
+    Returns ((out_a, saved_a), (out_b, saved_b)) as two _unit_fwd calls would: up to the regrouping of fp32 partial sums on the
+    shapes the balanced launch takes (the K cuts depend on how many problems share a launch), bit for bit with BE_NO_TRAIN_SK=1."""
     n, h, w, cin = xin.shape
     dev = xin.device
     o = native.ops()

@@ -1493,7 +1493,7 @@ int check_fwd_unit(const be_train_unit_fwd& u, const char* who) {
 
 // the two BatchNorm launches of the forward for nu units of the same [M, C]; S / ldp: the convolutions' K slices (S = 1: y is final)
 int fwd_bn_launches(const be_train_unit_fwd* const* u, int nu, const int* S, const int* ldp, float eps, float momentum, char* sc,
-                    hipStream_t s, const char* who, const be_sk::ConvGeom* sk = nullptr, float* const* sk_part = nullptr) {
+                    hipStream_t s, const char* who, const be::SkUnitOut* sk = nullptr) {
     const int M = u[0]->desc.n * u[0]->desc.h * u[0]->desc.w, C = u[0]->desc.cout;
     const RowBlocks sb = stat_blocks(M, C);
     const RowBlocks ab = apply_blocks(M, C, 256);
@@ -1504,7 +1504,7 @@ int fwd_bn_launches(const be_train_unit_fwd* const* u, int nu, const int* S, con
         BE_REQUIRE((size_t)sb.n * C * 2 * sizeof(double) <= sp.stats_b, "%s: statistics region too small", who);
         st.j[j] = StatsArgs{S[j] > 1 ? reinterpret_cast<const float*>(sp.conv) : nullptr, u[j]->packed_bias, u[j]->y,
                             reinterpret_cast<double*>(sp.stats), S[j] > 1 ? S[j] : 0, M, C, ldp[j], sb.rows, 0, {}};
-        if (sk) { st.j[j].partial = sk_part[j]; st.j[j].S = 1; st.j[j].ldp = (C + 63) / 64 * 64; st.j[j].sk = 1; st.j[j].g = sk[j]; }
+        if (sk) { st.j[j].partial = sk[j].cpart; st.j[j].S = 1; st.j[j].ldp = (C + 63) / 64 * 64; st.j[j].sk = 1; st.j[j].g = sk[j].cg; }
         fa.j[j] = FwdApplyArgs{u[j]->y, reinterpret_cast<const double*>(sp.stats), u[j]->gamma, u[j]->beta, u[j]->res, u[j]->run_mean,
                                u[j]->run_var, u[j]->mean, u[j]->invstd, u[j]->s_in, u[j]->out, sb.n, M, C, ab.rows, u[j]->act, eps, momentum};
     }
@@ -1518,6 +1518,26 @@ inline bool sk_fwd_enabled() {
     static const bool off = getenv("BE_NO_TRAIN_SK_FWD") != nullptr;
     return !off && be::sk_enabled();
 }
+// BE_NO_UNIT_PAIR: a pair call runs its units one after the other (A/B knob)
+inline bool unit_pair_enabled() {
+    static const bool off = getenv("BE_NO_UNIT_PAIR") != nullptr;
+    return !off;
+}
+inline be::SkRegions sk_regions(char* sc) {
+    return be::SkRegions{reinterpret_cast<float*>(sc + SCR_CONV), SCR_WGRAD - SCR_CONV, reinterpret_cast<float*>(sc + SCR_WGRAD), SCR_TOTAL - SCR_WGRAD};
+}
+
+// Round 6: the convolutions of nu (1 | 2) eligible units as problems of ONE balanced persistent launch (be_train_sk.hip; two units:
+// each one's raw slices in its half of the region), summed by k_bn_stats.  1 = "not mine": nothing was launched, the caller takes
+// rounds 3-5's path.
+int sk_units_fwd(const be_train_unit_fwd* const* u, int nu, float eps, float momentum, char* sc, hipStream_t s, const char* who) {
+    be::SkUnitOut out[2];
+    be::SkPlan plan;
+    if (be::sk_plan_fwd(u, nu, sk_regions(sc), be::sk_slots(), out, &plan)) return 1;
+    if (int rc = be::sk_run(&plan, s)) return rc;
+    const int S1[2] = {1, 1}, l0[2] = {0, 0};
+    return fwd_bn_launches(u, nu, S1, l0, eps, momentum, sc, s, who, out);
+}
 
 int unit_fwd_one(const be_train_unit_fwd& u, float eps, float momentum, char* sc, void* stream, const char* who) {
     if (int rc = check_fwd_unit(u, who)) return rc;
@@ -1525,15 +1545,8 @@ int unit_fwd_one(const be_train_unit_fwd& u, float eps, float momentum, char* sc
     int S = 1, ldp = 0;
     const be_train_unit_fwd* one[1] = {&u};
     if (sk_fwd_enabled() && be::sk_fwd_eligible(u.desc)) {
-        // round 6: the convolution on the balanced persistent launch (be_train_sk.hip), raw slices summed by k_bn_stats
-        be::SkFwdIn in{&u.desc, u.x, u.packed_w, reinterpret_cast<float*>(sc + SCR_CONV), SCR_WGRAD - SCR_CONV};
-        be_sk::ConvGeom cg;
-        be::SkPlan plan;
-        if (be::sk_plan_fwd(&in, 1, &cg, &plan) == BE_OK) {
-            if (int rc = be::sk_run(&plan, be::as_stream(stream))) return rc;
-            float* part[1] = {in.part};
-            return fwd_bn_launches(one, 1, &S, &ldp, eps, momentum, sc, be::as_stream(stream), who, &cg, part);
-        }
+        const int rc = sk_units_fwd(one, 1, eps, momentum, sc, be::as_stream(stream), who);
+        if (rc != 1) return rc;
     }
     if (int rc = be::conv_train(&dc, u.x, u.packed_w, u.packed_bias, nullptr, u.y, dc.cout, sc + SCR_CONV, SCR_WGRAD - SCR_CONV, &S, &ldp, stream))
         return rc;
@@ -1564,26 +1577,12 @@ extern "C" int be_train_unit_pair_fwd_f32(const be_train_unit_fwd* a, const be_t
     char* sc = static_cast<char*>(scratch);
     hipStream_t s = be::as_stream(stream);
     const be_train_unit_fwd* u[2] = {a, b};
-    static const bool no_pair = getenv("BE_NO_UNIT_PAIR") != nullptr;             // A/B knob
-    if (!no_pair && sk_fwd_enabled() && be::sk_fwd_eligible(a->desc) && be::sk_fwd_eligible(b->desc)) {
-        // round 6: both convolutions as problems of ONE balanced persistent launch; each unit's slices in its half of the region
-        be::SkFwdIn in[2];
-        for (int j = 0; j < 2; ++j) {
-            const ScrPart sp = scr_part(sc, j, 2);
-            in[j] = be::SkFwdIn{&u[j]->desc, u[j]->x, u[j]->packed_w, reinterpret_cast<float*>(sp.conv), sp.conv_b};
-        }
-        be_sk::ConvGeom cg[2];
-        be::SkPlan plan;
-        if (be::sk_plan_fwd(in, 2, cg, &plan) == BE_OK) {
-            if (int rc = be::sk_run(&plan, s)) return rc;
-            int S1[2] = {1, 1}, l0[2] = {0, 0};
-            float* part[2] = {in[0].part, in[1].part};
-            if (int rc = fwd_bn_launches(u, 2, S1, l0, eps, momentum, sc, s, who, cg, part)) return rc;
-            return be::check_launch(who);
-        }
+    if (unit_pair_enabled() && sk_fwd_enabled() && be::sk_fwd_eligible(a->desc) && be::sk_fwd_eligible(b->desc)) {
+        const int rc = sk_units_fwd(u, 2, eps, momentum, sc, s, who);
+        if (rc != 1) return rc ? rc : be::check_launch(who);
     }
     be::ConvPrep prep[2];
-    bool together = !no_pair;
+    bool together = unit_pair_enabled();
     for (int j = 0; j < 2 && together; ++j) {
         const ScrPart sp = scr_part(sc, j, 2);
         be_conv_desc dc = u[j]->desc; dc.act = 0;
@@ -1662,6 +1661,7 @@ int plan_wgrad(const be_train_unit_bwd& u, float* wpart, size_t wpart_bytes, WJo
     const int taps = d->ksize * d->ksize;
     const int64_t wsize = (int64_t)C * d->cin * taps;
     static const bool no128 = getenv("BE_NO_WGRAD128") != nullptr;            // A/B knob
+    static const bool no_pm = getenv("BE_NO_WGRAD_PM") != nullptr;            // A/B knob: the pixel-major walk of both kernels
     if (!no128 && u.layout_chw_hw == 0 && C % 128 == 0 && d->cin % 128 == 0 && M >= 256) {
         const int tiles = (C / 128) * (d->cin / 128) * taps;
         // slices: every one is another copy of dW to write and to sum (a 3x3 layer: 2.4-5.3 MB each), so few of them -
@@ -1676,7 +1676,6 @@ int plan_wgrad(const be_train_unit_bwd& u, float* wpart, size_t wpart_bytes, WJo
         int rows = (M + S - 1) / S; rows = (rows + 15) / 16 * 16;
         S = (M + rows - 1) / rows;
         wj->wkind = 1;
-        static const bool no_pm = getenv("BE_NO_WGRAD_PM") != nullptr;          // A/B knob
         const int pm = !no_pm && d->ksize == 3 && d->n % 16 == 0 && (int64_t)M * (C > d->cin ? C : d->cin) * 4 < ((int64_t)1 << 32);
         wj->w128 = Wgrad128Args{u.x, u.dy, wpart, M, d->h, d->w, d->h * d->w, d->cin, C, d->ksize, rows, d->cin / 128, pm};
         wj->wx = (C / 128) * (d->cin / 128); wj->wy = taps; wj->real = wj->wx * taps * S;
@@ -1692,8 +1691,7 @@ int plan_wgrad(const be_train_unit_bwd& u, float* wpart, size_t wpart_bytes, WJo
         int rows = (M + S - 1) / S; rows = (rows + 31) / 32 * 32;
         S = (M + rows - 1) / rows;
         wj->wkind = 0;
-        static const bool no_pm64 = getenv("BE_NO_WGRAD_PM") != nullptr;        // A/B knob
-        const int pm64 = !no_pm64 && d->ksize == 3 && d->n % 32 == 0 && u.layout_chw_hw == 0;
+        const int pm64 = !no_pm && d->ksize == 3 && d->n % 32 == 0 && u.layout_chw_hw == 0;
         wj->w64 = WgradArgs{u.x, u.dy, wpart, M, d->h, d->w, d->h * d->w, d->cin, C, d->ksize, rows, u.layout_chw_hw, it, pm64};
         wj->wx = ct * it; wj->wy = taps; wj->real = ct * it * taps * S;
         pj->wpart = wpart; pj->dw = u.dw; pj->wsize = wsize; pj->wS = S; pj->conv1_map = 0; pj->cout1 = C; pj->wtaps = 0;
@@ -1707,31 +1705,47 @@ inline dim3 wjob_grid(const WJob& w) { return dim3(w.wx, w.wy, w.real / (w.wx * 
 
 // Round 6: the balanced launch (be_train_sk.hip) for the units it takes.  Fills the post kernel's roles for unit j of `pa` (the
 // bias role's partials are the caller's).  The weight-gradient slices are [slice][tap][cout][cin] as k_wgrad128's.
-void sk_post_roles(const be_train_unit_bwd& u, const be::SkUnitIn& in, const be::SkUnitOut& out, PostArgs* pa, int j) {
+void sk_post_roles(const be_train_unit_bwd& u, const be::SkUnitOut& out, PostArgs* pa, int j) {
     const be_conv_desc* d = &u.desc;
     const int taps = d->ksize * d->ksize;
     PostJob& pj = pa->j[j];
-    pj.wpart = in.wpart; pj.dw = u.dw; pj.wsize = (int64_t)d->cout * d->cin * taps; pj.wS = 1; pj.conv1_map = 0; pj.cout1 = d->cout;
+    pj.wpart = out.wpart; pj.dw = u.dw; pj.wsize = (int64_t)d->cout * d->cin * taps; pj.wS = 1; pj.conv1_map = 0; pj.cout1 = d->cout;
     pj.wtaps = taps; pj.chw = u.layout_chw_hw;
     pj.nb_w = (int)cap_grid(pj.wsize / taps, 256, 1024);
     pa->sk = 1;
     pa->wsk[j] = out.wg;
     pa->xsk[j] = out.cg;
 }
-// one unit: true when the balanced launch ran (or failed: *rc), false = "not mine" (the caller takes rounds 3-5's path)
-bool sk_single(const be_train_unit_bwd& u, char* sc, hipStream_t s, PostArgs* pa, const char* who, int* rc) {
-    const be_conv_desc* d = &u.desc;
-    be::SkUnitIn in{&u, reinterpret_cast<float*>(sc + SCR_CONV), SCR_WGRAD - SCR_CONV, reinterpret_cast<float*>(sc + SCR_WGRAD), SCR_TOTAL - SCR_WGRAD};
-    be::SkUnitOut out;
+// k_bwd_post's input-gradient role: S slices [S][M][ldp] at part (+ add, the other branch of a residual block) -> dx [M, C]
+inline void post_dx_role(PostArgs* pa, const float* part, int ldp, int S, const float* add, float* dx, int64_t M, int C) {
+    pa->xpart = part; pa->xadd = add; pa->dx = dx; pa->xM = M; pa->xC = C; pa->xldp = ldp; pa->xS = S;
+}
+// The whole backward of nu (1 | 2) eligible units around the balanced launch: the plan (decided before anything is launched), the
+// BatchNorm launches, k_unit_gemms_sk, k_bwd_post (two units: u[0]->dx receives the sum of both input gradients).  The slice
+// regions are the planner's to split.  1 = "not mine": nothing was launched, the caller takes rounds 3-5's path.
+int sk_units_bwd(const be_train_unit_bwd* const* u, int nu, char* sc, hipStream_t s, const char* who) {
+    const be_conv_desc* d = &u[0]->desc;
+    const int M = d->n * d->h * d->w, C = d->cout;
+    be::SkUnitOut out[2];
     be::SkPlan plan;
-    if (be::sk_plan(&in, 1, &out, &plan)) return false;
-    *rc = be::sk_run(&plan, s);
-    if (*rc) return true;
-    sk_post_roles(u, in, out, pa, 0);
-    pa->xpart = in.cpart; pa->xadd = u.dx_add; pa->dx = u.dx; pa->xM = (int64_t)d->n * d->h * d->w; pa->xC = d->cin;
-    pa->xldp = out.ldp; pa->xS = 1;
-    (void)who;
-    return true;
+    if (be::sk_plan(u, nu, sk_regions(sc), be::sk_slots(), out, &plan)) return 1;
+    int nb_rows = 0;
+    if (int rc = bwd_bn_launches(u, nu, sc, s, &nb_rows, who)) return rc;
+    if (int rc = be::sk_run(&plan, s)) return rc;
+    PostArgs pa{};
+    pa.nj = nu;
+    int nb = 0;
+    for (int j = 0; j < nu; ++j) {
+        PostJob& pj = pa.j[j];
+        pj.dbpart = reinterpret_cast<const double*>(scr_part(sc, j, nu).dbpart); pj.db = u[j]->db; pj.nb_rows = nb_rows; pj.C = C; pj.nb_b = C / 32;
+        sk_post_roles(*u[j], out[j], &pa, j);
+        nb += pj.nb_w + pj.nb_b;
+    }
+    post_dx_role(&pa, out[0].cpart, out[0].ldp, 1, u[0]->dx_add, u[0]->dx, M, d->cin);
+    if (nu == 2) { pa.xpart2 = out[1].cpart; pa.xldp2 = out[1].ldp; pa.xS2 = 1; }
+    const int nb_x = (int)cap_grid((int64_t)M * (d->cin / 4), 256, 2048);
+    hipLaunchKernelGGL(k_bwd_post, dim3(nb + nb_x), dim3(256), 0, s, pa);
+    return BE_OK;
 }
 
 int unit_bwd_one(const be_train_unit_bwd& u, char* sc, void* stream, const char* who) {
@@ -1740,6 +1754,10 @@ int unit_bwd_one(const be_train_unit_bwd& u, char* sc, void* stream, const char*
     const int M = d->n * d->h * d->w, C = d->cout;
     hipStream_t s = be::as_stream(stream);
     const be_train_unit_bwd* one[1] = {&u};
+    if (be::sk_enabled() && be::sk_eligible(u)) {
+        const int rc = sk_units_bwd(one, 1, sc, s, who);
+        if (rc != 1) return rc;
+    }
     int nb_rows = 0;
     if (int rc = bwd_bn_launches(one, 1, sc, s, &nb_rows, who)) return rc;
     // 3. + 4. the weight-gradient GEMM and the data-gradient convolution (through the transposed / mirrored pack): slices of both
@@ -1747,7 +1765,6 @@ int unit_bwd_one(const be_train_unit_bwd& u, char* sc, void* stream, const char*
     PostArgs pa{};
     pa.nj = 1;
     PostJob& pj = pa.j[0];
-    int rc_sk = BE_OK;
     float* wpart = reinterpret_cast<float*>(sc + SCR_WGRAD);
     pj.dbpart = reinterpret_cast<const double*>(sc + SCR_DBPART); pj.db = u.db; pj.nb_rows = nb_rows; pj.C = C; pj.nb_b = C / 32;
     if (d->ksize == 7) {
@@ -1759,8 +1776,6 @@ int unit_bwd_one(const be_train_unit_bwd& u, char* sc, void* stream, const char*
         hipLaunchKernelGGL(k_wgrad_conv1_mfma, dim3(1, 4, S), dim3(256), 0, s, wa);
         pj.wpart = wpart; pj.dw = u.dw; pj.wsize = (int64_t)C * 147; pj.wS = S; pj.conv1_map = 1; pj.cout1 = C;
         pj.nb_w = (C * 147 + 255) / 256;
-    } else if (be::sk_enabled() && be::sk_eligible(u) && sk_single(u, sc, s, &pa, who, &rc_sk)) {
-        if (rc_sk) return rc_sk;
     } else {
         UnitGemmsArgs g{};
         double w_exec = 0.0;
@@ -1779,10 +1794,7 @@ int unit_bwd_one(const be_train_unit_bwd& u, char* sc, void* stream, const char*
             const double wflops = 2.0 * M * (double)pj.wsize;
             be::ProfileScope prof(s, BE_KERNEL_TRAIN_BWD_GEMMS, prep.flops + wflops, 0.0, prep.flops_exec + w_exec);
             if (int rc = launch_unit_gemms(prep.variant, g, (unsigned)(g.w_end[1] + g.c_real[0]), s)) return rc;
-            if (prep.S > 1) {
-                pa.xpart = reinterpret_cast<const float*>(sc + SCR_CONV); pa.xadd = u.dx_add; pa.dx = u.dx; pa.xM = M; pa.xC = d->cin;
-                pa.xldp = prep.ldp; pa.xS = prep.S;
-            }
+            if (prep.S > 1) post_dx_role(&pa, reinterpret_cast<const float*>(sc + SCR_CONV), prep.ldp, prep.S, u.dx_add, u.dx, M, d->cin);
         } else {
             if (g.w[0].wkind == 1) hipLaunchKernelGGL(k_wgrad128, wjob_grid(g.w[0]), dim3(256), 0, s, g.w[0].w128);
             else hipLaunchKernelGGL(k_wgrad, wjob_grid(g.w[0]), dim3(256), 0, s, g.w[0].w64);
@@ -1790,10 +1802,7 @@ int unit_bwd_one(const be_train_unit_bwd& u, char* sc, void* stream, const char*
                 int S = 1, ldp = 0;
                 if (int rc = be::conv_train(&dd, u.dy, u.dgrad_packed_w, u.dgrad_packed_bias, u.dx_add, u.dx, d->cin, sc + SCR_CONV,
                                             SCR_WGRAD - SCR_CONV, &S, &ldp, stream)) return rc;
-                if (S > 1) {
-                    pa.xpart = reinterpret_cast<const float*>(sc + SCR_CONV); pa.xadd = u.dx_add; pa.dx = u.dx; pa.xM = M; pa.xC = d->cin;
-                    pa.xldp = ldp; pa.xS = S;
-                }
+                if (S > 1) post_dx_role(&pa, reinterpret_cast<const float*>(sc + SCR_CONV), ldp, S, u.dx_add, u.dx, M, d->cin);
             }
         }
     }
@@ -1833,39 +1842,12 @@ extern "C" int be_train_unit_pair_bwd_f32(const be_train_unit_bwd* a, const be_t
     const be_train_unit_bwd* u[2] = {a, b};
     const be_conv_desc* d = &a->desc;
     const int M = d->n * d->h * d->w, C = d->cout;
-    static const bool no_pair = getenv("BE_NO_UNIT_PAIR") != nullptr;             // A/B knob
-    if (!no_pair && be::sk_enabled() && be::sk_eligible(*a) && be::sk_eligible(*b)) {
-        // Round 6: both units' weight gradients and data gradients as ONE balanced launch (be_train_sk.hip).  The slice regions are
-        // split in proportion to what a slice of each unit takes (a 3x3 weight gradient is nine times its block's 1x1 one).
-        const int64_t w0 = (int64_t)a->desc.ksize * a->desc.ksize, w1 = (int64_t)b->desc.ksize * b->desc.ksize;
-        const size_t wreg = SCR_TOTAL - SCR_WGRAD, creg = SCR_WGRAD - SCR_CONV;
-        const size_t wa = (size_t)((double)wreg * w0 / (w0 + w1)) & ~(size_t)255;
-        be::SkUnitIn in[2] = {{a, reinterpret_cast<float*>(sc + SCR_CONV), creg / 2, reinterpret_cast<float*>(sc + SCR_WGRAD), wa},
-                              {b, reinterpret_cast<float*>(sc + SCR_CONV + creg / 2), creg / 2, reinterpret_cast<float*>(sc + SCR_WGRAD + wa), wreg - wa}};
-        be::SkUnitOut out[2];
-        be::SkPlan plan;
-        if (be::sk_plan(in, 2, out, &plan) == BE_OK) {
-            int nb_rows = 0;
-            if (int rc = bwd_bn_launches(u, 2, sc, s, &nb_rows, who)) return rc;
-            if (int rc = be::sk_run(&plan, s)) return rc;
-            PostArgs pa{};
-            pa.nj = 2;
-            for (int j = 0; j < 2; ++j) {
-                const ScrPart sp = scr_part(sc, j, 2);
-                PostJob& pj = pa.j[j];
-                pj.dbpart = reinterpret_cast<const double*>(sp.dbpart); pj.db = u[j]->db; pj.nb_rows = nb_rows; pj.C = C; pj.nb_b = C / 32;
-                sk_post_roles(*u[j], in[j], out[j], &pa, j);
-            }
-            pa.xpart = in[0].cpart; pa.xldp = out[0].ldp; pa.xS = 1;
-            pa.xpart2 = in[1].cpart; pa.xldp2 = out[1].ldp; pa.xS2 = 1;
-            pa.dx = a->dx; pa.xM = M; pa.xC = d->cin;
-            const int nb_x = (int)cap_grid((int64_t)M * (d->cin / 4), 256, 2048);
-            hipLaunchKernelGGL(k_bwd_post, dim3(pa.j[0].nb_w + pa.j[0].nb_b + pa.j[1].nb_w + pa.j[1].nb_b + nb_x), dim3(256), 0, s, pa);
-            return be::check_launch(who);
-        }
+    if (unit_pair_enabled() && be::sk_enabled() && be::sk_eligible(*a) && be::sk_eligible(*b)) {
+        const int rc = sk_units_bwd(u, 2, sc, s, who);
+        if (rc != 1) return rc ? rc : be::check_launch(who);
     }
     be::ConvPrep prep[2];
-    bool together = !no_pair;
+    bool together = unit_pair_enabled();
     for (int j = 0; j < 2 && together; ++j) {
         const ScrPart sp = scr_part(sc, j, 2);
         be_conv_desc dd{d->n, d->h, d->w, C, d->cin, u[j]->desc.ksize, 0};

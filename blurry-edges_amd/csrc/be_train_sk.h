@@ -76,20 +76,23 @@ __host__ __device__ inline void tap_rect(int H, int W, int tdy, int tdx, int& y0
 }  // namespace be_sk
 
 // ---- host side (be_train_sk.hip), called by the unit entry points of be_train.hip
+struct be_train_unit_fwd;
 struct be_train_unit_bwd;
 struct be_conv_desc;
 namespace be {
-struct SkUnitIn { const ::be_train_unit_bwd* u; float* cpart; size_t cpart_bytes; float* wpart; size_t wpart_bytes; };
-struct SkUnitOut { be_sk::ConvGeom cg; be_sk::WGeom wg; int ldp; };
+// the WHOLE slice regions of the training scratch: the planner splits them between the units of a pair itself
+struct SkRegions { float* conv; size_t conv_bytes; float* wgrad; size_t wgrad_bytes; };
+// what the consumers of a unit's slices need: its geometry and where its parts of the regions begin (forward: cg, ldp, cpart)
+struct SkUnitOut { be_sk::ConvGeom cg; be_sk::WGeom wg; int ldp; float* cpart; float* wpart; };
 bool sk_enabled();                                     // BE_NO_TRAIN_SK unset
 bool sk_eligible(const ::be_train_unit_bwd& u);        // shapes k_unit_gemms_sk takes
-// the plan of the balanced backward GEMMs of nu (1 | 2) eligible units (kernel arguments + grid; nothing is launched):
-// BE_OK, or 1 = "not mine" (scratch too small) - decided BEFORE the caller launches anything of the unit
+int sk_slots();                                        // workgroup slots of the current device: CUs x BE_SK_SLOTS (3), a multiple of 8
+// the plan of the balanced backward GEMMs of nu (1 | 2) eligible units on G_total slots (kernel arguments + grid; nothing is
+// launched, no device touched): BE_OK, or 1 = "not mine" (scratch too small) - decided BEFORE the caller launches anything
 struct SkPlan { alignas(16) char blob[1536]; };
-int sk_plan(const SkUnitIn* in, int nu, SkUnitOut* out, SkPlan* plan);
+int sk_plan(const ::be_train_unit_bwd* const* units, int nu, const SkRegions& r, int G_total, SkUnitOut* out, SkPlan* plan);
 int sk_run(const SkPlan* plan, hipStream_t s);
-// the forward convolutions of nu (1 | 2) units on the same launch (conv-only problems): raw slices [slices][M][cout] at `part`
-struct SkFwdIn { const ::be_conv_desc* d; const float* x; const float* packed_w; float* part; size_t part_bytes; };
+// the forward convolutions of nu (1 | 2) units on the same launch (conv-only problems): raw slices [slices][M][ldp] at cpart
 bool sk_fwd_eligible(const ::be_conv_desc& d);
-int sk_plan_fwd(const SkFwdIn* in, int nu, be_sk::ConvGeom* out, SkPlan* plan);
+int sk_plan_fwd(const ::be_train_unit_fwd* const* units, int nu, const SkRegions& r, int G_total, SkUnitOut* out, SkPlan* plan);
 }  // namespace be

@@ -330,9 +330,23 @@ void k_unit_gemms_sk(SkArgs a) {
     }
 }
 
-double env_num(const char* name, double dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atof(v) : dflt;
+// The planner's tuning values, read from the environment once per process (re-tuning: tools/r6_sk_sweep.sh sets them per process).
+struct Tuning {
+    double ww, fw, fc;     // BE_SK_WW / FW / FC: cost of a weight-gradient chunk, fixed cost of a weight-gradient / convolution segment
+    double w8k, w4k;       // BE_SK_W8K / W4K: factors of the 128 x 64 / 64 x 64 weight-gradient tiles
+    int slots, prio;       // BE_SK_SLOTS: workgroups per CU; BE_SK_PRIO: s_setprio of the convolution workgroups
+    bool trace;            // BE_SK_TRACE (diagnostic): tools/sk_trace.py reads the stamps back
+};
+const Tuning& tuning() {
+    static const Tuning t = [] {
+        const auto num = [](const char* name, double dflt) {
+            const char* v = getenv(name);
+            return v && *v ? atof(v) : dflt;
+        };
+        return Tuning{num("BE_SK_WW", 1.0), num("BE_SK_FW", 0.0), num("BE_SK_FC", 0.0), num("BE_SK_W8K", 0.6), num("BE_SK_W4K", 0.4),
+                      (int)num("BE_SK_SLOTS", 3.0), (int)num("BE_SK_PRIO", 1.0), getenv("BE_SK_TRACE") != nullptr};
+    }();
+    return t;
 }
 
 struct Prob {            // planner's view of a problem
@@ -356,13 +370,10 @@ int worst_slices(int tiles, int Q, SpanOfTile span) {
     return worst;
 }
 
-// Workgroups per problem: proportional to its cost (chunks x weight + segments x fixed cost), multiples of 8, capped so that no
-// tile is cut into more slices than the consumers take / the scratch holds.  false: a problem's scratch holds fewer than two slices.
-bool share_workgroups(Prob* pr, int np) {
-    // ---- workgroups per problem: proportional to its cost (chunks x weight + segments x fixed cost), multiples of 8, capped so
-    //      that no tile is cut into more slices than the consumers take / the scratch holds
-    const int slots_per_cu = (int)env_num("BE_SK_SLOTS", 3.0);
-    const int G_total = (be::device_cu_count() * (slots_per_cu < 1 ? 1 : slots_per_cu)) & ~7;
+// Workgroups per problem out of G_total slots (a multiple of 8): proportional to its cost (chunks x weight + segments x fixed
+// cost), multiples of 8, capped so that no tile is cut into more slices than the consumers take / the scratch holds.  false: a
+// problem's scratch holds fewer than two slices.
+bool share_workgroups(Prob* pr, int np, int G_total) {
     int cap[4];
     for (int i = 0; i < np; ++i) {
         const int smax = pr[i].smax_buf < pr[i].smax ? pr[i].smax_buf : pr[i].smax;
@@ -415,18 +426,63 @@ int conv_geometry(be_sk::ConvGeom& g, int n, int h, int w, int cin, int ks, int 
     return tmax;
 }
 
-// quota of a convolution problem with pc.G workgroups; lowers G until no tile has more slices than allowed.  false: impossible
-bool settle_conv(Prob& pc, be_sk::ConvGeom& g) {
-    for (;;) {
-        pc.Q = (pc.L + pc.G - 1) / pc.G;
-        g.Q = pc.Q;
-        const int per_grp = g.HW * g.n_tiles;
-        const int worst = worst_slices(pc.tiles, pc.Q, [&](int t, int& ts, int& n) {
-            be_sk::conv_span(g, t / per_grp, (t % per_grp) / g.n_tiles, t % g.n_tiles, ts, n); });
-        if (worst <= pc.smax && worst <= pc.smax_buf) return true;
-        if (pc.G <= 8) return false;
-        pc.G -= 8;
+// fills a weight gradient's geometry (tile sizes, tile lengths) for x [n,h,w,cin], dy [n,h,w,cout], ks; returns the longest tile's chunks
+int w_geometry(be_sk::WGeom& g, int n, int h, int w, int cin, int cout, int ks) {
+    const int half = ks >> 1, taps = ks * ks;
+    g.tm = cout % 128 == 0 ? 128 : 64; g.tn = cin % 128 == 0 ? 128 : 64; g.cin = cin;
+    g.cin_tiles = (cin + g.tn - 1) / g.tn; g.wx = ((cout + g.tm - 1) / g.tm) * g.cin_tiles; g.ntaps = taps;
+    g.PT[0] = 0;
+    int nmax = 0;
+    for (int t = 0; t < taps; ++t) {
+        int y0, hv, x0, wv;
+        be_sk::tap_rect(h, w, t / ks - half, t % ks - half, y0, hv, x0, wv);
+        const int nn = (n / 16) * hv * wv;
+        g.PT[t + 1] = g.PT[t] + nn;
+        if (nn > nmax) nmax = nn;
     }
+    g.L = g.PT[taps] * g.wx;
+    return nmax;
+}
+
+// tile t of a problem's axis, in the order the kernel walks it
+inline void tile_span(const be_sk::WGeom& g, int t, int& ts, int& n) { be_sk::w_span(g, t / g.wx, t % g.wx, ts, n); }
+inline void tile_span(const be_sk::ConvGeom& g, int t, int& ts, int& n) {
+    const int per_grp = g.HW * g.n_tiles;
+    be_sk::conv_span(g, t / per_grp, (t % per_grp) / g.n_tiles, t % g.n_tiles, ts, n);
+}
+
+// quota of a problem (either geometry: its span is tile_span's overload) with p.G workgroups, then the real slice count of its
+// worst tile (defensive: share_workgroups' cap already bounds it); lowers G by 8 until no tile has more slices than allowed.
+// false: impossible
+template <class Geom>
+bool settle(Prob& p, Geom& g) {
+    for (;;) {
+        g.Q = p.Q = (p.L + p.G - 1) / p.G;
+        const int worst = worst_slices(p.tiles, p.Q, [&](int t, int& ts, int& n) { tile_span(g, t, ts, n); });
+        if (worst <= p.smax && worst <= p.smax_buf) return true;
+        if (p.G <= 8) return false;
+        p.G -= 8;
+    }
+}
+
+// The problem of a convolution [n,h,w,cin] x ks -> cout over x with the pack w (be_conv_pack_f32's rows; the data gradient: dy, the
+// pack of be_conv_pack_dgrad_f32 and the channel counts swapped), raw slices [slices][M][ldp] at part: kernel arguments + the
+// planner's view.
+Prob conv_problem(ConvProb& c, const be_conv_desc& d, int cin, int cout, const float* x, const float* w, float* part, size_t part_bytes) {
+    const int taps = d.ksize * d.ksize, M = d.n * d.h * d.w;
+    c.x = x; c.w = w; c.part = part; c.H = d.h; c.W = d.w; c.Cin = cin; c.ks = d.ksize;
+    c.Ktot = (cin / 32) * taps * 32; c.M = M; c.ldp = (cout + 63) / 64 * 64; c.rows_w = (cout + 31) / 32 * 32;
+    const int tmax = conv_geometry(c.g, d.n, d.h, d.w, cin, d.ksize, (cout + 63) / 64);
+    const size_t csize = (size_t)M * c.ldp * sizeof(float);
+    return Prob{c.g.L, tmax * c.g.kmul, c.g.ngrp * c.g.HW * c.g.n_tiles, 1.0, tuning().fc, (int)(part_bytes / csize), be_sk::MAX_SLICES_C, 0, 0};
+}
+
+// unit i's part of a slice region shared by nu units in the proportions share[]: the parts are rounded down to 256 bytes, the last
+// unit's ends where the region ends; one unit gets everything
+void region_part(float* base, size_t bytes, int nu, int i, const int64_t* share, float*& part, size_t& part_bytes) {
+    const size_t first = nu == 1 ? bytes : (size_t)((double)bytes * share[0] / (share[0] + share[1])) & ~(size_t)255;
+    part = i == 0 ? base : reinterpret_cast<float*>(reinterpret_cast<char*>(base) + first);
+    part_bytes = i == 0 ? first : bytes - first;
 }
 
 }  // namespace
@@ -455,16 +511,24 @@ bool sk_eligible(const be_train_unit_bwd& u) {
     return true;
 }
 
-// Plans k_unit_gemms_sk for nu (1 or 2) eligible units: nothing is launched.  Returns BE_OK, or 1 = "not mine" (scratch too small
-// for even two slices per tile): the caller then takes the old path.
+int sk_slots() {
+    const int per_cu = tuning().slots;
+    return (be::device_cu_count() * (per_cu < 1 ? 1 : per_cu)) & ~7;
+}
+
+// Plans k_unit_gemms_sk for nu (1 or 2) eligible units on G_total slots: nothing is launched, no device is touched.  Returns BE_OK,
+// or 1 = "not mine" (scratch too small for even two slices per tile): the caller then takes the old path.  Two units share the
+// slice regions: each gets half of the convolution region, and of the weight-gradient region what a slice of its weight gradient
+// takes (ksize^2: a 3x3 weight gradient is nine times its block's 1x1 one).
 struct SkPlanData { SkArgs a; int grid; double flops, flops_exec; };
 static_assert(sizeof(SkPlanData) <= sizeof(SkPlan), "SkPlan too small");
-int sk_plan(const SkUnitIn* in, int nu, SkUnitOut* out, SkPlan* plan) {
+int sk_plan(const be_train_unit_bwd* const* units, int nu, const SkRegions& r, int G_total, SkUnitOut* out, SkPlan* plan) {
     SkPlanData& pd = *reinterpret_cast<SkPlanData*>(plan->blob);
     SkArgs& a = pd.a;
     memset(&pd, 0, sizeof(pd));
     Prob pr[4];
     int np = 0;
+    const Tuning& tune = tuning();
     // Cost model, in convolution chunks (64 x 64 x 32: 16 MFMAs per wave).  A weight-gradient chunk (128 x 128 x 16) is 32 MFMAs per
     // wave, twice the matrix work - but what a workgroup's chunk COSTS on a CU shared by three workgroups is its serial stream (wait,
     // barrier, DMA issue, LDS latency, then the MFMAs), and the short chunk carries relatively more of the rest: the per-workgroup
@@ -477,67 +541,44 @@ int sk_plan(const SkUnitIn* in, int nu, SkUnitOut* out, SkPlan* plan) {
     // 1.2 segments per workgroup, almost no tile cut twice.  (Snapping every problem's quota to a divisor of its longest tile - fewer tiles in two slices - was built
     // and measured: 1.356-1.388 ms against 1.320-1.360 without, because tile STARTS stay unaligned in the natural tile order and the
     // snapped counts leave slots empty; removed.)  Environment overrides for re-tuning.
-    const double ww = env_num("BE_SK_WW", 1.0), fw = env_num("BE_SK_FW", 0.0), fc = env_num("BE_SK_FC", 0.0);
     double flops = 0.0, flops_exec = 0.0;
-    a.prio = (int)env_num("BE_SK_PRIO", 1.0);
-    static const bool trace = getenv("BE_SK_TRACE") != nullptr;       // diagnostic: tools/sk_trace.py reads the stamps back
+    a.prio = tune.prio;
     size_t w_reserve = 0;
-    if (trace) {        // the stamps go to the END of the last unit's weight-gradient region (the planner is told it is shorter)
+    if (tune.trace) {   // the stamps go to the END of the weight-gradient region (the last unit is told its part is shorter)
         w_reserve = 65536;
-        a.trace = reinterpret_cast<long long*>(reinterpret_cast<char*>(in[nu - 1].wpart) + in[nu - 1].wpart_bytes - w_reserve);
+        a.trace = reinterpret_cast<long long*>(reinterpret_cast<char*>(r.wgrad) + r.wgrad_bytes - w_reserve);
     }
+    const int64_t halves[2] = {1, 1};
+    const int64_t by_taps[2] = {(int64_t)units[0]->desc.ksize * units[0]->desc.ksize, (int64_t)units[nu - 1]->desc.ksize * units[nu - 1]->desc.ksize};
     for (int i = 0; i < nu; ++i) {
-        const be_train_unit_bwd& u = *in[i].u;
+        const be_train_unit_bwd& u = *units[i];
         const be_conv_desc& d = u.desc;
-        const int HW = d.h * d.w, ks = d.ksize, half = ks >> 1, taps = ks * ks, M = d.n * HW;
+        const int taps = d.ksize * d.ksize, M = d.n * d.h * d.w;
+        size_t cpart_bytes, wpart_bytes;
+        region_part(r.conv, r.conv_bytes, nu, i, halves, out[i].cpart, cpart_bytes);
+        region_part(r.wgrad, r.wgrad_bytes, nu, i, by_taps, out[i].wpart, wpart_bytes);
+        if (i == nu - 1) wpart_bytes -= w_reserve;
         // weight gradient
         WProb& w = a.w[i];
-        w.x = u.x; w.dy = u.dy; w.part = in[i].wpart; w.H = d.h; w.W = d.w; w.Cin = d.cin; w.Cout = d.cout; w.ks = ks;
-        w.g.tm = d.cout % 128 == 0 ? 128 : 64; w.g.tn = d.cin % 128 == 0 ? 128 : 64; w.g.cin = d.cin;
-        w.g.cin_tiles = (d.cin + w.g.tn - 1) / w.g.tn; w.g.wx = ((d.cout + w.g.tm - 1) / w.g.tm) * w.g.cin_tiles; w.g.ntaps = taps;
-        w.g.PT[0] = 0;
-        int nmax = 0;
-        for (int t = 0; t < taps; ++t) {
-            int y0, hv, x0, wv;
-            be_sk::tap_rect(d.h, d.w, t / ks - half, t % ks - half, y0, hv, x0, wv);
-            const int n = (d.n / 16) * hv * wv;
-            w.g.PT[t + 1] = w.g.PT[t] + n;
-            if (n > nmax) nmax = n;
-        }
-        w.g.L = w.g.PT[taps] * w.g.wx;
+        w.x = u.x; w.dy = u.dy; w.part = out[i].wpart; w.H = d.h; w.W = d.w; w.Cin = d.cin; w.Cout = d.cout; w.ks = d.ksize;
+        const int nmax = w_geometry(w.g, d.n, d.h, d.w, d.cin, d.cout, d.ksize);
         const size_t wsize = (size_t)d.cout * d.cin * taps * sizeof(float);
         // a chunk of a tm x tn tile is tm tn / 16384 of the 128 x 128 chunk's MFMAs; the small tiles carry relatively more of the rest
-        const double wtile = ww * (w.g.tm * w.g.tn == 16384 ? 1.0 : (w.g.tm * w.g.tn == 8192 ? env_num("BE_SK_W8K", 0.6) : env_num("BE_SK_W4K", 0.4)));
-        pr[np++] = Prob{w.g.L, nmax, w.g.wx * taps, wtile, fw, (int)((in[i].wpart_bytes - (i == nu - 1 ? w_reserve : 0)) / wsize), be_sk::MAX_SLICES_W, 0, 0};
+        const double wtile = tune.ww * (w.g.tm * w.g.tn == 16384 ? 1.0 : (w.g.tm * w.g.tn == 8192 ? tune.w8k : tune.w4k));
+        pr[np++] = Prob{w.g.L, nmax, w.g.wx * taps, wtile, tune.fw, (int)(wpart_bytes / wsize), be_sk::MAX_SLICES_W, 0, 0};
         // data gradient: a convolution of dy [M, Cout] with the transposed, tap-mirrored pack -> [M, Cin]
         ConvProb& c = a.c[i];
-        c.x = u.dy; c.w = u.dgrad_packed_w; c.part = in[i].cpart; c.H = d.h; c.W = d.w; c.Cin = d.cout; c.ks = ks;
-        c.Ktot = (d.cout / 32) * taps * 32; c.M = M; c.ldp = (d.cin + 63) / 64 * 64; c.rows_w = (d.cin + 31) / 32 * 32;
-        const int tmax = conv_geometry(c.g, d.n, d.h, d.w, d.cout, ks, (d.cin + 63) / 64);
-        const size_t csize = (size_t)M * c.ldp * sizeof(float);
-        pr[np++] = Prob{c.g.L, tmax * c.g.kmul, c.g.ngrp * HW * c.g.n_tiles, 1.0, fc, (int)(in[i].cpart_bytes / csize), be_sk::MAX_SLICES_C, 0, 0};
+        pr[np++] = conv_problem(c, d, d.cout, d.cin, u.dy, u.dgrad_packed_w, out[i].cpart, cpart_bytes);
         flops += 4.0 * M * (double)d.cin * d.cout * taps;
         flops_exec += (double)w.g.L * 2.0 * w.g.tm * w.g.tn * 16 + (double)c.g.L * 2.0 * 64 * 64 * 32;
         out[i].ldp = c.ldp;
     }
-    if (!share_workgroups(pr, np)) return 1;
-    int g0 = 0;
+    if (!share_workgroups(pr, np, G_total)) return 1;
     for (int i = 0; i < nu; ++i) {
-        Prob& pw = pr[2 * i];
-        Prob& pc = pr[2 * i + 1];
-        WProb& w = a.w[i];
-        ConvProb& c = a.c[i];
-        for (;;) {          // quota, then the real slice count of the worst tile (defensive: the cap above already bounds it)
-            pw.Q = (pw.L + pw.G - 1) / pw.G;
-            w.g.Q = pw.Q;
-            const int worst = worst_slices(pw.tiles, pw.Q, [&](int t, int& ts, int& n) { be_sk::w_span(w.g, t / w.g.wx, t % w.g.wx, ts, n); });
-            if (worst <= pw.smax && worst <= pw.smax_buf) break;
-            if (pw.G <= 8) return 1;
-            pw.G -= 8;
-        }
-        if (!settle_conv(pc, c.g)) return 1;
-        out[i].cg = c.g; out[i].wg = w.g;
+        if (!settle(pr[2 * i], a.w[i].g) || !settle(pr[2 * i + 1], a.c[i].g)) return 1;
+        out[i].cg = a.c[i].g; out[i].wg = a.w[i].g;
     }
+    int g0 = 0;
     for (int i = 0; i < nu; ++i) { a.w[i].g0 = g0; a.w[i].G = pr[2 * i].G; g0 += pr[2 * i].G; }       // the long chunks first
     for (int i = 0; i < nu; ++i) { a.c[i].g0 = g0; a.c[i].G = pr[2 * i + 1].G; g0 += pr[2 * i + 1].G; }
     a.nw = nu; a.nc = nu;
@@ -559,31 +600,31 @@ bool sk_fwd_eligible(const be_conv_desc& d) {
     return M * cmax * 4 < ((int64_t)1 << 31) && (int64_t)d.cin * d.cout * d.ksize * d.ksize * 4 < ((int64_t)1 << 31);
 }
 
-int sk_plan_fwd(const SkFwdIn* in, int nu, be_sk::ConvGeom* out, SkPlan* plan) {
+// the same plan for the forward convolutions of nu (1 | 2) eligible units: the convolution region alone, in halves for two
+int sk_plan_fwd(const be_train_unit_fwd* const* units, int nu, const SkRegions& r, int G_total, SkUnitOut* out, SkPlan* plan) {
     SkPlanData& pd = *reinterpret_cast<SkPlanData*>(plan->blob);
     SkArgs& a = pd.a;
     memset(&pd, 0, sizeof(pd));
     Prob pr[4];
-    const double fc = env_num("BE_SK_FC", 0.0);
     a.prio = 0;
+    const int64_t halves[2] = {1, 1};
     for (int i = 0; i < nu; ++i) {
-        const be_conv_desc& d = *in[i].d;
-        const int ks = d.ksize, taps = ks * ks, M = d.n * d.h * d.w;
+        const be_train_unit_fwd& u = *units[i];
+        const be_conv_desc& d = u.desc;
         ConvProb& c = a.c[i];
-        c.x = in[i].x; c.w = in[i].packed_w; c.part = in[i].part; c.H = d.h; c.W = d.w; c.Cin = d.cin; c.ks = ks;
-        c.Ktot = (d.cin / 32) * taps * 32; c.M = M; c.ldp = (d.cout + 63) / 64 * 64; c.rows_w = (d.cout + 31) / 32 * 32;
-        const int tmax = conv_geometry(c.g, d.n, d.h, d.w, d.cin, ks, (d.cout + 63) / 64);
-        const size_t csize = (size_t)M * c.ldp * sizeof(float);
-        pr[i] = Prob{c.g.L, tmax * c.g.kmul, c.g.ngrp * c.g.HW * c.g.n_tiles, 1.0, fc, (int)(in[i].part_bytes / csize), be_sk::MAX_SLICES_C, 0, 0};
-        pd.flops += 2.0 * M * (double)d.cin * d.cout * taps;
+        size_t part_bytes;
+        region_part(r.conv, r.conv_bytes, nu, i, halves, out[i].cpart, part_bytes);
+        pr[i] = conv_problem(c, d, d.cin, d.cout, u.x, u.packed_w, out[i].cpart, part_bytes);
+        pd.flops += 2.0 * d.n * d.h * d.w * (double)d.cin * d.cout * d.ksize * d.ksize;
         pd.flops_exec += (double)c.g.L * 2.0 * 64 * 64 * 32;
+        out[i].ldp = c.ldp;
     }
-    if (!share_workgroups(pr, nu)) return 1;
+    if (!share_workgroups(pr, nu, G_total)) return 1;
     int g0 = 0;
     for (int i = 0; i < nu; ++i) {
-        if (!settle_conv(pr[i], a.c[i].g)) return 1;
+        if (!settle(pr[i], a.c[i].g)) return 1;
         a.c[i].g0 = g0; a.c[i].G = pr[i].G; g0 += pr[i].G;
-        out[i] = a.c[i].g;
+        out[i].cg = a.c[i].g;
     }
     a.nw = 0; a.nc = nu;
     pd.grid = g0;
@@ -604,72 +645,78 @@ int sk_run(const SkPlan* plan, hipStream_t s) {
 
 }  // namespace be
 
-// Test / inspection hook (CPU, no launch): the plan k_unit_gemms_sk would run for ONE unit [n,h,w,cin] -> cout, ksize 1 | 3 with
-// `workgroups` slots split between its weight gradient and its data gradient in proportion `w_share` (0..1).  Writes, per segment,
-// {problem (0 weight gradient, 1 convolution), tile, first chunk, last chunk + 1, slice, slices of the tile} to seg (6 ints each, at
-// most cap segments) and returns the segment count (< 0: error).  tests/test_host_cpu.py checks that the segments of every tile
-// partition its chunks and that the slice numbers are 0 .. slices - 1 - the arithmetic producer and consumers share.
-extern "C" int be_train_sk_plan_debug(int n, int h, int w, int cin, int cout, int ksize, int workgroups, double w_share, int* seg,
-                                      int cap) {
-    BE_REQUIRE(seg && cap > 0 && n >= 64 && n % 64 == 0 && h >= 3 && w >= 3 && h * w <= be_sk::MAX_HW && (ksize == 1 || ksize == 3) &&
-               cin % 128 == 0 && cout % 128 == 0 && workgroups >= 16 && w_share > 0.0 && w_share < 1.0, "be_train_sk_plan_debug: bad arguments");
-    const int ks = ksize, half = ks >> 1, taps = ks * ks, HW = h * w;
-    be_sk::WGeom wg{};
-    wg.tm = wg.tn = 128; wg.cin = cin; wg.cin_tiles = cin / 128; wg.wx = (cout / 128) * (cin / 128); wg.ntaps = taps;
-    for (int t = 0; t < taps; ++t) {
-        int y0, hv, x0, wv;
-        be_sk::tap_rect(h, w, t / ks - half, t % ks - half, y0, hv, x0, wv);
-        wg.PT[t + 1] = wg.PT[t] + (n / 16) * hv * wv;
+namespace {
+inline int tile_find(const be_sk::WGeom& g, int p) {
+    int tap, j;
+    be_sk::w_find(g, p, tap, j);
+    return tap * g.wx + j;
+}
+inline int tile_find(const be_sk::ConvGeom& g, int p) {
+    int grp, pp, j;
+    be_sk::conv_find(g, p, grp, pp, j);
+    return (grp * g.HW + pp) * g.n_tiles + j;
+}
+// the walk of k_unit_gemms_sk over one problem of G workgroups: emit(tile, first chunk, last chunk + 1, slice, slices of the tile)
+template <class Geom, class Emit>
+void walk_problem(const Geom& g, int G, Emit emit) {
+    for (int bl = 0; bl < G; ++bl) {
+        int pos = ((bl & 7) * (G >> 3) + (bl >> 3)) * g.Q;
+        const int end = pos + g.Q < g.L ? pos + g.Q : g.L;
+        if (pos >= end) continue;
+        int t = tile_find(g, pos);
+        while (pos < end) {
+            int ts, n;
+            tile_span(g, t, ts, n);
+            const int k1 = n < end - ts ? n : end - ts;
+            emit(t, pos - ts, k1, pos / g.Q - ts / g.Q, be_sk::slices_of(ts, n, g.Q));
+            pos = ts + k1;
+            ++t;                // the kernel's (tap, j) / (grp, pp, j) counters step through the tiles in this order
+        }
     }
-    wg.L = wg.PT[taps] * wg.wx;
-    be_sk::ConvGeom cg{};
-    cg.HW = HW; cg.n_tiles = cin / 64; cg.kmul = cout / 32; cg.ngrp = n / 64;
-    for (int pp = 0; pp < HW; ++pp) {
-        int nt = 0;
-        for (int t = 0; t < taps; ++t)
-            nt += (unsigned)(pp / w + t / ks - half) < (unsigned)h && (unsigned)(pp % w + t % ks - half) < (unsigned)w;
-        cg.PP[pp + 1] = (unsigned short)(cg.PP[pp] + nt);
+}
+}  // namespace
+
+// Test / inspection hook (host only: no device call, no launch): the plan sk_plan / sk_plan_fwd make for the unit a, or the pair
+// a, b, on `slots` workgroup slots (rounded down to a multiple of 8) with slice regions of conv_bytes / wgrad_bytes, and the walk
+// of k_unit_gemms_sk over it.  Writes, per segment, {problem, tile, first chunk, last chunk + 1, slice, slices of the tile} to seg
+// (6 ints each, at most cap segments) and, per problem, {g0, G, Q, L} to problems; problems are numbered in the launch's order
+// (weight gradients, then convolutions).  Returns the segment count; BE_EINVAL: a unit the balanced launch does not take,
+// BE_EWORKSPACE: "not mine" (a region too small).  tests/test_host_cpu.py holds the plans to expectations worked out there.
+extern "C" int be_train_sk_plan_debug(const be_conv_desc* a, const be_conv_desc* b, int forward, int slots, size_t conv_bytes,
+                                      size_t wgrad_bytes, int* seg, int cap, int* problems) {
+    BE_REQUIRE(a && seg && cap > 0 && problems && slots >= 8, "be_train_sk_plan_debug: bad arguments");
+    const be_conv_desc* d[2] = {a, b};
+    const int nu = b ? 2 : 1;
+    BE_REQUIRE(nu == 1 || (a->n == b->n && a->h == b->h && a->w == b->w && a->cout == b->cout && (forward || a->cin == b->cin)),
+               "be_train_sk_plan_debug: the two units must produce the same [n,h,w,cout] (backward: from the same input)");
+    float* const dummy = reinterpret_cast<float*>((uintptr_t)1 << 20);      // stands for every buffer: nothing dereferences it
+    const be::SkRegions r{dummy, conv_bytes, dummy, wgrad_bytes};
+    be_train_unit_fwd uf[2] = {};
+    be_train_unit_bwd ub[2] = {};
+    const be_train_unit_fwd* pf[2] = {&uf[0], &uf[1]};
+    const be_train_unit_bwd* pb[2] = {&ub[0], &ub[1]};
+    for (int i = 0; i < nu; ++i) {
+        uf[i].desc = ub[i].desc = *d[i];
+        uf[i].x = uf[i].packed_w = ub[i].x = ub[i].dgrad_packed_w = dummy;
+        ub[i].dy = ub[i].dx = dummy;
+        BE_REQUIRE(forward ? be::sk_fwd_eligible(uf[i].desc) : be::sk_eligible(ub[i]), "be_train_sk_plan_debug: not a unit of the balanced launch");
     }
-    cg.L = cg.ngrp * (int)cg.PP[HW] * cg.n_tiles * cg.kmul;
-    int Gw = (int)(workgroups * w_share) & ~7, Gc = (workgroups - Gw) & ~7;
-    if (Gw < 8) Gw = 8;
-    if (Gc < 8) Gc = 8;
-    wg.Q = (wg.L + Gw - 1) / Gw;
-    cg.Q = (cg.L + Gc - 1) / Gc;
-    int ns = 0;
-    auto emit = [&](int prob, int tile, int k0, int k1, int slice, int cnt) {
+    be::SkUnitOut out[2];
+    be::SkPlan plan;
+    if (forward ? be::sk_plan_fwd(pf, nu, r, slots & ~7, out, &plan) : be::sk_plan(pb, nu, r, slots & ~7, out, &plan)) return BE_EWORKSPACE;
+    const SkArgs& k = reinterpret_cast<const be::SkPlanData*>(plan.blob)->a;
+    int ns = 0, prob = 0;
+    const auto emit = [&](int tile, int k0, int k1, int slice, int cnt) {
         if (ns < cap) { int* e = seg + 6 * ns; e[0] = prob; e[1] = tile; e[2] = k0; e[3] = k1; e[4] = slice; e[5] = cnt; }
         ++ns;
     };
-    for (int g = 0; g < Gw; ++g) {                      // the walk of k_unit_gemms_sk, weight gradient
-        int pos = g * wg.Q;
-        const int end = pos + wg.Q < wg.L ? pos + wg.Q : wg.L;
-        if (pos >= end) continue;
-        int tap, j;
-        be_sk::w_find(wg, pos, tap, j);
-        while (pos < end) {
-            int ts, nn;
-            be_sk::w_span(wg, tap, j, ts, nn);
-            const int v0 = pos - ts, v1 = nn < end - ts ? nn : end - ts;
-            emit(0, tap * wg.wx + j, v0, v1, pos / wg.Q - ts / wg.Q, be_sk::slices_of(ts, nn, wg.Q));
-            pos = ts + v1;
-            if (++j == wg.wx) { j = 0; ++tap; }
-        }
-    }
-    for (int g = 0; g < Gc; ++g) {                      // ... convolution
-        int pos = g * cg.Q;
-        const int end = pos + cg.Q < cg.L ? pos + cg.Q : cg.L;
-        if (pos >= end) continue;
-        int grp, pp, j;
-        be_sk::conv_find(cg, pos, grp, pp, j);
-        while (pos < end) {
-            int ts, nn;
-            be_sk::conv_span(cg, grp, pp, j, ts, nn);
-            const int k0 = pos - ts, k1 = nn < end - ts ? nn : end - ts;
-            emit(1, (grp * HW + pp) * cg.n_tiles + j, k0, k1, pos / cg.Q - ts / cg.Q, be_sk::slices_of(ts, nn, cg.Q));
-            pos = ts + k1;
-            if (++j == cg.n_tiles) { j = 0; if (++pp == HW) { pp = 0; ++grp; } }
-        }
-    }
+    const auto problem = [&](const auto& p) {
+        int* rec = problems + 4 * prob;
+        rec[0] = p.g0; rec[1] = p.G; rec[2] = p.g.Q; rec[3] = p.g.L;
+        walk_problem(p.g, p.G, emit);
+        ++prob;
+    };
+    for (int i = 0; i < k.nw; ++i) problem(k.w[i]);
+    for (int i = 0; i < k.nc; ++i) problem(k.c[i]);
     return ns;
 }

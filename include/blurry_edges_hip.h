@@ -773,7 +773,9 @@ int be_train_unit_bwd_f32(const be_conv_desc* desc_host, const float* x, const f
 /* The same two entry points for TWO units that are independent of each other and share their input - the 3x3 convolution
  * (unit a) and the 1x1 downsample (unit b) of a ResidualBlock (models/local_stage.py:20-28): every launch of the single form
  * carries both units' workgroups (the two convolutions in one grid, the BatchNorm kernels with one grid slice per unit, one
- * closing kernel), each unit in its own half of the scratch regions.  Results are those of the single calls, bit for bit.
+ * closing kernel), each unit in its own part of the scratch regions.  Results are those of the single calls up to the regrouping
+ * of fp32 partial sums on the shapes the balanced launch takes (below: where a tile's K loop is cut depends on how many problems
+ * share the launch), and bit for bit with BE_NO_TRAIN_SK=1 in the environment.
  * Forward: both units produce the same [n,h,w,cout].  Backward: the units also share x and cin; a->dx receives the SUM of
  * both input gradients (what ResidualBlock's autograd node accumulates), b->dx [M,cin] is working space (contents
  * unspecified afterwards), dx_add must be NULL in both.  Shapes the merged launches do not take run one unit after the
@@ -794,15 +796,26 @@ int be_train_unit_pair_fwd_f32(const be_train_unit_fwd* a, const be_train_unit_f
                                void* scratch, size_t scratch_bytes, void* stream);
 int be_train_unit_pair_bwd_f32(const be_train_unit_bwd* a, const be_train_unit_bwd* b, void* scratch, size_t scratch_bytes,
                                void* stream);
-/* Round 6: the backward of the units with channel counts that are multiples of 128 on maps of at most 11 x 11 (layers 1-3 of
- * models/local_stage.py:38-41 at batch 64 k, local_training.py:103-106) runs its weight-gradient GEMM and data-gradient
- * convolution as ONE persistent, balanced launch (csrc/be_train_sk.h: every problem lays its tiles end to end on an axis of K
- * chunks, workgroup g takes the chunks [g Q, (g + 1) Q)); BE_NO_TRAIN_SK=1 in the environment selects rounds 3-5's equal-slice
- * launch instead.  This call is the HOST-ONLY inspection hook of that arithmetic (no GPU, no launch): the plan for one unit
- * [n,h,w,cin] -> cout, ksize 1 | 3, with `workgroups` slots of which the fraction w_share goes to the weight gradient.  Per
- * segment six ints are written to seg (at most cap segments): problem (0 weight gradient, 1 convolution), tile, first chunk,
- * last chunk + 1, slice, slices of that tile.  Returns the segment count, < 0 on bad arguments. */
-int be_train_sk_plan_debug(int n, int h, int w, int cin, int cout, int ksize, int workgroups, double w_share, int* seg, int cap);
+/* Round 6: the matrix work of the four entry points above - forward convolutions, weight-gradient GEMMs, data-gradient
+ * convolutions - runs as ONE persistent, balanced launch per call (csrc/be_train_sk.h: every problem lays its tiles end to end on
+ * an axis of K chunks, workgroup g takes the chunks [g Q, (g + 1) Q)) for the units it takes, forward and backward alike: ksize
+ * 1 | 3, cin and cout multiples of 32 and >= 64 (the forward: any cin that is a multiple of 32), n a multiple of 64, maps of at
+ * most 11 x 11 (ksize 3: at least 3 x 3), h = w = 1 included (fc.1), backward: an input gradient wanted (every unit of
+ * models/local_stage.py:38-50 behind conv1 at batch 64 k, local_training.py:103-106).  Other shapes, and everything with
+ * BE_NO_TRAIN_SK=1 in the environment, take rounds 3-5's equal-slice launches.  The number of workgroups is the device's CU count
+ * x 3 (BE_SK_SLOTS), and it decides where the K loops are cut: results depend on the CU count in the grouping of their fp32
+ * partial sums, and are reproducible bit for bit on one device.
+ * This call is the HOST-ONLY inspection hook of that launch's planner (no GPU, no launch): it runs the planner the entry points
+ * run for the unit a (b NULL) or the pair a, b (the same [n,h,w,cout]; backward: the same cin too) - forward != 0: the forward
+ * convolutions, else the backward - on `slots` workgroup slots (rounded down to a multiple of 8, >= 8) with conv_bytes /
+ * wgrad_bytes of scratch for the convolution / weight-gradient slices, then walks the plan as the kernel does.  Per segment six
+ * ints are written to seg (at most cap segments): problem, tile, first chunk, last chunk + 1, slice, slices of that tile; per
+ * problem four to problems (room for 4 x 4): first workgroup, workgroups, quota, chunks.  Problems are numbered in the launch's
+ * order: the units' weight gradients, then their convolutions (one backward unit: 0 and 1; forward: convolutions only).
+ * Returns the segment count, BE_EINVAL for a unit the launch does not take, BE_EWORKSPACE where the planner declines ("not
+ * mine": a region holds fewer than two slices of a tile). */
+int be_train_sk_plan_debug(const be_conv_desc* a, const be_conv_desc* b, int forward, int slots, size_t conv_bytes,
+                           size_t wgrad_bytes, int* seg, int cap, int* problems);
 
 /* Parameter gradients of y = x W^T + b over many rows (the linears of GlobalStage in training, global_training.py:207-213 under
  * autograd): dw [cout,cin] = dy^T x and db [cout] = column sums of dy, in two launches (weight-gradient tiles + column-sum

@@ -503,50 +503,95 @@ def test_opencv_scan_conversion_rules_known_answers():
 def test_balanced_backward_plan_partitions_every_tile_and_numbers_its_slices():
     """Round 6 (csrc/be_train_sk.h): the backward GEMMs of a training unit run as ONE persistent launch in which workgroup g of a
     problem takes the K chunks [g Q, (g + 1) Q) of the problem's tiles laid end to end; a tile's segments write its slices 0, 1, ...
-    and the consumer (k_bwd_post) derives the slice count from the axis alone.  be_train_sk_plan_debug runs that arithmetic on the
-    host (the same inline functions the kernels use): for the shapes of LocalStage's layers 1-3 and some odd ones the segments of every
-    tile partition its chunks exactly, the slice numbers are 0 .. n - 1 in chunk order, and every segment reports the slice count the
-    consumer computes.  Expected tile lengths are worked out here independently (valid taps per pixel, valid pixels per tap)."""
+    and the consumers (k_bn_stats, k_bwd_post) derive the slice count from the axis alone.  be_train_sk_plan_debug runs THE planner
+    of the entry points (eligibility, sk_plan / sk_plan_fwd with the real region sizes: the water-filling and its caps, the settle
+    loops, the split of the regions between a pair) and then walks the plan as the kernel does, XCD remap included: for the shapes of
+    LocalStage's layers 0-3, fc.1, a block's pair and some odd ones, backward and forward, the segments of every tile partition its
+    chunks exactly, the slice numbers are 0 .. n - 1 in chunk order, every segment reports the slice count the consumer computes, no
+    tile has more slices than its consumer takes, and the problems' workgroup ranges tile [0, sum G) within the slots.  Expected tile
+    lengths are worked out here independently (valid taps per pixel, valid pixels per tap)."""
     import ctypes as C
     from be_hip import native
     lib = native.lib()
+    CONV_BYTES, WGRAD_BYTES = 40 << 20, 70 << 20              # be_train.hip: SCR_WGRAD - SCR_CONV, SCR_TOTAL - SCR_WGRAD
+    EINVAL, NOT_MINE = -1, -2                                 # BE_EINVAL, BE_EWORKSPACE
+    MAX_SLICES_W, MAX_SLICES_C = 16, 8                        # be_train_sk.h: what k_bwd_post / k_bn_stats take per tile
 
-    def plan(n, h, w, cin, cout, ks, wg, share):
+    def plan(units, forward, slots, conv_bytes=CONV_BYTES, wgrad_bytes=WGRAD_BYTES):
         cap = 50000
-        seg = (C.c_int * (6 * cap))()
-        ns = lib.be_train_sk_plan_debug(n, h, w, cin, cout, ks, wg, share, seg, cap)
+        seg, probs = (C.c_int * (6 * cap))(), (C.c_int * 16)()
+        d = [native.ConvDesc(n, h, w, cin, cout, ks, 0) for (n, h, w, cin, cout, ks) in units]
+        ns = lib.be_train_sk_plan_debug(C.byref(d[0]), C.byref(d[1]) if len(d) == 2 else None, int(forward), slots, conv_bytes, wgrad_bytes,
+                                        seg, cap, probs)
+        if ns < 0:
+            return ns, None, None
         assert 0 < ns <= cap, ns
-        return np.frombuffer(seg, dtype=np.int32)[:6 * ns].reshape(ns, 6).copy()
+        return ns, np.frombuffer(seg, dtype=np.int32)[:6 * ns].reshape(ns, 6).copy(), np.frombuffer(probs, dtype=np.int32).reshape(4, 4).copy()
 
-    for (n, h, w, cin, cout, ks, wg, share) in ((64, 6, 6, 384, 384, 3, 768, 0.5), (64, 6, 6, 256, 384, 3, 768, 0.45), (64, 6, 6, 256, 384, 1, 768, 0.5),
-                                                (128, 6, 6, 256, 256, 3, 768, 0.3), (64, 11, 11, 128, 128, 3, 768, 0.5), (64, 3, 3, 128, 256, 3, 64, 0.5),
-                                                (64, 6, 5, 384, 256, 3, 1000, 0.61), (192, 4, 7, 128, 128, 1, 333, 0.2)):
-        s = plan(n, h, w, cin, cout, ks, wg, share)
-        half = ks // 2
-        for prob in (0, 1):
+    def w_tiles(n, h, w, cin, cout, ks):      # weight gradient: tm x tn tiles per tap (128, or 64 where the channel count is no multiple
+        half = ks // 2                        # of 128; the last tile of a side may be half empty), a chunk = one valid pixel of 16 images
+        tm, tn = (128 if cout % 128 == 0 else 64), (128 if cin % 128 == 0 else 64)
+        wx = -(-cout // tm) * -(-cin // tn)
+        return {t * wx + j: (n // 16) * (h - abs(t // ks - half)) * (w - abs(t % ks - half)) for t in range(ks * ks) for j in range(wx)}
+
+    def conv_tiles(n, h, w, cin, cout, ks):   # convolution cin -> cout: a pixel of 64 images x 64 outputs (the last column tile may be half
+        half, nt, exp = ks // 2, -(-cout // 64), {}           # empty), cin / 32 chunks per valid tap
+        for g in range(n // 64):
+            for pp in range(h * w):
+                py, px = pp // w, pp % w
+                taps = sum(1 for t in range(ks * ks) if 0 <= py + t // ks - half < h and 0 <= px + t % ks - half < w)
+                for j in range(nt):
+                    exp[(g * h * w + pp) * nt + j] = taps * (cin // 32)
+        return exp
+
+    def check(units, forward, slots, **regions):
+        ns, s, pr = plan(units, forward, slots, **regions)
+        assert ns > 0, (units, forward, slots, ns)            # every listed shape must plan: none is skipped
+        # problems in the launch's order: the units' weight gradients, then their convolutions (the data gradient: cout -> cin)
+        exps = [conv_tiles(*u) for u in units] if forward else \
+               [w_tiles(*u) for u in units] + [conv_tiles(n, h, w, cout, cin, ks) for (n, h, w, cin, cout, ks) in units]
+        smax = [MAX_SLICES_C] * len(units) if forward else [MAX_SLICES_W] * len(units) + [MAX_SLICES_C] * len(units)
+        assert set(s[:, 0].tolist()) == set(range(len(exps)))
+        g_next, worst = 0, []
+        for prob, exp in enumerate(exps):
+            g0, G, Q, L = (int(v) for v in pr[prob])
+            assert G % 8 == 0 and G >= 8 and g0 == g_next, (units, forward, prob, g0, G)
+            assert L == sum(exp.values()) and Q == -(-L // G), (units, forward, prob, Q, L)
+            g_next += G
             tiles = {}
             for _, t, k0, k1, sl, cnt in s[s[:, 0] == prob]:
                 assert k1 > k0
                 tiles.setdefault(int(t), []).append((int(k0), int(k1), int(sl), int(cnt)))
-            exp = {}
-            if prob == 0:                                         # weight gradient: 128 x 128 tiles per tap, a chunk = one valid pixel of 16 images
-                wx = (cout // 128) * (cin // 128)
-                for t in range(ks * ks):
-                    dy, dx = t // ks - half, t % ks - half
-                    for j in range(wx):
-                        exp[t * wx + j] = (n // 16) * (h - abs(dy)) * (w - abs(dx))
-            else:                                                 # data gradient: a pixel of 64 images x 64 channels, cout / 32 chunks per valid tap
-                nt = cin // 64
-                for g in range(n // 64):
-                    for pp in range(h * w):
-                        py, px = pp // w, pp % w
-                        taps = sum(1 for t in range(ks * ks) if 0 <= py + t // ks - half < h and 0 <= px + t % ks - half < w)
-                        for j in range(nt):
-                            exp[(g * h * w + pp) * nt + j] = taps * (cout // 32)
             assert set(tiles) == set(exp), (prob, len(tiles), len(exp))
             for t, segs in tiles.items():
                 segs.sort()
                 assert segs[0][0] == 0 and segs[-1][1] == exp[t], (t, segs, exp[t])
                 assert all(a[1] == b[0] for a, b in zip(segs, segs[1:])), segs
                 assert [x[2] for x in segs] == list(range(len(segs))) and all(x[3] == len(segs) for x in segs), segs
-    assert lib.be_train_sk_plan_debug(63, 6, 6, 128, 128, 3, 768, 0.5, (C.c_int * 6)(), 1) < 0      # a ragged batch is not this launch's
+                assert len(segs) <= smax[prob], (units, forward, prob, t, len(segs))
+            worst.append(max(len(v) for v in tiles.values()))
+        assert g_next <= slots, (units, forward, g_next, slots)
+        return worst
+
+    singles = (((64, 6, 6, 384, 384, 3), 768), ((64, 6, 6, 256, 384, 3), 768), ((64, 6, 6, 256, 384, 1), 768), ((128, 6, 6, 256, 256, 3), 768),
+               ((64, 11, 11, 128, 128, 3), 768), ((64, 3, 3, 128, 256, 3), 64), ((64, 6, 5, 384, 256, 3), 1000), ((192, 4, 7, 128, 128, 1), 333),
+               ((64, 11, 11, 64, 96, 3), 768), ((64, 11, 11, 96, 96, 3), 768),       # layer0: 64-wide tiles, half-empty second column tile
+               ((64, 1, 1, 2304, 1024, 1), 768))                                    # fc.1 as the callers pass it
+    for u, slots in singles:
+        check([u], False, slots)
+        check([u], True, slots)
+    pair = [(64, 6, 6, 256, 384, 3), (64, 6, 6, 256, 384, 1)]                        # a block's 3x3 convolution and its 1x1 downsample
+    check(pair, False, 768)
+    check(pair, True, 768)
+    # the regions bound the slices: with room for exactly two slices of a tile the plan holds every tile to two ...
+    u = (64, 6, 6, 384, 384, 3)
+    csize, wsize = 64 * 36 * 384 * 4, 384 * 384 * 9 * 4
+    assert check([u], False, 768, conv_bytes=2 * csize)[1] <= 2 and check([u], False, 768, wgrad_bytes=2 * wsize)[0] <= 2
+    assert check([u], True, 768, conv_bytes=2 * csize)[0] <= 2
+    # ... and with less the planner declines ("not mine": the entry points then take the equal-slice launches)
+    assert plan([u], False, 768, conv_bytes=2 * csize - 4)[0] == NOT_MINE and plan([u], False, 768, wgrad_bytes=2 * wsize - 4)[0] == NOT_MINE
+    assert plan([u], True, 768, conv_bytes=2 * csize - 4)[0] == NOT_MINE and plan(pair, False, 768, conv_bytes=2 * csize)[0] == NOT_MINE
+    # not this launch's: a ragged batch, 48 channels, a 3x3 kernel on a 2 x 2 map, a pair whose units differ in their output
+    for bad in ([(63, 6, 6, 128, 128, 3)], [(64, 6, 6, 48, 128, 3)], [(64, 2, 2, 128, 128, 3)], [(64, 6, 6, 256, 384, 3), (64, 6, 6, 256, 256, 1)]):
+        assert plan(bad, False, 768)[0] == EINVAL, bad
+    assert plan([(63, 6, 6, 128, 128, 3)], True, 768)[0] == EINVAL and plan([(64, 6, 6, 128, 48, 3)], True, 768)[0] == EINVAL
