@@ -212,6 +212,8 @@ _SIGNATURES = {
     "be_train_unit_pair_bwd_f32": (C.c_int, [C.POINTER(TrainUnitBwd), C.POINTER(TrainUnitBwd), _P, C.c_size_t, _P]),
     "be_train_sk_plan_debug": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_size_t, C.c_size_t,
                                          C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "be_conv_plan_debug": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_int),
+                                     C.POINTER(C.c_double)]),
     "be_linear_param_grads_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "be_linear_small_fwd_f32": (C.c_int, [_P] * 4 + [C.c_int] * 3 + [_P]),
     "be_maxpool_nhwc_fwd_idx_f32": (C.c_int, [_P, _P, _P] + [C.c_int] * 7 + [_P]),

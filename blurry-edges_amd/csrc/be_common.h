@@ -90,7 +90,9 @@ bool rows_bf6_enabled();
 int vec_add_inplace(float* a, const float* b, int n, void* stream);
 
 // be_conv_pm.hip: pixel-major LDS-DMA convolution for large batches (3x3 (+ fused 1x1 on x2), or the 7x7 conv1 on the padded
-// staging with `wrow` pixels per row); returns 1 when the shape is not one it is built for (the caller falls back)
+// staging with `wrow` pixels per row); returns 1 when the shape is not one it is built for.  conv_pm_takes: that question on its
+// own (shape, 32-bit spans and the BE_NO_CONV_PM knob; no pointer, no device): be_conv.hip's planner routes by it
+bool conv_pm_takes(const be_conv_desc* d, int wrow, bool fused, int cin2, int ldy);
 int conv_pm(const be_conv_desc* d, const float* x, int wrow, const float* x2, int cin2, const float* pw, const float* pb,
             float* y, int ldy, int ktot, void* stream);
 
@@ -117,9 +119,10 @@ int wino_pair(const float* x, const float* packed_w1, const float* packed_bias1,
 // (read once per process).  pool_wino_in: be_maxpool_wino_in_11x11_f32; pooled may be null (the pooled map is then not stored)
 bool wino_ds_fold_enabled();
 int pool_wino_in(const float* x, float* pooled, int64_t n, int c, int next_cmid, float* workspace, size_t workspace_floats, void* stream);
-// be_conv.hip: convolution / linear of a training unit (small M).  With scratch the K loop may be split: then the S raw slices
-// are LEFT in scratch as [S][M][ldp] (S > 1 reported, nothing written to y, bias / res not applied) for the caller's kernel to sum;
-// S == 1: y = conv + bias (+ res).
+// be_conv.hip: convolution / linear of a training unit: planned (conv_plan, the planner of every be_conv_nhwc*_f32 entry point) and
+// launched.  With scratch the plan may split the K loop of a small-M tile: then the S raw slices are LEFT in scratch as [S][M][ldp]
+// (S > 1 reported, nothing written to y, bias / res not applied) for the caller's kernel to sum; S == 1: y = conv + bias (+ res).
+// conv_train_prepare (be_igemm_body.h) makes the same plan and hands it back instead of launching it.
 int conv_train(const be_conv_desc* d, const float* x, const float* pw, const float* pb, const float* res, float* y, int ldy,
                void* scratch, size_t scratch_bytes, int* S_out, int* ldp_out, void* stream);
 

@@ -21,6 +21,11 @@
 //   - pixel-major M tiles for large batches (a tile = one pixel position of BM images): the taps that fall into the
 //     zero padding are skipped for the whole tile; an image group's tiles share one XCD (see the kernel)
 //   - an optional second input x2 appends a 1x1 conv to the K loop (residual block: downsample branch fused in)
+//
+// Host side: every entry point (be_conv_nhwc_f32, _fused2, _batched, _splitk, be::conv_train, be::conv_train_prepare) states its
+// problem as a ConvProblem; conv_plan checks it and decides route, tile, K-chunk, grid, K split and profile record without touching
+// a device; conv_launch launches the plan.  What follows a split K loop is each caller's own part.  be_conv_plan_debug runs the
+// planner on a machine without a GPU (tests/test_host_cpu.py).
 #include <mutex>
 #include "be_common.h"
 #include "be_device_math.h"
@@ -63,37 +68,44 @@ double executed_chunks(const ConvArgs& a, bool row8, int bkt) {
     return chunks;
 }
 
-template <int WM, int WN, int MT, int NT, int MODE, int BKT = 32, int PRIO = 0, bool UNI = false>
-int launch_conv(const ConvArgs& a, hipStream_t s, int kernel_id) {
+// What conv_plan decides (further down): the route, the tile and its K-chunk, the kernel arguments, the grid (gx x S x nbatch) and
+// the profile record of the launch.  Nothing in it touches a device.
+enum ConvRoute { ROUTE_ROWS = 0, ROUTE_PM = 1, ROUTE_IGEMM = 2 };
+struct ConvPlan {
+    int route, tile, bkt, kernel_id;
+    ConvArgs a;
+    unsigned gx;
+    int S, ldp;                          // S > 1: the raw K slices go to a.partial [S][M][ldp], the caller sums them
+    double flops, bytes, flops_exec;
+};
+
+// The profile record of a launch with bm x bn tiles and K-chunks of bkt floats.  Algorithmic work: 2*M*K*Cout with the REAL K (no
+// padding), bytes = in + weights + out.  MFMA work actually issued: every tile runs (its number of K chunks) x (2*bm*bn*bkt) flops,
+// padding included.
+void conv_work(ConvPlan* p, int bm, int bn) {
+    const ConvArgs& a = p->a;
+    const bool row8 = p->tile == be::TILE_ROW8;
+    const double k_real = row8 ? 3.0 * 49.0 : (double)a.Cin * a.ks * a.ks, cin_real = row8 ? 3.0 : (double)a.Cin;
+    const double k2_real = a.x2 ? (double)a.Cin2 : 0.0;
+    const double nb = a.nbatch > 1 ? a.nbatch : 1;
+    p->flops = nb * 2.0 * a.M * (k_real + k2_real) * a.Cout;
+    p->bytes = nb * 4.0 * (a.M * (cin_real + k2_real) + (k_real + k2_real) * a.Cout + (double)a.M * a.Cout * (a.res ? 2 : 1));
+    p->flops_exec = nb * executed_chunks(a, row8, p->bkt) * 2.0 * bm * bn * p->bkt;
+}
+
+template <int WM, int WN, int MT, int NT, int MODE, int BKT, int PRIO = 0, bool UNI = false>
+int launch_conv(const ConvPlan& p, hipStream_t s) {
     constexpr int BN = WN * NT * 32;
     constexpr int BM = WM * MT * 32;
     constexpr size_t lds = (size_t)2 * (BM + BN) * (BKT + 4) * sizeof(float);
     static be::DeviceFlags attr_set{};                      // dynamic-LDS cap raised once per device (thread-safe)
     if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_conv_igemm<WM, WN, MT, NT, MODE, BKT, PRIO, UNI>), lds, attr_set)) return rc_;
-    // slots per XCD: flat tiles are dealt round-robin; pixel-major tiles keep a group of images on one XCD
-    const int per_xcd = a.pixmaj == 1 ? ((a.m_tiles / a.HW + 7) / 8) * a.HW : (a.m_tiles + 7) / 8;
-    const unsigned grid = (unsigned)(8 * per_xcd * a.n_tiles);
-    {   // algorithmic work of this launch: 2*M*K*Cout with the REAL K (no padding); bytes = in + weights + out
-        const double k_real = MODE == MODE_ROW8 ? 3.0 * 49.0 : (double)a.Cin * a.ks * a.ks;
-        const double cin_real = MODE == MODE_ROW8 ? 3.0 : (double)a.Cin;
-        // MFMA work actually issued: every tile runs (its number of K chunks) x (2*BM*BN*BKT) flops, padding included;
-        // pixel-major tiles visit only the taps inside the image
-        const double chunks = executed_chunks(a, MODE == MODE_ROW8, BKT);
-        const double k2_real = a.x2 ? (double)a.Cin2 : 0.0;
-        const double nb = a.nbatch > 1 ? a.nbatch : 1;
-        be::ProfileScope prof(s, kernel_id, nb * 2.0 * a.M * (k_real + k2_real) * a.Cout,
-                              nb * 4.0 * (a.M * (cin_real + k2_real) + (k_real + k2_real) * a.Cout + (double)a.M * a.Cout * (a.res ? 2 : 1)),
-                              nb * chunks * 2.0 * BM * BN * BKT);
-        hipLaunchKernelGGL((k_conv_igemm<WM, WN, MT, NT, MODE, BKT, PRIO, UNI>), dim3(grid, a.ksplit > 1 ? a.ksplit : 1, a.nbatch > 1 ? a.nbatch : 1),
-                           dim3(256), lds, s, a);
+    {
+        be::ProfileScope prof(s, p.kernel_id, p.flops, p.bytes, p.flops_exec);
+        hipLaunchKernelGGL((k_conv_igemm<WM, WN, MT, NT, MODE, BKT, PRIO, UNI>), dim3(p.gx, p.S, p.a.nbatch > 1 ? p.a.nbatch : 1),
+                           dim3(256), lds, s, p.a);
     }
     return be::check_launch("be_conv_nhwc_f32");
-}
-
-// tuning knob for A/B runs: BE_CONV_VARIANT=32 selects the K-chunk-32 instantiations
-inline int conv_variant() {
-    static const int v = getenv("BE_CONV_VARIANT") ? atoi(getenv("BE_CONV_VARIANT")) : 0;
-    return v;
 }
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -468,9 +480,6 @@ extern "C" int be_conv_pack_jobs_f32(const be_pack_job* jobs_device, int njobs, 
     return be::check_launch("be_conv_pack_jobs_f32");
 }
 
-struct BatchParams { int n; int64_t xb, wb, yb; };
-static thread_local BatchParams g_batch = {1, 0, 0, 0};   // set around one dispatch by be_conv_nhwc_batched_f32
-
 // y = act(sum_s partial[s] + bias (+ res)): the epilogue of a split-K launch, fixed summation order
 __global__ void k_splitk_reduce(const float* __restrict__ partial, int S, int64_t M, int Cout, int ldp,
                                 const float* __restrict__ bias, const float* __restrict__ res, int act,
@@ -490,17 +499,180 @@ __global__ void k_splitk_reduce(const float* __restrict__ partial, int S, int64_
     }
 }
 
-// defer (training units): when the K loop was split the S raw slices stay in scratch [S][M][ldp] and NO reduce kernel is launched -
-// the caller's own kernel sums them (with the bias) while it does its other work on the tile; S = 1: y = conv + bias as always
-struct SplitOut { int S, ldp; be::ConvPrep* prep; bool pad64; };   // prep != null: do not launch at all - hand the prepared launch back;
-                                                                    // pad64: 96 output channels may run as two 64-wide uniform tiles
-static int conv_dispatch(const be_conv_desc* d, const float* x, const float* x2, int cin2, const float* pw, const float* pb,
-                         const float* res, float* y, int ldy, void* stream, void* scratch = nullptr, size_t scratch_bytes = 0,
-                         SplitOut* defer = nullptr);
+namespace {
+// ------------------------------------------------------------------------------------------- plan, then launch
+// One convolution problem, as every entry point states it.  scratch: lent by the callers that can sum K slices themselves
+// (be_conv_nhwc_splitk_f32, the training units); pad64: 96-wide outputs may run as two 64-wide uniform tiles.
+struct ConvProblem {
+    const be_conv_desc* d;
+    const float *x, *pw, *pb, *res;
+    float* y;
+    int ldy;
+    void* scratch = nullptr;
+    size_t scratch_bytes = 0;
+    bool pad64 = false;
+    const float* x2 = nullptr;
+    int cin2 = 0, nbatch = 1;
+    int64_t xb = 0, wb = 0, yb = 0;
+};
+
+// A/B knobs, read once per process ("set at all" counts).  BE_CONV_VARIANT=32: the K-chunk-32 builds, and no LDS-DMA kernel;
+// 99: no pixel-major tiles
+struct ConvKnobs { int variant; bool no_rows, no_uni, no_pad64; };
+const ConvKnobs& conv_knobs() {
+    static const ConvKnobs k{getenv("BE_CONV_VARIANT") ? atoi(getenv("BE_CONV_VARIANT")) : 0, getenv("BE_NO_GEMM_ROWS") != nullptr,
+                             getenv("BE_NO_UNI_TILES") != nullptr, getenv("BE_NO_PAD64") != nullptr};
+    return k;
+}
+
+struct TileShape { int bm, bn, kernel_id; };
+constexpr TileShape kTile[] = {   // by be::ConvTile
+    {64, 64, BE_KERNEL_CONV_SMALL}, {128, 32, BE_KERNEL_CONV_SMALL}, {64, 64, BE_KERNEL_CONV_SMALL}, {128, 128, BE_KERNEL_CONV_128x128},
+    {128, 96, BE_KERNEL_CONV_128x96}, {128, 64, BE_KERNEL_CONV_128x64}, {128, 32, BE_KERNEL_CONV_128x32}, {128, 64, BE_KERNEL_CONV_ROW8_128x64}};
+// K-chunk 16 (40 KB of LDS, three workgroups per CU) measured 8 % faster than 32 (two per CU); 8 is slower again (barrier per 16
+// MFMAs); s_setprio around the MFMA phase and a 4th workgroup per CU change nothing.  The 128x64 and 128x32 tiles are built with 32 only.
+int tile_bkt(int tile) {
+    if (be::tile_is_small(tile)) return 16;
+    return tile == be::TILE_128x64 || tile == be::TILE_128x32 || conv_knobs().variant == 32 ? 32 : 16;
+}
+int launch_tile(const ConvPlan& p, hipStream_t s) {
+    const bool k32 = p.bkt == 32;
+    switch (p.tile) {
+    case be::TILE_S64:     return launch_conv<2, 2, 1, 1, MODE_TAPS, 16>(p, s);
+    case be::TILE_S128x32: return launch_conv<4, 1, 1, 1, MODE_TAPS, 16>(p, s);
+    case be::TILE_S64_UNI: return launch_conv<2, 2, 1, 1, MODE_TAPS, 16, 0, true>(p, s);
+    case be::TILE_128x128: return k32 ? launch_conv<2, 2, 2, 2, MODE_TAPS, 32>(p, s) : launch_conv<2, 2, 2, 2, MODE_TAPS, 16>(p, s);
+    case be::TILE_128x96:  return k32 ? launch_conv<4, 1, 1, 3, MODE_TAPS, 32>(p, s) : launch_conv<4, 1, 1, 3, MODE_TAPS, 16>(p, s);
+    case be::TILE_128x64:  return launch_conv<4, 1, 1, 2, MODE_TAPS, 32>(p, s);
+    case be::TILE_128x32:  return launch_conv<4, 1, 1, 1, MODE_TAPS, 32>(p, s);
+    default:               return k32 ? launch_conv<4, 1, 1, 2, MODE_ROW8, 32>(p, s) : launch_conv<4, 1, 1, 2, MODE_ROW8, 16>(p, s);
+    }
+}
+
+// Checks the arguments and decides everything about the launch; makes no HIP call.  Preparing a convolution is planning it.
+int conv_plan(const ConvProblem& q, ConvPlan* p) {
+    const be_conv_desc* d = q.d;
+    BE_REQUIRE(d && q.x && q.pw && q.y, "be_conv_nhwc_f32: null pointer");
+    BE_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0 && d->cout > 0, "be_conv_nhwc_f32: empty shape");
+    BE_REQUIRE(d->h < 32768 && d->w < 32768, "be_conv_nhwc_f32: image too large");
+    const bool row8 = d->ksize == 7;
+    if (row8) BE_REQUIRE(d->cin == 4, "be_conv_nhwc_f32: ksize 7 needs the NHWC4 input (cin = 4)");
+    else BE_REQUIRE((d->ksize == 1 || d->ksize == 3) && d->cin % BK == 0,
+                    "be_conv_nhwc_f32: ksize %d / cin %d unsupported", d->ksize, d->cin);
+    BE_REQUIRE(q.ldy >= d->cout, "be_conv_nhwc_f32: ldy < cout");
+    BE_REQUIRE(be::aligned16(q.x) && be::aligned16(q.pw), "be_conv_nhwc_f32: x / packed_w must be 16-byte aligned");
+    const int64_t M = (int64_t)d->n * d->h * d->w;
+    BE_REQUIRE(M * (int64_t)d->cin < (int64_t)1 << 40 && M < (int64_t)1 << 31, "be_conv_nhwc_f32: batch too large");
+    const ConvKnobs& knob = conv_knobs();
+    const int cp = round_up(d->cout, 32);
+    ConvArgs& a = p->a;
+    a.x = q.x; a.w = q.pw; a.bias = q.pb; a.res = q.res; a.y = q.y;
+    a.M = (int)M; a.H = d->h; a.W = d->w; a.HW = d->h * d->w; a.Cin = d->cin; a.Cout = d->cout; a.ldy = q.ldy;
+    a.ks = d->ksize; a.nchunk = conv_nchunk(d->cin, d->ksize); a.Ktot = a.nchunk * BK + (q.x2 ? q.cin2 : 0); a.act = d->act;
+    a.x2 = q.x2; a.Cin2 = q.cin2;
+    a.m_tiles = (int)((M + 127) / 128);
+    a.pixmaj = 0; a.Nimg = d->n;
+    a.ksplit = 1; a.ldp = 0; a.partial = nullptr;
+    a.nbatch = q.nbatch; a.xb = q.xb; a.wb = q.wb; a.yb = q.yb;
+    p->route = ROUTE_IGEMM; p->S = 1; p->ldp = 0;
+    const bool single = !q.x2 && a.nbatch <= 1;
+    // Small-M regime (training at batch 64: M = 2304 rows at 6x6): the 128-row tiles give a few dozen workgroups on 256 CUs and
+    // one launch lasts as long as ONE workgroup's serial K loop.  Below ~1.5 workgroups per CU: 64x64 (or 128x32) tiles, 4x the
+    // workgroups, each with a quarter of the work.
+    const bool small = !row8 && (int64_t)a.m_tiles * ((cp + 127) / 128) < 384;
+    if (d->ksize == 1 && single && !knob.no_rows && d->cin % 16 == 0 &&
+        ((cp == 128 && M >= 16384) || (!small && cp % 128 == 0 && M >= 4096))) {
+        // 1x1 convolutions / linears of large batches are plain row GEMMs: the LDS-DMA kernel of be_wino.hip (bit-identical).  A
+        // 128-wide output over >= 16384 rows (GlobalStage at 8 x 4096 tokens) is "few tiles" for the rule above, which sent it
+        // to 64x64 tiles (33 us per launch): it comes here whatever that rule says.  be::gemm_rows sizes its own grid
+        p->route = ROUTE_ROWS; p->tile = be::TILE_128x128; a.n_tiles = cp / 128;
+    } else if (small) {
+        // full 64-image tiles (the training batch) are pixel-major too, dealt round-robin over the XCDs (few image groups)
+        const bool pm2 = d->ksize > 1 && d->n >= 64 && d->n % 64 == 0 && knob.variant != 99;
+        // uniform 64 x 64 tiles (be_igemm_body.h, UNI): those pixel-major tiles, and 1x1 convolutions / linears whose row count is
+        // a multiple of 64 - no border test, addresses = per-thread constant + uniform offset (32-bit: hence the spans)
+        const bool uni = !knob.no_uni && single && M * (int64_t)d->cin * 4 < ((int64_t)1 << 32) &&
+                         (int64_t)cp * a.Ktot * 4 < ((int64_t)1 << 32) && (pm2 || (d->ksize == 1 && M % 64 == 0));
+        // 96 output channels (the data gradients that flow into layer0 / layer1) as TWO 64-wide uniform tiles, the second half
+        // empty (a third more MFMA work, on tiles twice as fast as the bordered 128 x 32 ones).  Only where the caller allows it -
+        // the backward: the forward keeps its tiles, and with them its bits
+        const bool pad64 = q.pad64 && cp % 64 == 32 && cp > 64 && uni && !knob.no_pad64;
+        // (round 3 tried 64 x 128 tiles for the training convolutions onto 384 channels: 1 % of the step, the narrower layers lose,
+        // and the different split of the K loop moves the train-mode logits by 1e-6.  Not kept)
+        if (cp % 64 == 0 || pad64) {
+            p->tile = uni ? be::TILE_S64_UNI : be::TILE_S64;
+            a.m_tiles = pm2 ? a.HW * (d->n / 64) : (int)((M + 63) / 64);
+            a.n_tiles = (cp + 63) / 64;
+            a.pixmaj = pm2 ? 2 : 0;
+        } else {
+            p->tile = be::TILE_S128x32; a.n_tiles = cp / 32;
+        }
+        // split-K when the caller lent scratch: a few hundred workgroups each walking the whole K loop leave most of the chip idle
+        // (batch-64 training: 144-216 tiles, up to 216 chunks each); S slices make S times the workgroups, each 1/S as long
+        if (q.scratch) {
+            const int64_t tiles = (int64_t)a.m_tiles * a.n_tiles;
+            const int kchunks = a.nchunk * 2;                               // 16-float chunks of the longest tile
+            int S = (int)((768 + tiles - 1) / tiles);
+            if (S > 8) S = 8;
+            while (S > 1 && kchunks / S < 12) --S;
+            while (S > 1 && (size_t)S * M * cp * sizeof(float) > q.scratch_bytes) --S;
+            if (S > 1) { p->S = a.ksplit = S; p->ldp = a.ldp = cp; a.partial = static_cast<float*>(q.scratch); }
+        }
+    } else if (d->ksize == 3 && d->n >= 512 && !q.res && a.nbatch <= 1 && knob.variant == 0 && be::aligned16(q.y) && q.ldy % 4 == 0 &&
+               be::conv_pm_takes(d, d->w, q.x2 != nullptr, q.cin2, q.ldy)) {
+        // large batches of small images, 3x3: the pixel-major LDS-DMA kernel (be_conv_pm.hip; bit-identical), 256 images x 96
+        p->route = ROUTE_PM; p->tile = be::TILE_128x96;
+        a.pixmaj = 1; a.m_tiles = a.HW * ((d->n + 255) / 256); a.n_tiles = cp / 96;
+    } else {
+        // large batches of small images: pixel-major tiles skip the taps that fall into the zero padding
+        if (d->ksize > 1 && d->n >= 512 && knob.variant != 99) {
+            a.pixmaj = 1;
+            a.m_tiles = a.HW * ((d->n + 127) / 128);
+        }
+        if (row8) BE_REQUIRE(cp == 64, "be_conv_nhwc_f32: ksize 7 is built for cout 64 (got %d)", d->cout);
+        p->tile = row8 ? be::TILE_ROW8 : cp % 128 == 0 ? be::TILE_128x128 : cp % 96 == 0 ? be::TILE_128x96
+                  : cp % 64 == 0 ? be::TILE_128x64 : be::TILE_128x32;
+        a.n_tiles = cp / kTile[p->tile].bn;
+    }
+    const bool igemm = p->route == ROUTE_IGEMM;
+    p->bkt = igemm ? tile_bkt(p->tile) : 16;
+    p->kernel_id = p->route == ROUTE_ROWS ? BE_KERNEL_GEMM_ROWS : kTile[p->tile].kernel_id;
+    // slots per XCD: flat tiles are dealt round-robin; pixel-major tiles keep a group of images on one XCD
+    const int per_xcd = a.pixmaj == 1 ? ((a.m_tiles / a.HW + 7) / 8) * a.HW : (a.m_tiles + 7) / 8;
+    p->gx = p->route == ROUTE_ROWS ? 0 : (unsigned)(8 * per_xcd * a.n_tiles);
+    conv_work(p, p->route == ROUTE_PM ? 256 : kTile[p->tile].bm, kTile[p->tile].bn);
+    return BE_OK;
+}
+
+// Launches what the plan says.  S > 1: the raw slices are left in a.partial - summing them is the caller's part
+int conv_launch(const ConvPlan& p, void* stream) {
+    const ConvArgs& a = p.a;
+    if (p.route == ROUTE_ROWS) return be::gemm_rows(a.x, a.M, a.Cin, a.w, a.Cout, a.bias, a.res, a.act, a.y, a.ldy, stream);
+    if (p.route == ROUTE_PM) {
+        const be_conv_desc d{a.Nimg, a.H, a.W, a.Cin, a.Cout, a.ks, a.act};
+        const int rc = be::conv_pm(&d, a.x, a.W, a.x2, a.Cin2, a.w, a.bias, a.y, a.ldy, a.Ktot, stream);
+        return rc == 1 ? be::fail(BE_EINVAL, "be_conv_nhwc_f32: the pixel-major kernel refused a shape planned for it") : rc;
+    }
+    return launch_tile(p, be::as_stream(stream));
+}
+int conv_run(const ConvProblem& q, void* stream, ConvPlan* p) {
+    if (int rc = conv_plan(q, p)) return rc;
+    return conv_launch(*p, stream);
+}
+int conv_run(const ConvProblem& q, void* stream) { ConvPlan p; return conv_run(q, stream, &p); }
+
+// what be::conv_train_prepare hands back: the plan of a small-M tile with scratch lent; nothing (TILE_NONE) for any other plan
+be::ConvPrep plan_to_prep(const ConvPlan& p, const void* scratch) {
+    if (p.route == ROUTE_IGEMM && be::tile_is_small(p.tile) && scratch) return be::ConvPrep{p.a, p.tile, p.S, p.ldp, p.gx, p.flops, p.flops_exec};
+    be::ConvPrep none{};
+    none.variant = be::TILE_NONE;
+    return none;
+}
+}  // namespace
 
 extern "C" int be_conv_nhwc_f32(const be_conv_desc* d, const float* x, const float* pw, const float* pb,
                                 const float* res, float* y, int ldy, void* stream) {
-    return conv_dispatch(d, x, nullptr, 0, pw, pb, res, y, ldy, stream);
+    return conv_run(ConvProblem{d, x, pw, pb, res, y, ldy}, stream);
 }
 
 extern "C" int be_conv_nhwc_fused2_f32(const be_conv_desc* d, const float* x, const float* x2, int cin2, const float* pw,
@@ -508,181 +680,76 @@ extern "C" int be_conv_nhwc_fused2_f32(const be_conv_desc* d, const float* x, co
     BE_REQUIRE(x2 && cin2 > 0 && cin2 % BK == 0, "be_conv_nhwc_fused2_f32: x2 / cin2 (%% 32 == 0) required");
     BE_REQUIRE(d && d->ksize != 7, "be_conv_nhwc_fused2_f32: not available for the 7x7 row-gather mode");
     BE_REQUIRE(be::aligned16(x2), "be_conv_nhwc_fused2_f32: x2 must be 16-byte aligned");
-    return conv_dispatch(d, x, x2, cin2, pw, pb, nullptr, y, ldy, stream);
+    ConvProblem q{d, x, pw, pb, nullptr, y, ldy};
+    q.x2 = x2; q.cin2 = cin2;
+    return conv_run(q, stream);
 }
 
 extern "C" int be_conv_nhwc_batched_f32(const be_conv_desc* d, const float* x, const float* pw, const float* pb, float* y, int ldy,
                                         int nbatch, int64_t x_stride, int64_t w_stride, int64_t y_stride, void* stream) {
     BE_REQUIRE(nbatch >= 1 && nbatch <= 65535, "be_conv_nhwc_batched_f32: nbatch outside [1, 65535]");
     BE_REQUIRE(x_stride % 4 == 0 && w_stride % 4 == 0, "be_conv_nhwc_batched_f32: strides must keep 16-byte alignment");
-    g_batch = {nbatch, x_stride, w_stride, y_stride};
-    const int rc = conv_dispatch(d, x, nullptr, 0, pw, pb, nullptr, y, ldy, stream);
-    g_batch = {1, 0, 0, 0};
-    return rc;
+    ConvProblem q{d, x, pw, pb, nullptr, y, ldy};
+    q.nbatch = nbatch; q.xb = x_stride; q.wb = w_stride; q.yb = y_stride;
+    return conv_run(q, stream);
 }
 
+// the split-K entry: y = act(sum of the slices + bias (+ res)) by k_splitk_reduce when the plan split the K loop
 extern "C" int be_conv_nhwc_splitk_f32(const be_conv_desc* d, const float* x, const float* pw, const float* pb,
                                        const float* res, float* y, int ldy, void* scratch, size_t scratch_bytes, void* stream) {
     BE_REQUIRE(scratch && be::aligned16(scratch), "be_conv_nhwc_splitk_f32: scratch required (16-byte aligned)");
-    return conv_dispatch(d, x, nullptr, 0, pw, pb, res, y, ldy, stream, scratch, scratch_bytes);
+    ConvPlan p;
+    if (int rc = conv_run(ConvProblem{d, x, pw, pb, res, y, ldy, scratch, scratch_bytes}, stream, &p)) return rc;
+    if (p.S == 1) return BE_OK;
+    hipLaunchKernelGGL(k_splitk_reduce, dim3(grid_cap((int64_t)p.a.M * d->cout, 256)), dim3(256), 0, be::as_stream(stream), p.a.partial,
+                       p.S, (int64_t)p.a.M, d->cout, p.ldp, pb, res, d->act, y, ldy);
+    return be::check_launch("be_conv_nhwc_splitk_f32");
 }
 
+// the training units (be_train.hip): the slices stay in scratch, S / ldp say where (S == 1: y = conv + bias (+ res))
 int be::conv_train(const be_conv_desc* d, const float* x, const float* pw, const float* pb, const float* res, float* y, int ldy,
                    void* scratch, size_t scratch_bytes, int* S_out, int* ldp_out, void* stream) {
-    SplitOut so{1, 0, nullptr, false};
-    const int rc = conv_dispatch(d, x, nullptr, 0, pw, pb, res, y, ldy, stream, scratch, scratch_bytes, &so);
-    *S_out = so.S; *ldp_out = so.ldp;
+    ConvPlan p;
+    p.S = 1; p.ldp = 0;
+    const int rc = conv_run(ConvProblem{d, x, pw, pb, res, y, ldy, scratch, scratch_bytes}, stream, &p);
+    *S_out = p.S; *ldp_out = p.ldp;
     return rc;
 }
 
+// the same plan handed back for k_unit_gemms to run; variant is TILE_NONE for anything but a small-M tile with scratch: the caller
+// launches that unit on its own
 int be::conv_train_prepare(const be_conv_desc* d, const float* x, const float* pw, const float* pb, const float* res, float* y, int ldy,
                            void* scratch, size_t scratch_bytes, be::ConvPrep* prep, bool pad64) {
-    prep->variant = -1;
-    SplitOut so{1, 0, prep, pad64};
-    const int rc = conv_dispatch(d, x, nullptr, 0, pw, pb, res, y, ldy, nullptr, scratch, scratch_bytes, &so);
-    return rc;        // prep->variant stays -1 for a shape outside the small-M tiles: the caller launches it on its own instead
+    prep->variant = be::TILE_NONE;
+    ConvPlan p;
+    if (int rc = conv_plan(ConvProblem{d, x, pw, pb, res, y, ldy, scratch, scratch_bytes, pad64}, &p)) return rc;
+    *prep = plan_to_prep(p, scratch);
+    return BE_OK;
 }
 
-static int conv_dispatch(const be_conv_desc* d, const float* x, const float* x2, int cin2, const float* pw, const float* pb,
-                         const float* res, float* y, int ldy, void* stream, void* scratch, size_t scratch_bytes, SplitOut* defer) {
-    BE_REQUIRE(d && x && pw && y, "be_conv_nhwc_f32: null pointer");
-    BE_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0 && d->cout > 0, "be_conv_nhwc_f32: empty shape");
-    BE_REQUIRE(d->h < 32768 && d->w < 32768, "be_conv_nhwc_f32: image too large");
-    const bool row8 = d->ksize == 7;
-    if (row8) BE_REQUIRE(d->cin == 4, "be_conv_nhwc_f32: ksize 7 needs the NHWC4 input (cin = 4)");
-    else BE_REQUIRE((d->ksize == 1 || d->ksize == 3) && d->cin % BK == 0,
-                    "be_conv_nhwc_f32: ksize %d / cin %d unsupported", d->ksize, d->cin);
-    BE_REQUIRE(ldy >= d->cout, "be_conv_nhwc_f32: ldy < cout");
-    BE_REQUIRE(be::aligned16(x) && be::aligned16(pw), "be_conv_nhwc_f32: x / packed_w must be 16-byte aligned");
-    const int64_t M = (int64_t)d->n * d->h * d->w;
-    BE_REQUIRE(M * (int64_t)d->cin < (int64_t)1 << 40 && M < (int64_t)1 << 31, "be_conv_nhwc_f32: batch too large");
-    ConvArgs a;
-    a.x = x; a.w = pw; a.bias = pb; a.res = res; a.y = y;
-    a.M = (int)M; a.H = d->h; a.W = d->w; a.HW = d->h * d->w; a.Cin = d->cin; a.Cout = d->cout; a.ldy = ldy;
-    a.ks = d->ksize; a.nchunk = conv_nchunk(d->cin, d->ksize); a.Ktot = a.nchunk * BK + (x2 ? cin2 : 0); a.act = d->act;
-    a.x2 = x2; a.Cin2 = cin2;
-    a.m_tiles = (int)((M + 127) / 128);
-    a.pixmaj = 0; a.Nimg = d->n;
-    a.ksplit = 1; a.ldp = 0; a.partial = nullptr;
-    a.nbatch = g_batch.n; a.xb = g_batch.xb; a.wb = g_batch.wb; a.yb = g_batch.yb;
-    const int cp = round_up(d->cout, 32);
-    hipStream_t s = be::as_stream(stream);
-    // Small-M regime (training at batch 64: M = 2304 rows at 6x6): the 128-row tiles give a few dozen workgroups on
-    // 256 CUs and one launch lasts as long as ONE workgroup's serial K loop.  Below ~1.5 workgroups per CU switch to
-    // 64x64 (or 128x32) tiles: 4x the workgroups, each with a quarter of the work.
-    static const bool no_rows = getenv("BE_NO_GEMM_ROWS") != nullptr;             // A/B knob
-    // linears over many rows with a 128-wide output (GlobalStage at 8 x 4096 tokens: out-projection, second feed-forward linear
-    // and three of the four data gradients): 256 row tiles x ONE column tile is "few tiles" for the rule below, which sent them to
-    // 64x64 tiles (33 us per launch); they are plain row GEMMs for the LDS-DMA kernel (bit-identical, see further down)
-    // prepare-only calls (be::conv_train_prepare: `stream` is not the caller's stream and the operands may not be final yet): a
-    // shape that is not handed back as a prepared small-M launch must leave WITHOUT launching anything - prep->variant stays -1
-    // and the caller runs the unit on its own (layer0 at batch >= 406 and wide linears over >= 16384 rows fell
-    // through to a launch on the null stream here, inside a hipGraph capture among others)
-    const bool prep_only = defer && defer->prep;
-    if (d->ksize == 1 && !x2 && cp == 128 && M >= 16384 && a.nbatch <= 1 && !no_rows && d->cin % 16 == 0) {
-        if (prep_only) return BE_OK;
-        return be::gemm_rows(x, M, d->cin, pw, d->cout, pb, res, d->act, y, ldy, stream);
-    }
-    if (prep_only && !(!row8 && (int64_t)a.m_tiles * ((cp + 127) / 128) < 384 && scratch)) return BE_OK;
-    if (!row8 && (int64_t)a.m_tiles * ((cp + 127) / 128) < 384) {
-        // 96 output channels (the data gradients that flow into layer0 / layer1, whose inputs have 96 channels) as TWO 64-wide uniform
-        // tiles, the second half empty (a third more MFMA work, on tiles that are twice as fast as the bordered 128 x 32 ones).  Only
-        // where the caller allows it - the backward: the forward keeps its tiles, and with them its bits (pad64)
-        const bool pad64 = defer && defer->pad64 && cp % 64 == 32 && cp > 64 && !x2 && a.nbatch <= 1 &&
-                           ((d->ksize > 1 && d->n >= 64 && d->n % 64 == 0 && conv_variant() != 99) || (d->ksize == 1 && M % 64 == 0)) &&
-                           M * (int64_t)d->cin * 4 < ((int64_t)1 << 32) && (int64_t)cp * a.Ktot * 4 < ((int64_t)1 << 32) &&
-                           getenv("BE_NO_UNI_TILES") == nullptr && getenv("BE_NO_PAD64") == nullptr;      // = every condition of `uni` below
-        const bool t64 = cp % 64 == 0 || pad64;
-        // (round 3 tried 64 x 128 tiles - a wave owning 32 x 64 - for the training convolutions onto 384 channels: 79 -> 66 us and
-        // 56 -> 48 us for those two layers, 1 % of the step; the narrower layers lose.  Not kept: the different split of the K loop
-        // moves the train-mode logits by 1e-6, and on the teacher-forced test's worst-conditioned batch that is a 7e-6 loss
-        // difference against a 3e-6 bound written for the 64 x 64 tiles)
-        if (t64) {
-            a.m_tiles = (int)((M + 63) / 64); a.n_tiles = (cp + 63) / 64;
-            if (d->ksize > 1 && d->n >= 64 && d->n % 64 == 0 && conv_variant() != 99) {
-                // full 64-image tiles (the training batch): pixel-major here too, tiles dealt round-robin over the
-                // XCDs because there are only a few image groups
-                a.pixmaj = 2;
-                a.m_tiles = a.HW * (d->n / 64);
-            }
-        } else {
-            a.n_tiles = cp / 32;
-        }
-        // uniform 64 x 64 tiles (be_igemm_body.h, UNI): the pixel-major tiles of whole 64-image groups, and 1x1 convolutions /
-        // linears whose row count is a multiple of 64 - no border test, addresses = per-thread constant + uniform offset
-        static const bool no_uni = getenv("BE_NO_UNI_TILES") != nullptr;              // A/B knob
-        const bool uni = t64 && !no_uni && !x2 && a.nbatch <= 1 && M * (int64_t)d->cin * 4 < ((int64_t)1 << 32) &&
-                         (int64_t)cp * a.Ktot * 4 < ((int64_t)1 << 32) && (a.pixmaj == 2 || (d->ksize == 1 && M % 64 == 0));
-        // split-K when the caller lent scratch: a few hundred workgroups each walking the whole K loop leave most of
-        // the chip idle (batch-64 training: 144-216 tiles, up to 216 chunks each); S slices make S times the
-        // workgroups, each 1/S as long, and a small reduce kernel applies bias / residual / activation
-        if (scratch) {
-            const int64_t tiles = (int64_t)a.m_tiles * a.n_tiles;
-            const int kchunks = a.nchunk * 2;                               // 16-float chunks of the longest tile
-            int S = (int)((768 + tiles - 1) / tiles);
-            if (S > 8) S = 8;
-            while (S > 1 && kchunks / S < 12) --S;
-            while (S > 1 && (size_t)S * M * cp * sizeof(float) > scratch_bytes) --S;
-            if (defer && defer->prep) {                                     // hand the launch back (be_train.hip: k_unit_gemms)
-                if (S > 1) { a.ksplit = S; a.ldp = cp; a.partial = static_cast<float*>(scratch); }
-                be::ConvPrep* pr = defer->prep;
-                pr->args = a; pr->variant = uni ? 2 : (t64 ? 0 : 1); pr->S = S > 1 ? S : 1; pr->ldp = S > 1 ? cp : 0;
-                pr->gx = (unsigned)(8 * ((a.m_tiles + 7) / 8) * a.n_tiles);
-                pr->flops = 2.0 * a.M * (double)a.Cin * a.ks * a.ks * a.Cout;
-                pr->flops_exec = executed_chunks(a, false, 16) * 2.0 * (t64 ? 64.0 * 64.0 : 128.0 * 32.0) * 16.0;
-                return BE_OK;
-            }
-            if (S > 1) {
-                a.ksplit = S; a.ldp = cp; a.partial = static_cast<float*>(scratch);
-                const int rc = uni ? launch_conv<2, 2, 1, 1, MODE_TAPS, 16, 0, true>(a, s, BE_KERNEL_CONV_SMALL)
-                               : t64 ? launch_conv<2, 2, 1, 1, MODE_TAPS, 16, 0>(a, s, BE_KERNEL_CONV_SMALL)
-                                     : launch_conv<4, 1, 1, 1, MODE_TAPS, 16, 0>(a, s, BE_KERNEL_CONV_SMALL);
-                if (rc) return rc;
-                if (defer) { defer->S = S; defer->ldp = cp; return BE_OK; }
-                const int64_t total = M * d->cout;
-                hipLaunchKernelGGL(k_splitk_reduce, dim3(grid_cap(total, 256)), dim3(256), 0, s, a.partial, S, M, d->cout, cp,
-                                   pb, res, d->act, y, ldy);
-                return be::check_launch("be_conv_nhwc_splitk_f32");
-            }
-        }
-        return uni ? launch_conv<2, 2, 1, 1, MODE_TAPS, 16, 0, true>(a, s, BE_KERNEL_CONV_SMALL)
-               : t64 ? launch_conv<2, 2, 1, 1, MODE_TAPS, 16, 0>(a, s, BE_KERNEL_CONV_SMALL)
-                     : launch_conv<4, 1, 1, 1, MODE_TAPS, 16, 0>(a, s, BE_KERNEL_CONV_SMALL);
-    }
-    // 1x1 convolutions / linears of large batches are plain row GEMMs: the LDS-DMA kernel of be_wino.hip (bit-identical)
-    if (d->ksize == 1 && !x2 && cp % 128 == 0 && M >= 4096 && a.nbatch <= 1 && !no_rows && d->cin % 16 == 0)
-        return be::gemm_rows(x, M, d->cin, pw, d->cout, pb, res, d->act, y, ldy, stream);
-    // large batches of small images, 3x3: the pixel-major LDS-DMA kernel (be_conv_pm.hip; bit-identical)
-    if (d->ksize == 3 && d->n >= 512 && !res && a.nbatch <= 1 && conv_variant() == 0 && be::aligned16(y) && ldy % 4 == 0) {
-        const int rc = be::conv_pm(d, x, d->w, x2, cin2, pw, pb, y, ldy, a.Ktot, stream);
-        if (rc != 1) return rc;
-    }
-    // large batches of small images: pixel-major tiles skip the taps that fall into the zero padding
-    if (d->ksize > 1 && d->n >= 512 && conv_variant() != 99) {
-        a.pixmaj = 1;
-        a.m_tiles = a.HW * ((d->n + 127) / 128);
-    }
-    if (row8) {
-        BE_REQUIRE(cp == 64, "be_conv_nhwc_f32: ksize 7 is built for cout 64 (got %d)", d->cout);
-        a.n_tiles = 1;
-        if (conv_variant() == 32) return launch_conv<4, 1, 1, 2, MODE_ROW8, 32, 0>(a, s, BE_KERNEL_CONV_ROW8_128x64);
-        return launch_conv<4, 1, 1, 2, MODE_ROW8, 16, 0>(a, s, BE_KERNEL_CONV_ROW8_128x64);
-    }
-    if (cp % 128 == 0) {
-        a.n_tiles = cp / 128;
-        // K-chunk 16 (40 KB of LDS, three workgroups per CU) measured 8 % faster than 32 (two per CU); 8 is slower
-        // again (barrier per 16 MFMAs); s_setprio around the MFMA phase and a 4th workgroup per CU change nothing.
-        if (conv_variant() == 32) return launch_conv<2, 2, 2, 2, MODE_TAPS, 32, 0>(a, s, BE_KERNEL_CONV_128x128);
-        return launch_conv<2, 2, 2, 2, MODE_TAPS, 16, 0>(a, s, BE_KERNEL_CONV_128x128);
-    }
-    if (cp % 96 == 0) {
-        a.n_tiles = cp / 96;
-        if (conv_variant() == 32) return launch_conv<4, 1, 1, 3, MODE_TAPS, 32, 0>(a, s, BE_KERNEL_CONV_128x96);
-        return launch_conv<4, 1, 1, 3, MODE_TAPS, 16, 0>(a, s, BE_KERNEL_CONV_128x96);
-    }
-    if (cp % 64 == 0)  { a.n_tiles = cp / 64;  return launch_conv<4, 1, 1, 2, MODE_TAPS>(a, s, BE_KERNEL_CONV_128x64); }
-    a.n_tiles = cp / 32;
-    return launch_conv<4, 1, 1, 1, MODE_TAPS>(a, s, BE_KERNEL_CONV_128x32);
+// Test / inspection hook (host only: no device call, no launch): the plan conv_plan makes, under the process's knobs, for d with an
+// optional fused x2 (cin2 > 0), residual, nbatch (> 1: batched) and scratch_bytes of lent scratch (0 = none).  mode 0: as the
+// be_conv_nhwc*_f32 entry points state the problem, 1: as the training units do, 2: those with pad64.  out[16] = {route, tile,
+// K-chunk, kernel id, pixmaj, m_tiles, n_tiles, grid x, y, z, S, ldp, what conv_train_prepare hands back for the same problem:
+// variant (-1: nothing), S, ldp, gx}; *flops_exec = the executed FLOPs of the profile record.
+extern "C" int be_conv_plan_debug(const be_conv_desc* d, int cin2, int has_res, int ldy, int nbatch, size_t scratch_bytes, int mode,
+                                  int* out, double* flops_exec) {
+    BE_REQUIRE(d && out && flops_exec && mode >= 0 && mode <= 2 && nbatch >= 1, "be_conv_plan_debug: bad arguments");
+    BE_REQUIRE(cin2 >= 0 && cin2 % BK == 0, "be_conv_nhwc_fused2_f32: x2 / cin2 (%% 32 == 0) required");       // as that entry point
+    float* const dummy = reinterpret_cast<float*>((uintptr_t)1 << 20);      // stands for every buffer: nothing dereferences it
+    ConvProblem q{d, dummy, dummy, dummy};
+    q.x2 = cin2 > 0 ? dummy : nullptr; q.cin2 = cin2; q.res = has_res ? dummy : nullptr; q.y = dummy; q.ldy = ldy;
+    q.nbatch = nbatch; q.xb = q.wb = q.yb = nbatch > 1 ? 1 << 20 : 0;
+    q.scratch = scratch_bytes ? dummy : nullptr; q.scratch_bytes = scratch_bytes; q.pad64 = mode == 2;
+    ConvPlan p;
+    if (int rc = conv_plan(q, &p)) return rc;
+    const be::ConvPrep prep = plan_to_prep(p, mode > 0 ? q.scratch : nullptr);
+    const int rec[16] = {p.route, p.tile, p.bkt, p.kernel_id, p.a.pixmaj, p.a.m_tiles, p.a.n_tiles, (int)p.gx, p.S,
+                         p.a.nbatch > 1 ? p.a.nbatch : 1, p.S, p.ldp, prep.variant, prep.variant < 0 ? 0 : prep.S,
+                         prep.variant < 0 ? 0 : prep.ldp, prep.variant < 0 ? 0 : (int)prep.gx};
+    for (int i = 0; i < 16; ++i) out[i] = rec[i];
+    *flops_exec = p.flops_exec;
+    return BE_OK;
 }
 
 extern "C" int be_maxpool_nhwc_f32(const float* x, float* y, int n, int h, int w, int c, int k, int stride, int pad,

@@ -258,13 +258,24 @@ int launch_pm(const PmArgs& a, hipStream_t s, int kernel_id) {
 
 }  // namespace
 
-// Called by conv_dispatch (be_conv.hip) for large batches (n >= 512): 3x3 convolutions (optionally with the fused 1x1 on
-// x2) with cout_pad % 96 == 0 or % 64 == 0, and the 7x7 conv1 on the padded staging (wrow = 28).  Returns BE_OK, an error,
-// or 1 = "not mine" (the caller falls back to k_conv_igemm).
+// The shapes this kernel is built for: 3x3 convolutions (optionally with the fused 1x1 on x2) with cout_pad % 96 == 0, and the 7x7
+// conv1 (cout_pad 64) on the padded staging (wrow = 28).  Pure: conv_plan (be_conv.hip) routes by it, conv_pm checks it again.
+bool be::conv_pm_takes(const be_conv_desc* d, int wrow, bool fused, int cin2, int ldy) {
+    static const bool off = getenv("BE_NO_CONV_PM") != nullptr;                   // A/B knob
+    if (off || d->h < 3 || d->w < 3) return false;
+    const int cp = (d->cout + 31) / 32 * 32;
+    const int64_t hw = (int64_t)d->h * d->w, istride = d->ksize == 7 ? (int64_t)d->h * wrow * 4 : hw * d->cin, istride2 = hw * cin2;
+    // 32-bit lane offsets: 256 images of input / output must span < 2^32 bytes
+    if (256 * 4 * (istride > istride2 ? istride : istride2) >= ((int64_t)1 << 32) || 256 * 4 * hw * ldy >= ((int64_t)1 << 32)) return false;
+    if (d->ksize == 7) return cp == 64 && d->cin == 4 && wrow >= d->w + 7;
+    return d->ksize == 3 && d->cin % 32 == 0 && !(fused && cin2 % 16) && cp % 96 == 0;
+}
+
+// Called by conv_launch (be_conv.hip) for the plans of its pixel-major route (large batches, n >= 512) and by
+// be_conv7x7_nhwc4p_f32.  Returns BE_OK, an error, or 1 = "not mine" (a shape conv_pm_takes refuses).
 int be::conv_pm(const be_conv_desc* d, const float* x, int wrow, const float* x2, int cin2, const float* pw, const float* pb,
                 float* y, int ldy, int ktot, void* stream) {
-    static const bool off = getenv("BE_NO_CONV_PM") != nullptr;                   // A/B knob
-    if (off) return 1;
+    if (!be::conv_pm_takes(d, wrow, x2 != nullptr, cin2, ldy)) return 1;
     const int cp = (d->cout + 31) / 32 * 32;
     PmArgs a;
     a.x = x; a.x2 = x2; a.w = pw; a.bias = pb; a.y = y;
@@ -273,18 +284,11 @@ int be::conv_pm(const be_conv_desc* d, const float* x, int wrow, const float* x2
     a.istride = d->ksize == 7 ? (int64_t)d->h * wrow * 4 : (int64_t)a.HW * d->cin;
     a.istride2 = (int64_t)a.HW * cin2;
     hipStream_t s = be::as_stream(stream);
-    // 32-bit lane offsets: 256 images of input / output must span < 2^32 bytes
-    const int64_t span = 256 * 4 * (a.istride > a.istride2 ? a.istride : a.istride2);
-    if (span >= ((int64_t)1 << 32) || 256 * 4 * (int64_t)a.HW * ldy >= ((int64_t)1 << 32) || d->h < 3 || d->w < 3) return 1;
+    a.groups = (d->n + 255) / 256;
     if (d->ksize == 7) {
-        if (cp != 64 || d->cin != 4 || wrow < d->w + 7) return 1;
-        a.groups = (d->n + 255) / 256; a.n_tiles = 1;
+        a.n_tiles = 1;
         return launch_pm<2, 2, PM_ROW8>(a, s, BE_KERNEL_CONV_ROW8_128x64);
     }
-    if (d->ksize != 3 || d->cin % 32 || (x2 && cin2 % 16)) return 1;
-    if (cp % 96 == 0) {
-        a.groups = (d->n + 255) / 256; a.n_tiles = cp / 96;
-        return launch_pm<2, 3, PM_TAPS3>(a, s, BE_KERNEL_CONV_128x96);
-    }
-    return 1;
+    a.n_tiles = cp / 96;
+    return launch_pm<2, 3, PM_TAPS3>(a, s, BE_KERNEL_CONV_128x96);
 }

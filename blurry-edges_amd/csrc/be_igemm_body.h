@@ -39,7 +39,7 @@ struct ConvArgs {
 // (pixel-major tiles of whole image groups; 1x1 convolutions / linears with M a multiple of the tile): no border test, no zero
 // fill, and the operand addresses are a per-thread constant + a wave-uniform offset - the register-staged loop then issues ~0 VALU
 // instructions per chunk instead of ~30 (the 64 x 64 training tiles issued 4 VALU per MFMA, profiles/r03_train_pmc_summary.json).
-// The host asserts the preconditions (conv_dispatch).  Same arithmetic, same order: bit-identical to UNI = false.
+// The host asserts the preconditions (conv_plan in be_conv.hip).  Same arithmetic, same order: bit-identical to UNI = false.
 template <int WM, int WN, int MT, int NT, int MODE, int BKT, int PRIO, bool UNI = false>
 __device__ __forceinline__ void conv_igemm_body(ConvArgs a, float* smem, const int bx, const int by, const int bz) {
     static_assert(WM * WN == 4, "4 waves");
@@ -373,9 +373,16 @@ __device__ __forceinline__ void conv_igemm_body(ConvArgs a, float* smem, const i
 }  // namespace be_igemm
 
 namespace be {
-// be_conv.hip: a small-M training convolution PREPARED but not launched: the kernel arguments, the tile variant (0: 64x64 tiles =
-// conv_igemm_body<2,2,1,1,MODE_TAPS,16,0>, 1: 128x32 tiles = <4,1,1,1,...>, 2: 64x64 uniform tiles = <2,2,1,1,...,UNI>), its grid (gx workgroups x S K-slices) and where the raw
-// slices go ([S][M][ldp] in scratch when S > 1; S == 1: the epilogue writes y = conv + bias (+ res)).
+// The block tiles of conv_igemm_body, each named once (be_conv.hip maps a tile to its k_conv_igemm build).  The three small-M
+// tiles come first: they are also k_unit_gemms' template argument (be_train.hip) and what a ConvPrep carries.
+//   TILE_S64 = <2,2,1,1,MODE_TAPS,16,0>, TILE_S128x32 = <4,1,1,1,...>, TILE_S64_UNI = <2,2,1,1,...,UNI>
+enum ConvTile { TILE_NONE = -1, TILE_S64 = 0, TILE_S128x32 = 1, TILE_S64_UNI = 2, TILE_128x128, TILE_128x96, TILE_128x64, TILE_128x32,
+                TILE_ROW8 };
+inline bool tile_is_small(int tile) { return tile >= TILE_S64 && tile <= TILE_S64_UNI; }
+
+// be_conv.hip: a small-M training convolution PLANNED but not launched: the kernel arguments, the tile (`variant`: one of the three
+// small tiles, TILE_NONE = not a small-M launch), its grid (gx workgroups x S K-slices) and where the raw slices go ([S][M][ldp]
+// in scratch when S > 1; S == 1: the epilogue writes y = conv + bias (+ res)).
 struct ConvPrep { be_igemm::ConvArgs args; int variant, S, ldp; unsigned gx; double flops, flops_exec; };
 int conv_train_prepare(const be_conv_desc* d, const float* x, const float* pw, const float* pb, const float* res, float* y, int ldy,
                        void* scratch, size_t scratch_bytes, ConvPrep* prep, bool pad64 = false);

@@ -498,7 +498,7 @@ void k_wgrad128(Wgrad128Args a) {
 // other, forward and backward: workgroups [0, w_end[0]) take the first weight gradient, [w_end[0], w_end[1]) the second (the long
 // ones first), then the convolutions ([.., c_end0) the first, the rest the second; the forward pair is two convolutions and no
 // weight gradient).  Every range is padded to a multiple of 8 so that the convolution's XCD-aware tile map - workgroup id mod
-// 8 = XCD - is unchanged.  CV: the convolutions' tile variant (be::ConvPrep), the same for both.
+// 8 = XCD - is unchanged.  CV: the convolutions' small tile (be::ConvTile, as be::ConvPrep::variant carries it), the same for both.
 struct WJob {
     Wgrad128Args w128;
     WgradArgs w64;
@@ -1476,8 +1476,9 @@ int launch_unit_gemms(const UnitGemmsArgs& g, unsigned grid, hipStream_t s) {
     hipLaunchKernelGGL(k_unit_gemms<CV>, dim3(grid), dim3(256), lds, s, g);
     return BE_OK;
 }
-inline int launch_unit_gemms(int variant, const UnitGemmsArgs& g, unsigned grid, hipStream_t s) {
-    return variant == 0 ? launch_unit_gemms<0>(g, grid, s) : variant == 1 ? launch_unit_gemms<1>(g, grid, s) : launch_unit_gemms<2>(g, grid, s);
+inline int launch_unit_gemms(int tile, const UnitGemmsArgs& g, unsigned grid, hipStream_t s) {      // tile: be::ConvPrep::variant
+    return tile == be::TILE_S64 ? launch_unit_gemms<be::TILE_S64>(g, grid, s)
+           : tile == be::TILE_S128x32 ? launch_unit_gemms<be::TILE_S128x32>(g, grid, s) : launch_unit_gemms<be::TILE_S64_UNI>(g, grid, s);
 }
 inline int pad8(int v) { return (v + 7) / 8 * 8; }
 
@@ -1782,7 +1783,7 @@ int unit_bwd_one(const be_train_unit_bwd& u, char* sc, void* stream, const char*
         if (int rc = plan_wgrad(u, wpart, SCR_TOTAL - SCR_WGRAD, &g.w[0], &pj, &w_exec, who)) return rc;
         static const bool no_merge = getenv("BE_NO_BWD_MERGE") != nullptr;        // A/B knob
         be::ConvPrep prep;
-        prep.variant = -1;
+        prep.variant = be::TILE_NONE;
         be_conv_desc dd{d->n, d->h, d->w, C, d->cin, d->ksize, 0};
         if (u.dx && !no_merge)
             if (int rc = be::conv_train_prepare(&dd, u.dy, u.dgrad_packed_w, u.dgrad_packed_bias, u.dx_add, u.dx, d->cin, sc + SCR_CONV,

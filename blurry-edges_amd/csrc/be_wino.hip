@@ -1410,7 +1410,7 @@ int wino_args_ok(const char* who, int64_t n, int cin, int cout) {
 }  // namespace
 
 // 1x1 convolutions and linears of large batches through the same kernel: y[M][ldy] = act(x[M][K] w[Npad][K]^T + bias (+ res)).
-// The caller (conv_dispatch in be_conv.hip) has checked: K % 16 == 0, Npad % 128 == 0, 16-byte aligned x / w, M >= 4096.
+// The caller (conv_plan in be_conv.hip chose the route) has checked: K % 16 == 0, Npad % 128 == 0, 16-byte aligned x / w, M >= 4096.
 // Same order of operations per output element as k_conv_igemm (K ascending in chunks of 16, fp32 MFMA): bit-identical.
 int be::gemm_rows(const float* x, int64_t M, int K, const float* packed_w, int N, const float* bias, const float* res, int act,
                   float* y, int ldy, void* stream) {

@@ -567,6 +567,18 @@ int be_conv_nhwc_f32(const be_conv_desc* desc_host, const float* x, const float*
  * scratch: 8 * M * cout_pad32 * 4 bytes is always enough (fewer slices are used when it is smaller). */
 int be_conv_nhwc_splitk_f32(const be_conv_desc* d, const float* x, const float* packed_w, const float* packed_bias,
                             const float* residual, float* y, int ldy, void* scratch, size_t scratch_bytes, void* stream);
+/* HOST-ONLY inspection hook of the fp32 convolution's planner (no GPU, no launch): the plan that be_conv_nhwc_f32 and its fused2
+ * / batched / splitk forms (mode 0) or the training units' convolutions (mode 1; 2: where 96-wide outputs may run as two 64-wide
+ * tiles, the backward) make for desc under the process's BE_* knobs, with a fused second input of cin2 channels (0: none), a
+ * residual (has_res != 0), nbatch batched problems (1: not batched) and scratch_bytes of lent scratch (0: none).  out[16]:
+ * route (0 row GEMM, 1 pixel-major LDS-DMA, 2 implicit GEMM), tile (0 small 64x64, 1 small 128x32, 2 small 64x64 uniform,
+ * 3 128x128, 4 128x96, 5 128x64, 6 128x32, 7 row-gather), K-chunk in floats, BE_KERNEL_* id, pixmaj, m_tiles, n_tiles,
+ * grid x / y / z (x = 0: the row GEMM sizes its own grid), K slices S, ldp (row stride of the slices; 0 when S = 1), then what
+ * a training pair is handed to run the convolution in its merged launch: small tile or -1 (none: mode 0, no scratch, or not a
+ * small tile), S, ldp, grid x.  *flops_executed: the MFMA work of the launch as its profile record states it.
+ * Returns BE_OK, or BE_EINVAL with the message the entry points give for the same arguments. */
+int be_conv_plan_debug(const be_conv_desc* desc_host, int cin2, int has_res, int ldy, int nbatch, size_t scratch_bytes, int mode,
+                       int* out, double* flops_executed);
 /* ResidualBlock tail in ONE launch (models/local_stage.py:22-27): y = act(conv_kxk(x) + conv_1x1(x2) + bias) where the
  * second branch is the block's downsample; its 1x1 conv is appended to the K loop of the first (no residual tensor
  * in HBM).  Weights: both branches (each with its own folded BatchNorm) packed side by side, biases summed. */

@@ -595,3 +595,149 @@ def test_balanced_backward_plan_partitions_every_tile_and_numbers_its_slices():
     for bad in ([(63, 6, 6, 128, 128, 3)], [(64, 6, 6, 48, 128, 3)], [(64, 2, 2, 128, 128, 3)], [(64, 6, 6, 256, 384, 3), (64, 6, 6, 256, 256, 1)]):
         assert plan(bad, False, 768)[0] == EINVAL, bad
     assert plan([(63, 6, 6, 128, 128, 3)], True, 768)[0] == EINVAL and plan([(64, 6, 6, 128, 48, 3)], True, 768)[0] == EINVAL
+
+
+# ---- the fp32 convolution's planner (be_conv.hip: conv_plan) through its host-only hook be_conv_plan_debug
+_ROUTE_ROWS, _ROUTE_PM, _ROUTE_IGEMM = 0, 1, 2
+_SMALL_TILES, _TILE_BN = (0, 1, 2), {0: 64, 1: 32, 2: 64, 3: 128, 4: 96, 5: 64, 6: 32, 7: 64}
+_PLAN_FIELDS = ("route", "tile", "bkt", "kernel", "pixmaj", "m_tiles", "n_tiles", "gx", "gy", "gz", "S", "ldp", "variant", "prep_S", "prep_ldp",
+                "prep_gx")
+
+
+def _conv_plan(shape, cin2=0, res=False, ldy=None, nbatch=1, scratch=0, mode=0):
+    """-> (rc, {field: value, "flops_exec": ..} | the refusal's message)"""
+    import ctypes as C
+    from be_hip import native
+    lib = native.lib()
+    n, h, w, cin, cout, ks = shape
+    d, out, fe = native.ConvDesc(n, h, w, cin, cout, ks, 1), (C.c_int * 16)(), C.c_double()
+    rc = lib.be_conv_plan_debug(C.byref(d), cin2, int(res), cout if ldy is None else ldy, nbatch, scratch, mode, out, C.byref(fe))
+    if rc:
+        return rc, lib.be_last_error().decode()
+    return 0, dict(zip(_PLAN_FIELDS, list(out)), flops_exec=fe.value)
+
+
+def _conv_plan_cases():
+    """the cases of tests/test_conv_routes_gpu.py (with their scratch in bytes), LocalStage's layers at n = 64 and n = 1024,
+    GlobalStage's linears over 32768 rows"""
+    from test_conv_routes_gpu import CASES
+    cases = []
+    for c in CASES:
+        n, h, w, cin, cout, ks = c["shape"]
+        cases.append((c["key"], c["shape"], dict(cin2=c["cin2"], res=c["res"], nbatch=c["nbatch"],
+                                                 scratch=(c["scratch"] or 0) * n * h * w * ((cout + 31) // 32 * 32) * 4)))
+    from be_hip.train import CONVS
+    maps = {"conv1": 21, "layer0": 11, "layer1": 6, "layer2": 6, "layer3": 3}
+    for n in (64, 1024):
+        for name, cout, cin, ks in CONVS:
+            hw = maps[name.split(".")[0]]
+            cases.append((f"{name}_n{n}", (n, hw, hw, 4 if ks == 7 else cin, cout, ks), {}))
+        cases += [(f"fc.1_n{n}", (n, 1, 1, 2304, 1024, 1), {}), (f"fc.4_n{n}", (n, 1, 1, 1024, 10, 1), {})]
+    cases += [(f"global_{cin}_{cout}", (32768, 1, 1, cin, cout, 1), {}) for cin, cout in ((128, 128), (128, 384), (128, 512), (512, 128))]
+    return cases
+
+
+def _check_plan_invariants(key, shape, p, scratch):
+    n, h, w, cin, cout, ks = shape
+    M, cp = n * h * w, (cout + 31) // 32 * 32
+    assert p["route"] in (_ROUTE_ROWS, _ROUTE_PM, _ROUTE_IGEMM) and p["tile"] in _TILE_BN, (key, p)
+    if p["route"] != _ROUTE_ROWS:                                # (the row GEMM sizes its own grid: gx = 0)
+        assert p["gx"] >= p["m_tiles"] * p["n_tiles"] and p["gx"] % 8 == 0, (key, p)      # the grid covers every tile
+    if p["pixmaj"] == 1:                                         # whole image groups stay on one XCD slot
+        groups = p["m_tiles"] // (h * w)
+        assert p["m_tiles"] == groups * h * w and p["gx"] == 8 * -(-groups // 8) * h * w * p["n_tiles"], (key, p)
+    assert p["S"] >= 1 and p["gy"] == p["S"], (key, p)
+    if p["S"] > 1:
+        assert p["S"] * M * p["ldp"] * 4 <= scratch and p["tile"] in _SMALL_TILES, (key, p)
+    if not scratch:
+        assert p["S"] == 1, (key, p)
+    assert p["ldp"] == (cp if p["S"] > 1 else 0), (key, p)       # round_up(cout, 32) exactly when the K loop is split
+
+
+def test_convolution_plan_invariants_goldens_and_refusals():
+    """conv_plan, the planner of every be_conv_nhwc*_f32 entry point and of the training units' convolutions, run on the CPU: the
+    grid covers the tiles, the K slices fit the scratch, preparing is planning, pad64 moves only 96-wide outputs, bad shapes keep
+    their messages, and for the cases recorded on the GPU (tests/golden/conv_routes.json, from the library before the planner
+    existed) the planned kernel, launch count and executed FLOPs are the recorded ones."""
+    import json
+    from test_conv_routes_gpu import CASES, GOLDEN
+    with open(GOLDEN) as f:
+        golden = json.load(f)["cases"]
+    recorded = {c["key"] for c in CASES}
+    AMPLE = 40 << 20
+    for key, shape, kw in _conv_plan_cases():
+        rc, p = _conv_plan(shape, **kw)
+        assert rc == 0, (key, p)
+        _check_plan_invariants(key, shape, p, kw.get("scratch", 0))
+        assert p["variant"] == -1, (key, p)                      # nothing is handed back outside the training modes
+        if key in recorded:
+            launches = golden[key]["launches"]
+            assert len(launches) == 1 and p["kernel"] == launches[0][0] and p["flops_exec"] == launches[0][3], (key, p, launches)
+        if kw.get("cin2") or kw.get("nbatch", 1) > 1:
+            continue
+        cp = (shape[4] + 31) // 32 * 32
+        for scratch in (0, AMPLE):                               # the training units: train mode launches, prepare mode hands back
+            plans = {}
+            for mode in (1, 2):
+                rc, t = _conv_plan(shape, res=kw.get("res", False), scratch=scratch, mode=mode)
+                assert rc == 0, (key, t)
+                _check_plan_invariants(key, shape, t, scratch)
+                small = t["route"] == _ROUTE_IGEMM and t["tile"] in _SMALL_TILES
+                assert (t["variant"] >= 0) == (small and scratch > 0), (key, mode, t)
+                if t["variant"] >= 0:
+                    assert (t["variant"], t["prep_S"], t["prep_ldp"], t["prep_gx"]) == (t["tile"], t["S"], t["ldp"], t["gx"]), (key, mode, t)
+                plans[mode] = t
+            if plans[1] != plans[2]:                             # pad64: two 64-wide uniform tiles for a 96-wide output, nothing else
+                assert cp % 64 == 32 and cp > 64 and plans[1]["tile"] == 1 and plans[2]["tile"] == 2, (key, plans)
+    # layer0's data gradients at batch 64 do take the padded tiles (and the forward's plan does not)
+    assert _conv_plan((64, 11, 11, 96, 96, 3), scratch=AMPLE, mode=2)[1]["tile"] == 2
+    assert _conv_plan((64, 11, 11, 96, 96, 3), scratch=AMPLE, mode=1)[1]["tile"] == 1
+    EINVAL = -1
+    for shape, kw, msg in (((8, 6, 6, 48, 64, 3), {}, "be_conv_nhwc_f32: ksize 3 / cin 48 unsupported"),
+                           ((8, 6, 6, 32, 64, 5), {}, "be_conv_nhwc_f32: ksize 5 / cin 32 unsupported"),
+                           ((8, 6, 6, 32, 64, 3), dict(ldy=63), "be_conv_nhwc_f32: ldy < cout"),
+                           ((2, 21, 21, 4, 128, 7), {}, "be_conv_nhwc_f32: ksize 7 is built for cout 64 (got 128)"),
+                           ((2, 21, 21, 4, 128, 7), dict(scratch=AMPLE, mode=1), "be_conv_nhwc_f32: ksize 7 is built for cout 64 (got 128)")):
+        assert _conv_plan(shape, **kw) == (EINVAL, msg), (shape, kw)
+
+
+_KNOB_ARM = """
+import json, sys
+sys.path[:0] = {paths!r}
+import test_host_cpu as t
+out = {{}}
+for key, shape, kw in t._conv_plan_cases():
+    out[key] = [t._conv_plan(shape, **kw)[1]] + [t._conv_plan(shape, scratch=40 << 20, mode=m)[1] for m in (1, 2) if not kw.get("cin2") and kw.get("nbatch", 1) == 1]
+print(json.dumps(out))
+"""
+
+
+def _plans_under(knob):
+    import json, subprocess, sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, **{knob[0]: knob[1]})
+    r = subprocess.run([sys.executable, "-c", _KNOB_ARM.format(paths=[here] + [p for p in sys.path if p])], env=env, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads(r.stdout.splitlines()[-1])
+
+
+def test_convolution_plan_knob_arms():
+    """The knobs are read once per process: each arm plans in a child interpreter.  BE_CONV_VARIANT=32: the K-chunk-32 builds of the
+    tiles that have one, and no LDS-DMA kernel; BE_NO_UNI_TILES=1: no uniform tile, hence no pad64 either."""
+    base = {key: _conv_plan(shape, **kw)[1] for key, shape, kw in _conv_plan_cases()}
+    v32 = _plans_under(("BE_CONV_VARIANT", "32"))
+    for key, plans in v32.items():
+        p, b = plans[0], base[key]
+        assert p["route"] != _ROUTE_PM and p["bkt"] == (16 if p["tile"] in _SMALL_TILES or p["route"] == _ROUTE_ROWS else 32), (key, p)
+        if b["route"] != _ROUTE_PM:
+            assert {k: v for k, v in p.items() if k not in ("bkt", "flops_exec")} == {k: v for k, v in b.items() if k not in ("bkt", "flops_exec")}, key
+    assert v32["pm_lds_dma"][0]["tile"] == 4 and v32["pm_lds_dma"][0]["pixmaj"] == 1          # the pixel-major implicit GEMM instead
+    nouni = _plans_under(("BE_NO_UNI_TILES", "1"))
+    assert any(b["tile"] == 2 for b in base.values())
+    for key, plans in nouni.items():
+        assert all(p["tile"] != 2 for p in plans), (key, plans)
+        if len(plans) == 3:
+            assert plans[1] == plans[2], key                                                  # pad64 needs the uniform tile
+        b = base[key]
+        assert plans[0] == (dict(b, tile=0) if b["tile"] == 2 else b), key                    # bordered tiles: same grid, same executed FLOPs

@@ -42,7 +42,7 @@ LINEAR_SMALL_CASES = [(1, 4, 1), (3, 1024, 10), (64, 1024, 10), (5, 64, 256)]
 LINEAR_GRAD_CASES = [(256, 128, 128), (300, 128, 256), (600, 256, 128)]
 # the units: name -> dict(shape = (n, h, w, cin, cout, ks), chw, res, act, dx_add, want_dx, path).  `path` = (forward, weight gradient,
 # backward launch) as the host code decides them (unit_fwd_one / sk_fwd_eligible, plan_wgrad, unit_bwd_one / sk_eligible /
-# conv_dispatch); expected_path() below re-derives it from the shape, and the CPU test holds the two together.
+# conv_plan); expected_path() below re-derives it from the shape, and the CPU test holds the two together.
 UNIT_CASES = {
     # n = 3: no 64-image group -> not the balanced launch; cout 32: 64-wide flat tiles (n % 32 != 0); dgrad onto cp = 32 -> 128x32 (variant 1)
     "flat64_v1": dict(shape=(3, 5, 7, 32, 32, 3), chw=0, res=True, act=True, dx_add=True, want_dx=True, path=("small", "flat64", "merged_v1")),
@@ -91,7 +91,7 @@ def wgrad_slices(n, h, w, cin, cout, ks):
 
 def expected_path(shape, chw, want_dx):
     """(forward, weight gradient, backward launch) from the host code's conditions (be_train.hip unit_fwd_one / plan_wgrad /
-    unit_bwd_one, be_train_sk.hip sk_eligible / sk_fwd_eligible, be_conv.hip conv_dispatch's small-M branch)."""
+    unit_bwd_one, be_train_sk.hip sk_eligible / sk_fwd_eligible, be_conv.hip conv_plan's small-M branch)."""
     n, h, w, cin, cout, ks = shape
     M = n * h * w
     if ks == 7:
