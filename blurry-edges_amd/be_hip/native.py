@@ -214,6 +214,8 @@ _SIGNATURES = {
                                          C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "be_conv_plan_debug": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_int),
                                      C.POINTER(C.c_double)]),
+    "be_local_stage_layout_debug": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_int]),
+    "be_local_stage_route_debug": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "be_linear_param_grads_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "be_linear_small_fwd_f32": (C.c_int, [_P] * 4 + [C.c_int] * 3 + [_P]),
     "be_maxpool_nhwc_fwd_idx_f32": (C.c_int, [_P, _P, _P] + [C.c_int] * 7 + [_P]),
@@ -934,6 +936,30 @@ def local_stage_forward_view(packed, view, patches_per_image: int, n: int, devic
                                                 dptr(workspace), workspace.numel() * 4, C.byref(opts), stream_ptr(device)),
           "be_local_stage_forward_view_f32")
     return out, workspace
+
+
+LOCAL_STAGE_FORMS = ("f32", "fused2", "wino", "ds_f32", "rows_bf6", "l0_bf6", "wino_ds", "zero")
+LOCAL_STAGE_ROUTE_FIELDS = ("staging", "conv1", "conv1_pools", "l0_bf6", "chain", "blocks6", "store_maps", "fc1_bf6")
+
+
+def local_stage_layout():
+    """The packed LocalStage buffer's regions in buffer order (be_local_stage_layout_debug; no GPU): dicts of layer (-1: none), form
+    (LOCAL_STAGE_FORMS), w_off / w_floats / b_off / b_floats, and reads = the index of the region its pack call reads, or None."""
+    a, o = (C.c_int * 96)(), (C.c_int64 * 128)()
+    n = lib().be_local_stage_layout_debug(a, o, 32)
+    if n < 0:
+        check(n, "be_local_stage_layout_debug")
+    return [dict(layer=a[3 * k], form=LOCAL_STAGE_FORMS[a[3 * k + 1]], w_off=o[4 * k], w_floats=o[4 * k + 1], b_off=o[4 * k + 2],
+                 b_floats=o[4 * k + 3], reads=a[3 * k + 2] if a[3 * k + 2] >= 0 else None) for k in range(n)]
+
+
+def local_stage_route(winograd, nb):
+    """The kernels a sub-batch of nb patches takes (be_local_stage_route_debug; no GPU) -> {LOCAL_STAGE_ROUTE_FIELDS: int}."""
+    out = (C.c_int * 8)()
+    n = lib().be_local_stage_route_debug(int(bool(winograd)), int(nb), out)
+    if n < 0:
+        check(n, "be_local_stage_route_debug")
+    return dict(zip(LOCAL_STAGE_ROUTE_FIELDS, list(out)[:n]))
 
 
 KERNEL_NAMES = {0: "k_conv_igemm<2,2,2,2,TAPS> (128x128)", 1: "k_conv_igemm<4,1,1,3,TAPS> (128x96)",

@@ -19,6 +19,9 @@
 // (be_conv1_pool_bf6.hip on the row-padded staging; BE_C1_F32=1 / BE_WINO_F32=1: the fp32 routing by sub-batch size).  No allocation, no
 // synchronisation, no process-wide state: graph-capturable, re-entrant.  opts->winograd = 0 runs layers 1-3 as direct launches
 // like layer0, all in fp32.
+// Three facts are each stated once below: where a piece lies in the packed buffer (Layout: one ordered table of regions, asked
+// for by (layer, form)), where a map lies in the workspace (the Span constants and their static_asserts; carve), and which
+// kernels a sub-batch takes (Knobs, read once per process; route_of).
 #include "be_common.h"
 #include <cstdlib>
 #include <initializer_list>
@@ -36,65 +39,174 @@ constexpr LayerSpec kLayers[15] = {
     {1024, 2304, 1, 9},
     {10, 1024, 1, 0},
 };
+// the residual blocks (layer0 .. layer3): their three layers and the side of the map they run on
+struct Block { int conv1, conv2, ds, hw; };
+constexpr Block kBlocks[4] = {{1, 2, 3, 11}, {4, 5, 6, 6}, {7, 8, 9, 6}, {10, 11, 12, 6}};
+inline const Block* block_of(int layer) {
+    for (const Block& b : kBlocks) if (layer == b.conv1 || layer == b.conv2 || layer == b.ds) return &b;
+    return nullptr;
+}
 
 inline size_t cout_pad(int c) { return (size_t)((c + 31) / 32 * 32); }
 
-struct PackedLayout {
-    size_t w_off[15], b_off[15], total;
-    size_t uw_off[15], ub_off[15];     // Winograd form (be_wino_math.h: 8x5 tiles) of the 3x3 convs on the 6x6 maps (layers 4,5,7,8,10,11)
-    size_t dw_off[15], db_off[15];     // their blocks' 1x1 downsample convs as stand-alone convs (layers 6, 9, 12)
-    PackedLayout() {
-        size_t o = 0;
-        for (int i = 0; i < 15; ++i) {
-            const bool conv2 = i == 2 || i == 5 || i == 8 || i == 11;        // carries its block's downsample too
-            const bool ds = i == 3 || i == 6 || i == 9 || i == 12;            // ... which therefore has no slot
-            w_off[i] = o;
-            if (conv2) o += be_conv_fused2_packed_floats(kLayers[i].cout, kLayers[i].cin, kLayers[i].ks, kLayers[i + 1].cin);
-            else if (!ds) o += be_conv_packed_floats(kLayers[i].cout, kLayers[i].cin, kLayers[i].ks);
-            b_off[i] = o;
-            if (!ds) o += cout_pad(kLayers[i].cout);
-        }
-        for (int i = 4; i < 13; ++i) {
-            const bool ds = i == 6 || i == 9 || i == 12;
-            uw_off[i] = ub_off[i] = dw_off[i] = db_off[i] = 0;
-            if (ds) {
-                dw_off[i] = o; o += be_conv_packed_floats(kLayers[i].cout, kLayers[i].cin, 1);
-                db_off[i] = o; o += cout_pad(kLayers[i].cout);
-            } else {
-                uw_off[i] = o; o += be_wino_packed_floats(kLayers[i].cout, kLayers[i].cin);
-                ub_off[i] = o; o += cout_pad(kLayers[i].cout);
-            }
-        }
-        zero_off = o; o += 384;            // a zero "bias" for the Winograd blocks' downsample convolutions (their bias lives in conv2's)
-        for (int i = 0; i < 15; ++i) sw_off[i] = 0;
-        for (int i : {6, 9, 12, 13}) {     // hi / mid / lo bf16 planes of the downsamples' and fc.1's packed matrices (split-bf16 row GEMMs)
-            sw_off[i] = o; o += be_gemm_rows_bf6_packed_floats(kLayers[i].cout, kLayers[i].cin);
-        }
-        for (int i : {1, 2}) {             // layer0's two pixel-major 3x3 matrices (conv2's with the downsample's columns) likewise
-            sw_off[i] = o; o += be_conv3x3_pm_bf6_packed_floats(kLayers[i].cout, kLayers[i].cin, i == 2 ? kLayers[3].cin : 0);
-        }
-        for (int i = 0; i < 15; ++i) xw_off[i] = 0;
-        for (int i : {6, 9, 12}) {         // the downsamples of layers 1-3 as conv2's second K segment (be_wino_ds_pack_f32; behind all else)
-            xw_off[i] = o; o += be_wino_ds_packed_floats(kLayers[i].cout, kLayers[i].cin);
-        }
-        total = o;
-    }
-    size_t zero_off;
-    size_t sw_off[15];
-    size_t xw_off[15];
+// The forms a layer's parameters are packed in (be_local_stage_layout_debug reports these numbers)
+enum Form {
+    F32,        // the fp32 matrix and bias (be_conv_pack_f32): conv1, each block's conv1, fc.1, fc.4
+    FUSED2,     // a block's conv2 with its downsample's columns, biases summed (be_conv_pack_fused2_f32)
+    WINO,       // Winograd U with its planes, and the bias (be_wino_pack_f32; be_wino_math.h: 8x5 tiles): the 3x3s of the 6x6 blocks
+    DS_F32,     // a 6x6 block's 1x1 downsample as a stand-alone fp32 convolution; its bias is ADDED to conv2's WINO bias after both are packed
+    ROWS_BF6,   // hi / mid / lo bf16 planes of a DS_F32 / fc.1's F32 matrix (split-bf16 row GEMM)
+    L0_BF6,     // layer0's pixel-major planes, made from its F32 / FUSED2 matrix; the bias is that form's
+    WINO_DS,    // a 6x6 block's downsample as conv2's second K segment in the transform domain (be_wino_ds_pack_f32)
+    ZERO,       // 384 zero floats: the "bias" of the bias-free fp32 downsample launch
+    FORMS
 };
-const PackedLayout& layout() { static PackedLayout l; return l; }
 
-// workspace regions, floats per patch (lifetimes: see be_local_stage_forward_f32; RA holds conv1's output, then
-// each block's intermediate t)
-constexpr size_t RA = 28224, RB = 13824, RC = 13824;
-// Winograd path: RW = transform-domain input + output of the widest layer (room for 100 values per channel: 25 positions x 4 tiles; the 8x5 tiles use 80,
-// 384 + 384 channels), RR = the block's downsample branch [6,6,384]
-// (round 14: a block that folds its downsample into conv2's GEMMs keeps three transform-domain buffers, be_wino_pair_ds_workspace_floats)
-constexpr size_t RW = 100 * (384 + 384 + 384), RR = 13824;
-constexpr size_t WS_FLOATS_PER_PATCH = RA + RB + RC + RW + RR;
+// One piece of the packed buffer: a matrix part and a bias part (either may be empty), in floats.  reads: the table index of the
+// region whose matrix this region's pack call reads (BatchNorm already folded there), -1: packed from the state-dict tensors.
+struct Region { int layer, form; size_t w_off, w_n, b_off, b_n; int reads; };
+
+struct Layout {
+    Region r[32];
+    int n = 0, zero = -1, at_[15][FORMS];
+    size_t total = 0;
+    int add(int layer, Form f, size_t w_n, size_t b_n, int reads = -1) {
+        r[n] = {layer, f, total, w_n, total + w_n, b_n, reads};
+        total += w_n + b_n;
+        if (layer >= 0) at_[layer][f] = n;
+        return n++;
+    }
+    // the table, in the order of the buffer
+    Layout() {
+        for (auto& row : at_) for (int& v : row) v = -1;
+        for (int i = 0; i < 15; ++i) {                 // every layer in index order; a downsample lies in its conv2's FUSED2
+            const LayerSpec& s = kLayers[i];
+            const Block* b = block_of(i);
+            if (b && i == b->ds) continue;
+            if (b && i == b->conv2) add(i, FUSED2, be_conv_fused2_packed_floats(s.cout, s.cin, s.ks, kLayers[b->ds].cin), cout_pad(s.cout));
+            else add(i, F32, be_conv_packed_floats(s.cout, s.cin, s.ks), cout_pad(s.cout));
+        }
+        for (int i = kBlocks[1].conv1; i <= kBlocks[3].ds; ++i) {      // the 6x6 blocks again, as the Winograd path reads them
+            const LayerSpec& s = kLayers[i];
+            if (i == block_of(i)->ds) add(i, DS_F32, be_conv_packed_floats(s.cout, s.cin, 1), cout_pad(s.cout));
+            else add(i, WINO, be_wino_packed_floats(s.cout, s.cin), cout_pad(s.cout));
+        }
+        zero = add(-1, ZERO, 0, 384);
+        for (int i : {kBlocks[1].ds, kBlocks[2].ds, kBlocks[3].ds, 13})
+            add(i, ROWS_BF6, be_gemm_rows_bf6_packed_floats(kLayers[i].cout, kLayers[i].cin), 0, at_[i][i == 13 ? F32 : DS_F32]);
+        const Block& l0 = kBlocks[0];                  // K order of the packed matrices = the pixel-major K walk
+        add(l0.conv1, L0_BF6, be_conv3x3_pm_bf6_packed_floats(kLayers[l0.conv1].cout, kLayers[l0.conv1].cin, 0), 0, at_[l0.conv1][F32]);
+        add(l0.conv2, L0_BF6, be_conv3x3_pm_bf6_packed_floats(kLayers[l0.conv2].cout, kLayers[l0.conv2].cin, kLayers[l0.ds].cin), 0,
+            at_[l0.conv2][FUSED2]);
+        for (int k = 1; k < 4; ++k)                    // (round 14: behind all else)
+            add(kBlocks[k].ds, WINO_DS, be_wino_ds_packed_floats(kLayers[kBlocks[k].ds].cout, kLayers[kBlocks[k].ds].cin), 0);
+    }
+    const Region& at(int layer, Form f) const { return r[at_[layer][f]]; }
+    const float* w(const float* packed, int layer, Form f) const { return packed + at(layer, f).w_off; }
+    const float* b(const float* packed, int layer, Form f) const { return packed + at(layer, f).b_off; }
+};
+const Layout& layout() { static Layout l; return l; }
+
+// The workspace, in floats per patch: a sub-batch of nb patches has nb times each number, regions and what lies in them alike.
+struct Span { size_t at, n; };
+constexpr size_t end(Span s) { return s.at + s.n; }
+constexpr bool inside(Span s, Span host) { return s.at >= host.at && end(s) <= end(host); }
+constexpr bool apart(Span a, Span b) { return end(a) <= b.at || end(b) <= a.at; }
+// RA holds conv1's output, then each block's intermediate t and last fc.1's output; RB and RC the blocks' inputs and outputs in turn.
+// Winograd path: RW = transform-domain input + output of the widest layer (room for 100 values per channel: 25 positions x 4 tiles;
+// the 8x5 tiles use 80; 384 + 384 channels, and round 14: a block that folds its downsample into conv2's GEMMs keeps three
+// transform-domain buffers, be_wino_pair_ds_workspace_floats), RR = the block's downsample branch [6,6,384]
+constexpr Span RA = {0, 28224}, RB = {end(RA), 13824}, RC = {end(RB), 13824}, RW = {end(RC), 100 * (384 + 384 + 384)}, RR = {end(RW), 13824};
+constexpr size_t WS_FLOATS_PER_PATCH = end(RR);
+constexpr size_t map_floats(int hw, int c) { return (size_t)hw * hw * c; }
+// the staging [21,21,4], or with 28 pixels per row (3 zero pixels left, 4 right: the pixel-major conv1 kernels); the first pool's
+// output p1 lies behind it in RB, so that the staging can die into it: behind TWO plain stagings, which is behind one padded one
+constexpr Span X4 = {RB.at, 21 * 21 * 4}, X4P = {RB.at, 21 * 28 * 4}, P1 = {RB.at + 2 * X4.n, map_floats(11, 64)};
+constexpr Span C1 = {RA.at, map_floats(21, 64)};
+// block k: its input, conv1's result t (which a Winograd block keeps in registers: k_wino_out_in) and its output
+constexpr Span blk_in(int k, size_t at) { return {at, map_floats(kBlocks[k].hw, kLayers[kBlocks[k].conv1].cin)}; }
+constexpr Span blk_out(int k, size_t at) { return {at, map_floats(kBlocks[k].hw, kLayers[kBlocks[k].conv1].cout)}; }
+constexpr Span P2 = blk_in(1, RB.at);                  // the second pool's output
+constexpr Span BIN[4] = {P1, P2, blk_in(2, RC.at), blk_in(3, RB.at)};
+constexpr Span BT[4] = {blk_out(0, RA.at), blk_out(1, RA.at), blk_out(2, RA.at), blk_out(3, RA.at)};
+constexpr Span BOUT[4] = {blk_out(0, RC.at), blk_out(1, RC.at), blk_out(2, RB.at), blk_out(3, RC.at)};
+// maxpool(2,2) of layer3 = the (H,W,C) flatten.  Winograd path: layer3's output transform pools in registers and writes p3 where the
+// direct path's full map would lie (RB is still the block's input); the direct path pools that map into RB
+constexpr Span P3_WINO = {RC.at, map_floats(3, 256)}, P3_DIRECT = {RB.at, map_floats(3, 256)}, F1 = {RA.at, 1024};
+constexpr Span DS = {RR.at, map_floats(6, 384)};       // the 1x1 downsample's raw accumulators where it is a launch of its own
+
+static_assert(apart(X4, P1) && apart(X4P, P1) && inside(X4, RB) && inside(X4P, RB) && inside(P1, RB), "staging | p1 side by side in RB");
+static_assert(inside(C1, RA) && apart(C1, P1), "conv1's map fills RA");
+static_assert(inside(BIN[0], RB) && inside(BT[0], RA) && inside(BOUT[0], RC), "layer0: RB -> RA -> RC");
+static_assert(inside(P2, RB) && apart(P2, BOUT[0]), "the second pool: RC -> RB");
+static_assert(BIN[2].n == BOUT[1].n && BIN[2].at == BOUT[1].at && BIN[3].n == BOUT[2].n && BIN[3].at == BOUT[2].at, "a block reads what the last one wrote");
+static_assert(inside(BIN[1], RB) && inside(BT[1], RA) && inside(BOUT[1], RC), "layer1: RB -> RA -> RC");
+static_assert(inside(BIN[2], RC) && inside(BT[2], RA) && inside(BOUT[2], RB), "layer2: RC -> RA -> RB");
+static_assert(inside(BIN[3], RB) && inside(BT[3], RA) && inside(BOUT[3], RC), "layer3: RB -> RA -> RC");
+static_assert(inside(P3_WINO, RC) && apart(P3_WINO, BIN[3]) && inside(P3_DIRECT, RB) && apart(P3_DIRECT, BOUT[3]), "p3 beside what it is pooled from");
+static_assert(inside(F1, RA) && apart(F1, P3_WINO) && apart(F1, P3_DIRECT), "fc.1: p3 -> RA");
+static_assert(inside(DS, RR) && DS.n >= BOUT[1].n && DS.n >= BOUT[2].n && DS.n >= BOUT[3].n, "the downsample branch of the widest block");
+static_assert(WS_FLOATS_PER_PATCH == 28224 + 3 * 13824 + 115200, "be_local_stage_workspace_bytes: 739 584 B per patch");
+
+// one sub-batch's pointers
+struct Carved {
+    float *x4, *c1, *p1, *p2, *p3, *f1, *in[4], *t[4], *out[4], *wino, *ds;
+    size_t wino_floats;
+};
+Carved carve(float* ws, int nb, bool wino) {
+    const auto at = [&](Span s) { return ws + (size_t)nb * s.at; };
+    Carved c;
+    c.x4 = at(X4); c.c1 = at(C1); c.p1 = at(P1); c.p2 = at(P2); c.p3 = at(wino ? P3_WINO : P3_DIRECT); c.f1 = at(F1);
+    for (int k = 0; k < 4; ++k) { c.in[k] = at(BIN[k]); c.t[k] = at(BT[k]); c.out[k] = at(BOUT[k]); }
+    c.wino = at(RW); c.wino_floats = (size_t)nb * RW.n; c.ds = at(DS);
+    return c;
+}
+
 constexpr int kDefaultChunk = 8192;   // measured: 8192 > 4096 > 2048 (fewer partial rounds of the 512 resident blocks)
 inline int chunk_of(int chunk) { return chunk > 0 ? chunk : kDefaultChunk; }
+
+// The knobs this file reads, once per process.  BE_NO_CONV_PM and BE_NO_CONV1_POOL (A/B knobs of the fp32 routing): set at all;
+// BE_WINO_NO_CHAIN: set and not 0; the four arithmetic arms: their kernels' own answers (be_common.h)
+struct Knobs { bool no_conv_pm, no_conv1_pool, no_chain, l0_bf6, rows_bf6, c1_bf6, ds_fold; };
+const Knobs& knobs() {
+    static const Knobs k = {getenv("BE_NO_CONV_PM") != nullptr, getenv("BE_NO_CONV1_POOL") != nullptr, be::knob_on("BE_WINO_NO_CHAIN"),
+                            be::l0_bf6_enabled(), be::rows_bf6_enabled(), be::c1_bf6_enabled(), be::wino_ds_fold_enabled()};
+    return k;
+}
+
+// Which kernels a sub-batch of nb patches takes (be_local_stage_route_debug reports these numbers, in this order)
+enum Staging { STAGE_NHWC4, STAGE_NHWC4P };
+enum Conv1 { C1_IGEMM, C1_PM, C1_POOL, C1_POOL_BF6 };       // k_conv_igemm; the pixel-major LDS-DMA kernel; fp32 / split-bf16 conv1 + pool
+enum Blocks6 { B6_DIRECT, B6_WINO_FOLD, B6_WINO_DS_BF6, B6_WINO_DS_F32 };
+struct Route {
+    int staging;      // Staging: the padded rows are what the three pixel-major conv1 forms read
+    int conv1;        // Conv1
+    int conv1_pools;  // conv1's launch writes p1 (no k_maxpool_nhwc, conv1's map never reaches HBM)
+    int l0_bf6;       // layer0 in split-bf16 arithmetic, else the fp32 kernels
+    int chain;        // the Winograd blocks chained through the start of RW (header comment; be::wino_pair)
+    int blocks6;      // Blocks6: direct fused convolutions, or Winograd with the downsample folded / a split-bf16 launch / an fp32 launch
+    int store_maps;   // the second pool's map and the maps between the 6x6 blocks are written (chained and folded: nothing reads them)
+    int fc1_bf6;      // fc.1 on the split-bf16 row GEMM, else the fp32 convolution
+};
+constexpr int kRouteFields = 8;
+Route route_of(const Knobs& k, int winograd, int nb) {
+    const bool wino = winograd != 0;
+    // Winograd path: conv1 + Smish + the first max-pool in split-bf16 arithmetic at EVERY sub-batch size, so that a patch's bits
+    // depend on neither batch nor chunk; else the fp32 routing: large sub-batches on the pixel-major kernels, fused with the pool
+    // (bit-identical to the pair) unless BE_NO_CONV1_POOL
+    const bool c1_bf6 = wino && k.c1_bf6 && !k.no_conv_pm && !k.no_conv1_pool;
+    const bool padded = c1_bf6 || (nb >= 512 && !k.no_conv_pm);
+    Route r;
+    r.staging = padded ? STAGE_NHWC4P : STAGE_NHWC4;
+    r.conv1 = !padded ? C1_IGEMM : c1_bf6 ? C1_POOL_BF6 : !k.no_conv1_pool ? C1_POOL : C1_PM;
+    r.conv1_pools = r.conv1 == C1_POOL || r.conv1 == C1_POOL_BF6;
+    r.l0_bf6 = wino && k.l0_bf6;
+    r.chain = wino && !k.no_chain;
+    r.blocks6 = !wino ? B6_DIRECT : k.ds_fold ? B6_WINO_FOLD : k.rows_bf6 ? B6_WINO_DS_BF6 : B6_WINO_DS_F32;
+    r.store_maps = !(r.chain && r.blocks6 == B6_WINO_FOLD);
+    r.fc1_bf6 = wino && k.rows_bf6;
+    return r;
+}
 
 }  // namespace
 
@@ -106,141 +218,132 @@ extern "C" size_t be_local_stage_workspace_bytes(int64_t n, int chunk) {
     return (size_t)nb * WS_FLOATS_PER_PATCH * sizeof(float);
 }
 
-extern "C" int be_local_stage_pack_f32(const float* const* t, float bn_eps, float* packed, void* stream) {
-    BE_REQUIRE(t && packed, "be_local_stage_pack_f32: null pointer");
-    for (int i = 0; i < BE_LOCAL_STAGE_NTENSORS; ++i) BE_REQUIRE(t[i], "be_local_stage_pack_f32: tensor %d is null", i);
-    const PackedLayout& L = layout();
-    for (int i = 0; i < 13; ++i) {                    // conv + BatchNorm2d pairs
-        const float* const* e = t + 6 * i;            // weight, bias, gamma, beta, mean, var
-        const bool conv2 = i == 2 || i == 5 || i == 8 || i == 11, ds = i == 3 || i == 6 || i == 9 || i == 12;
-        if (ds) continue;                              // packed together with the block's conv2
-        int rc;
-        if (conv2) {
-            const float* const* d = t + 6 * (i + 1);  // the block's downsample conv + BN
-            rc = be_conv_pack_fused2_f32(e[0], e[1], e[2], e[3], e[4], e[5], d[0], d[1], d[2], d[3], d[4], d[5], bn_eps,
-                                         kLayers[i].cout, kLayers[i].cin, kLayers[i].ks, kLayers[i + 1].cin,
-                                         packed + L.w_off[i], packed + L.b_off[i], stream);
-        } else {
-            rc = be_conv_pack_f32(e[0], e[1], e[2], e[3], e[4], e[5], bn_eps, kLayers[i].cout, kLayers[i].cin,
-                                  kLayers[i].ks, 0, packed + L.w_off[i], packed + L.b_off[i], stream);
-        }
-        if (rc) return rc;
-    }
-    for (int i = 4; i < 13; ++i) {                    // 6x6 blocks again, in the form the Winograd path reads
-        const float* const* e = t + 6 * i;
-        const bool ds = i == 6 || i == 9 || i == 12;
-        const int rc = ds ? be_conv_pack_f32(e[0], e[1], e[2], e[3], e[4], e[5], bn_eps, kLayers[i].cout, kLayers[i].cin, 1, 0,
-                                             packed + L.dw_off[i], packed + L.db_off[i], stream)
-                          : be_wino_pack_f32(e[0], e[1], e[2], e[3], e[4], e[5], bn_eps, kLayers[i].cout, kLayers[i].cin,
-                                             packed + L.uw_off[i], packed + L.ub_off[i], stream);
-        if (rc) return rc;
-    }
-    // Winograd blocks: the downsample's (folded) bias moves into conv2's, so that the 1x1 downsample itself is a bias-free GEMM -
-    // raw accumulators, which the weight-stationary GEMM kernel can write (be::gemm_rows_ws) - and joins in conv2's output
-    // transform exactly as before: y = act(A^T M A + (b2 + b_ds) + x W_ds)
-    for (int l0 = 4; l0 < 13; l0 += 3) {
-        if (int rc = be::vec_add_inplace(packed + L.ub_off[l0 + 1], packed + L.db_off[l0 + 2], (int)cout_pad(kLayers[l0].cout), stream)) return rc;
-    }
-    if (hipMemsetAsync(packed + L.zero_off, 0, 384 * sizeof(float), be::as_stream(stream)) != hipSuccess)
-        return be::fail(BE_ELAUNCH, "be_local_stage_pack_f32: hipMemsetAsync failed");
-    const float* const* f = t + 78;                   // fc.1.w, fc.1.b, fc.2.{gamma,beta,mean,var}, fc.4.w, fc.4.b
-    int rc = be_conv_pack_f32(f[0], f[1], f[2], f[3], f[4], f[5], bn_eps, 1024, 2304, 1, 9,
-                              packed + L.w_off[13], packed + L.b_off[13], stream);
-    if (rc) return rc;
-    if ((rc = be_conv_pack_f32(f[6], f[7], nullptr, nullptr, nullptr, nullptr, bn_eps, 10, 1024, 1, 0,
-                               packed + L.w_off[14], packed + L.b_off[14], stream))) return rc;
-    // the planes of the four matrices the split-bf16 row GEMMs read, from the packed fp32 matrices (BatchNorm folded, fc.1's columns
-    // permuted), which stay for the fp32 arms
-    for (int i : {6, 9, 12, 13}) {
-        const float* src = packed + (i == 13 ? L.w_off[13] : L.dw_off[i]);
-        if ((rc = be_gemm_rows_bf6_pack_f32(src, kLayers[i].cout, kLayers[i].cin, packed + L.sw_off[i], stream))) return rc;
-    }
-    for (int i : {6, 9, 12}) {                        // the same downsamples in the transform domain: conv2's second K segment
-        const float* const* e = t + 6 * i;
-        if ((rc = be_wino_ds_pack_f32(e[0], e[1], e[2], e[3], e[4], e[5], bn_eps, kLayers[i].cout, kLayers[i].cin, packed + L.xw_off[i],
-                                      nullptr, stream))) return rc;
-    }
-    for (int i : {1, 2}) {                            // layer0: K order of the packed matrices = the pixel-major K walk
-        if ((rc = be_conv3x3_pm_bf6_pack_f32(packed + L.w_off[i], kLayers[i].cout, kLayers[i].cin, i == 2 ? kLayers[3].cin : 0,
-                                             packed + L.sw_off[i], stream))) return rc;
-    }
-    return BE_OK;
-}
-
 namespace {
 
-int conv(const float* packed, int li, const float* x, const float* res, float* y, int n, int hw, int act, int ldy,
-         void* stream) {
-    const PackedLayout& L = layout();
-    be_conv_desc d;
-    d.n = n; d.h = hw; d.w = hw;
-    d.cin = li == 0 ? 4 : kLayers[li].cin;
-    d.cout = kLayers[li].cout; d.ksize = kLayers[li].ks; d.act = act;
-    return be_conv_nhwc_f32(&d, x, packed + L.w_off[li], packed + L.b_off[li], res, y, ldy, stream);
-}
-
-// ResidualBlock (models/local_stage.py:20-28): Smish(BN(conv3(Smish(BN(conv3(x))))) + BN(conv1x1(x))) in two launches:
-// the downsample 1x1 rides in the K loop of conv2 (be_conv_nhwc_fused2_f32), no residual tensor in HBM
-int block(const float* packed, int l0, const float* x, float* t, float* o, int n, int hw, void* stream) {
-    const int c = kLayers[l0].cout;
-    int rc;
-    if ((rc = conv(packed, l0, x, nullptr, t, n, hw, 1, c, stream))) return rc;
-    const PackedLayout& L = layout();
-    be_conv_desc d;
-    d.n = n; d.h = hw; d.w = hw; d.cin = kLayers[l0 + 1].cin; d.cout = c; d.ksize = 3; d.act = 1;
-    return be_conv_nhwc_fused2_f32(&d, t, x, kLayers[l0 + 2].cin, packed + L.w_off[l0 + 1], packed + L.b_off[l0 + 1], o, c, stream);
-}
-
-// layer0's block in split-bf16 arithmetic (be_conv_pm_bf6.hip): the same two launches on ONE kernel for every sub-batch size
-int block_l0_bf6(const float* packed, const float* x, float* t, float* o, int n, void* stream) {
-    const PackedLayout& L = layout();
-    be_conv_desc d;
-    d.n = n; d.h = 11; d.w = 11; d.cin = kLayers[1].cin; d.cout = 96; d.ksize = 3; d.act = 1;
-    if (int rc = be::conv3x3_pm_bf6(&d, x, nullptr, 0, packed + L.sw_off[1], packed + L.b_off[1], t, 96, stream)) return rc;
-    d.cin = kLayers[2].cin;
-    return be::conv3x3_pm_bf6(&d, t, x, kLayers[3].cin, packed + L.sw_off[2], packed + L.b_off[2], o, 96, stream);
-}
-
-// The same block on a 6x6 map with both 3x3 convolutions in Winograd F(3x3,3x3) form (be_wino.hip): 2.56x fewer multiplies
-// than the direct form; the 1x1 downsample runs as its own convolution into `r` and joins in the output transform of conv2.
-// x_in_v / next_cmid: the block as a link of the chain (be::wino_pair): x's transform is already in `w` / the next block's is left there
-// Default (round 14, be::wino_ds_fold_enabled): no `r` at all - the downsample is a second K segment of conv2's GEMMs over x's
-// transform (be::wino_pair's ds_planes).  x may then be null with x_in_v and o with next_cmid (a chained block reads and writes
-// transforms only).  BE_WINO_DS_GEMM=1 and the fp32 / round-7 arms keep the separate launch below.
-int block_wino(const float* packed, int l0, const float* x, float* t, float* o, float* r, float* w, int n, void* stream, int pool2 = 0,
-               int x_in_v = 0, int next_cmid = 0) {
-    const PackedLayout& L = layout();
-    const int c = kLayers[l0].cout;
-    (void)t;                                          // conv1's 6x6 result only ever exists in registers (k_wino_out_in)
-    if (be::wino_ds_fold_enabled()) {
-        const bool bare = x_in_v && next_cmid > 0;    // nothing reads the block's output map
-        return be::wino_pair(x_in_v ? nullptr : x, packed + L.uw_off[l0], packed + L.ub_off[l0], 1, packed + L.uw_off[l0 + 1],
-                             packed + L.ub_off[l0 + 1], nullptr, 1, bare ? nullptr : o, n, kLayers[l0].cin, c, c, w, (size_t)n * RW, stream,
-                             pool2, x_in_v, next_cmid,
-                             packed + L.xw_off[l0 + 2]);
+// the pack call of one region
+int pack_region(const Layout& L, const Region& r, const float* const* t, float bn_eps, float* packed, void* stream) {
+    float *w = packed + r.w_off, *b = packed + r.b_off;
+    if (r.form == ZERO)
+        return hipMemsetAsync(b, 0, r.b_n * sizeof(float), be::as_stream(stream)) == hipSuccess
+                   ? BE_OK : be::fail(BE_ELAUNCH, "be_local_stage_pack_f32: hipMemsetAsync failed");
+    // weight, bias, then BatchNorm's gamma, beta, mean, var: 6 tensors per layer (fc.1's BatchNorm1d is fc.2), fc.4 has the first two
+    const float* const* e = t + 6 * r.layer;
+    const float *g = r.layer == 14 ? nullptr : e[2], *bt = g ? e[3] : nullptr, *m = g ? e[4] : nullptr, *v = g ? e[5] : nullptr;
+    const LayerSpec& s = kLayers[r.layer];
+    const Block* k = block_of(r.layer);
+    const float* src = r.reads >= 0 ? packed + L.r[r.reads].w_off : nullptr;
+    switch (r.form) {
+    case F32: return be_conv_pack_f32(e[0], e[1], g, bt, m, v, bn_eps, s.cout, s.cin, s.ks, s.chw_hw, w, b, stream);
+    case FUSED2: {
+        const float* const* d = t + 6 * k->ds;         // the block's downsample conv + BN
+        return be_conv_pack_fused2_f32(e[0], e[1], g, bt, m, v, d[0], d[1], d[2], d[3], d[4], d[5], bn_eps, s.cout, s.cin, s.ks,
+                                       kLayers[k->ds].cin, w, b, stream);
     }
-    // the 1x1 downsample, bias-free (its bias sits in conv2's, see be_local_stage_pack_f32), raw accumulators: the split-bf16 row
-    // GEMM at every batch size.  fp32 arm (BE_ROWS_F32=1 / BE_WINO_F32=1): large sub-batches on the weight-stationary GEMM
-    // (128 TFLOP/s where the row GEMM does 92-119), others on the general kernel with a zero bias
-    if (be::rows_bf6_enabled()) {
-        if (int rc = be::gemm_rows_bf6(x, (int64_t)n * 36, kLayers[l0 + 2].cin, packed + L.sw_off[l0 + 2], c, nullptr, nullptr, 0, r, c,
-                                       stream)) return rc;
-    } else {
-        int rc = be::gemm_rows_ws(x, (int64_t)n * 36, kLayers[l0 + 2].cin, packed + L.dw_off[l0 + 2], c, r, c, stream);
-        if (rc < 0) return rc;
-        if (rc > 0) {
-            be_conv_desc d;
-            d.n = n; d.h = 6; d.w = 6; d.cin = kLayers[l0 + 2].cin; d.cout = c; d.ksize = 1; d.act = 0;
-            if ((rc = be_conv_nhwc_f32(&d, x, packed + L.dw_off[l0 + 2], packed + L.zero_off, nullptr, r, c, stream))) return rc;
-        }
+    case WINO: return be_wino_pack_f32(e[0], e[1], g, bt, m, v, bn_eps, s.cout, s.cin, w, b, stream);
+    case DS_F32: return be_conv_pack_f32(e[0], e[1], g, bt, m, v, bn_eps, s.cout, s.cin, 1, 0, w, b, stream);
+    case ROWS_BF6: return be_gemm_rows_bf6_pack_f32(src, s.cout, s.cin, w, stream);
+    case L0_BF6: return be_conv3x3_pm_bf6_pack_f32(src, s.cout, s.cin, r.layer == k->conv2 ? kLayers[k->ds].cin : 0, w, stream);
+    default: return be_wino_ds_pack_f32(e[0], e[1], g, bt, m, v, bn_eps, s.cout, s.cin, w, nullptr, stream);      // WINO_DS
     }
-    return be::wino_pair(x, packed + L.uw_off[l0], packed + L.ub_off[l0], 1, packed + L.uw_off[l0 + 1], packed + L.ub_off[l0 + 1], r,
-                         1, o, n, kLayers[l0].cin, c, c, w, (size_t)n * RW, stream, pool2, x_in_v, next_cmid);
 }
 
 }  // namespace
 
+// The order of the calls is part of the contract (profiles/HISTORY.md rounds 28-29: an open fault is sensitive to what follows
+// what): each step packs, in table order, the regions of the named forms whose layer lies in [lo, hi]
+extern "C" int be_local_stage_pack_f32(const float* const* t, float bn_eps, float* packed, void* stream) {
+    BE_REQUIRE(t && packed, "be_local_stage_pack_f32: null pointer");
+    for (int i = 0; i < BE_LOCAL_STAGE_NTENSORS; ++i) BE_REQUIRE(t[i], "be_local_stage_pack_f32: tensor %d is null", i);
+    const Layout& L = layout();
+    const auto step = [&](unsigned forms, int lo, int hi) {
+        for (int k = 0; k < L.n; ++k) {
+            if (!((forms >> L.r[k].form) & 1) || L.r[k].layer < lo || L.r[k].layer > hi) continue;
+            if (int rc = pack_region(L, L.r[k], t, bn_eps, packed, stream)) return rc;
+        }
+        return (int)BE_OK;
+    };
+    int rc;
+    if ((rc = step((1u << F32) | (1u << FUSED2), 0, 12))) return rc;        // conv + BatchNorm2d pairs
+    if ((rc = step((1u << WINO) | (1u << DS_F32), 0, 12))) return rc;       // 6x6 blocks again, in the form the Winograd path reads
+    // Winograd blocks: the downsample's (folded) bias moves into conv2's, so that the 1x1 downsample itself is a bias-free GEMM -
+    // raw accumulators, which the weight-stationary GEMM kernel can write (be::gemm_rows_ws) - and joins in conv2's output
+    // transform exactly as before: y = act(A^T M A + (b2 + b_ds) + x W_ds)
+    for (int k = 1; k < 4; ++k) {
+        const Block& b = kBlocks[k];
+        if ((rc = be::vec_add_inplace(packed + L.at(b.conv2, WINO).b_off, L.b(packed, b.ds, DS_F32), (int)L.at(b.conv2, WINO).b_n, stream)))
+            return rc;
+    }
+    if ((rc = step(1u << ZERO, -1, -1))) return rc;
+    if ((rc = step(1u << F32, 13, 14))) return rc;                      // fc.1 (+ fc.2), fc.4
+    // planes from the packed fp32 matrices (BatchNorm folded, fc.1's columns permuted), which stay for the fp32 arms: Region::reads
+    if ((rc = step(1u << ROWS_BF6, 0, 14))) return rc;
+    if ((rc = step(1u << WINO_DS, 0, 14))) return rc;
+    return step(1u << L0_BF6, 0, 14);
+}
+
 namespace {
+
+int conv(const Layout& L, const float* packed, int li, const float* x, const float* res, float* y, int n, int hw, int act, int ldy,
+         void* stream) {
+    be_conv_desc d;
+    d.n = n; d.h = hw; d.w = hw;
+    d.cin = li == 0 ? 4 : kLayers[li].cin;
+    d.cout = kLayers[li].cout; d.ksize = kLayers[li].ks; d.act = act;
+    return be_conv_nhwc_f32(&d, x, L.w(packed, li, F32), L.b(packed, li, F32), res, y, ldy, stream);
+}
+
+// ResidualBlock (models/local_stage.py:20-28): Smish(BN(conv3(Smish(BN(conv3(x))))) + BN(conv1x1(x))) in two launches:
+// the downsample 1x1 rides in the K loop of conv2 (be_conv_nhwc_fused2_f32), no residual tensor in HBM
+int block(const Layout& L, const float* packed, const Block& b, const float* x, float* t, float* o, int n, void* stream) {
+    const int c = kLayers[b.conv1].cout;
+    if (int rc = conv(L, packed, b.conv1, x, nullptr, t, n, b.hw, 1, c, stream)) return rc;
+    be_conv_desc d;
+    d.n = n; d.h = b.hw; d.w = b.hw; d.cin = kLayers[b.conv2].cin; d.cout = c; d.ksize = 3; d.act = 1;
+    return be_conv_nhwc_fused2_f32(&d, t, x, kLayers[b.ds].cin, L.w(packed, b.conv2, FUSED2), L.b(packed, b.conv2, FUSED2), o, c, stream);
+}
+
+// layer0's block in split-bf16 arithmetic (be_conv_pm_bf6.hip): the same two launches on ONE kernel for every sub-batch size
+int block_l0_bf6(const Layout& L, const float* packed, const float* x, float* t, float* o, int n, void* stream) {
+    const Block& b = kBlocks[0];
+    be_conv_desc d;
+    d.n = n; d.h = b.hw; d.w = b.hw; d.cin = kLayers[b.conv1].cin; d.cout = 96; d.ksize = 3; d.act = 1;
+    if (int rc = be::conv3x3_pm_bf6(&d, x, nullptr, 0, L.w(packed, b.conv1, L0_BF6), L.b(packed, b.conv1, F32), t, 96, stream)) return rc;
+    d.cin = kLayers[b.conv2].cin;
+    return be::conv3x3_pm_bf6(&d, t, x, kLayers[b.ds].cin, L.w(packed, b.conv2, L0_BF6), L.b(packed, b.conv2, FUSED2), o, 96, stream);
+}
+
+// The same block on a 6x6 map with both 3x3 convolutions in Winograd F(3x3,3x3) form (be_wino.hip): 2.56x fewer multiplies
+// than the direct form; conv1's result only ever exists in registers (k_wino_out_in).  route.chain: the block as a link of the chain
+// (be::wino_pair): x's transform is already in `w`, and with next_cmid > 0 the next block's is left there.
+// B6_WINO_FOLD (round 14, the default): the downsample is a second K segment of conv2's GEMMs over x's transform (be::wino_pair's
+// ds_planes); a chained block reads and writes transforms only, so x and - with next_cmid - o are not passed.  The other two
+// forms run the 1x1 downsample as its own convolution into `r`, which joins in the output transform of conv2.
+int block_wino(const Layout& L, const float* packed, const Route& route, const Block& b, const float* x, float* o, float* r, float* w,
+               size_t w_floats, int n, void* stream, int pool2, int next_cmid) {
+    const int c = kLayers[b.conv1].cout, cin = kLayers[b.conv1].cin, x_in_v = route.chain;
+    const float *u1 = L.w(packed, b.conv1, WINO), *b1 = L.b(packed, b.conv1, WINO), *u2 = L.w(packed, b.conv2, WINO),
+                *b2 = L.b(packed, b.conv2, WINO);
+    if (route.blocks6 == B6_WINO_FOLD) {
+        const bool bare = x_in_v && next_cmid > 0;    // nothing reads the block's output map
+        return be::wino_pair(x_in_v ? nullptr : x, u1, b1, 1, u2, b2, nullptr, 1, bare ? nullptr : o, n, cin, c, c, w, w_floats, stream,
+                             pool2, x_in_v, next_cmid, L.w(packed, b.ds, WINO_DS));
+    }
+    // the 1x1 downsample, bias-free (its bias sits in conv2's, see be_local_stage_pack_f32), raw accumulators: the split-bf16 row
+    // GEMM at every batch size.  fp32 arm (BE_ROWS_F32=1 / BE_WINO_F32=1): large sub-batches on the weight-stationary GEMM
+    // (128 TFLOP/s where the row GEMM does 92-119), others - its answer at run time - on the general kernel with a zero bias
+    if (route.blocks6 == B6_WINO_DS_BF6) {
+        if (int rc = be::gemm_rows_bf6(x, (int64_t)n * 36, cin, L.w(packed, b.ds, ROWS_BF6), c, nullptr, nullptr, 0, r, c, stream)) return rc;
+    } else {
+        int rc = be::gemm_rows_ws(x, (int64_t)n * 36, cin, L.w(packed, b.ds, DS_F32), c, r, c, stream);
+        if (rc < 0) return rc;
+        if (rc > 0) {
+            be_conv_desc d;
+            d.n = n; d.h = 6; d.w = 6; d.cin = cin; d.cout = c; d.ksize = 1; d.act = 0;
+            if ((rc = be_conv_nhwc_f32(&d, x, L.w(packed, b.ds, DS_F32), packed + L.r[L.zero].b_off, nullptr, r, c, stream))) return rc;
+        }
+    }
+    return be::wino_pair(x, u1, b1, 1, u2, b2, r, 1, o, n, cin, c, c, w, w_floats, stream, pool2, x_in_v, next_cmid);
+}
 
 // x != nullptr: flat patches [n,3,21,21]; else the patches are gathered from `view` (image pair, f2)
 int forward_impl(const float* packed, const float* x, const be_patch_view* view, int64_t P, float* out, int64_t n,
@@ -255,95 +358,56 @@ int forward_impl(const float* packed, const float* x, const be_patch_view* view,
     if (workspace_bytes < be_local_stage_workspace_bytes(n, g_chunk))
         return be::fail(BE_EWORKSPACE, "%s: workspace %zu B < %zu B needed", who, workspace_bytes,
                         be_local_stage_workspace_bytes(n, g_chunk));
-    float* ws = static_cast<float*>(workspace);
+    const Layout& L = layout();
+    const float *w0 = L.w(packed, 0, F32), *b0 = L.b(packed, 0, F32);
     for (int64_t first = 0; first < n; first += g_chunk) {
         const int nb = (int)((n - first) < g_chunk ? (n - first) : g_chunk);
-        float* ra = ws;
-        float* rb = ra + (size_t)nb * RA;
-        float* rc_ = rb + (size_t)nb * RB;
-        float* rw = rc_ + (size_t)nb * RC;                // Winograd transform-domain buffers
-        float* rr = rw + (size_t)nb * RW;                 // downsample branch of the current block
-        const bool wino = g_wino != 0;
+        const Route r = route_of(knobs(), g_wino, nb);
+        const Carved c = carve(static_cast<float*>(workspace), nb, g_wino != 0);
         int rc;
-        // x4 -> RB ; conv1 -> RA ; pool -> RB(after x4 is dead: RB is big enough to hold both side by side)
-        float* x4 = rb;                                   // nb*1764
-        float* p1 = rb + (size_t)nb * 1764 * 2;           // nb*7744, placed behind x4 (1764*2 + 7744 <= 13824)
-        // large sub-batches: conv1 on the pixel-major LDS-DMA kernel, which reads a staging with 28 pixels per row (3 zero
-        // pixels left, 4 right; 2352 floats per patch, still in front of p1)
-        static const bool no_pm = getenv("BE_NO_CONV_PM") != nullptr;
-        static const bool no_c1p = getenv("BE_NO_CONV1_POOL") != nullptr;
-        // Winograd path: conv1 + Smish + the first max-pool in split-bf16 arithmetic (be_conv1_pool_bf6.hip) at EVERY sub-batch size,
-        // so that a patch's bits depend on neither batch nor chunk (the padded staging fits in front of p1 at any nb);
-        // BE_C1_F32=1 / BE_WINO_F32=1 (and the two A/B knobs of the fp32 routing): the fp32 routing below, unchanged
-        const bool c1_bf6 = wino && be::c1_bf6_enabled() && !no_pm && !no_c1p;
-        bool pooled = false;
-        if (c1_bf6 || (nb >= 512 && !no_pm)) {
-            if (x) rc = be_nchw3_to_nhwc4p_f32(x + first * 3 * BE_NPIX, x4, nb, BE_R, BE_R, 28, stream);
-            else rc = be_view_to_nhwc4p_f32(view, P, first, x4, nb, 28, stream);
-            if (rc) return rc;
-            const PackedLayout& L = layout();
-            // conv1 + Smish + the first max-pool in one image-major launch (be_conv1_pool.hip): the 21 x 21 x 64 map never reaches
-            // HBM; bit-identical to the pixel-major conv1 followed by the pool kernel (BE_NO_CONV1_POOL=1: that pair, for A/B runs)
-            if (c1_bf6) {
-                if ((rc = be_conv7x7_pool_bf6_nhwc4p_f32(x4, nb, packed + L.w_off[0], packed + L.b_off[0], p1, stream))) return rc;
-                pooled = true;
-            } else if (!no_c1p) {
-                if ((rc = be_conv7x7_pool_nhwc4p_f32(x4, nb, packed + L.w_off[0], packed + L.b_off[0], p1, stream))) return rc;
-                pooled = true;
-            } else {
-                be_conv_desc d;
-                d.n = nb; d.h = 21; d.w = 21; d.cin = 4; d.cout = 64; d.ksize = 7; d.act = 1;
-                if ((rc = be_conv7x7_nhwc4p_f32(&d, x4, 28, packed + L.w_off[0], packed + L.b_off[0], ra, 64, stream))) return rc;
-            }
-        } else {
-            if (x) rc = be_nchw3_to_nhwc4_f32(x + first * 3 * BE_NPIX, x4, nb, BE_NPIX, stream);
-            else rc = be_view_to_nhwc4_f32(view, P, first, x4, nb, stream);
-            if (rc) return rc;
-            if ((rc = conv(packed, 0, x4, nullptr, ra, nb, 21, 1, 64, stream))) return rc;
-        }
-        if (!pooled && (rc = be_maxpool_nhwc_f32(ra, p1, nb, 21, 21, 64, 3, 2, 1, stream))) return rc;
-        // layer0 @11x11: t in RA, out in RC
-        // (Winograd path: split-bf16 at every sub-batch size; BE_L0_F32=1 / BE_WINO_F32=1 and opts->winograd = 0: the fp32 kernels)
-        if ((rc = (wino && be::l0_bf6_enabled()) ? block_l0_bf6(packed, p1, ra, rc_, nb, stream)
-                                                 : block(packed, 1, p1, ra, rc_, nb, 11, stream))) return rc;
-        float* p2 = rb;                                   // nb*3456
-        // Winograd path, at every sub-batch size: the blocks are chained through the start of RW.  The pool leaves layer1's input
-        // transform there, layers 1 and 2 end in the kernel that also writes the next layer's, so no block reads its input map a
-        // second time.  Lifetimes in RW: a block's V and M are
-        // dead once its last GEMMs ran, except M, which the boundary kernel reads while it writes the next V below M's start.  With the
-        // downsamples folded into conv2's GEMMs (the default) x's transform stays alive beside conv1's (three regions) and nothing
-        // reads the maps themselves; under BE_WINO_DS_GEMM=1 the 1x1 downsample launch reads them, and they are written.
-        static const bool no_chain = getenv("BE_WINO_NO_CHAIN") != nullptr && atoi(getenv("BE_WINO_NO_CHAIN")) != 0;   // A/B knob
-        const int chain = wino && !no_chain;
-        // (with the downsamples folded into conv2's GEMMs nothing reads the pooled map or the maps between the blocks: not stored)
-        if (chain) rc = be::pool_wino_in(rc_, be::wino_ds_fold_enabled() ? nullptr : p2, nb, 96, kLayers[4].cout, rw, (size_t)nb * RW, stream);
-        else rc = be_maxpool_nhwc_f32(rc_, p2, nb, 11, 11, 96, 3, 2, 1, stream);
+        if (r.staging == STAGE_NHWC4P)
+            rc = x ? be_nchw3_to_nhwc4p_f32(x + first * 3 * BE_NPIX, c.x4, nb, BE_R, BE_R, 28, stream)
+                   : be_view_to_nhwc4p_f32(view, P, first, c.x4, nb, 28, stream);
+        else
+            rc = x ? be_nchw3_to_nhwc4_f32(x + first * 3 * BE_NPIX, c.x4, nb, BE_NPIX, stream) : be_view_to_nhwc4_f32(view, P, first, c.x4, nb, stream);
         if (rc) return rc;
-        // layer1: in RB, t RA, out RC
-        if ((rc = wino ? block_wino(packed, 4, p2, ra, rc_, rr, rw, nb, stream, 0, chain, chain ? kLayers[7].cout : 0)
-                       : block(packed, 4, p2, ra, rc_, nb, 6, stream))) return rc;
-        // layer2: in RC, t RA, out RB
-        if ((rc = wino ? block_wino(packed, 7, rc_, ra, rb, rr, rw, nb, stream, 0, chain, chain ? kLayers[10].cout : 0)
-                       : block(packed, 7, rc_, ra, rb, nb, 6, stream))) return rc;
-        // layer3: in RB, t RA, out RC; then maxpool(2,2) -> p3 [nb,3,3,256] = the (H,W,C) flatten.  Winograd path: the
-        // output transform pools in registers and writes p3 directly (into RC: RB is still the block's input)
-        float* p3;
-        if (wino) {
-            p3 = rc_;
-            if ((rc = block_wino(packed, 10, rb, ra, p3, rr, rw, nb, stream, 1, chain))) return rc;
-        } else {
-            if ((rc = block(packed, 10, rb, ra, rc_, nb, 6, stream))) return rc;
-            p3 = rb;                                      // nb*2304
-            if ((rc = be_maxpool_nhwc_f32(rc_, p3, nb, 6, 6, 256, 2, 2, 0, stream))) return rc;
+        switch (r.conv1) {
+        case C1_POOL_BF6: rc = be_conv7x7_pool_bf6_nhwc4p_f32(c.x4, nb, w0, b0, c.p1, stream); break;
+        // conv1 + Smish + the first max-pool in one image-major launch (be_conv1_pool.hip)
+        case C1_POOL: rc = be_conv7x7_pool_nhwc4p_f32(c.x4, nb, w0, b0, c.p1, stream); break;
+        case C1_PM: {
+            be_conv_desc d;
+            d.n = nb; d.h = 21; d.w = 21; d.cin = 4; d.cout = 64; d.ksize = 7; d.act = 1;
+            rc = be_conv7x7_nhwc4p_f32(&d, c.x4, 28, w0, b0, c.c1, 64, stream);
+            break;
         }
-        float* f1 = ra;                                   // nb*1024
-        // fc.1 (+ BN1d + Smish): where the Winograd path runs, the split-bf16 row GEMM at every batch size
-        if (wino && be::rows_bf6_enabled()) {
-            const PackedLayout& L = layout();
-            if ((rc = be::gemm_rows_bf6(p3, nb, 2304, packed + L.sw_off[13], 1024, packed + L.b_off[13], nullptr, 1, f1, 1024, stream)))
-                return rc;
-        } else if ((rc = conv(packed, 13, p3, nullptr, f1, nb, 1, 1, 1024, stream))) return rc;
-        if ((rc = conv(packed, 14, f1, nullptr, out + first * BE_LOCAL_OUT, nb, 1, 0, BE_LOCAL_OUT, stream))) return rc;
+        default: rc = conv(L, packed, 0, c.x4, nullptr, c.c1, nb, 21, 1, 64, stream);
+        }
+        if (rc) return rc;
+        if (!r.conv1_pools && (rc = be_maxpool_nhwc_f32(c.c1, c.p1, nb, 21, 21, 64, 3, 2, 1, stream))) return rc;
+        if ((rc = r.l0_bf6 ? block_l0_bf6(L, packed, c.in[0], c.t[0], c.out[0], nb, stream)
+                           : block(L, packed, kBlocks[0], c.in[0], c.t[0], c.out[0], nb, stream))) return rc;
+        // Chained (the Winograd path, at every sub-batch size): the blocks are linked through the start of RW.  The pool leaves
+        // layer1's input transform there, layers 1 and 2 end in the kernel that also writes the next layer's, so no block reads its
+        // input map a second time.  Lifetimes in RW: a block's V and M are dead once its last GEMMs ran, except M, which the boundary
+        // kernel reads while it writes the next V below M's start.  With the downsamples folded into conv2's GEMMs x's transform
+        // stays alive beside conv1's (three regions) and nothing reads the maps themselves (!store_maps); under BE_WINO_DS_GEMM=1
+        // the 1x1 downsample launch reads them, and they are written.
+        if (r.chain) rc = be::pool_wino_in(c.out[0], r.store_maps ? c.p2 : nullptr, nb, 96, kLayers[kBlocks[1].conv1].cout, c.wino, c.wino_floats, stream);
+        else rc = be_maxpool_nhwc_f32(c.out[0], c.p2, nb, 11, 11, 96, 3, 2, 1, stream);
+        if (rc) return rc;
+        for (int k = 1; k < 4; ++k) {                     // layer3's Winograd block writes p3 itself (pool2)
+            if (r.blocks6 == B6_DIRECT) rc = block(L, packed, kBlocks[k], c.in[k], c.t[k], c.out[k], nb, stream);
+            else rc = block_wino(L, packed, r, kBlocks[k], c.in[k], k == 3 ? c.p3 : c.out[k], c.ds, c.wino, c.wino_floats, nb, stream, k == 3,
+                                 r.chain && k < 3 ? kLayers[kBlocks[k + 1].conv1].cout : 0);
+            if (rc) return rc;
+        }
+        if (r.blocks6 == B6_DIRECT && (rc = be_maxpool_nhwc_f32(c.out[3], c.p3, nb, 6, 6, 256, 2, 2, 0, stream))) return rc;
+        // fc.1 (+ BN1d + Smish), fc.4
+        if (r.fc1_bf6) rc = be::gemm_rows_bf6(c.p3, nb, 2304, L.w(packed, 13, ROWS_BF6), 1024, L.b(packed, 13, F32), nullptr, 1, c.f1, 1024, stream);
+        else rc = conv(L, packed, 13, c.p3, nullptr, c.f1, nb, 1, 1, 1024, stream);
+        if (rc) return rc;
+        if ((rc = conv(L, packed, 14, c.f1, nullptr, out + first * BE_LOCAL_OUT, nb, 1, 0, BE_LOCAL_OUT, stream))) return rc;
     }
     return BE_OK;
 }
@@ -363,4 +427,26 @@ extern "C" int be_local_stage_forward_view_f32(const float* packed, const be_pat
                "be_local_stage_forward_view_f32: bad view");
     return forward_impl(packed, nullptr, view, patches_per_image, out, n, workspace, workspace_bytes, opts, stream,
                         "be_local_stage_forward_view_f32");
+}
+
+// HOST-ONLY inspection hooks (no device): the region table and a sub-batch's route, as the pack and the forward use them
+extern "C" int be_local_stage_layout_debug(int* layer_form_reads, int64_t* w_b_off_n, int cap) {
+    const Layout& L = layout();
+    BE_REQUIRE(layer_form_reads && w_b_off_n && cap >= L.n, "be_local_stage_layout_debug: room for %d regions needed", L.n);
+    for (int k = 0; k < L.n; ++k) {
+        const Region& r = L.r[k];
+        const int a[3] = {r.layer, r.form, r.reads};
+        const size_t o[4] = {r.w_off, r.w_n, r.b_off, r.b_n};
+        for (int j = 0; j < 3; ++j) layer_form_reads[3 * k + j] = a[j];
+        for (int j = 0; j < 4; ++j) w_b_off_n[4 * k + j] = (int64_t)o[j];
+    }
+    return L.n;
+}
+
+extern "C" int be_local_stage_route_debug(int winograd, int nb, int* out) {
+    BE_REQUIRE(out && nb >= 1, "be_local_stage_route_debug: bad arguments");
+    const Route r = route_of(knobs(), winograd, nb);
+    const int a[kRouteFields] = {r.staging, r.conv1, r.conv1_pools, r.l0_bf6, r.chain, r.blocks6, r.store_maps, r.fc1_bf6};
+    for (int j = 0; j < kRouteFields; ++j) out[j] = a[j];
+    return kRouteFields;
 }

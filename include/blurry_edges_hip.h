@@ -531,6 +531,23 @@ int be_local_stage_forward_view_f32(const float* packed, const be_patch_view* vi
                                     float* out, int64_t n, void* workspace, size_t workspace_bytes,
                                     const be_local_stage_opts* opts, void* stream);
 
+/* HOST-ONLY inspection hooks of the LocalStage eval path (no GPU, no launch).
+ * be_local_stage_layout_debug: the table of regions of the packed buffer, in the order they lie in it; together they tile
+ * [0, be_local_stage_packed_floats()).  Region k: layer_form_reads[3k..] = {layer (state_dict() order: 0 conv1, 1-12 the blocks'
+ * conv1 / conv2 / downsample, 13 fc.1, 14 fc.4; -1: none), form, index of the region whose matrix its pack call reads or -1};
+ * w_b_off_n[4k..] = {matrix offset, matrix floats, bias offset, bias floats}.  Forms: 0 fp32 matrix + bias, 1 conv2 fused with its
+ * downsample's columns, 2 Winograd U with its planes + bias (the downsample's bias added), 3 the 1x1 downsample as an fp32
+ * convolution of its own, 4 split-bf16 row-GEMM planes, 5 layer0's pixel-major planes, 6 the downsample as conv2's second K segment,
+ * 7 the 384-float zero bias.  Returns the number of regions (<= 32), or BE_EINVAL when cap is smaller.
+ * be_local_stage_route_debug: the kernels a sub-batch of nb patches takes under opts->winograd and the process's BE_* knobs.
+ * out[8]: staging (0 [21,21,4], 1 rows padded to 28 pixels), conv1 (0 k_conv_igemm, 1 pixel-major LDS-DMA, 2 fp32 conv1 + pool,
+ * 3 split-bf16 conv1 + pool), conv1's launch pools, layer0 in split-bf16, the Winograd blocks chained, the 6x6 blocks (0 direct
+ * fused convolutions, 1 Winograd with the downsample folded into conv2's GEMMs, 2 Winograd + a split-bf16 downsample launch,
+ * 3 Winograd + an fp32 downsample launch), the second pool's and the inter-block maps are stored, fc.1 on the split-bf16 row GEMM.
+ * Returns 8. */
+int be_local_stage_layout_debug(int* layer_form_reads, int64_t* w_b_off_n, int cap);
+int be_local_stage_route_debug(int winograd, int nb, int* out);
+
 /* Layer-level entry points (used by the layer-by-layer parity tests and by the training path).
  * Activations are NHWC.  act: 0 none, 1 Smish (models/local_stage.py:4-6), 2 ReLU (GlobalStage FFN). */
 typedef struct be_conv_desc {
