@@ -181,6 +181,12 @@ _SIGNATURES = {
     "be_tsdf_mean_f32": (C.c_int, [C.POINTER(C.c_int), C.c_int] + [_P] * 6 + [_P]),
     "be_tsdf_raycast_f32": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int)] + [C.POINTER(C.c_float)] * 4
                             + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [_P] * 3 + [_P]),
+    "be_exclusive_scan_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "be_exclusive_scan_u8_i32": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
+    "be_tsdf_mesh_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "be_tsdf_mesh_count_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_float] + [_P] * 6 + [C.c_size_t, _P]),
+    "be_tsdf_mesh_emit_f32": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int)] + [C.POINTER(C.c_float)] * 2 + [C.c_float] + [_P] * 4
+                              + [C.c_int64, C.c_int64] + [_P] * 7 + [_P]),
     "be_depth_normals_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.c_int, C.c_float, _P, _P]),
     "be_icp_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "be_icp_linearize_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [C.POINTER(C.c_float), _P, _P, _P, C.c_int, C.c_int]
@@ -1661,6 +1667,101 @@ def tsdf_raycast(volume, cam_dst, pose, size, z_range, step=None, normals=False,
         nrm = depth_normals(d, cam_dst, **dict(normals_kw or {}))
         out.update(normal=nrm["normal"], normal_valid=nrm["valid"])
     return out
+
+
+def exclusive_scan(counts):
+    """counts: a uint8 tensor [n] on the GPU (n >= 0) -> (offsets int32 [n], offsets[i] = counts[0] + .. + counts[i - 1], total int64
+    [1] on the device = the sum of all counts).  Three launches - sums per workgroup of 1024 counts, a scan of those sums in 64
+    bits by one workgroup, 256 at a time, and the apply pass - with wave shuffles inside; integer sums, so the result is the same
+    on every run.  No workgroup waits for another.  Nothing synchronises with the host."""
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.uint8 or counts.dim() != 1:
+        raise ValueError(f"exclusive_scan: counts must be a uint8 tensor [n], got {getattr(counts, 'dtype', type(counts).__name__)} "
+                         f"{tuple(getattr(counts, 'shape', ()))}")
+    if not counts.is_cuda:
+        raise ValueError("exclusive_scan: counts must be on the GPU; nothing here computes on the CPU (numpy.cumsum is the host statement)")
+    counts = counts.contiguous()
+    o = ops()
+    if o is not None:
+        return tuple(o.exclusive_scan(counts))
+    n, dev = counts.numel(), counts.device
+    offsets = torch.empty(n, dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    nbytes = lib().be_exclusive_scan_workspace_bytes(n)
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    check(lib().be_exclusive_scan_u8_i32(dptr(counts, "counts", (torch.uint8,)) if n else None, n, dptr(offsets) if n else None,
+                                         dptr(total, "total", (torch.int64,)), dptr(ws, "workspace", (torch.int64,)), nbytes, stream_ptr(dev)),
+          "be_exclusive_scan_u8_i32")
+    return offsets, total
+
+
+def mesh_field(D, W, Fm=None, origin=(0.0, 0.0, 0.0), voxel=(1.0, 1.0, 1.0), min_weight=0.0, normals=True):
+    """A triangle mesh out of a signed distance field: D, W [Nz,Ny,Nx] and Fm [C,Nz,Ny,Nx] or None (float32 on the GPU, as tsdf_mean
+    returns them), origin = (X0, Y0, Z0) the centre of voxel (0, 0, 0) and voxel = (sX, sY, sZ) in metres.  Marching tetrahedra on
+    the Kuhn split of every cell whose 8 voxels have W > min_weight; the surface is D = 0 and its triangles are wound so that
+    their normals point towards D > 0.  -> dict(vertices [V,3] (X, Y, Z in the field's frame), faces [T,3] int32, weight [V],
+    feat [C,V] or None, normal [V,3] = the normalised gradient of D and normal_valid [V] bool (None with normals=False), edge [V]
+    int64 = 7 * (owner voxel's linear index) + (edge type): the vertex's identity).  Vertices are shared between triangles and lie
+    in the order of edge; V == 0 and T == 0 is a legal result.  A count phase, one read-back of the two totals - the one
+    synchronisation with the host, the cost of a result of variable length - and an emit phase; no atomics, the same bits on
+    every run.  mesh.extract is the host statement, bit for bit."""
+    from . import mesh
+    import numpy as np
+    for name, t in (("D", D), ("W", W)) + ((("Fm", Fm),) if Fm is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"mesh_field: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    dims, origin, voxel, min_weight, C_ = mesh.check_field("mesh_field", D, W, Fm, origin, voxel, min_weight)
+    if not D.is_cuda:
+        raise ValueError("mesh_field: the field lives on the GPU; nothing here computes on the CPU (mesh.extract is the host statement)")
+    dev = D.device
+    for name, t in (("W", W), ("Fm", Fm)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"mesh_field: {name} is on {t.device}, D on {dev}")
+    D, W = D.contiguous(), W.contiguous()
+    Fm = torch.empty((0,) + dims, dtype=torch.float32, device=dev) if Fm is None else Fm.contiguous()
+    normals = bool(normals)
+    origin, voxel = np.array(origin, np.float32), np.array(voxel, np.float32)
+    o = ops()
+    if o is not None:
+        vertices, faces, weight, feat, normal, normal_valid, edge, totals = o.tsdf_mesh(D, W, Fm, torch.from_numpy(origin), torch.from_numpy(voxel),
+                                                                                        min_weight, normals)
+        mesh.check_totals(int(totals[0]), int(totals[1]))
+    else:
+        n = D.numel()
+        idims = np.array(dims, np.int32)
+        nt, mask = (torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2))
+        voff, toff = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        nbytes = lib().be_tsdf_mesh_workspace_bytes(n)
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        u8, i64 = (torch.uint8,), (torch.int64,)
+        check(lib().be_tsdf_mesh_count_f32(dptr(D), dptr(W), _iptr(idims), min_weight, dptr(nt, "nt", u8), dptr(mask, "mask", u8), dptr(voff),
+                                           dptr(toff), dptr(totals, "totals", i64), dptr(ws, "workspace", i64), nbytes, stream_ptr(dev)),
+              "be_tsdf_mesh_count_f32")
+        V, T = mesh.check_totals(*totals.tolist())                      # the read-back: synchronises with the stream
+        vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(T, 3, dtype=torch.int32, device=dev)
+        weight = torch.empty(V, dtype=torch.float32, device=dev)
+        feat = torch.empty(C_, V, dtype=torch.float32, device=dev)
+        edge = torch.empty(V, dtype=torch.int64, device=dev)
+        normal = torch.empty(V if normals else 0, 3, dtype=torch.float32, device=dev)
+        normal_valid = torch.empty(V if normals else 0, dtype=torch.bool, device=dev)
+        if V or T:
+            check(lib().be_tsdf_mesh_emit_f32(dptr(D), dptr(W), dptr(Fm if C_ else None), C_, _iptr(idims), _fptr(origin), _fptr(voxel), min_weight,
+                                              dptr(nt, "nt", u8), dptr(mask, "mask", u8), dptr(voff), dptr(toff), V, T, dptr(vertices),
+                                              dptr(faces), dptr(weight), dptr(feat if C_ else None), dptr(normal if normals else None),
+                                              dptr(normal_valid if normals else None, "normal_valid", (torch.bool,)), dptr(edge, "edge", i64),
+                                              stream_ptr(dev)), "be_tsdf_mesh_emit_f32")
+    return dict(vertices=vertices, faces=faces, weight=weight, feat=feat if C_ else None, normal=normal if normals else None,
+                normal_valid=normal_valid if normals else None, edge=edge)
+
+
+def tsdf_mesh(volume, min_weight=0.0, normals=True):
+    """The surface a volume (native.tsdf_volume / tsdf_integrate) holds, as one triangle mesh in the volume's frame: tsdf_mean, then
+    mesh_field on the means - a cell takes part when all 8 of its voxels hold a sum of weights > min_weight (0: the ray cast's
+    rule), and the volume's C channels ride along as feat [C,V].  mesh.extract_volume is the host statement, bit for bit."""
+    _, origin, voxel = _tsdf_state("tsdf_mesh", volume)
+    D, W, Fm = tsdf_mean(volume)
+    return mesh_field(D, W, Fm if volume.C else None, tuple(origin.tolist()), tuple(voxel.tolist()), min_weight, normals)
 
 
 def depth_normals(depth, cam, step=3, max_jump=0.05, scale=1, window_origin=(0, 0)):

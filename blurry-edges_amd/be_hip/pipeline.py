@@ -489,7 +489,7 @@ class DepthPipeline:
         return res
 
 
-    # ---- TSDF volumes: views integrated one at a time into a voxel grid, any camera ray-cast out of it -----------------------
+    # ---- TSDF volumes: views integrated one at a time into a voxel grid, any camera ray-cast and a mesh extracted out of it ---
     @torch.no_grad()
     def integrate(self, views, volume=None, dims=None, origin=None, voxel=None, trunc=0.05, want=("shpd",), source="depth_map",
                   near=1e-3, complete_kw=None):
@@ -573,6 +573,35 @@ class DepthPipeline:
         if normals:
             res.update(normal=out["normal"], normal_valid=out["normal_valid"])
         return res
+
+    @torch.no_grad()
+    def extract_mesh(self, volume, min_weight=0.0, normals=True):
+        """volume: what integrate returned -> the surface it holds as one triangle mesh in the volume's frame (native.tsdf_mesh:
+        marching tetrahedra over the cells whose 8 voxels hold a sum of conf > min_weight): dict(vertices [V,3] = (X, Y, Z) in
+        metres, faces [T,3] int32 into the vertices, wound so that their normals face free space (the cameras' side), weight [V]
+        = the interpolated sum of conf, the maps the volume was integrated with as [channels,V] (shpd [3,V]), split as raycast
+        splits them, and normal [V,3] / normal_valid [V] = the normalised gradient of the signed distance (None with
+        normals=False)).  Vertices are shared between triangles; V == 0 is a legal result.  camera.pose moves the mesh into another
+        frame; save_mesh writes it."""
+        meta = getattr(volume, "meta", None) or {}
+        out = native.tsdf_mesh(volume, min_weight=min_weight, normals=normals)
+        res = {k: out[k] for k in ("vertices", "faces", "weight")}
+        c = 0
+        for k, lead, n in meta.get("channels", ()):
+            res[k] = out["feat"][c:c + n].reshape(lead + (out["vertices"].shape[0],))
+            c += n
+        res.update(normal=out["normal"], normal_valid=out["normal_valid"])
+        return res
+
+    @staticmethod
+    def save_mesh(path, mesh):
+        """mesh: what extract_mesh returned -> a binary PLY file at `path` (mesh.write_ply): positions, normals when the mesh holds
+        them, faces, and shpd as 8-bit vertex colours when the mesh holds it."""
+        from . import mesh as mesh_
+        host = lambda t: None if t is None else t.detach().cpu().numpy()
+        shpd = mesh.get("shpd")
+        mesh_.write_ply(path, dict(vertices=host(mesh["vertices"]), faces=host(mesh["faces"]), normal=host(mesh.get("normal"))),
+                        colour=None if shpd is None else host(shpd).reshape(3, -1))
 
 
     # ---- registration: surface normals of a depth map, and the pose between two pairs from their depth ---------------------

@@ -15,6 +15,7 @@ formats (argument names and defaults = utils/args.py of the reference):
     ... eval --reproject CAM.npz [--out_path DIR]          also write every pair's depth and colours as the camera of CAM sees them
     ... eval --fuse FILE.npz [--out_path DIR]              also merge every V consecutive pairs, with the poses of FILE, in one camera
                                                            (with tsdf_dims / tsdf_origin / tsdf_voxel in FILE: also in a TSDF volume)
+                                                           (with tsdf_mesh > 0 beside them: also that volume's triangle mesh)
     ... eval --normals [--out_path DIR]                    also write every pair's surface normals (of its completed depth)
     ... eval --complete [--out_path DIR]                   also write and score every pair's depth map completed to a dense one
     ... eval --complete --complete_method diffuse          ... by edge-aware diffusion instead of the nearest sample's depth
@@ -334,7 +335,9 @@ def load_fusion(path):
     pair's), tau, min_views, peel, recentre and scale (the source lattice) -> dict(poses, cam, size, scale, kw = the keywords of
     DepthPipeline.fuse that the file sets), checked by be_hip.camera; tau, min_views and peel by native.fuse_views.  An optional
     integer `register` > 0 (-> cfg["register"]) asks for every view's pose to be refined against view 0 by that many iterations of
-    DepthPipeline.register, starting from the pose given, before the group is merged."""
+    DepthPipeline.register, starting from the pose given, before the group is merged.  tsdf_dims, tsdf_origin, tsdf_voxel (and
+    optionally tsdf_trunc) describe a TSDF volume (-> cfg["tsdf"]); an integer tsdf_mesh > 0 beside them (-> cfg["tsdf_mesh"]) asks
+    for that volume's mesh as well."""
     from . import camera
     with np.load(path) as f:
         if "poses" not in f:
@@ -370,6 +373,14 @@ def load_fusion(path):
                                                                 np.asarray(f["tsdf_voxel"]).reshape(-1).tolist(),
                                                                 one("tsdf_trunc", float) if "tsdf_trunc" in f else 0.05)
             cfg["tsdf"] = dict(dims=dims, origin=origin, voxel=voxel, trunc=trunc)
+        if "tsdf_mesh" in f:                                                # absent: the dict holds what it held before
+            n = np.asarray(f["tsdf_mesh"]).reshape(-1)[0]
+            if int(n) != n or n < 0:
+                raise ValueError(f"--fuse: tsdf_mesh must be an integer >= 0 (> 0: also write the volume's mesh), got {f['tsdf_mesh']!r}")
+            if n > 0 and "tsdf" not in cfg:
+                raise ValueError(f"--fuse: tsdf_mesh extracts the mesh of the TSDF volume; {path} lacks the keys that describe one: "
+                                 "tsdf_dims, tsdf_origin, tsdf_voxel (tsdf_trunc is optional)")
+            cfg["tsdf_mesh"] = int(n)
         return cfg
 
 
@@ -422,6 +433,9 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     = (Nz, Ny, Nx), tsdf_origin = (X0, Y0, Z0) and tsdf_voxel = (sX, sY, sZ) (and optionally tsdf_trunc, 0.05) in the settings file
     each group is also integrated into a TSDF volume of that description, DepthPipeline.integrate, and ray-cast into view 0's
     camera, DepthPipeline.raycast: {args.out_path}/tsdf_{g:04d}.npz (depth, valid, weight, normal, shpd), outside the timed region.
+    With an integer tsdf_mesh > 0 beside them the volume's surface is also extracted, DepthPipeline.extract_mesh, in the frame of the
+    poses: {args.out_path}/mesh_{g:04d}.ply (positions, normals, shpd as colours) and mesh_{g:04d}.npz (vertices, faces, weight, shpd,
+    normal, normal_valid), outside the timed region.
     args.normals (not in the reference): every pair's surface normals, DepthPipeline.normals(source="complete"), go to
     {args.out_path}/normals_{j:04d}.npz (normal [3,H,W], valid), outside the timed region."""
     import data, models, utils
@@ -527,6 +541,10 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
                     cast = pipe.raycast(vol, pose=gposes[0], normals=True)           # view 0's camera, where view 0 stands
                     np.savez(os.path.join(args.out_path, f"tsdf_{j // len(group):04d}.npz"),
                              **{k: cast[k].cpu().numpy() for k in ("depth", "valid", "weight", "normal", "shpd")})
+                    if fcfg.get("tsdf_mesh", 0) > 0:
+                        tri = pipe.extract_mesh(vol)
+                        pipe.save_mesh(os.path.join(args.out_path, f"mesh_{j // len(group):04d}.ply"), tri)
+                        np.savez(os.path.join(args.out_path, f"mesh_{j // len(group):04d}.npz"), **{k: v.cpu().numpy() for k, v in tri.items()})
                 group = []
         depth = maps["depth_map"][None]
         m = np.array(utils.eval_depth(depth, gt[None].to(depth.dtype), depth, crop=args.crop))

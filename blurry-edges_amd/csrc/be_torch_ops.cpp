@@ -759,6 +759,61 @@ std::tuple<Tensor, Tensor, Tensor> tsdf_raycast(const Tensor& D, const Tensor& W
     return {dout, wout, fout};
 }
 
+// counts [n] uint8 on the GPU -> (offsets [n] int32 = the exclusive prefix sums, total [1] int64 on the device)
+std::tuple<Tensor, Tensor> exclusive_scan(const Tensor& counts) {
+    TORCH_CHECK(counts.is_cuda() && counts.dim() == 1 && counts.scalar_type() == at::kByte && counts.is_contiguous(),
+                "exclusive_scan: counts must be a contiguous uint8 tensor [n] on the GPU");
+    const int64_t n = counts.numel();
+    TORCH_CHECK(n <= 0x7fffffff, "exclusive_scan: at most 2^31 - 1 counts");
+    Tensor offsets = at::empty({n}, counts.options().dtype(at::kInt)), total = at::empty({1}, counts.options().dtype(at::kLong));
+    const size_t bytes = be_exclusive_scan_workspace_bytes(n);
+    Tensor ws = at::empty({(int64_t)(bytes / 8)}, counts.options().dtype(at::kLong));
+    check(be_exclusive_scan_u8_i32(counts.data_ptr<uint8_t>(), n, offsets.data_ptr<int32_t>(), total.data_ptr<int64_t>(), ws.data_ptr<int64_t>(),
+                                   bytes, stream_of(counts)), "be_exclusive_scan_u8_i32");
+    return {offsets, total};
+}
+
+// D, W [Nz,Ny,Nx], Fm [C,Nz,Ny,Nx] as tsdf_mean returns them -> [vertices [V,3], faces [T,3] int32, weight [V], feat [C,V],
+// normal [V,3], normal_valid [V] bool (both empty without normals), edge [V] int64, totals [2] int64 on the CPU = (V, T)].  Count,
+// one read-back of the totals (the synchronisation a result of variable length costs), allocation, emit.  A total >= 2^31 emits
+// nothing: every output is empty beside totals, which the caller refuses (mesh.check_totals).
+std::vector<Tensor> tsdf_mesh(const Tensor& D, const Tensor& W, const Tensor& Fm, const Tensor& origin, const Tensor& voxel, double min_weight,
+                              bool normals) {
+    int dims[3];
+    tsdf_dims(D, "tsdf_mesh", dims);
+    fp(D, "D");
+    fp(W, "W");
+    TORCH_CHECK(W.sizes() == D.sizes() && W.device() == D.device(), "tsdf_mesh: W [Nz,Ny,Nx] on D's device");
+    TORCH_CHECK(Fm.dim() == 4 && Fm.sizes().slice(1) == D.sizes() && Fm.device() == D.device(), "tsdf_mesh: Fm [C,Nz,Ny,Nx] on D's device");
+    const int64_t C = Fm.size(0), n = D.numel();
+    const float* fm = C > 0 ? fp(Fm, "Fm") : nullptr;
+    const float* org = host_floats(origin, 3, "tsdf_mesh(origin)");
+    const float* vox = host_floats(voxel, 3, "tsdf_mesh(voxel)");
+    auto ob = D.options().dtype(at::kByte), oi = D.options().dtype(at::kInt), ol = D.options().dtype(at::kLong);
+    Tensor nt = at::empty({n}, ob), mask = at::empty({n}, ob), voff = at::empty({n}, oi), toff = at::empty({n}, oi), totals = at::empty({2}, ol);
+    const size_t bytes = be_tsdf_mesh_workspace_bytes(n);
+    Tensor ws = at::empty({(int64_t)(bytes / 8)}, ol);
+    void* stream = stream_of(D);
+    check(be_tsdf_mesh_count_f32(D.data_ptr<float>(), W.data_ptr<float>(), dims, (float)min_weight, nt.data_ptr<uint8_t>(), mask.data_ptr<uint8_t>(),
+                                 voff.data_ptr<int32_t>(), toff.data_ptr<int32_t>(), totals.data_ptr<int64_t>(), ws.data_ptr<int64_t>(), bytes,
+                                 stream), "be_tsdf_mesh_count_f32");
+    Tensor host = totals.cpu();                                         // synchronises with the current stream
+    int64_t V = host.data_ptr<int64_t>()[0], T = host.data_ptr<int64_t>()[1];
+    const bool fits = V >= 0 && T >= 0 && V <= 0x7fffffff && T <= 0x7fffffff;
+    if (!fits) V = T = 0;
+    Tensor vertices = at::empty({V, 3}, D.options()), faces = at::empty({T, 3}, oi), weight = at::empty({V}, D.options());
+    Tensor feat = at::empty({C, V}, D.options()), edge = at::empty({V}, ol);
+    Tensor normal = at::empty({normals ? V : 0, 3}, D.options()), normal_valid = at::empty({normals ? V : 0}, D.options().dtype(at::kBool));
+    if (fits && (V > 0 || T > 0))
+        check(be_tsdf_mesh_emit_f32(D.data_ptr<float>(), W.data_ptr<float>(), fm, (int)C, dims, org, vox, (float)min_weight, nt.data_ptr<uint8_t>(),
+                                    mask.data_ptr<uint8_t>(), voff.data_ptr<int32_t>(), toff.data_ptr<int32_t>(), V, T, vertices.data_ptr<float>(),
+                                    faces.data_ptr<int32_t>(), weight.data_ptr<float>(), C > 0 ? feat.data_ptr<float>() : nullptr,
+                                    normals ? normal.data_ptr<float>() : nullptr,
+                                    normals ? reinterpret_cast<uint8_t*>(normal_valid.data_ptr<bool>()) : nullptr, edge.data_ptr<int64_t>(), stream),
+              "be_tsdf_mesh_emit_f32");
+    return {vertices, faces, weight, feat, normal, normal_valid, edge, host};
+}
+
 // depth registration: normal [3,H,W] of depth [H,W]; cam [4] a CPU float32 tensor as for unproject
 Tensor depth_normals(const Tensor& depth, const Tensor& cam, int64_t step, double max_jump, int64_t scale, int64_t top, int64_t left) {
     TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "depth_normals: depth [H,W], 1 .. 2^31 - 1 samples");
@@ -977,6 +1032,8 @@ TORCH_LIBRARY(be, m) {
     m.def("tsdf_integrate(Tensor depth, Tensor? weight, Tensor? feat, Tensor cam_src, Tensor pose, float near, int scale, int top, int left, "
           "Tensor origin, Tensor voxel, float trunc, Tensor(a!) sw, Tensor(b!) swd, Tensor(c!) swf) -> ()");
     m.def("tsdf_mean(Tensor sw, Tensor swd, Tensor swf) -> (Tensor, Tensor, Tensor)");
+    m.def("exclusive_scan(Tensor counts) -> (Tensor, Tensor)");
+    m.def("tsdf_mesh(Tensor D, Tensor W, Tensor Fm, Tensor origin, Tensor voxel, float min_weight, bool normals) -> Tensor[]");
     m.def("tsdf_raycast(Tensor D, Tensor W, Tensor Fm, Tensor origin, Tensor voxel, Tensor cam_dst, Tensor pose, int Ho, int Wo, float z_near, "
           "float step, int n) -> (Tensor, Tensor, Tensor)");
     m.def("depth_normals(Tensor depth, Tensor cam, int step, float max_jump, int scale, int top, int left) -> Tensor");
@@ -1048,6 +1105,8 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("tsdf_integrate", tsdf_integrate);
     m.impl("tsdf_mean", tsdf_mean);
     m.impl("tsdf_raycast", tsdf_raycast);
+    m.impl("exclusive_scan", exclusive_scan);
+    m.impl("tsdf_mesh", tsdf_mesh);
     m.impl("depth_normals", depth_normals);
     m.impl("icp_linearize", icp_linearize);
     m.impl("fill_nearest", fill_nearest);

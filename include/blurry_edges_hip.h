@@ -325,6 +325,46 @@ int be_tsdf_raycast_f32(const float* D, const float* W, const float* Fm, int C, 
                         const float* cam_dst, const float* pose, int Ho, int Wo, float z_near, float step, int n, float* depth_out,
                         float* weight_out, float* feat_out, void* stream);
 
+/* A triangle mesh out of a volume's means (D, W, Fm as be_tsdf_mean_f32 left them): marching tetrahedra on the Kuhn split of every
+ * cell into 6 tetrahedra about the body diagonal 000-111.  be_hip/mesh.py is the statement - the numbering of corners, edge types
+ * and tetrahedra, the case table (csrc/be_tsdf_mesh_table.h is generated from it), the order of the outputs and every float
+ * operation - and the kernels equal it bit for bit.  A voxel is observed iff W > min_weight and positive iff D > 0; a cell (8
+ * voxels) is valid iff all its corners are observed; an edge (owner voxel v, type e = 0..6 with the offsets (dx, dy, dz) = (1,0,0),
+ * (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1)) carries a vertex iff its endpoints differ in positivity and a valid cell
+ * contains both.  Two phases, every buffer the caller's, n = Nz Ny Nx:
+ *
+ * be_tsdf_mesh_count_f32: nt [n] uint8 = the triangles of the cell whose origin corner is the voxel (0..12), mask [n] uint8 = bit e
+ * set when the voxel's edge e carries a vertex, voff / toff [n] int32 = the exclusive prefix sums of popcount(mask) / nt in voxel
+ * order (the low 32 bits where a total exceeds them), totals [2] int64 on the device = (V, T).  workspace: 8-byte aligned,
+ * be_tsdf_mesh_workspace_bytes(n) bytes.  Nothing synchronises with the host: the caller reads totals (one synchronisation, the
+ * cost of a result of variable length), refuses V or T >= 2^31, allocates the outputs and calls
+ *
+ * be_tsdf_mesh_emit_f32 with the same D, W, dims, min_weight and the four count buffers: vertices [V,3] (X, Y, Z in the volume's
+ * frame), weight [V], feat [C,V] (NULL when C == 0), normal [V,3] and normal_valid [V] uint8 (both NULL: no normals), edge [V]
+ * int64 = 7 * owner + e, faces [T,3] int32.  Vertex of edge a -> b: t = Da / (Da - Db), x = xa + t * (xb - xa) per axis with
+ * xa = X0 + (float) ix * sX, xb = X0 + (float)(ix + dx) * sX; weight and channels likewise.  Normal: per endpoint and axis
+ * (D[+1] - D[-1]) * 0.5f / s where both neighbours exist and are observed, else (D[+1] - D[p]) / s or (D[p] - D[-1]) / s;
+ * g = ga + t * (gb - ga), l = sqrtf((gx gx + gy gy) + gz gz), normal = g / l where 0 < l < inf, else +0 and normal_valid 0.
+ * Vertices lie in increasing (owner, e), triangles in increasing (cell, tetrahedron, table order), wound so that their normal
+ * points towards D > 0.  Every output element is written exactly once; no atomics; a repeated run gives the same bits.
+ *
+ * be_exclusive_scan_u8_i32: offsets[i] = counts[0] + .. + counts[i - 1] (the low 32 bits) and *total = the sum of all n counts, on
+ * the device; 0 <= n < 2^31 (n == 0 writes total alone).  Three launches: sums per workgroup of BE_SCAN_SPAN elements, an exclusive
+ * scan of those sums in 64 bits by one workgroup, BE_SCAN_SUMS_PER_PASS at a time, and the apply pass; no workgroup waits for
+ * another.  workspace: 8-byte aligned, be_exclusive_scan_workspace_bytes(n) bytes. */
+#define BE_SCAN_SPAN 1024
+#define BE_SCAN_SUMS_PER_PASS 256
+size_t be_exclusive_scan_workspace_bytes(int64_t n);
+int be_exclusive_scan_u8_i32(const uint8_t* counts, int64_t n, int32_t* offsets, int64_t* total, void* workspace, size_t workspace_bytes,
+                             void* stream);
+size_t be_tsdf_mesh_workspace_bytes(int64_t n);
+int be_tsdf_mesh_count_f32(const float* D, const float* W, const int* dims, float min_weight, uint8_t* nt, uint8_t* mask, int32_t* voff,
+                           int32_t* toff, int64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
+int be_tsdf_mesh_emit_f32(const float* D, const float* W, const float* Fm, int C, const int* dims, const float* origin, const float* voxel,
+                          float min_weight, const uint8_t* nt, const uint8_t* mask, const int32_t* voff, const int32_t* toff, int64_t V,
+                          int64_t T, float* vertices, int32_t* faces, float* weight, float* feat, float* normal, uint8_t* normal_valid,
+                          int64_t* edge, void* stream);
+
 /* Depth registration: the two kernels of a point-to-plane ICP on depth maps; the loop around them is be_hip/registration.py.
  * Lattice, camera and pose arguments are be_reproject_f32's; all per-sample arithmetic is fp32, one rounding per operation.
  *
