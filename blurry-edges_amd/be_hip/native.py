@@ -187,6 +187,9 @@ _SIGNATURES = {
     "be_tsdf_mesh_count_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_float] + [_P] * 6 + [C.c_size_t, _P]),
     "be_tsdf_mesh_emit_f32": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int)] + [C.POINTER(C.c_float)] * 2 + [C.c_float] + [_P] * 4
                               + [C.c_int64, C.c_int64] + [_P] * 7 + [_P]),
+    "be_mesh_raster_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "be_mesh_raster_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int, _P, _P] + [C.POINTER(C.c_float)] * 2
+                           + [C.c_float, C.c_int, C.c_int, C.c_int] + [_P] * 7 + [_P, C.c_size_t, _P]),
     "be_depth_normals_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.c_int, C.c_float, _P, _P]),
     "be_icp_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "be_icp_linearize_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [C.POINTER(C.c_float), _P, _P, _P, C.c_int, C.c_int]
@@ -1762,6 +1765,70 @@ def tsdf_mesh(volume, min_weight=0.0, normals=True):
     _, origin, voxel = _tsdf_state("tsdf_mesh", volume)
     D, W, Fm = tsdf_mean(volume)
     return mesh_field(D, W, Fm if volume.C else None, tuple(origin.tolist()), tuple(voxel.tolist()), min_weight, normals)
+
+
+def raster_mesh(mesh, cam_dst, pose, size, near=1e-3, cull="none", want=("feat", "normal", "weight", "bary")):
+    """A triangle mesh as the camera cam_dst sees it from `pose` (camera.pose: the camera's frame -> the mesh's, as tsdf_raycast
+    takes it; None: the identity), size = (Ho, Wo) with 1 <= Ho, Wo <= 16384.  mesh: a dict as mesh_field / tsdf_mesh return it,
+    on the GPU: vertices [V,3] float32, faces [T,3] int32, and optionally (absent or None) weight [V], feat [C,V], normal [V,3]
+    with normal_valid [V] bool.  A z-buffered rasteriser: vertices are projected and snapped to 1/256 pixel, coverage is exact on
+    those integers with the top-left rule (two triangles that share an edge cover each pixel centre on it once), depth is
+    interpolated perspective-correctly and the nearest fragment wins, the lowest face index on a tie.  A triangle with a vertex at
+    Z <= near in the camera's frame, or further than 2^14 pixels from the image origin, is dropped whole: nothing is clipped.  A
+    triangle faces the camera when its winding normal (mesh.py: towards free space) points at it; cull = "back" drops the others,
+    "front" those, "none" neither.  -> dict(depth [Ho,Wo] = Z in the camera's frame, face [Ho,Wo] int32 = the triangle seen (-1:
+    none), valid (face >= 0; on the device, no sync), and, of `want`, what the mesh holds: weight [Ho,Wo], feat [C,Ho,Wo], normal
+    [3,Ho,Wo] in the camera's frame with normal_valid, bary [3,Ho,Wo] = the perspective-correct barycentric coordinates in the
+    face's vertex order; None otherwise); +0 / -1 / False where nothing landed.  A face whose index lies outside [0, V) is dropped
+    (the statement refuses it; finding it here would cost a read-back).  Three kernels and a memset; order-independent atomics,
+    the same bits on every run; nothing synchronises with the host.  raster.render is the host statement, bit for bit."""
+    from . import camera, raster, volume as volume_
+    V, T, C_ = raster.check_mesh("raster_mesh", mesh)
+    Ho, Wo, near, cull, want = raster.check_params("raster_mesh", size, near, cull, want)
+    kinds = dict(vertices=torch.float32, faces=torch.int32, weight=torch.float32, feat=torch.float32, normal=torch.float32, normal_valid=torch.bool)
+    dev = getattr(mesh["vertices"], "device", None)
+    m = {}
+    for name, dt in kinds.items():
+        t = mesh.get(name)
+        if t is None:
+            m[name] = None
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f"raster_mesh: {name} must be a {str(dt).replace('torch.', '')} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if not t.is_cuda:
+            raise ValueError("raster_mesh: the mesh lives on the GPU; nothing here computes on the CPU (raster.render is the host statement)")
+        if t.device != dev:
+            raise ValueError(f"raster_mesh: {name} is on {t.device}, vertices on {dev}")
+        m[name] = t.contiguous()
+    cd = camera.as_pinhole(cam_dst, "raster_mesh(cam_dst)").f32()
+    camera.as_pose(pose, "raster_mesh(pose)")
+    q12 = volume_.inverse_pose(pose)
+    weight = m["weight"] if "weight" in want else None
+    feat = m["feat"] if "feat" in want else None
+    normal = m["normal"] if "normal" in want else None
+    nvalid = m["normal_valid"] if normal is not None else None
+    bary = "bary" in want
+    o = ops()
+    if o is not None:
+        d, face, w, f, nrm, nv, b = o.mesh_raster(m["vertices"], m["faces"], weight, feat, normal, nvalid, torch.from_numpy(cd),
+                                                  torch.from_numpy(q12), near, cull, Ho, Wo, bary)
+    else:
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+        d, face = new(Ho, Wo), new(Ho, Wo, dtype=torch.int32)
+        w = new(Ho, Wo) if weight is not None else None
+        f = new(C_, Ho, Wo) if feat is not None else None
+        nrm, nv = (new(3, Ho, Wo), new(Ho, Wo, dtype=torch.bool)) if normal is not None else (None, None)
+        b = new(3, Ho, Wo) if bary else None
+        nbytes = lib().be_mesh_raster_workspace_bytes(V, Ho, Wo)
+        ws = new((nbytes + 15) // 16, 2, dtype=torch.int64)
+        u8 = (torch.bool,)
+        check(lib().be_mesh_raster_f32(dptr(m["vertices"]), V, dptr(m["faces"]), T, dptr(weight), dptr(feat if C_ else None), C_, dptr(normal),
+                                       dptr(nvalid, "normal_valid", u8), _fptr(cd), _fptr(q12), near, cull, Ho, Wo, dptr(d), dptr(face), dptr(w),
+                                       dptr(f if C_ else None), dptr(nrm), dptr(nv, "normal_valid", u8), dptr(b),
+                                       dptr(ws, "workspace", (torch.int64,)), nbytes, stream_ptr(dev)), "be_mesh_raster_f32")
+    keep = lambda t, has: t if has else None
+    return dict(depth=d, face=face, valid=face >= 0, weight=keep(w, weight is not None), feat=keep(f, feat is not None),
+                normal=keep(nrm, normal is not None), normal_valid=keep(nv, normal is not None), bary=keep(b, bary))
 
 
 def depth_normals(depth, cam, step=3, max_jump=0.05, scale=1, window_origin=(0, 0)):

@@ -593,6 +593,47 @@ class DepthPipeline:
         res.update(normal=out["normal"], normal_valid=out["normal_valid"])
         return res
 
+    @torch.no_grad()
+    def render_mesh(self, mesh, cam_dst=None, pose=None, size=None, want=("shpd",), cull="none", normals=True):
+        """mesh: what extract_mesh returned (or any dict of vertices [V,3], faces [T,3] int32 and per-vertex maps on the GPU) -> the
+        camera cam_dst at `pose` (camera.pose: the camera's frame -> the mesh's; None: the identity), size = (Ho, Wo), looking at
+        it (native.raster_mesh: a z-buffered rasteriser, exact coverage on a 1/256 pixel lattice, perspective-correct
+        interpolation, the nearest surface per pixel): depth [Ho,Wo] along cam_dst's axis, valid, face [Ho,Wo] int32 = the
+        triangle each pixel sees (-1: none), weight (the interpolated sum of conf, None when the mesh has none), the `want`ed
+        maps of the mesh named as extract_mesh names them (shpd [3,Ho,Wo]; any [.., V] map of the mesh may be asked for), and,
+        with normals=True and a mesh that holds them, normal [3,Ho,Wo] in the camera's frame and normal_valid (None otherwise).
+        +0 / -1 / False where nothing landed.  Defaults: the pipeline's own camera dcal.intrinsics(Ho, Wo) of the size asked
+        for and the identity pose; size is needed.  Triangles that reach behind the camera are dropped whole, not clipped; cull =
+        "back" keeps only the triangles that face the camera.  The result holds the keys register's destination view takes
+        (depth, weight, normal): like raycast's, it is a frame-to-model target, from the mesh instead of the volume."""
+        if size is None:
+            raise ValueError("render_mesh: size = (Ho, Wo) is needed (a mesh does not remember a camera)")
+        if not isinstance(mesh, dict) or "vertices" not in mesh or "faces" not in mesh:
+            raise ValueError("render_mesh: mesh must be the dict extract_mesh returned (vertices, faces, ...)")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        V = mesh["vertices"].shape[0]
+        parts = []
+        for k in want:
+            t = mesh.get(k)
+            if k in ("vertices", "faces", "weight", "normal", "normal_valid", "feat") or not isinstance(t, torch.Tensor) or t.shape[-1] != V:
+                raise ValueError(f"render_mesh: want names the maps of the mesh with a last axis of {V} vertices; {k!r} is not one")
+            parts.append((k, tuple(t.shape[:-1]), t.reshape(-1, V).to(torch.float32)))
+        if cam_dst is None:
+            try:
+                cam_dst = self.dcal.intrinsics(*size)
+            except TypeError:
+                raise ValueError(f"render_mesh: size must be (Ho, Wo), got {size!r}") from None
+        m = dict(vertices=mesh["vertices"], faces=mesh["faces"], weight=mesh.get("weight"), feat=torch.cat([p[2] for p in parts]) if parts else None,
+                 normal=mesh.get("normal") if normals else None, normal_valid=mesh.get("normal_valid") if normals else None)
+        out = native.raster_mesh(m, cam_dst, pose, size, cull=cull, want=("feat", "weight") + (("normal",) if normals else ()))
+        res = {k: out[k] for k in ("depth", "valid", "face", "weight")}
+        c = 0
+        for k, lead, t in parts:
+            res[k] = out["feat"][c:c + t.shape[0]].reshape(lead + tuple(out["depth"].shape))
+            c += t.shape[0]
+        res.update(normal=out["normal"], normal_valid=out["normal_valid"])
+        return res
+
     @staticmethod
     def save_mesh(path, mesh):
         """mesh: what extract_mesh returned -> a binary PLY file at `path` (mesh.write_ply): positions, normals when the mesh holds

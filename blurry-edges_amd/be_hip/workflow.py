@@ -16,6 +16,7 @@ formats (argument names and defaults = utils/args.py of the reference):
     ... eval --fuse FILE.npz [--out_path DIR]              also merge every V consecutive pairs, with the poses of FILE, in one camera
                                                            (with tsdf_dims / tsdf_origin / tsdf_voxel in FILE: also in a TSDF volume)
                                                            (with tsdf_mesh > 0 beside them: also that volume's triangle mesh)
+                                                           (with mesh_render > 0 beside them: also that mesh seen by view 0's camera)
     ... eval --normals [--out_path DIR]                    also write every pair's surface normals (of its completed depth)
     ... eval --complete [--out_path DIR]                   also write and score every pair's depth map completed to a dense one
     ... eval --complete --complete_method diffuse          ... by edge-aware diffusion instead of the nearest sample's depth
@@ -337,7 +338,8 @@ def load_fusion(path):
     integer `register` > 0 (-> cfg["register"]) asks for every view's pose to be refined against view 0 by that many iterations of
     DepthPipeline.register, starting from the pose given, before the group is merged.  tsdf_dims, tsdf_origin, tsdf_voxel (and
     optionally tsdf_trunc) describe a TSDF volume (-> cfg["tsdf"]); an integer tsdf_mesh > 0 beside them (-> cfg["tsdf_mesh"]) asks
-    for that volume's mesh as well."""
+    for that volume's mesh as well, and an integer mesh_render > 0 (-> cfg["mesh_render"]) for that mesh rendered into view 0's
+    camera."""
     from . import camera
     with np.load(path) as f:
         if "poses" not in f:
@@ -381,6 +383,14 @@ def load_fusion(path):
                 raise ValueError(f"--fuse: tsdf_mesh extracts the mesh of the TSDF volume; {path} lacks the keys that describe one: "
                                  "tsdf_dims, tsdf_origin, tsdf_voxel (tsdf_trunc is optional)")
             cfg["tsdf_mesh"] = int(n)
+        if "mesh_render" in f:                                              # absent: the dict holds what it held before
+            n = np.asarray(f["mesh_render"]).reshape(-1)[0]
+            if int(n) != n or n < 0:
+                raise ValueError(f"--fuse: mesh_render must be an integer >= 0 (> 0: also render the volume's mesh), got {f['mesh_render']!r}")
+            if n > 0 and "tsdf" not in cfg:
+                raise ValueError(f"--fuse: mesh_render renders the mesh of the TSDF volume; {path} lacks the keys that describe one: "
+                                 "tsdf_dims, tsdf_origin, tsdf_voxel (tsdf_trunc is optional)")
+            cfg["mesh_render"] = int(n)
         return cfg
 
 
@@ -435,7 +445,9 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     camera, DepthPipeline.raycast: {args.out_path}/tsdf_{g:04d}.npz (depth, valid, weight, normal, shpd), outside the timed region.
     With an integer tsdf_mesh > 0 beside them the volume's surface is also extracted, DepthPipeline.extract_mesh, in the frame of the
     poses: {args.out_path}/mesh_{g:04d}.ply (positions, normals, shpd as colours) and mesh_{g:04d}.npz (vertices, faces, weight, shpd,
-    normal, normal_valid), outside the timed region.
+    normal, normal_valid), outside the timed region.  With an integer mesh_render > 0 beside them that mesh is also rasterised into
+    view 0's camera, DepthPipeline.render_mesh: {args.out_path}/mesh_render_{g:04d}.npz (depth, valid, face, normal, shpd), outside
+    the timed region; without the key nothing changes.
     args.normals (not in the reference): every pair's surface normals, DepthPipeline.normals(source="complete"), go to
     {args.out_path}/normals_{j:04d}.npz (normal [3,H,W], valid), outside the timed region."""
     import data, models, utils
@@ -541,10 +553,14 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
                     cast = pipe.raycast(vol, pose=gposes[0], normals=True)           # view 0's camera, where view 0 stands
                     np.savez(os.path.join(args.out_path, f"tsdf_{j // len(group):04d}.npz"),
                              **{k: cast[k].cpu().numpy() for k in ("depth", "valid", "weight", "normal", "shpd")})
+                    tri = pipe.extract_mesh(vol) if fcfg.get("tsdf_mesh", 0) > 0 or fcfg.get("mesh_render", 0) > 0 else None
                     if fcfg.get("tsdf_mesh", 0) > 0:
-                        tri = pipe.extract_mesh(vol)
                         pipe.save_mesh(os.path.join(args.out_path, f"mesh_{j // len(group):04d}.ply"), tri)
                         np.savez(os.path.join(args.out_path, f"mesh_{j // len(group):04d}.npz"), **{k: v.cpu().numpy() for k, v in tri.items()})
+                    if fcfg.get("mesh_render", 0) > 0:                               # view 0's camera, where view 0 stands
+                        seen = pipe.render_mesh(tri, cam_dst=vol.meta["camera"], pose=gposes[0], size=vol.meta["size"])
+                        np.savez(os.path.join(args.out_path, f"mesh_render_{j // len(group):04d}.npz"),
+                                 **{k: seen[k].cpu().numpy() for k in ("depth", "valid", "face", "normal", "shpd")})
                 group = []
         depth = maps["depth_map"][None]
         m = np.array(utils.eval_depth(depth, gt[None].to(depth.dtype), depth, crop=args.crop))

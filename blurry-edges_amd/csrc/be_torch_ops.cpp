@@ -814,6 +814,50 @@ std::vector<Tensor> tsdf_mesh(const Tensor& D, const Tensor& W, const Tensor& Fm
     return {vertices, faces, weight, feat, normal, normal_valid, edge, host};
 }
 
+// vertices [V,3], faces [T,3] int32 and the optional per-vertex maps weight [V], feat [C,V], normal [V,3], normal_valid [V] bool on
+// the GPU; cam_dst [4] and pose [12] (mesh frame -> camera frame) CPU float32 tensors -> [depth [Ho,Wo], face [Ho,Wo] int32,
+// weight [Ho,Wo], feat [C,Ho,Wo], normal [3,Ho,Wo], normal_valid [Ho,Wo] bool, bary [3,Ho,Wo]]; an output whose input is absent
+// (bary: want_bary false) is an empty tensor.  Nothing synchronises with the host.
+std::vector<Tensor> mesh_raster(const Tensor& vertices, const Tensor& faces, const c10::optional<Tensor>& weight, const c10::optional<Tensor>& feat,
+                                const c10::optional<Tensor>& normal, const c10::optional<Tensor>& normal_valid, const Tensor& cam_dst,
+                                const Tensor& pose, double near, int64_t cull, int64_t Ho, int64_t Wo, bool want_bary) {
+    fp(vertices, "mesh_raster(vertices)");
+    TORCH_CHECK(vertices.dim() == 2 && vertices.size(1) == 3, "mesh_raster: vertices [V,3]");
+    TORCH_CHECK(faces.is_cuda() && faces.dim() == 2 && faces.size(1) == 3 && faces.scalar_type() == at::kInt && faces.is_contiguous() &&
+                faces.device() == vertices.device(), "mesh_raster: faces must be a contiguous int32 tensor [T,3] on vertices' device");
+    TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= BE_RASTER_MAX_SIZE && Wo <= BE_RASTER_MAX_SIZE, "mesh_raster: size must be in [1, ", BE_RASTER_MAX_SIZE, "]");
+    const int64_t V = vertices.size(0), T = faces.size(0);
+    auto given = [&](const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); };
+    const bool has_w = given(weight), has_f = given(feat), has_n = given(normal), has_nv = given(normal_valid);
+    if (has_w) TORCH_CHECK(weight->dim() == 1 && weight->size(0) == V && weight->device() == vertices.device(), "mesh_raster: weight [V] on vertices' device");
+    if (has_f) TORCH_CHECK(feat->dim() == 2 && feat->size(1) == V && feat->device() == vertices.device(), "mesh_raster: feat [C,V] on vertices' device");
+    if (has_n) TORCH_CHECK(normal->dim() == 2 && normal->size(0) == V && normal->size(1) == 3 && normal->device() == vertices.device(),
+                           "mesh_raster: normal [V,3] on vertices' device");
+    TORCH_CHECK(!has_nv || has_n, "mesh_raster: normal_valid needs normal");
+    if (has_nv) TORCH_CHECK(normal_valid->is_cuda() && normal_valid->dim() == 1 && normal_valid->size(0) == V && normal_valid->scalar_type() == at::kBool &&
+                            normal_valid->is_contiguous() && normal_valid->device() == vertices.device(),
+                            "mesh_raster: normal_valid must be a contiguous bool tensor [V] on vertices' device");
+    const int64_t C = has_f ? feat->size(0) : 0;
+    auto of = vertices.options();
+    Tensor depth = at::empty({Ho, Wo}, of), face = at::empty({Ho, Wo}, of.dtype(at::kInt));
+    Tensor wout = at::empty({has_w ? Ho : 0, has_w ? Wo : 0}, of), fout = at::empty({C, has_f ? Ho : 0, has_f ? Wo : 0}, of);
+    Tensor nout = at::empty({has_n ? 3 : 0, has_n ? Ho : 0, has_n ? Wo : 0}, of);
+    Tensor nvout = at::empty({has_n ? Ho : 0, has_n ? Wo : 0}, of.dtype(at::kBool));
+    Tensor bary = at::empty({want_bary ? 3 : 0, want_bary ? Ho : 0, want_bary ? Wo : 0}, of);
+    const size_t bytes = be_mesh_raster_workspace_bytes(V, (int)Ho, (int)Wo);
+    TORCH_CHECK(bytes > 0, "mesh_raster: at most 2^31 - 1 vertices");
+    Tensor ws = at::empty({(int64_t)((bytes + 15) / 16), 2}, of.dtype(at::kLong));
+    check(be_mesh_raster_f32(vertices.data_ptr<float>(), V, faces.data_ptr<int32_t>(), T, has_w ? fp(*weight, "mesh_raster(weight)") : nullptr,
+                             has_f && C > 0 ? fp(*feat, "mesh_raster(feat)") : nullptr, (int)C, has_n ? fp(*normal, "mesh_raster(normal)") : nullptr,
+                             has_nv ? reinterpret_cast<const uint8_t*>(normal_valid->data_ptr<bool>()) : nullptr,
+                             host_floats(cam_dst, 4, "mesh_raster(cam_dst)"), host_floats(pose, 12, "mesh_raster(pose)"), (float)near, (int)cull,
+                             (int)Ho, (int)Wo, depth.data_ptr<float>(), face.data_ptr<int32_t>(), has_w ? wout.data_ptr<float>() : nullptr,
+                             has_f && C > 0 ? fout.data_ptr<float>() : nullptr, has_n ? nout.data_ptr<float>() : nullptr,
+                             has_n ? reinterpret_cast<uint8_t*>(nvout.data_ptr<bool>()) : nullptr, want_bary ? bary.data_ptr<float>() : nullptr,
+                             ws.data_ptr<int64_t>(), bytes, stream_of(vertices)), "be_mesh_raster_f32");
+    return {depth, face, wout, fout, nout, nvout, bary};
+}
+
 // depth registration: normal [3,H,W] of depth [H,W]; cam [4] a CPU float32 tensor as for unproject
 Tensor depth_normals(const Tensor& depth, const Tensor& cam, int64_t step, double max_jump, int64_t scale, int64_t top, int64_t left) {
     TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "depth_normals: depth [H,W], 1 .. 2^31 - 1 samples");
@@ -1034,6 +1078,8 @@ TORCH_LIBRARY(be, m) {
     m.def("tsdf_mean(Tensor sw, Tensor swd, Tensor swf) -> (Tensor, Tensor, Tensor)");
     m.def("exclusive_scan(Tensor counts) -> (Tensor, Tensor)");
     m.def("tsdf_mesh(Tensor D, Tensor W, Tensor Fm, Tensor origin, Tensor voxel, float min_weight, bool normals) -> Tensor[]");
+    m.def("mesh_raster(Tensor vertices, Tensor faces, Tensor? weight, Tensor? feat, Tensor? normal, Tensor? normal_valid, Tensor cam_dst, "
+          "Tensor pose, float near, int cull, int Ho, int Wo, bool want_bary) -> Tensor[]");
     m.def("tsdf_raycast(Tensor D, Tensor W, Tensor Fm, Tensor origin, Tensor voxel, Tensor cam_dst, Tensor pose, int Ho, int Wo, float z_near, "
           "float step, int n) -> (Tensor, Tensor, Tensor)");
     m.def("depth_normals(Tensor depth, Tensor cam, int step, float max_jump, int scale, int top, int left) -> Tensor");
@@ -1107,6 +1153,7 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("tsdf_raycast", tsdf_raycast);
     m.impl("exclusive_scan", exclusive_scan);
     m.impl("tsdf_mesh", tsdf_mesh);
+    m.impl("mesh_raster", mesh_raster);
     m.impl("depth_normals", depth_normals);
     m.impl("icp_linearize", icp_linearize);
     m.impl("fill_nearest", fill_nearest);

@@ -365,6 +365,36 @@ int be_tsdf_mesh_emit_f32(const float* D, const float* W, const float* Fm, int C
                           int64_t T, float* vertices, int32_t* faces, float* weight, float* feat, float* normal, uint8_t* normal_valid,
                           int64_t* edge, void* stream);
 
+/* A z-buffered triangle rasteriser: the mesh (vertices [V,3] = X, Y, Z, faces [T,3] int32) seen by camera cam_dst (fy, fx, cy, cx)
+ * of Ho x Wo pixels under pose = the 12 numbers (row-major R, then t) that map the MESH's frame to the CAMERA's.  be_hip/raster.py
+ * is the statement - every float operation, the integer coverage rule, the key - and the kernels equal it bit for bit.
+ *   vertex:   Xc = ((r0 X + r1 Y) + r2 Z) + t0 (Yc, Zc likewise), u = (fx Xc) / Zc + cx, v = (fy Yc) / Zc + cy,
+ *             xs = floorf(u * BE_RASTER_SUB + 0.5f), ys likewise, q = 1 / Zc; usable iff near < Zc < inf and |xs|, |ys| <=
+ *             BE_RASTER_GUARD (NaN fails).  A triangle with a vertex that is not usable is dropped whole: nothing is clipped.
+ *   triangle: A = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) in int64; A == 0 is dropped; the triangle faces the camera iff A < 0;
+ *             cull 0 keeps both, 1 drops A > 0 (back faces), 2 drops A < 0; A < 0 exchanges vertices 1 and 2.  E_i = the edge
+ *             function of the edge opposite vertex i at (BE_RASTER_SUB x, BE_RASTER_SUB y); pixel (y, x) is inside iff every
+ *             E_i > 0, or E_i == 0 on a top or left edge (dy < 0, or dy == 0 and dx > 0).
+ *   depth:    w_i = (float) E_i / (float) A, iz = (w0 q0 + w1 q1) + w2 q2, z = 1 / iz; a fragment iff inside and 0 < z < inf.
+ *   z-buffer: the unsigned minimum of (bits of z) << 32 | face index: the nearest surface, the lowest face index on a tie.
+ *   resolve:  l_i = (w_i q_i) * z; an attribute is (l0 a0 + l1 a1) + l2 a2; the normal is interpolated, rotated by R and divided
+ *             by its length l = sqrtf((mx mx + my my) + mz mz), valid iff the three vertices' normal_valid and 0 < l < inf.
+ * depth_out [Ho,Wo], face_out [Ho,Wo] int32 (-1: nothing landed) always; weight_out [Ho,Wo] of weight [V], feat_out [C,Ho*Wo] of
+ * feat [C,V], normal_out [3,Ho*Wo] and normal_valid_out [Ho,Wo] uint8 of normal [V,3] and normal_valid [V] uint8 (NULL: all valid),
+ * bary_out [3,Ho*Wo] = l in the face's own vertex order: each NULL when not wanted; +0 where nothing landed.  A face whose index
+ * lies outside [0, V) is dropped.  workspace: 16-byte aligned, be_mesh_raster_workspace_bytes(V, Ho, Wo) bytes (0: bad arguments).
+ * Three kernels and a memset on `stream`: one thread per vertex, one wave per triangle (8 x 8 pixel blocks, one 64-bit atomic
+ * minimum per fragment), one thread per pixel; every output element is written exactly once; nothing synchronises with the host;
+ * a repeated run gives the same bits.  0 <= V, T < 2^31; 1 <= Ho, Wo <= BE_RASTER_MAX_SIZE; 0 <= C <= BE_FUSE_MAX_CHANNELS. */
+#define BE_RASTER_SUB 256
+#define BE_RASTER_GUARD 4194304
+#define BE_RASTER_MAX_SIZE 16384
+size_t be_mesh_raster_workspace_bytes(int64_t V, int Ho, int Wo);
+int be_mesh_raster_f32(const float* vertices, int64_t V, const int32_t* faces, int64_t T, const float* weight, const float* feat, int C,
+                       const float* normal, const uint8_t* normal_valid, const float* cam_dst, const float* pose, float near, int cull,
+                       int Ho, int Wo, float* depth_out, int32_t* face_out, float* weight_out, float* feat_out, float* normal_out,
+                       uint8_t* normal_valid_out, float* bary_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Depth registration: the two kernels of a point-to-plane ICP on depth maps; the loop around them is be_hip/registration.py.
  * Lattice, camera and pose arguments are be_reproject_f32's; all per-sample arithmetic is fp32, one rounding per operation.
  *
