@@ -111,6 +111,33 @@ def as_pose(p, who="pose"):
     raise ValueError(f"{who}: expected 12 numbers (R row-major, then t), a 3x4 or a 4x4 matrix, got shape {a.shape}")
 
 
+def check_size(who, size, max_side, wording, max_pixels=None):
+    """size = (Ho, Wo) of a target image -> (Ho, Wo) as ints: whole numbers (no bools) in [1, max_side] whose product is at most
+    max_pixels (None: no bound).  `wording` is the sentence of the refusal, "size must be (Ho, Wo), ..": the caller states its bound."""
+    try:
+        Ho, Wo = size
+        ok = all(not isinstance(v, bool) and int(v) == v and 1 <= v <= max_side for v in (Ho, Wo))
+        ok = ok and (max_pixels is None or Ho * Wo <= max_pixels)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{who}: {wording}, got {size!r}")
+    return int(Ho), int(Wo)
+
+
+def check_number(who, name, v, lo=0.0, hi=np.inf, lo_open=False, hi_closed=False):
+    """v -> float(v), a finite number with lo <= v < hi (lo_open: lo < v; hi_closed: v <= hi); anything else - a string, None, NaN,
+    an infinity - is refused as "{who}: {name} must be a finite number >= {lo}"."""
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        v = np.nan
+    if not (lo < v if lo_open else lo <= v) or not (v <= hi if hi_closed else v < hi) or v == np.inf:   # NaN fails
+        raise ValueError(f"{who}: {name} must be a finite number {'>' if lo_open else '>='} {lo:g}"
+                         + ("" if hi == np.inf else f" and {'<=' if hi_closed else '<'} {hi:g}"))
+    return v
+
+
 def _geometry(dtype, cam_src, cam_dst, pose12):
     s = np.asarray(as_pinhole(cam_src).f32(), dtype)
     d = np.asarray(as_pinhole(cam_dst).f32(), dtype)

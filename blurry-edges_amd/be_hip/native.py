@@ -1328,16 +1328,99 @@ def fold_refocus_stack_points(opts, consts, records, rho_primes, H, W, points, h
     return out.view((len(vals), 3) + lead)
 
 
+# ---- the geometry entries (unproject .. fill_diffuse): one statement per kind of argument.  A new entry starts from these; the numbers
+# that need no torch (check_size, check_number) sit in camera.py beside as_pinhole / as_pose.  The tensor checks take CPU tensors too,
+# except _depth_map's on_gpu: tests/test_geometry_args_cpu.py runs every one of them without a GPU.
+TARGET_MAX_SIDE, TARGET_MAX_PIXELS = 1 << 24, 0x7fffffff                # a target image: float32 holds its coordinates, int32 its pixel indices
+
+
+def _got(t):
+    return f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}"
+
+
+def _target_size(who, size):
+    """size -> (Ho, Wo) of the image a splatting or ray-casting entry writes (raster.check_params states the rasteriser's own bound)."""
+    from . import camera
+    return camera.check_size(who, size, TARGET_MAX_SIDE, "size must be (Ho, Wo), integers >= 1 with Ho * Wo < 2^31", TARGET_MAX_PIXELS)
+
+
+def _near(who, near):
+    """near -> float, or "{who}: near must be a finite number >= 0"."""
+    from . import camera
+    return camera.check_number(who, "near", near)
+
+
+def _depth_map(who, depth, statement, dims="[Hs,Ws]", on_gpu=True):
+    """A depth map: a float32 tensor [H,W] with at least one sample, on the GPU -> depth.  `statement` names the host statement."""
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 2 or depth.numel() == 0:
+        raise ValueError(f"{who}: depth must be a float32 tensor {dims}, got {_got(depth)}")
+    if on_gpu and not depth.is_cuda:
+        raise ValueError(f"{who}: depth is not on the GPU; nothing here computes on the CPU ({statement} is the host statement)")
+    return depth
+
+
+def _map_like(who, name, t, depth, dtypes=(torch.float32,), kind="a float32"):
+    """An optional map on the samples of depth (weight, edge): one of `dtypes`, depth's shape, on depth's device -> float32 and
+    contiguous (a bool mask becomes 1 / 0); None stays None."""
+    if t is None:
+        return None
+    H, W = depth.shape
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or tuple(t.shape) != (H, W):
+        raise ValueError(f"{who}: {name} must be {kind} tensor [{H},{W}], got {_got(t)}")
+    if t.device != depth.device:
+        raise ValueError(f"{who}: {name} is on {t.device}, depth on {depth.device}")
+    return t.to(torch.float32).contiguous()
+
+
+def _channels(who, name, t, depth, C=None, required=False):
+    """Channels that ride on the samples of depth (feat; normal_d: C=3, required): float32 [C,Hs,Ws] or [C,Hs*Ws] on depth's device
+    -> [C,Hs*Ws] contiguous; None stays None unless required."""
+    if t is None and not required:
+        return None
+    Hs, Ws = depth.shape
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (2, 3) or (C is not None and t.shape[0] != C)
+            or tuple(t.shape[1:]) not in ((Hs, Ws), (Hs * Ws,))):
+        raise ValueError(f"{who}: {name} must be a float32 tensor [{C or 'C'},{Hs},{Ws}] or [{C or 'C'},{Hs * Ws}], got {_got(t)}")
+    if t.device != depth.device:
+        raise ValueError(f"{who}: {name} is on {t.device}, depth on {depth.device}")
+    return t.reshape(t.shape[0], Hs * Ws).contiguous()
+
+
+def view_list(who, views, of):
+    """views -> list(views), or "{who}: views must be a list of {of}" for what cannot be iterated."""
+    try:
+        return list(views)
+    except TypeError:
+        raise ValueError(f"{who}: views must be a list of {of}, got {type(views).__name__}") from None
+
+
+def _new(dev):
+    """The allocator of the ctypes arms: new(*shape, dtype=float32) -> an uninitialised tensor on dev."""
+    return lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+
+
+def _view(who, v, keys, cam_key, dev=None, whose=None):
+    """One view dict (fuse_views / tsdf_integrate: FUSE_VIEW_KEYS, "cam_src"; icp_linearize / register_depth: ICP_VIEW_KEYS, "cam"),
+    validated -> (depth [Hs,Ws], weight [Hs,Ws] or None, feat [C,Hs*Ws] or None, camera float32 [4], pose float32 [12], scale, top,
+    left), every tensor contiguous on one device - `dev`, which belongs to `whose`, when given."""
+    if not isinstance(v, dict) or "depth" not in v or cam_key not in v:
+        raise ValueError(f"{who}: a view is a dict with the keys {keys} (depth and {cam_key} at least)")
+    unknown = [k for k in v if k not in keys]
+    if unknown:
+        raise ValueError(f"{who}: unknown keys {unknown}; a view holds {keys}")
+    scale = v.get("scale", 1)
+    depth, (cs,), p12, top, left = _reproject_args(who, v["depth"], [(cam_key, v[cam_key])], v.get("pose"), scale, v.get("window_origin", (0, 0)))
+    if dev is not None and depth.device != dev:
+        raise ValueError(f"{who}: depth is on {depth.device}, {whose} on {dev}")
+    return depth, _map_like(who, "weight", v.get("weight"), depth), _channels(who, "feat", v.get("feat"), depth), cs, p12, scale, top, left
+
+
 def _reproject_args(who, depth, cams, pose, scale, window_origin):
     """The host side unproject and reproject share, before the library is touched: depth [Hs,Ws] float32 on the GPU, the cameras
     (camera.Pinhole, (fy, fx, cy, cx) or a 3x3 K) and the pose (camera.as_pose) as float32 numpy, scale in 1..16, the window
     origin.  -> (depth, [camera float32 [4]], pose float32 [12], top, left)."""
     from . import camera, tiling
-    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 2 or depth.numel() == 0:
-        raise ValueError(f"{who}: depth must be a float32 tensor [Hs,Ws], got "
-                         f"{getattr(depth, 'dtype', type(depth).__name__)} {tuple(getattr(depth, 'shape', ()))}")
-    if not depth.is_cuda:
-        raise ValueError(f"{who}: depth is not on the GPU; nothing here computes on the CPU (camera.splat_f32 is the host statement)")
+    _depth_map(who, depth, "camera.splat_f32")
     if depth.numel() > 0x7fffffff:
         raise ValueError(f"{who}: {depth.numel()} source samples; at most 2^31 - 1 (the index map is int32)")
     if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= tiling.MAX_SCALE:
@@ -1381,41 +1464,21 @@ def reproject(depth, cam_src, cam_dst, pose, size, feat=None, near=1e-3, scale=1
     on the order of execution; camera.splat_f32 is the host statement, bit for bit."""
     depth, (cs, cd), p12, top, left = _reproject_args("reproject", depth, [("cam_src", cam_src), ("cam_dst", cam_dst)], pose, scale,
                                                       window_origin)
-    try:
-        Ho, Wo = size
-        ok = all(not isinstance(v, bool) and int(v) == v and 1 <= v <= 1 << 24 for v in (Ho, Wo)) and Ho * Wo <= 0x7fffffff
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"reproject: size must be (Ho, Wo), integers >= 1 with Ho * Wo < 2^31, got {size!r}")
-    Ho, Wo = int(Ho), int(Wo)
-    try:
-        near = float(near)
-    except (TypeError, ValueError):
-        near = -1.0
-    if not 0 <= near < float("inf"):
-        raise ValueError("reproject: near must be a finite number >= 0")
+    Ho, Wo = _target_size("reproject", size)
+    near = _near("reproject", near)
     Hs, Ws = depth.shape
     dev = depth.device
-    if feat is not None:
-        if (not isinstance(feat, torch.Tensor) or feat.dtype != torch.float32 or feat.dim() not in (2, 3)
-                or tuple(feat.shape[1:]) not in ((Hs, Ws), (Hs * Ws,))):
-            raise ValueError(f"reproject: feat must be a float32 tensor [C,{Hs},{Ws}] or [C,{Hs * Ws}], got "
-                             f"{getattr(feat, 'dtype', type(feat).__name__)} {tuple(getattr(feat, 'shape', ()))}")
-        if feat.device != dev:
-            raise ValueError(f"reproject: feat is on {feat.device}, depth on {dev}")
-        feat = feat.reshape(feat.shape[0], Hs * Ws).contiguous()
+    feat = _channels("reproject", "feat", feat, depth)
     o = ops()
     if o is not None:
         d, index, f = o.reproject(depth, torch.from_numpy(cs), torch.from_numpy(cd), torch.from_numpy(p12), near, Ho, Wo, feat, scale,
                                   top, left)
         f = f if feat is not None else None
     else:
-        zbuf = torch.empty(Ho * Wo, dtype=torch.int64, device=dev)
-        d = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
-        index = torch.empty(Ho, Wo, dtype=torch.int32, device=dev)
+        new = _new(dev)
+        zbuf, d, index = new(Ho * Wo, dtype=torch.int64), new(Ho, Wo), new(Ho, Wo, dtype=torch.int32)
         C_ = 0 if feat is None else feat.shape[0]
-        f = None if feat is None else torch.empty(C_, Ho, Wo, dtype=torch.float32, device=dev)
+        f = None if feat is None else new(C_, Ho, Wo)
         check(lib().be_reproject_f32(dptr(depth, "depth", (torch.float32,)), Hs, Ws, scale, top, left, _fptr(cs), _fptr(cd), _fptr(p12),
                                      near, Ho, Wo, dptr(feat if C_ else None), C_, dptr(zbuf, "zbuf", (torch.int64,)), dptr(d),
                                      dptr(index), dptr(f if C_ else None), stream_ptr(dev)), "be_reproject_f32")
@@ -1423,40 +1486,6 @@ def reproject(depth, cam_src, cam_dst, pose, size, feat=None, near=1e-3, scale=1
 
 
 FUSE_VIEW_KEYS = ("depth", "weight", "feat", "cam_src", "pose", "scale", "window_origin")
-
-
-def _fuse_view(who, v, dev, whose):
-    """One view dict of fuse_views / tsdf_integrate, validated -> (depth [Hs,Ws], weight [Hs,Ws] or None, feat [C,Hs*Ws] or None,
-    camera float32 [4], pose float32 [12], scale, top, left), every tensor contiguous on `dev` (None: the depth's own device)."""
-    if not isinstance(v, dict) or "depth" not in v or "cam_src" not in v:
-        raise ValueError(f"{who}: a view is a dict with the keys {FUSE_VIEW_KEYS} (depth and cam_src at least)")
-    unknown = [k for k in v if k not in FUSE_VIEW_KEYS]
-    if unknown:
-        raise ValueError(f"{who}: unknown keys {unknown}; a view holds {FUSE_VIEW_KEYS}")
-    depth, (cs,), p12, top, left = _reproject_args(who, v["depth"], [("cam_src", v["cam_src"])], v.get("pose"), v.get("scale", 1),
-                                                   v.get("window_origin", (0, 0)))
-    Hs, Ws = depth.shape
-    dev = depth.device if dev is None else dev
-    if depth.device != dev:
-        raise ValueError(f"{who}: depth is on {depth.device}, {whose} on {dev}")
-    w = v.get("weight")
-    if w is not None:
-        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != (Hs, Ws):
-            raise ValueError(f"{who}: weight must be a float32 tensor [{Hs},{Ws}], got "
-                             f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}")
-        if w.device != dev:
-            raise ValueError(f"{who}: weight is on {w.device}, depth on {dev}")
-        w = w.contiguous()
-    f = v.get("feat")
-    if f is not None:
-        if (not isinstance(f, torch.Tensor) or f.dtype != torch.float32 or f.dim() not in (2, 3)
-                or tuple(f.shape[1:]) not in ((Hs, Ws), (Hs * Ws,))):
-            raise ValueError(f"{who}: feat must be a float32 tensor [C,{Hs},{Ws}] or [C,{Hs * Ws}], got "
-                             f"{getattr(f, 'dtype', type(f).__name__)} {tuple(getattr(f, 'shape', ()))}")
-        if f.device != dev:
-            raise ValueError(f"{who}: feat is on {f.device}, depth on {dev}")
-        f = f.reshape(f.shape[0], Hs * Ws).contiguous()
-    return depth, w, f, cs, p12, v.get("scale", 1), top, left
 
 
 def fuse_views(views, cam_dst, size, tau=0.05, min_views=1, recentre=True, peel=0, near=1e-3):
@@ -1477,33 +1506,16 @@ def fuse_views(views, cam_dst, size, tau=0.05, min_views=1, recentre=True, peel=
     exact while fewer than 2^16 samples agree on one pixel.  Nothing synchronises with the host.  fusion.fuse is the host
     statement, bit for bit; with tau=0, recentre=False, peel=0 and one view depth and valid are reproject's."""
     from . import camera, fusion
-    try:
-        views = list(views)
-    except TypeError:
-        raise ValueError(f"fuse_views: views must be a list of dicts with the keys {FUSE_VIEW_KEYS}, got {type(views).__name__}") from None
+    views = view_list("fuse_views", views, f"dicts with the keys {FUSE_VIEW_KEYS}")
     tau, min_views, recentre, peel = fusion.check_params("fuse_views", len(views), tau, min_views, recentre, peel)
-    try:
-        Ho, Wo = size
-        ok = all(not isinstance(v, bool) and int(v) == v and 1 <= v <= 1 << 24 for v in (Ho, Wo)) and Ho * Wo <= 0x7fffffff
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"fuse_views: size must be (Ho, Wo), integers >= 1 with Ho * Wo < 2^31, got {size!r}")
-    Ho, Wo = int(Ho), int(Wo)
-    try:
-        near = float(near)
-    except (TypeError, ValueError):
-        near = -1.0
-    if not 0 <= near < float("inf"):
-        raise ValueError("fuse_views: near must be a finite number >= 0")
+    Ho, Wo = _target_size("fuse_views", size)
+    near = _near("fuse_views", near)
     cd = camera.as_pinhole(cam_dst, "fuse_views(cam_dst)").f32()
-    depths, weights, feats, cams, poses, scales, tops, lefts = [], [], [], [], [], [], [], []
-    dev = None
+    checked, dev = [], None
     for i, v in enumerate(views):
-        depth, w, f, cs, p12, scale, top, left = _fuse_view(f"fuse_views(views[{i}])", v, dev, "the first view's")
-        dev = depth.device
-        depths.append(depth); weights.append(w); feats.append(f); cams.append(cs); poses.append(p12)
-        scales.append(scale); tops.append(top); lefts.append(left)
+        checked.append(_view(f"fuse_views(views[{i}])", v, FUSE_VIEW_KEYS, "cam_src", dev, "the first view's"))
+        dev = checked[0][0].device
+    depths, weights, feats, cams, poses, scales, tops, lefts = map(list, zip(*checked))
     Cs = sorted({0 if f is None else f.shape[0] for f in feats})
     if len(Cs) != 1:
         raise ValueError(f"fuse_views: every view must carry the same number of feat channels (or none), got {Cs}")
@@ -1520,11 +1532,10 @@ def fuse_views(views, cam_dst, size, tau=0.05, min_views=1, recentre=True, peel=
                                                         torch.from_numpy(cam_all), torch.from_numpy(pose_all), torch.from_numpy(cd), near, Ho, Wo,
                                                         scales, tops, lefts, tau, min_views, recentre, peel)
     else:
-        scratch = torch.empty(lib().be_fuse_scratch_bytes(Ho, Wo, C_) // 8 + 1, dtype=torch.int64, device=dev)
-        d = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
-        wsum = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
-        nviews, count, layer = (torch.empty(Ho, Wo, dtype=torch.int32, device=dev) for _ in range(3))
-        f = torch.empty(C_, Ho, Wo, dtype=torch.float32, device=dev)
+        new = _new(dev)
+        scratch = new(lib().be_fuse_scratch_bytes(Ho, Wo, C_) // 8 + 1, dtype=torch.int64)
+        d, wsum, f = new(Ho, Wo), new(Ho, Wo), new(C_, Ho, Wo)
+        nviews, count, layer = (new(Ho, Wo, dtype=torch.int32) for _ in range(3))
         ptrs = lambda ts: (C.c_void_p * V)(*[None if t is None else t.data_ptr() for t in ts])
         ints = lambda xs: (C.c_int * V)(*xs)
         check(lib().be_fuse_views_f32(V, ptrs(depths), ptrs(weights), ptrs(feats) if C_ else None, C_, ints([t.shape[0] for t in depths]),
@@ -1579,21 +1590,13 @@ def tsdf_integrate(volume, views, near=1e-3):
     sums depend neither on the order of the views nor on how they are grouped into calls; exact below 2^19 views.  Nothing
     synchronises with the host.  volume.integrate is the host statement, bit for bit."""
     dims, origin, voxel = _tsdf_state("tsdf_integrate", volume)
-    try:
-        views = list(views)
-    except TypeError:
-        raise ValueError(f"tsdf_integrate: views must be a list of dicts with the keys {FUSE_VIEW_KEYS}, got {type(views).__name__}") from None
-    try:
-        near = float(near)
-    except (TypeError, ValueError):
-        near = -1.0
-    if not 0 <= near < float("inf"):
-        raise ValueError("tsdf_integrate: near must be a finite number >= 0")
+    views = view_list("tsdf_integrate", views, f"dicts with the keys {FUSE_VIEW_KEYS}")
+    near = _near("tsdf_integrate", near)
     dev = volume.sw.device
     checked = []
     for i, v in enumerate(views):
         who = f"tsdf_integrate(views[{i}])"
-        item = _fuse_view(who, v, dev, "the volume")
+        item = _view(who, v, FUSE_VIEW_KEYS, "cam_src", dev, "the volume")
         if (0 if item[2] is None else item[2].shape[0]) != volume.C:
             raise ValueError(f"{who}: feat holds {0 if item[2] is None else item[2].shape[0]} channels, the volume {volume.C}")
         checked.append(item)
@@ -1641,14 +1644,7 @@ def tsdf_raycast(volume, cam_dst, pose, size, z_range, step=None, normals=False,
     then the ray cast; nothing synchronises with the host.  volume.raycast is the host statement, bit for bit."""
     from . import camera, volume as volume_
     dims, origin, voxel = _tsdf_state("tsdf_raycast", volume)
-    try:
-        Ho, Wo = size
-        ok = all(not isinstance(v, bool) and int(v) == v and 1 <= v <= 1 << 24 for v in (Ho, Wo)) and Ho * Wo <= 0x7fffffff
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"tsdf_raycast: size must be (Ho, Wo), integers >= 1 with Ho * Wo < 2^31, got {size!r}")
-    Ho, Wo = int(Ho), int(Wo)
+    Ho, Wo = _target_size("tsdf_raycast", size)
     z_near, _, step, n = volume_.check_raycast("tsdf_raycast", z_range, step, volume.trunc)
     cd = camera.as_pinhole(cam_dst, "tsdf_raycast(cam_dst)").f32()
     p12 = camera.as_pose(pose, "tsdf_raycast(pose)")
@@ -1659,9 +1655,8 @@ def tsdf_raycast(volume, cam_dst, pose, size, z_range, step=None, normals=False,
         d, w, f = o.tsdf_raycast(D, W, Fm, torch.from_numpy(origin), torch.from_numpy(voxel), torch.from_numpy(cd), torch.from_numpy(p12),
                                  Ho, Wo, z_near, step, n)
     else:
-        d = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
-        w = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
-        f = torch.empty(volume.C, Ho, Wo, dtype=torch.float32, device=dev)
+        new = _new(dev)
+        d, w, f = new(Ho, Wo), new(Ho, Wo), new(volume.C, Ho, Wo)
         check(lib().be_tsdf_raycast_f32(dptr(D), dptr(W), dptr(Fm if volume.C else None), volume.C, _iptr(dims), _fptr(origin), _fptr(voxel),
                                         _fptr(cd), _fptr(p12), Ho, Wo, z_near, step, n, dptr(d), dptr(w), dptr(f if volume.C else None),
                                         stream_ptr(dev)), "be_tsdf_raycast_f32")
@@ -1813,7 +1808,7 @@ def raster_mesh(mesh, cam_dst, pose, size, near=1e-3, cull="none", want=("feat",
         d, face, w, f, nrm, nv, b = o.mesh_raster(m["vertices"], m["faces"], weight, feat, normal, nvalid, torch.from_numpy(cd),
                                                   torch.from_numpy(q12), near, cull, Ho, Wo, bary)
     else:
-        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+        new = _new(dev)
         d, face = new(Ho, Wo), new(Ho, Wo, dtype=torch.int32)
         w = new(Ho, Wo) if weight is not None else None
         f = new(C_, Ho, Wo) if feat is not None else None
@@ -1856,28 +1851,6 @@ def depth_normals(depth, cam, step=3, max_jump=0.05, scale=1, window_origin=(0, 
 ICP_VIEW_KEYS = ("depth", "weight", "cam", "scale", "window_origin")
 
 
-def _icp_view(who, v, dev=None):
-    """One view of icp_linearize / register_depth -> (depth, weight or None, camera float32 [4], scale, top, left)."""
-    if not isinstance(v, dict) or "depth" not in v or "cam" not in v:
-        raise ValueError(f"{who}: a view is a dict with the keys {ICP_VIEW_KEYS} (depth and cam at least)")
-    unknown = [k for k in v if k not in ICP_VIEW_KEYS]
-    if unknown:
-        raise ValueError(f"{who}: unknown keys {unknown}; a view holds {ICP_VIEW_KEYS}")
-    scale = v.get("scale", 1)
-    depth, (cs,), _, top, left = _reproject_args(who, v["depth"], [("cam", v["cam"])], None, scale, v.get("window_origin", (0, 0)))
-    if dev is not None and depth.device != dev:
-        raise ValueError(f"{who}: depth is on {depth.device}, the source's on {dev}")
-    w = v.get("weight")
-    if w is not None:
-        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != tuple(depth.shape):
-            raise ValueError(f"{who}: weight must be a float32 tensor [{depth.shape[0]},{depth.shape[1]}], got "
-                             f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}")
-        if w.device != depth.device:
-            raise ValueError(f"{who}: weight is on {w.device}, depth on {depth.device}")
-        w = w.contiguous()
-    return depth, w, cs, scale, top, left
-
-
 def icp_linearize(src, dst, normal_d, pose, near=1e-3, max_dist=0.1, huber=0.0, rows=False):
     """The linearised point-to-plane step of a depth registration at `pose` (source frame -> target frame; None: the identity).
     src, dst: dicts with the keys depth [H,W] (float32 on the GPU), weight [H,W] or None (1 everywhere), cam, scale and
@@ -1892,20 +1865,14 @@ def icp_linearize(src, dst, normal_d, pose, near=1e-3, max_dist=0.1, huber=0.0, 
     registration.linearize is the host statement, bit for bit."""
     from . import camera, registration
     near, max_dist, huber = registration.check_linearize_params("icp_linearize", near, max_dist, huber)
-    ds, ws, cs, scale, top, left = _icp_view("icp_linearize(src)", src)
+    ds, ws, _, cs, _, scale, top, left = _view("icp_linearize(src)", src, ICP_VIEW_KEYS, "cam")
     dev = ds.device
-    dd, wd, cd, dscale, dtop, dleft = _icp_view("icp_linearize(dst)", dst, dev)
+    dd, wd, _, cd, _, dscale, dtop, dleft = _view("icp_linearize(dst)", dst, ICP_VIEW_KEYS, "cam", dev, "the source's")
     if dscale != 1 or (dtop, dleft) != (0, 0):
         raise ValueError("icp_linearize(dst): the target's samples are the pixels of its camera: scale must be 1 and window_origin (0, 0)")
     Hs, Ws = ds.shape
     Hd, Wd = dd.shape
-    if (not isinstance(normal_d, torch.Tensor) or normal_d.dtype != torch.float32 or normal_d.dim() not in (2, 3)
-            or tuple(normal_d.shape) not in ((3, Hd, Wd), (3, Hd * Wd))):
-        raise ValueError(f"icp_linearize: normal_d must be a float32 tensor [3,{Hd},{Wd}], got "
-                         f"{getattr(normal_d, 'dtype', type(normal_d).__name__)} {tuple(getattr(normal_d, 'shape', ()))}")
-    if normal_d.device != dev:
-        raise ValueError(f"icp_linearize: normal_d is on {normal_d.device}, the source's depth on {dev}")
-    normal_d = normal_d.reshape(3, Hd, Wd).contiguous()
+    normal_d = _channels("icp_linearize", "normal_d", normal_d, dd, C=3, required=True).view(3, Hd, Wd)
     p12 = camera.as_pose(pose, "icp_linearize(pose)")
     rows = bool(rows)
     o = ops()
@@ -1938,8 +1905,8 @@ def register_depth(src, dst, pose0=None, **kw):
     unknown = [k for k in kw if k not in ("iters", "damping", "max_dist", "huber", "step", "max_jump", "near", "tol")]
     if unknown:
         raise ValueError(f"register_depth: unknown keywords {unknown}")
-    _icp_view("register_depth(src)", src)
-    _icp_view("register_depth(dst)", dst, src["depth"].device)
+    _view("register_depth(src)", src, ICP_VIEW_KEYS, "cam")
+    _view("register_depth(dst)", dst, ICP_VIEW_KEYS, "cam", src["depth"].device, "the source's")
 
     def normals(depth, cam, step, max_jump):
         return depth_normals(depth, cam, step=step, max_jump=max_jump)["normal"]
@@ -1955,6 +1922,21 @@ FUSE_MAX_CHANNELS = 64
 FILL_MAX_SIDE, FILL_MAX_SMOOTH = 16384, 8
 
 
+def _fill_args(who, statement, depth, weight, edge, smooth, sigma_z):
+    """What fill_nearest and fill_diffuse take alike, checked in the order both state it: depth [H,W] on the GPU with H, W <=
+    FILL_MAX_SIDE, weight (float32, or a bool mask) and edge (fill_diffuse's; None otherwise) [H,W] or None, smooth in 0..8, sigma_z
+    -> (depth, weight, edge - contiguous float32 -, smooth, sigma_z as a float)."""
+    from . import camera
+    H, W = _depth_map(who, depth, statement, "[H,W]").shape
+    if H > FILL_MAX_SIDE or W > FILL_MAX_SIDE:
+        raise ValueError(f"{who}: H and W must be at most {FILL_MAX_SIDE} (squared distances are int32), got {H} x {W}")
+    weight = _map_like(who, "weight", weight, depth, (torch.float32, torch.bool), "a float32 (or bool: a mask)")
+    edge = _map_like(who, "edge", edge, depth)
+    if isinstance(smooth, bool) or not isinstance(smooth, int) or not 0 <= smooth <= FILL_MAX_SMOOTH:
+        raise ValueError(f"{who}: smooth must be an integer in [0, {FILL_MAX_SMOOTH}], got {smooth!r}")
+    return depth.contiguous(), weight, edge, smooth, camera.check_number(who, "sigma_z", sigma_z, lo_open=True)
+
+
 def fill_nearest(depth, weight=None, smooth=2, sigma_z=0.02, fuse=True):
     """Dense depth from sparse samples: depth [H,W] float32 on the GPU, weight [H,W] (None: 1 everywhere).  A pixel is a seed iff
     its weight is > 0 and its depth a finite number > 0; every other pixel takes the depth of the seed jump flooding assigns it -
@@ -1965,40 +1947,17 @@ def fill_nearest(depth, weight=None, smooth=2, sigma_z=0.02, fuse=True):
     seed.  fuse: run the last passes (steps <= 8) as one launch over LDS tiles - the same integers either way.  The result is a
     function of the inputs alone; fill.fill_nearest_f32 is the host statement, bit for bit.  General: with depth=out["depth"],
     weight=out["valid"] (a bool mask counts as weights 1 / 0) it closes the holes of a reproject result."""
-    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 2 or depth.numel() == 0:
-        raise ValueError(f"fill_nearest: depth must be a float32 tensor [H,W], got "
-                         f"{getattr(depth, 'dtype', type(depth).__name__)} {tuple(getattr(depth, 'shape', ()))}")
-    if not depth.is_cuda:
-        raise ValueError("fill_nearest: depth is not on the GPU; nothing here computes on the CPU (fill.fill_nearest_f32 is the host statement)")
+    depth, weight, _, smooth, sigma_z = _fill_args("fill_nearest", "fill.fill_nearest_f32", depth, weight, None, smooth, sigma_z)
     H, W = depth.shape
-    if H > FILL_MAX_SIDE or W > FILL_MAX_SIDE:
-        raise ValueError(f"fill_nearest: H and W must be at most {FILL_MAX_SIDE} (squared distances are int32), got {H} x {W}")
-    if weight is not None:
-        if not isinstance(weight, torch.Tensor) or weight.dtype not in (torch.float32, torch.bool) or tuple(weight.shape) != (H, W):
-            raise ValueError(f"fill_nearest: weight must be a float32 (or bool: a mask) tensor [{H},{W}], got "
-                             f"{getattr(weight, 'dtype', type(weight).__name__)} {tuple(getattr(weight, 'shape', ()))}")
-        if weight.device != depth.device:
-            raise ValueError(f"fill_nearest: weight is on {weight.device}, depth on {depth.device}")
-        weight = weight.to(torch.float32).contiguous()
-    if isinstance(smooth, bool) or not isinstance(smooth, int) or not 0 <= smooth <= FILL_MAX_SMOOTH:
-        raise ValueError(f"fill_nearest: smooth must be an integer in [0, {FILL_MAX_SMOOTH}], got {smooth!r}")
-    try:
-        sigma_z = float(sigma_z)
-    except (TypeError, ValueError):
-        sigma_z = -1.0
-    if not 0 < sigma_z < float("inf"):
-        raise ValueError("fill_nearest: sigma_z must be a finite number > 0")
-    depth = depth.contiguous()
     fuse = bool(fuse)
     o = ops()
     if o is not None:
         d, index, dist2 = o.fill_nearest(depth, weight, smooth, sigma_z, fuse)
     else:
         dev = depth.device
-        scratch = torch.empty(3 if smooth > 0 else 2, H, W, dtype=torch.int32, device=dev)
-        d = torch.empty(H, W, dtype=torch.float32, device=dev)
-        index = torch.empty(H, W, dtype=torch.int32, device=dev)
-        dist2 = torch.empty(H, W, dtype=torch.int32, device=dev)
+        new = _new(dev)
+        scratch = new(3 if smooth > 0 else 2, H, W, dtype=torch.int32)
+        d, index, dist2 = new(H, W), new(H, W, dtype=torch.int32), new(H, W, dtype=torch.int32)
         check(lib().be_fill_nearest_f32(dptr(depth, "depth", (torch.float32,)), dptr(weight), H, W, smooth, sigma_z, int(fuse),
                                         dptr(scratch, "scratch", (torch.int32,)), dptr(d), dptr(index, "index", (torch.int32,)),
                                         dptr(dist2, "dist2", (torch.int32,)), stream_ptr(dev)), "be_fill_nearest_f32")
@@ -2021,45 +1980,12 @@ def fill_diffuse(depth, weight=None, edge=None, smooth=2, sigma_z=0.02, leak=1e-
     sweeps per level.  fuse False runs one sweep per launch (the baseline tools/bench_diffuse.py times).  The schedule depends on
     (H, W, iters) alone; nothing synchronises with the host; repeated calls give the same bits.  diffuse.fill_diffuse is the host
     statement (close, not bit-equal: the kernels contract to FMA), diffuse.solve_exact the float64 direct solve."""
-    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 2 or depth.numel() == 0:
-        raise ValueError(f"fill_diffuse: depth must be a float32 tensor [H,W], got "
-                         f"{getattr(depth, 'dtype', type(depth).__name__)} {tuple(getattr(depth, 'shape', ()))}")
-    if not depth.is_cuda:
-        raise ValueError("fill_diffuse: depth is not on the GPU; nothing here computes on the CPU (diffuse.fill_diffuse is the host statement)")
+    from . import camera
+    depth, weight, edge, smooth, sigma_z = _fill_args("fill_diffuse", "diffuse.fill_diffuse", depth, weight, edge, smooth, sigma_z)
     H, W = depth.shape
-    if H > FILL_MAX_SIDE or W > FILL_MAX_SIDE:
-        raise ValueError(f"fill_diffuse: H and W must be at most {FILL_MAX_SIDE} (squared distances are int32), got {H} x {W}")
-    if weight is not None:
-        if not isinstance(weight, torch.Tensor) or weight.dtype not in (torch.float32, torch.bool) or tuple(weight.shape) != (H, W):
-            raise ValueError(f"fill_diffuse: weight must be a float32 (or bool: a mask) tensor [{H},{W}], got "
-                             f"{getattr(weight, 'dtype', type(weight).__name__)} {tuple(getattr(weight, 'shape', ()))}")
-        if weight.device != depth.device:
-            raise ValueError(f"fill_diffuse: weight is on {weight.device}, depth on {depth.device}")
-        weight = weight.to(torch.float32).contiguous()
-    if edge is not None:
-        if not isinstance(edge, torch.Tensor) or edge.dtype != torch.float32 or tuple(edge.shape) != (H, W):
-            raise ValueError(f"fill_diffuse: edge must be a float32 tensor [{H},{W}], got "
-                             f"{getattr(edge, 'dtype', type(edge).__name__)} {tuple(getattr(edge, 'shape', ()))}")
-        if edge.device != depth.device:
-            raise ValueError(f"fill_diffuse: edge is on {edge.device}, depth on {depth.device}")
-        edge = edge.contiguous()
-    if isinstance(smooth, bool) or not isinstance(smooth, int) or not 0 <= smooth <= FILL_MAX_SMOOTH:
-        raise ValueError(f"fill_diffuse: smooth must be an integer in [0, {FILL_MAX_SMOOTH}], got {smooth!r}")
-    try:
-        sigma_z = float(sigma_z)
-    except (TypeError, ValueError):
-        sigma_z = -1.0
-    if not 0 < sigma_z < float("inf"):
-        raise ValueError("fill_diffuse: sigma_z must be a finite number > 0")
-    try:
-        leak = float(leak)
-    except (TypeError, ValueError):
-        leak = -1.0
-    if not 0 < leak <= 1:
-        raise ValueError("fill_diffuse: leak must be a number in (0, 1]")
+    leak = camera.check_number("fill_diffuse", "leak", leak, lo_open=True, hi=1, hi_closed=True)
     if iters is not None and (isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= FILL_MAX_ITERS):
         raise ValueError(f"fill_diffuse: iters must be None or an integer in [1, {FILL_MAX_ITERS}], got {iters!r}")
-    depth = depth.contiguous()
     iters = 0 if iters is None else iters
     fuse = bool(fuse)
     o = ops()
@@ -2067,11 +1993,9 @@ def fill_diffuse(depth, weight=None, edge=None, smooth=2, sigma_z=0.02, leak=1e-
         d, index, dist2, residual = o.fill_diffuse(depth, weight, edge, smooth, sigma_z, leak, iters, fuse)
     else:
         dev = depth.device
-        scratch = torch.empty(lib().be_fill_diffuse_scratch_bytes(H, W) // 4, dtype=torch.int32, device=dev)
-        d = torch.empty(H, W, dtype=torch.float32, device=dev)
-        index = torch.empty(H, W, dtype=torch.int32, device=dev)
-        dist2 = torch.empty(H, W, dtype=torch.int32, device=dev)
-        residual = torch.empty(1, dtype=torch.float32, device=dev)
+        new = _new(dev)
+        scratch = new(lib().be_fill_diffuse_scratch_bytes(H, W) // 4, dtype=torch.int32)
+        d, index, dist2, residual = new(H, W), new(H, W, dtype=torch.int32), new(H, W, dtype=torch.int32), new(1)
         check(lib().be_fill_diffuse_f32(dptr(depth, "depth", (torch.float32,)), dptr(weight), dptr(edge), H, W, smooth, sigma_z, leak, iters,
                                         int(fuse), dptr(scratch, "scratch", (torch.int32,)), dptr(d), dptr(index, "index", (torch.int32,)),
                                         dptr(dist2, "dist2", (torch.int32,)), dptr(residual), stream_ptr(dev)), "be_fill_diffuse_f32")

@@ -422,21 +422,37 @@ class DepthPipeline:
         cam_dst = cam_src if cam_dst is None else cam_dst
         size = (g["H"], g["W"]) if size is None else size
         z = src["depth_map"]
-        Ns = z.numel()
-        feat = torch.cat([src[k].reshape(-1, Ns) for k in want]) if want else None
+        feat, channels = pack_channels(src, want, z.numel())
         out = native.reproject(z, cam_src, cam_dst, pose, size, feat=feat, near=near, scale=lat["scale"],
                                window_origin=lat["window"][:2])
         res = dict(depth=out["depth"], valid=out["valid"], index=out["index"], lattice=lat)
-        c = 0
-        for k in want:
-            lead = tuple(src[k].shape[:-2])
-            n = src[k].numel() // Ns
-            res[k] = out["feat"][c:c + n].reshape(lead + tuple(out["depth"].shape))
-            c += n
+        res.update(unpack_channels(out["feat"], channels, out["depth"].shape))
         return res
 
 
     # ---- multi-view fusion: the depth of several pairs, each with its pose, merged in one camera -----------------------------
+    def _views(self, who, views, want, scale=1, depth_thres=None, source="depth_map", complete_kw=None):
+        """[(maps, pose), ..] of fuse / integrate (a list: _view_pairs) -> (the view dicts native.fuse_views and native.tsdf_integrate
+        take - the samples of _depth_samples, conf as weight, the `want`ed maps packed as feat, each view in the camera
+        dcal.intrinsics(H, W) of its own size; source="complete": complete(maps, **complete_kw)'s dense depth in place of depth_map -,
+        the first view's layout = dict(want, channels (pack_channels), camera, size))."""
+        vs, layout = [], None
+        for i, item in enumerate(views):
+            try:
+                maps, pose = item
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: views[{i}] must be (maps, pose)") from None
+            src, lat = self._depth_samples(f"{who}(views[{i}])", maps, scale, None, want + ("conf",), depth_thres)
+            g = maps["grid"]
+            cam = self.dcal.intrinsics(g["H"], g["W"])
+            z = src["depth_map"] if source == "depth_map" else self.complete(maps, **dict(complete_kw or {}))["depth_dense"]
+            feat, channels = pack_channels(src, want, z.numel())
+            if layout is None:
+                layout = dict(want=want, channels=channels, camera=cam, size=(g["H"], g["W"]))
+            vs.append(dict(depth=z, weight=src["conf"].reshape(z.shape).to(torch.float32), feat=feat, cam_src=cam, pose=pose,
+                           scale=lat["scale"], window_origin=lat["window"][:2]))
+        return vs, layout
+
     @torch.no_grad()
     def fuse(self, views, cam_dst=None, size=None, want=("shpd",), tau=0.05, min_views=1, recentre=True, peel=0, scale=1, near=1e-3,
              depth_thres=None):
@@ -453,39 +469,12 @@ class DepthPipeline:
         confirms.  Defaults: the first view's camera and size.  The result does not depend on the order of the views.  Holes are
         left open: native.fill_nearest and native.fill_diffuse, called as (out["depth"], out["weight"]), close what is left."""
         want = tuple(want)
-        try:
-            views = list(views)
-        except TypeError:
-            raise ValueError(f"fuse: views must be a list of (maps, pose), got {type(views).__name__}") from None
-        if not views:
-            raise ValueError("fuse: views must hold at least one (maps, pose)")
-        vs, srcs = [], []
-        for i, item in enumerate(views):
-            try:
-                maps, pose = item
-            except (TypeError, ValueError):
-                raise ValueError(f"fuse: views[{i}] must be (maps, pose)") from None
-            src, lat = self._depth_samples(f"fuse(views[{i}])", maps, scale, None, want + ("conf",), depth_thres)
-            g = maps["grid"]
-            cam = self.dcal.intrinsics(g["H"], g["W"])
-            if i == 0:
-                cam_dst = cam if cam_dst is None else cam_dst
-                size = (g["H"], g["W"]) if size is None else size
-            z = src["depth_map"]
-            Ns = z.numel()
-            feat = torch.cat([src[k].reshape(-1, Ns) for k in want]) if want else None
-            vs.append(dict(depth=z, weight=src["conf"].reshape(z.shape).to(torch.float32), feat=feat, cam_src=cam, pose=pose,
-                           scale=lat["scale"], window_origin=lat["window"][:2]))
-            srcs.append(src)
+        vs, layout = self._views("fuse", _view_pairs("fuse", views), want, scale, depth_thres)
+        cam_dst = layout["camera"] if cam_dst is None else cam_dst
+        size = layout["size"] if size is None else size
         out = native.fuse_views(vs, cam_dst, size, tau=tau, min_views=min_views, recentre=recentre, peel=peel, near=near)
         res = {k: out[k] for k in ("depth", "valid", "weight", "views", "count", "layer")}
-        c, src = 0, srcs[0]
-        for k in want:
-            Ns = src["depth_map"].numel()
-            lead = tuple(src[k].shape[:-2])
-            n = src[k].numel() // Ns
-            res[k] = out["feat"][c:c + n].reshape(lead + tuple(out["depth"].shape))
-            c += n
+        res.update(unpack_channels(out["feat"], layout["channels"], out["depth"].shape))
         return res
 
 
@@ -507,35 +496,14 @@ class DepthPipeline:
             raise ValueError(f"integrate: source must be 'depth_map' or 'complete', got {source!r}")
         if complete_kw and source != "complete":
             raise ValueError(f"integrate: {sorted(complete_kw)} are keywords of complete; they need source='complete'")
-        try:
-            views = list(views)
-        except TypeError:
-            raise ValueError(f"integrate: views must be a list of (maps, pose), got {type(views).__name__}") from None
-        if not views:
-            raise ValueError("integrate: views must hold at least one (maps, pose)")
+        views = _view_pairs("integrate", views)
         if volume is not None:
             if dims is not None or origin is not None or voxel is not None:
                 raise ValueError("integrate: pass either a volume or dims, origin and voxel, not both")
             want = tuple(volume.meta.get("want", want))
         elif dims is None or origin is None or voxel is None:
             raise ValueError("integrate: without a volume, dims = (Nz, Ny, Nx), origin = (X0, Y0, Z0) and voxel = (sX, sY, sZ) are needed")
-        vs, layout = [], None
-        for i, item in enumerate(views):
-            try:
-                maps, pose = item
-            except (TypeError, ValueError):
-                raise ValueError(f"integrate: views[{i}] must be (maps, pose)") from None
-            src, lat = self._depth_samples(f"integrate(views[{i}])", maps, 1, None, want + ("conf",), None)
-            g = maps["grid"]
-            cam = self.dcal.intrinsics(g["H"], g["W"])
-            z = src["depth_map"] if source == "depth_map" else self.complete(maps, **dict(complete_kw or {}))["depth_dense"]
-            Ns = z.numel()
-            feat = torch.cat([src[k].reshape(-1, Ns) for k in want]) if want else None
-            if layout is None:
-                layout = dict(want=want, channels=[(k, tuple(src[k].shape[:-2]), src[k].numel() // Ns) for k in want], camera=cam,
-                              size=(g["H"], g["W"]))
-            vs.append(dict(depth=z, weight=src["conf"].reshape(z.shape).to(torch.float32), feat=feat, cam_src=cam, pose=pose,
-                           scale=lat["scale"], window_origin=lat["window"][:2]))
+        vs, layout = self._views("integrate", views, want, source=source, complete_kw=complete_kw)
         if volume is None:
             volume = native.tsdf_volume(dims, origin, voxel, trunc, C=sum(n for _, _, n in layout["channels"]), device=vs[0]["depth"].device)
             volume.meta.update(layout)
@@ -566,10 +534,7 @@ class DepthPipeline:
             z_range = (max(min(zs), min(volume.voxel)), max(zs))
         out = native.tsdf_raycast(volume, cam_dst, pose, size, z_range, step=step, normals=normals, normals_kw=normals_kw)
         res = {k: out[k] for k in ("depth", "valid", "weight")}
-        c = 0
-        for k, lead, n in meta.get("channels", ()):
-            res[k] = out["feat"][c:c + n].reshape(lead + tuple(out["depth"].shape))
-            c += n
+        res.update(unpack_channels(out["feat"], meta.get("channels", ()), out["depth"].shape))
         if normals:
             res.update(normal=out["normal"], normal_valid=out["normal_valid"])
         return res
@@ -586,10 +551,7 @@ class DepthPipeline:
         meta = getattr(volume, "meta", None) or {}
         out = native.tsdf_mesh(volume, min_weight=min_weight, normals=normals)
         res = {k: out[k] for k in ("vertices", "faces", "weight")}
-        c = 0
-        for k, lead, n in meta.get("channels", ()):
-            res[k] = out["feat"][c:c + n].reshape(lead + (out["vertices"].shape[0],))
-            c += n
+        res.update(unpack_channels(out["feat"], meta.get("channels", ()), out["vertices"].shape[:1]))
         res.update(normal=out["normal"], normal_valid=out["normal_valid"])
         return res
 
@@ -612,25 +574,21 @@ class DepthPipeline:
             raise ValueError("render_mesh: mesh must be the dict extract_mesh returned (vertices, faces, ...)")
         want = (want,) if isinstance(want, str) else tuple(want)
         V = mesh["vertices"].shape[0]
-        parts = []
         for k in want:
             t = mesh.get(k)
             if k in ("vertices", "faces", "weight", "normal", "normal_valid", "feat") or not isinstance(t, torch.Tensor) or t.shape[-1] != V:
                 raise ValueError(f"render_mesh: want names the maps of the mesh with a last axis of {V} vertices; {k!r} is not one")
-            parts.append((k, tuple(t.shape[:-1]), t.reshape(-1, V).to(torch.float32)))
+        feat, channels = pack_channels({k: mesh[k].to(torch.float32) for k in want}, want, V, tail=1)
         if cam_dst is None:
             try:
                 cam_dst = self.dcal.intrinsics(*size)
             except TypeError:
                 raise ValueError(f"render_mesh: size must be (Ho, Wo), got {size!r}") from None
-        m = dict(vertices=mesh["vertices"], faces=mesh["faces"], weight=mesh.get("weight"), feat=torch.cat([p[2] for p in parts]) if parts else None,
+        m = dict(vertices=mesh["vertices"], faces=mesh["faces"], weight=mesh.get("weight"), feat=feat,
                  normal=mesh.get("normal") if normals else None, normal_valid=mesh.get("normal_valid") if normals else None)
         out = native.raster_mesh(m, cam_dst, pose, size, cull=cull, want=("feat", "weight") + (("normal",) if normals else ()))
         res = {k: out[k] for k in ("depth", "valid", "face", "weight")}
-        c = 0
-        for k, lead, t in parts:
-            res[k] = out["feat"][c:c + t.shape[0]].reshape(lead + tuple(out["depth"].shape))
-            c += t.shape[0]
+        res.update(unpack_channels(out["feat"], channels, out["depth"].shape))
         res.update(normal=out["normal"], normal_valid=out["normal_valid"])
         return res
 
@@ -778,6 +736,33 @@ class DepthPipeline:
         if method == "diffuse":
             res["residual"] = out["residual"]
         return res
+
+
+def pack_channels(src, want, N, tail=2):
+    """The maps src[k] [*lead, *tail] for k in `want`, N samples in the `tail` last axes (2: a lattice [Hs,Ws]; 1: vertices [V]) ->
+    (feat [C,N] - the maps flattened to channels and stacked in the order of want, None when want is empty -, channels =
+    [(k, lead, n), ..]: what unpack_channels needs to split a result again, and what volume.meta["channels"] keeps)."""
+    parts = [src[k].reshape(-1, N) for k in want]
+    channels = [(k, tuple(src[k].shape[:-tail]), p.shape[0]) for k, p in zip(want, parts)]
+    return (torch.cat(parts) if parts else None), channels
+
+
+def unpack_channels(feat, channels, tail_shape):
+    """feat [C, ..] as an entry returned it for pack_channels' feat, over samples of shape tail_shape -> {k: [*lead, *tail_shape]};
+    {} when feat is None."""
+    res, c = {}, 0
+    for k, lead, n in channels if feat is not None else ():
+        res[k] = feat[c:c + n].reshape(tuple(lead) + tuple(tail_shape))
+        c += n
+    return res
+
+
+def _view_pairs(who, views):
+    """views of fuse / integrate -> a list of at least one (maps, pose); the pairs themselves are unpacked by DepthPipeline._views."""
+    views = native.view_list(who, views, "(maps, pose)")
+    if not views:
+        raise ValueError(f"{who}: views must hold at least one (maps, pose)")
+    return views
 
 
 def _points_on(points, device, who):

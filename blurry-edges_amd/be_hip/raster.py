@@ -71,13 +71,8 @@ _CHUNK = 1 << 21                                                        # candid
 
 def check_params(who, size, near, cull, want):
     """size, near, cull and want, validated -> (Ho, Wo, near as a python float holding a float32, the cull code, want as a tuple)."""
-    try:
-        Ho, Wo = size
-        ok = all(not isinstance(v, bool) and int(v) == v and 1 <= v <= MAX_SIZE for v in (Ho, Wo))
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{who}: size must be (Ho, Wo), integers in [1, {MAX_SIZE}], got {size!r}")
+    # MAX_SIZE, not the 2^24 of the splatting entries (native.TARGET_MAX_SIDE): the rasteriser's sub-pixel integers bound the image
+    Ho, Wo = camera.check_size(who, size, MAX_SIZE, f"size must be (Ho, Wo), integers in [1, {MAX_SIZE}]")
     try:
         near = float(_F(near))
     except (TypeError, ValueError):

@@ -36,16 +36,6 @@ MAX_STEP, MAX_BLOCKS, TERMS = 8, 64, 30
 VIEW_KEYS = ("depth", "weight", "cam", "scale", "window_origin")
 
 
-def _number(who, name, v, lo=0.0, hi=np.inf, lo_open=False):
-    try:
-        v = float(v)
-    except (TypeError, ValueError):
-        v = np.nan
-    if not (lo < v if lo_open else lo <= v) or not v < hi:              # NaN fails
-        raise ValueError(f"{who}: {name} must be a finite number {'>' if lo_open else '>='} {lo:g}" + ("" if hi == np.inf else f" and < {hi:g}"))
-    return v
-
-
 def _integer(who, name, v, lo, hi):
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
         raise ValueError(f"{who}: {name} must be an integer in [{lo}, {hi}], got {v!r}")
@@ -54,18 +44,18 @@ def _integer(who, name, v, lo, hi):
 
 def check_normals_params(who, step, max_jump):
     """-> (step, max_jump as float): step an integer in 1..8, max_jump (metres per pixel of step) finite and >= 0."""
-    return _integer(who, "step", step, 1, MAX_STEP), _number(who, "max_jump", max_jump)
+    return _integer(who, "step", step, 1, MAX_STEP), camera.check_number(who, "max_jump", max_jump)
 
 
 def check_linearize_params(who, near, max_dist, huber):
     """-> (near, max_dist, huber) as floats: all finite and >= 0."""
-    return _number(who, "near", near), _number(who, "max_dist", max_dist), _number(who, "huber", huber)
+    return camera.check_number(who, "near", near), camera.check_number(who, "max_dist", max_dist), camera.check_number(who, "huber", huber)
 
 
 def check_params(who, iters, damping, max_dist, huber, step, max_jump, near, tol):
     """The parameter checks native.register_depth and this statement share -> the checked values in the same order."""
     iters = _integer(who, "iters", iters, 0, 1000)
-    damping, tol = _number(who, "damping", damping), _number(who, "tol", tol)
+    damping, tol = camera.check_number(who, "damping", damping), camera.check_number(who, "tol", tol)
     near, max_dist, huber = check_linearize_params(who, near, max_dist, huber)
     step, max_jump = check_normals_params(who, step, max_jump)
     return iters, damping, max_dist, huber, step, max_jump, near, tol

@@ -312,6 +312,14 @@ def focus_sweep(dcal, k, near, far):
     return np.linspace(dcal.focus2rho(far), dcal.focus2rho(near), k)
 
 
+def _npz_size(who, f):
+    """size = (Ho, Wo) out of a settings .npz -> two ints >= 1 (the entry that takes them states its own upper bound)."""
+    size = np.asarray(f["size"]).reshape(-1)
+    if size.shape != (2,) or not all(int(v) == v and v >= 1 for v in size):
+        raise ValueError(f"{who}: size must be (Ho, Wo), integers >= 1, got {f['size']!r}")
+    return int(size[0]), int(size[1])
+
+
 def load_camera(path):
     """The settings file of `eval --reproject`: an .npz holding K ([4] = fy, fx, cy, cx, or [3,3]), R [3,3] and t [3] (the pose from
     the depth camera's frame to this camera's; absent: the identity, zero), size = (Ho, Wo) and optionally scale (the source
@@ -321,13 +329,11 @@ def load_camera(path):
         missing = [k for k in ("K", "size") if k not in f]
         if missing:
             raise ValueError(f"--reproject: {path} lacks {missing}; it must hold K, size and optionally R, t, scale")
-        size = np.asarray(f["size"]).reshape(-1)
-        if size.shape != (2,) or not all(int(v) == v and v >= 1 for v in size):
-            raise ValueError(f"--reproject: size must be (Ho, Wo), integers >= 1, got {f['size']!r}")
+        size = _npz_size("--reproject", f)
         scale = int(np.asarray(f["scale"]).reshape(-1)[0]) if "scale" in f else 1
         return dict(cam=camera.as_pinhole(f["K"], "--reproject(K)"),
                     pose=camera.pose(f["R"] if "R" in f else None, f["t"] if "t" in f else None),
-                    size=(int(size[0]), int(size[1])), scale=scale)
+                    size=size, scale=scale)
 
 
 def load_fusion(path):
@@ -349,12 +355,7 @@ def load_fusion(path):
         if P.ndim < 2 or not 1 <= P.shape[0] <= 32 or tuple(P.shape[1:]) not in ((12,), (3, 4), (4, 4)):
             raise ValueError(f"--fuse: poses must be [V,12], [V,3,4] or [V,4,4] with 1 <= V <= 32, got {P.shape}")
         poses = [camera.as_pose(p, f"--fuse(poses[{i}])") for i, p in enumerate(P)]
-        size = None
-        if "size" in f:
-            size = np.asarray(f["size"]).reshape(-1)
-            if size.shape != (2,) or not all(int(v) == v and v >= 1 for v in size):
-                raise ValueError(f"--fuse: size must be (Ho, Wo), integers >= 1, got {f['size']!r}")
-            size = (int(size[0]), int(size[1]))
+        size = _npz_size("--fuse", f) if "size" in f else None
         one = lambda k, t: t(np.asarray(f[k]).reshape(-1)[0])
         kw = {k: one(k, t) for k, t in (("tau", float), ("min_views", int), ("peel", int), ("recentre", bool)) if k in f}
         cfg = dict(poses=poses, cam=camera.as_pinhole(f["K"], "--fuse(K)") if "K" in f else None, size=size,

@@ -598,9 +598,30 @@ static const float* host_floats(const Tensor& t, int64_t n, const char* what) {
     return t.data_ptr<float>();
 }
 
+// The three argument checks the geometry operators share (be_hip/native.py states the same three for the ctypes binding).
+// A depth map: float32 [H,W] on the GPU, contiguous, 1 .. 2^31 - 1 samples (the index maps are int32) -> its data.
+static const float* depth_map(const char* who, const Tensor& depth, const char* name = "depth", const char* dims = "[Hs,Ws]") {
+    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, who, ": ", name, " ", dims, ", 1 .. 2^31 - 1 samples");
+    return fp(depth, name);
+}
+
+// A target image of Ho x Wo pixels: sides in 1 .. 2^24, pixel indices int32.
+static void target_size(const char* who, int64_t Ho, int64_t Wo) {
+    TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= (1 << 24) && Wo <= (1 << 24) && Ho * Wo <= 0x7fffffff, who, ": bad target size");
+}
+
+static bool given(const optional<Tensor>& t) { return t.has_value() && t->defined(); }
+
+// An optional map that rides on a depth map (weight, edge): depth's sizes, on depth's device -> its data, nullptr when absent.
+static const float* map_like(const char* who, const optional<Tensor>& t, const Tensor& depth, const char* name, const char* dims = "[Hs,Ws]",
+                             const char* of = "depth") {
+    if (!given(t)) return nullptr;
+    TORCH_CHECK(t->sizes() == depth.sizes() && t->device() == depth.device(), who, ": ", name, " ", dims, " on ", of, "'s device");
+    return fp(*t, name);
+}
+
 Tensor unproject(const Tensor& depth, const Tensor& cam_src, const Tensor& pose, int64_t scale, int64_t top, int64_t left) {
-    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "unproject: depth [Hs,Ws], 1 .. 2^31 - 1 samples");
-    fp(depth, "depth");
+    depth_map("unproject", depth);
     Tensor xyz = at::empty({3, depth.size(0), depth.size(1)}, depth.options());
     check(be_unproject_f32(depth.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)scale, (int)top, (int)left,
                            host_floats(cam_src, 4, "unproject(cam_src)"), host_floats(pose, 12, "unproject(pose)"), xyz.data_ptr<float>(),
@@ -612,13 +633,12 @@ Tensor unproject(const Tensor& depth, const Tensor& cam_src, const Tensor& pose,
 std::tuple<Tensor, Tensor, Tensor> reproject(const Tensor& depth, const Tensor& cam_src, const Tensor& cam_dst, const Tensor& pose, double near,
                                              int64_t Ho, int64_t Wo, const c10::optional<Tensor>& feat, int64_t scale, int64_t top,
                                              int64_t left) {
-    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "reproject: depth [Hs,Ws], 1 .. 2^31 - 1 samples");
-    TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= (1 << 24) && Wo <= (1 << 24), "reproject: bad target size");
-    fp(depth, "depth");
+    depth_map("reproject", depth);
+    target_size("reproject", Ho, Wo);
     const int64_t Ns = depth.numel();
     int64_t C = 0;
     const float* pf = nullptr;
-    if (feat.has_value() && feat->defined()) {
+    if (given(feat)) {
         TORCH_CHECK(feat->dim() == 2 && feat->size(1) == Ns, "reproject: feat [C,Hs*Ws]");
         TORCH_CHECK(feat->device() == depth.device(), "reproject: feat and depth on one device");
         C = feat->size(0);
@@ -627,7 +647,7 @@ std::tuple<Tensor, Tensor, Tensor> reproject(const Tensor& depth, const Tensor& 
     auto o = depth.options();
     Tensor zbuf = at::empty({Ho * Wo}, o.dtype(at::kLong));
     Tensor dout = at::empty({Ho, Wo}, o), index = at::empty({Ho, Wo}, o.dtype(at::kInt));
-    Tensor fout = feat.has_value() && feat->defined() ? at::empty({C, Ho, Wo}, o) : at::empty({0}, o);
+    Tensor fout = given(feat) ? at::empty({C, Ho, Wo}, o) : at::empty({0}, o);
     check(be_reproject_f32(depth.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)scale, (int)top, (int)left,
                            host_floats(cam_src, 4, "reproject(cam_src)"), host_floats(cam_dst, 4, "reproject(cam_dst)"),
                            host_floats(pose, 12, "reproject(pose)"), (float)near, (int)Ho, (int)Wo, pf, (int)C,
@@ -648,20 +668,15 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fuse_views(at::Tensor
     TORCH_CHECK(V >= 1 && V <= BE_FUSE_MAX_VIEWS, "fuse_views: 1 .. ", BE_FUSE_MAX_VIEWS, " views");
     TORCH_CHECK((int64_t)weight.size() == V && (feat.size() == 0 || (int64_t)feat.size() == V), "fuse_views: weight and feat hold one entry per view");
     TORCH_CHECK((int64_t)scale.size() == V && (int64_t)top.size() == V && (int64_t)left.size() == V, "fuse_views: scale, top, left hold one entry per view");
-    TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= (1 << 24) && Wo <= (1 << 24), "fuse_views: bad target size");
+    target_size("fuse_views", Ho, Wo);
     const int64_t C = feat.size() == 0 ? 0 : feat[0].size(0);
     std::vector<const float*> pd(V), pw(V), pf(V);
     std::vector<int> hs(V), ws(V), sc(V), tp(V), lf(V);
     for (int64_t v = 0; v < V; ++v) {
         const Tensor& d = depth[v];
-        TORCH_CHECK(d.dim() == 2 && d.numel() > 0 && d.numel() <= 0x7fffffff, "fuse_views: depth [Hs,Ws], 1 .. 2^31 - 1 samples");
+        pd[v] = depth_map("fuse_views", d);
         TORCH_CHECK(d.device() == depth[0].device(), "fuse_views: every view on one device");
-        pd[v] = fp(d, "depth");
-        pw[v] = nullptr;
-        if (weight[v].numel() > 0) {
-            TORCH_CHECK(weight[v].sizes() == d.sizes() && weight[v].device() == d.device(), "fuse_views: weight [Hs,Ws] on depth's device");
-            pw[v] = fp(weight[v], "weight");
-        }
+        pw[v] = weight[v].numel() > 0 ? map_like("fuse_views", weight[v], d, "weight") : nullptr;     // an empty tensor: 1 everywhere
         pf[v] = nullptr;
         if (C > 0) {
             TORCH_CHECK(feat[v].dim() == 2 && feat[v].size(0) == C && feat[v].size(1) == d.numel() && feat[v].device() == d.device(),
@@ -708,18 +723,16 @@ static int64_t tsdf_sums(const Tensor& sw, const Tensor& swd, const Tensor& swf,
 void tsdf_integrate(const Tensor& depth, const c10::optional<Tensor>& weight, const c10::optional<Tensor>& feat, const Tensor& cam_src,
                     const Tensor& pose, double near, int64_t scale, int64_t top, int64_t left, const Tensor& origin, const Tensor& voxel,
                     double trunc, Tensor& sw, Tensor& swd, Tensor& swf) {
-    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "tsdf_integrate: depth [Hs,Ws], 1 .. 2^31 - 1 samples");
-    fp(depth, "depth");
+    depth_map("tsdf_integrate", depth);
     int dims[3];
     const int64_t C = tsdf_sums(sw, swd, swf, "tsdf_integrate", dims);
     TORCH_CHECK(sw.device() == depth.device(), "tsdf_integrate: the volume and depth on one device");
-    if (weight.has_value() && weight->defined())
-        TORCH_CHECK(weight->sizes() == depth.sizes() && weight->device() == depth.device(), "tsdf_integrate: weight [Hs,Ws] on depth's device");
-    const bool has_feat = feat.has_value() && feat->defined();
+    const float* pw = map_like("tsdf_integrate", weight, depth, "weight");
+    const bool has_feat = given(feat);
     TORCH_CHECK((has_feat ? feat->size(0) : 0) == C, "tsdf_integrate: feat must hold the volume's ", C, " channels");
     if (has_feat)
         TORCH_CHECK(feat->dim() == 2 && feat->size(1) == depth.numel() && feat->device() == depth.device(), "tsdf_integrate: feat [C,Hs*Ws] on depth's device");
-    check(be_tsdf_integrate_f32(depth.data_ptr<float>(), fpo(weight, "weight"), C > 0 ? fp(*feat, "feat") : nullptr, (int)C, (int)depth.size(0),
+    check(be_tsdf_integrate_f32(depth.data_ptr<float>(), pw, C > 0 ? fp(*feat, "feat") : nullptr, (int)C, (int)depth.size(0),
                                 (int)depth.size(1), (int)scale, (int)top, (int)left, host_floats(cam_src, 4, "tsdf_integrate(cam_src)"),
                                 host_floats(pose, 12, "tsdf_integrate(pose)"), (float)near, dims, host_floats(origin, 3, "tsdf_integrate(origin)"),
                                 host_floats(voxel, 3, "tsdf_integrate(voxel)"), (float)trunc, sw.data_ptr<int32_t>(), swd.data_ptr<int64_t>(),
@@ -747,7 +760,7 @@ std::tuple<Tensor, Tensor, Tensor> tsdf_raycast(const Tensor& D, const Tensor& W
     fp(W, "W");
     TORCH_CHECK(W.sizes() == D.sizes() && W.device() == D.device(), "tsdf_raycast: W [Nz,Ny,Nx] on D's device");
     TORCH_CHECK(Fm.dim() == 4 && Fm.sizes().slice(1) == D.sizes() && Fm.device() == D.device(), "tsdf_raycast: Fm [C,Nz,Ny,Nx] on D's device");
-    TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= (1 << 24) && Wo <= (1 << 24) && Ho * Wo <= 0x7fffffff, "tsdf_raycast: bad target size");
+    target_size("tsdf_raycast", Ho, Wo);
     TORCH_CHECK(n >= 1 && n <= BE_TSDF_MAX_STEPS, "tsdf_raycast: n must be in [1, ", BE_TSDF_MAX_STEPS, "]");
     const int64_t C = Fm.size(0);
     Tensor dout = at::empty({Ho, Wo}, D.options()), wout = at::empty({Ho, Wo}, D.options()), fout = at::empty({C, Ho, Wo}, D.options());
@@ -827,7 +840,6 @@ std::vector<Tensor> mesh_raster(const Tensor& vertices, const Tensor& faces, con
                 faces.device() == vertices.device(), "mesh_raster: faces must be a contiguous int32 tensor [T,3] on vertices' device");
     TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho <= BE_RASTER_MAX_SIZE && Wo <= BE_RASTER_MAX_SIZE, "mesh_raster: size must be in [1, ", BE_RASTER_MAX_SIZE, "]");
     const int64_t V = vertices.size(0), T = faces.size(0);
-    auto given = [&](const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); };
     const bool has_w = given(weight), has_f = given(feat), has_n = given(normal), has_nv = given(normal_valid);
     if (has_w) TORCH_CHECK(weight->dim() == 1 && weight->size(0) == V && weight->device() == vertices.device(), "mesh_raster: weight [V] on vertices' device");
     if (has_f) TORCH_CHECK(feat->dim() == 2 && feat->size(1) == V && feat->device() == vertices.device(), "mesh_raster: feat [C,V] on vertices' device");
@@ -860,8 +872,7 @@ std::vector<Tensor> mesh_raster(const Tensor& vertices, const Tensor& faces, con
 
 // depth registration: normal [3,H,W] of depth [H,W]; cam [4] a CPU float32 tensor as for unproject
 Tensor depth_normals(const Tensor& depth, const Tensor& cam, int64_t step, double max_jump, int64_t scale, int64_t top, int64_t left) {
-    TORCH_CHECK(depth.dim() == 2 && depth.numel() > 0 && depth.numel() <= 0x7fffffff, "depth_normals: depth [H,W], 1 .. 2^31 - 1 samples");
-    fp(depth, "depth");
+    depth_map("depth_normals", depth, "depth", "[H,W]");
     Tensor normal = at::empty({3, depth.size(0), depth.size(1)}, depth.options());
     check(be_depth_normals_f32(depth.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)scale, (int)top, (int)left,
                                host_floats(cam, 4, "depth_normals(cam)"), (int)step, (float)max_jump, normal.data_ptr<float>(),
@@ -875,23 +886,21 @@ std::tuple<Tensor, Tensor> icp_linearize(const Tensor& depth_s, const c10::optio
                                          int64_t top, int64_t left, const Tensor& depth_d, const Tensor& normal_d,
                                          const c10::optional<Tensor>& weight_d, const Tensor& cam_dst, const Tensor& pose, double near,
                                          double max_dist, double huber, bool rows) {
-    TORCH_CHECK(depth_s.dim() == 2 && depth_s.numel() > 0 && depth_s.numel() <= 0x7fffffff, "icp_linearize: depth_s [Hs,Ws], 1 .. 2^31 - 1 samples");
-    TORCH_CHECK(depth_d.dim() == 2 && depth_d.numel() > 0 && depth_d.numel() <= 0x7fffffff, "icp_linearize: depth_d [Hd,Wd], 1 .. 2^31 - 1 samples");
+    const float* ps = depth_map("icp_linearize", depth_s, "depth_s");
+    const float* pd = depth_map("icp_linearize", depth_d, "depth_d", "[Hd,Wd]");
     const int64_t Hs = depth_s.size(0), Ws = depth_s.size(1), Hd = depth_d.size(0), Wd = depth_d.size(1);
     TORCH_CHECK(normal_d.numel() == 3 * Hd * Wd && normal_d.size(0) == 3 && normal_d.device() == depth_s.device() && depth_d.device() == depth_s.device(),
                 "icp_linearize: normal_d [3,Hd,Wd] and depth_d on depth_s's device");
-    if (weight_s.has_value() && weight_s->defined())
-        TORCH_CHECK(weight_s->sizes() == depth_s.sizes() && weight_s->device() == depth_s.device(), "icp_linearize: weight_s [Hs,Ws] on depth_s's device");
-    if (weight_d.has_value() && weight_d->defined())
-        TORCH_CHECK(weight_d->sizes() == depth_d.sizes() && weight_d->device() == depth_s.device(), "icp_linearize: weight_d [Hd,Wd] on depth_s's device");
+    const float* pws = map_like("icp_linearize", weight_s, depth_s, "weight_s", "[Hs,Ws]", "depth_s");
+    const float* pwd = map_like("icp_linearize", weight_d, depth_d, "weight_d", "[Hd,Wd]", "depth_s");   // depth_d is on depth_s's device
     const int64_t bytes = be_icp_scratch_bytes((int)Hs, (int)Ws);
     TORCH_CHECK(bytes > 0, "icp_linearize: no scratch size for ", Hs, " x ", Ws);
     auto o = depth_s.options();
     Tensor scratch = at::empty({bytes / 8}, o.dtype(at::kDouble)), sums = at::empty({32}, o.dtype(at::kDouble));
     Tensor rout = rows ? at::empty({8, Hs * Ws}, o) : at::empty({0}, o);
-    check(be_icp_linearize_f32(fp(depth_s, "depth_s"), fpo(weight_s, "weight_s"), (int)Hs, (int)Ws, (int)scale, (int)top, (int)left,
-                               host_floats(cam_src, 4, "icp_linearize(cam_src)"), fp(depth_d, "depth_d"), fp(normal_d, "normal_d"),
-                               fpo(weight_d, "weight_d"), (int)Hd, (int)Wd, host_floats(cam_dst, 4, "icp_linearize(cam_dst)"),
+    check(be_icp_linearize_f32(ps, pws, (int)Hs, (int)Ws, (int)scale, (int)top, (int)left,
+                               host_floats(cam_src, 4, "icp_linearize(cam_src)"), pd, fp(normal_d, "normal_d"), pwd,
+                               (int)Hd, (int)Wd, host_floats(cam_dst, 4, "icp_linearize(cam_dst)"),
                                host_floats(pose, 12, "icp_linearize(pose)"), (float)near, (float)max_dist, (float)huber,
                                scratch.data_ptr<double>(), sums.data_ptr<double>(), rows ? rout.data_ptr<float>() : nullptr,
                                stream_of(depth_s)), "be_icp_linearize_f32");
@@ -907,12 +916,11 @@ std::tuple<Tensor, Tensor, Tensor> fill_nearest(const Tensor& depth, const c10::
     TORCH_CHECK(smooth_r >= 0 && smooth_r <= 8, "fill_nearest: smooth_r must be in [0, 8]");
     fp(depth, "depth");
     const int64_t H = depth.size(0), W = depth.size(1);
-    if (weight.has_value() && weight->defined())
-        TORCH_CHECK(weight->sizes() == depth.sizes() && weight->device() == depth.device(), "fill_nearest: weight [H,W] on depth's device");
+    const float* pw = map_like("fill_nearest", weight, depth, "weight", "[H,W]");
     auto o = depth.options();
     Tensor scratch = at::empty({smooth_r > 0 ? 3 : 2, H, W}, o.dtype(at::kInt));
     Tensor dout = at::empty({H, W}, o), index = at::empty({H, W}, o.dtype(at::kInt)), dist2 = at::empty({H, W}, o.dtype(at::kInt));
-    check(be_fill_nearest_f32(depth.data_ptr<float>(), fpo(weight, "weight"), (int)H, (int)W, (int)smooth_r, (float)sigma_z, fuse ? 1 : 0,
+    check(be_fill_nearest_f32(depth.data_ptr<float>(), pw, (int)H, (int)W, (int)smooth_r, (float)sigma_z, fuse ? 1 : 0,
                               scratch.data_ptr<int32_t>(), dout.data_ptr<float>(), index.data_ptr<int32_t>(), dist2.data_ptr<int32_t>(),
                               stream_of(depth)), "be_fill_nearest_f32");
     return {dout, index, dist2};
@@ -929,17 +937,15 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> fill_diffuse(const Tensor& depth, con
     TORCH_CHECK(iters >= 0 && iters <= 4096, "fill_diffuse: iters must be in [0, 4096]");
     fp(depth, "depth");
     const int64_t H = depth.size(0), W = depth.size(1);
-    if (weight.has_value() && weight->defined())
-        TORCH_CHECK(weight->sizes() == depth.sizes() && weight->device() == depth.device(), "fill_diffuse: weight [H,W] on depth's device");
-    if (edge.has_value() && edge->defined())
-        TORCH_CHECK(edge->sizes() == depth.sizes() && edge->device() == depth.device(), "fill_diffuse: edge [H,W] on depth's device");
+    const float* pw = map_like("fill_diffuse", weight, depth, "weight", "[H,W]");
+    const float* pe = map_like("fill_diffuse", edge, depth, "edge", "[H,W]");
     auto o = depth.options();
     const int64_t bytes = be_fill_diffuse_scratch_bytes((int)H, (int)W);
     TORCH_CHECK(bytes > 0, "fill_diffuse: no scratch size for ", H, " x ", W);
     Tensor scratch = at::empty({bytes / 4}, o.dtype(at::kInt));
     Tensor dout = at::empty({H, W}, o), index = at::empty({H, W}, o.dtype(at::kInt)), dist2 = at::empty({H, W}, o.dtype(at::kInt));
     Tensor residual = at::empty({1}, o);
-    check(be_fill_diffuse_f32(depth.data_ptr<float>(), fpo(weight, "weight"), fpo(edge, "edge"), (int)H, (int)W, (int)smooth_r,
+    check(be_fill_diffuse_f32(depth.data_ptr<float>(), pw, pe, (int)H, (int)W, (int)smooth_r,
                               (float)sigma_z, (float)leak, (int)iters, fuse ? 1 : 0, scratch.data_ptr<int32_t>(), dout.data_ptr<float>(),
                               index.data_ptr<int32_t>(), dist2.data_ptr<int32_t>(), residual.data_ptr<float>(), stream_of(depth)),
           "be_fill_diffuse_f32");
