@@ -190,6 +190,13 @@ _SIGNATURES = {
     "be_mesh_raster_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "be_mesh_raster_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int, _P, _P] + [C.POINTER(C.c_float)] * 2
                            + [C.c_float, C.c_int, C.c_int, C.c_int] + [_P] * 7 + [_P, C.c_size_t, _P]),
+    "be_mesh_components_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "be_mesh_components_i32": (C.c_int, [_P, C.c_int64, C.c_int64] + [_P] * 5 + [C.c_size_t, _P]),
+    "be_mesh_components_stats": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
+    "be_mesh_components_decide": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_int, _P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "be_mesh_select_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "be_mesh_select_count": (C.c_int, [_P, C.c_int64, C.c_int64] + [_P] * 5 + [C.c_size_t, _P]),
+    "be_mesh_select_emit": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int] + [_P] * 7 + [C.c_int64, C.c_int64] + [_P] * 10 + [_P]),
     "be_depth_normals_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.c_int, C.c_float, _P, _P]),
     "be_icp_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "be_icp_linearize_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [C.POINTER(C.c_float), _P, _P, _P, C.c_int, C.c_int]
@@ -1824,6 +1831,194 @@ def raster_mesh(mesh, cam_dst, pose, size, near=1e-3, cull="none", want=("feat",
     keep = lambda t, has: t if has else None
     return dict(depth=d, face=face, valid=face >= 0, weight=keep(w, weight is not None), feat=keep(f, feat is not None),
                 normal=keep(nrm, normal is not None), normal_valid=keep(nv, normal is not None), bary=keep(b, bary))
+
+
+MESH_KINDS = dict(vertices=torch.float32, faces=torch.int32, weight=torch.float32, feat=torch.float32, normal=torch.float32,
+                  normal_valid=torch.bool, edge=torch.int64)
+_I64, _BOOL = (torch.int64,), (torch.bool,)
+
+
+def _mesh_on_gpu(who, mesh):
+    """A mesh dict for the cleaning entries: components.check_mesh, every member a tensor of its MESH_KINDS dtype on one GPU ->
+    (V, T, C, the members contiguous - None for what the mesh does not hold -, the device)."""
+    from . import components
+    V, T, C_ = components.check_mesh(who, mesh)
+    dev = getattr(mesh["vertices"], "device", None)
+    m = {}
+    for name, dt in MESH_KINDS.items():
+        t = mesh.get(name)
+        if t is None:
+            m[name] = None
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f"{who}: {name} must be a {str(dt).replace('torch.', '')} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if not t.is_cuda:
+            raise ValueError(f"{who}: the mesh lives on the GPU; nothing here computes on the CPU (be_hip.components is the host statement)")
+        if t.device != dev:
+            raise ValueError(f"{who}: {name} is on {t.device}, vertices on {dev}")
+        m[name] = t.contiguous()
+    return V, T, C_, m, dev
+
+
+def _components_label(m, V, T, dev):
+    """-> (label [V], component [V], face_component [T] int32, total [1] int64 on the device = K); no synchronisation."""
+    o = ops()
+    if o is not None:
+        return tuple(o.mesh_components(m["faces"], V))
+    new = _new(dev)
+    label, component, fc = new(V, dtype=torch.int32), new(V, dtype=torch.int32), new(T, dtype=torch.int32)
+    total = new(1, dtype=torch.int64)
+    nbytes = lib().be_mesh_components_workspace_bytes(V)
+    ws = new((nbytes + 7) // 8, dtype=torch.int64)
+    check(lib().be_mesh_components_i32(dptr(m["faces"]), V, T, dptr(label), dptr(component), dptr(fc), dptr(total, "total", _I64),
+                                       dptr(ws, "workspace", _I64), nbytes, stream_ptr(dev)), "be_mesh_components_i32")
+    return label, component, fc, total
+
+
+def _components_stats(m, V, T, component, Kcap, dev):
+    """-> (triangles, vertices int32 [Kcap], area_q int64 [Kcap]) per dense id; 0 from K on."""
+    o = ops()
+    if o is not None:
+        return tuple(o.mesh_components_stats(m["vertices"], m["faces"], component, Kcap))
+    new = _new(dev)
+    tri, nv, aq = new(Kcap, dtype=torch.int32), new(Kcap, dtype=torch.int32), new(Kcap, dtype=torch.int64)
+    check(lib().be_mesh_components_stats(dptr(m["vertices"]), dptr(m["faces"]), V, T, dptr(component), Kcap, dptr(tri), dptr(nv),
+                                         dptr(aq, "area_q", _I64), stream_ptr(dev)), "be_mesh_components_stats")
+    return tri, nv, aq
+
+
+def _components_decide(tri, aq, total, mt, ma, largest, component, dev):
+    """-> (keep [Kcap] bool, False from K on, vertex_keep [V] bool = keep[component] or None); K is read on the device."""
+    o = ops()
+    if o is not None:
+        keep, vk = o.mesh_components_decide(tri, aq, total, mt, ma, largest, component)
+        return keep, (vk if component is not None else None)
+    Kcap, V = tri.numel(), 0 if component is None else component.numel()
+    keep = torch.zeros(Kcap, dtype=torch.bool, device=dev)
+    vk = None if component is None else torch.empty(V, dtype=torch.bool, device=dev)
+    ws = torch.empty(1, dtype=torch.int64, device=dev)
+    check(lib().be_mesh_components_decide(dptr(tri), dptr(aq, "area_q", _I64), dptr(total, "total", _I64), Kcap, mt, ma, int(largest),
+                                          dptr(keep, "keep", _BOOL), dptr(component), V, dptr(vk, "vertex_keep", _BOOL),
+                                          dptr(ws, "workspace", _I64), 8, stream_ptr(dev)), "be_mesh_components_decide")
+    return keep, vk
+
+
+def _select_count(m, V, T, vertex_keep, dev):
+    """-> (voff [V], foff [T] int32, totals [2] int64 on the device = (V', T')); no synchronisation."""
+    o = ops()
+    if o is not None:
+        return tuple(o.mesh_select_count(m["faces"], vertex_keep))
+    new = _new(dev)
+    voff, foff, totals = new(V, dtype=torch.int32), new(T, dtype=torch.int32), new(2, dtype=torch.int64)
+    nbytes = lib().be_mesh_select_workspace_bytes(V, T)
+    ws = new((nbytes + 7) // 8, dtype=torch.int64)
+    check(lib().be_mesh_select_count(dptr(m["faces"]), V, T, dptr(vertex_keep, "vertex_keep", _BOOL), dptr(voff), dptr(foff),
+                                     dptr(totals, "totals", _I64), dptr(ws, "workspace", _I64), nbytes, stream_ptr(dev)), "be_mesh_select_count")
+    return voff, foff, totals
+
+
+def _select_emit(m, V, T, C_, component, vertex_keep, voff, foff, V2, T2, dev):
+    """The emit phase -> the compacted mesh (components.select's keys, and component [V2] when one was given)."""
+    has = lambda k: m[k] is not None
+    o = ops()
+    if o is not None:
+        v, f, w, ft, n, nv, e, c, vi, fi = o.mesh_select(m["vertices"], m["faces"], m["weight"], m["feat"], m["normal"], m["normal_valid"], m["edge"],
+                                                         component, vertex_keep, voff, foff, V2, T2)
+    else:
+        new = _new(dev)
+        v, f = new(V2, 3), new(T2, 3, dtype=torch.int32)
+        w = new(V2) if has("weight") else None
+        ft = new(C_, V2) if has("feat") else None
+        n = new(V2, 3) if has("normal") else None
+        nv = new(V2, dtype=torch.bool) if has("normal_valid") else None
+        e = new(V2, dtype=torch.int64) if has("edge") else None
+        c = new(V2, dtype=torch.int32) if component is not None else None
+        vi, fi = new(V2, dtype=torch.int32), new(T2, dtype=torch.int32)
+        check(lib().be_mesh_select_emit(dptr(m["vertices"]), dptr(m["faces"]), V, T, dptr(m["weight"]), dptr(m["feat"] if C_ else None), C_,
+                                        dptr(m["normal"]), dptr(m["normal_valid"], "normal_valid", _BOOL), dptr(m["edge"], "edge", _I64),
+                                        dptr(component), dptr(vertex_keep, "vertex_keep", _BOOL), dptr(voff), dptr(foff), V2, T2, dptr(v), dptr(f),
+                                        dptr(w), dptr(ft if C_ else None), dptr(n), dptr(nv, "normal_valid", _BOOL), dptr(e, "edge", _I64), dptr(c),
+                                        dptr(vi), dptr(fi), stream_ptr(dev)), "be_mesh_select_emit")
+    keep = lambda t, k: t if has(k) else None
+    out = dict(vertices=v, faces=f, weight=keep(w, "weight"), feat=keep(ft, "feat"), normal=keep(n, "normal"),
+               normal_valid=keep(nv, "normal_valid"), edge=keep(e, "edge"), vertex_index=vi, face_index=fi)
+    if component is not None:
+        out["component"] = c
+    return out
+
+
+def _components_dict(tri, nv, aq, K):
+    from . import components
+    aq = aq[:K]
+    return dict(triangles=tri[:K], vertices=nv[:K], area_q=aq, area=aq.to(torch.float64) * 2.0 ** -components.AREA_BITS)
+
+
+def mesh_components(mesh):
+    """The connected components of a mesh on the GPU (a dict as mesh_field / tsdf_mesh return it: vertices [V,3] float32, faces
+    [T,3] int32): two vertices are connected when a chain of faces joins them, one shared vertex being enough.  -> dict(label [V]
+    int32 = the least vertex index of the vertex's component, component [V] int32 = its dense id 0..K-1 in increasing order of
+    label, face_component [T] int32 (-1: a face with an index outside [0, V), which is ignored - the statement refuses it; finding
+    it here would cost a read-back), K (a python int: the one read-back), and per component triangles, vertices int32 [K], area_q
+    int64 [K] (2^-40 m^2, summed as integers), area float64 [K] in m^2).  A lock-free union-find (atomicMin links from the larger
+    root to the smaller, so a root is its component's least index), the scan for the dense ids, integer atomics for the sizes:
+    the same bits on every run.  components.label / stats are the host statement, bit for bit."""
+    V, T, _, m, dev = _mesh_on_gpu("mesh_components", mesh)
+    label, component, fc, total = _components_label(m, V, T, dev)
+    K = int(total.item())                                                # the read-back: synchronises with the stream
+    tri, nv, aq = _components_stats(m, V, T, component, K, dev)
+    return dict(label=label, component=component, face_component=fc, K=K, **_components_dict(tri, nv, aq, K))
+
+
+def _vertex_keep(who, vertex_keep, V, dev):
+    if not isinstance(vertex_keep, torch.Tensor) or vertex_keep.dtype != torch.bool or tuple(vertex_keep.shape) != (V,):
+        raise ValueError(f"{who}: vertex_keep must be a bool tensor [{V}], got {_got(vertex_keep)}")
+    if vertex_keep.device != dev:
+        raise ValueError(f"{who}: vertex_keep is on {vertex_keep.device}, vertices on {dev}")
+    return vertex_keep.contiguous()
+
+
+def mesh_select(mesh, vertex_keep):
+    """The mesh compacted to the vertices vertex_keep [V] bool names: they stay in their order, the faces whose three indices are
+    all in range and kept stay in theirs, re-indexed, and every per-vertex array the mesh holds (weight, feat [C,V], normal,
+    normal_valid, edge) is gathered; None stays None.  vertex_index [V'] / face_index [T'] int32 give the old positions; V' == 0 and
+    T' == 0 are legal.  Two scans, one read-back of (V', T'), one gather.  components.select is the host statement, bit for bit."""
+    V, T, C_, m, dev = _mesh_on_gpu("mesh_select", mesh)
+    vertex_keep = _vertex_keep("mesh_select", vertex_keep, V, dev)
+    voff, foff, totals = _select_count(m, V, T, vertex_keep, dev)
+    V2, T2 = totals.tolist()                                            # the read-back: synchronises with the stream
+    return _select_emit(m, V, T, C_, None, vertex_keep, voff, foff, V2, T2, dev)
+
+
+def mesh_clean(mesh, min_triangles=None, min_area=None, largest=False):
+    """The mesh without its small components: a component stays when it holds at least min_triangles triangles and min_area square
+    metres (None: not asked); largest=True keeps, of those, only the one with the most triangles (the lowest id on a tie).  ->
+    mesh_select's result for the vertices of the components that stay, with component [V'] int32 = their OLD dense ids and
+    components = dict(triangles, vertices, area_q, area, keep [K] bool) over all K components.  ONE read-back: the per-component
+    arrays are sized by V (K <= V) and the decision reads K on the device, so (K, V', T') come back together, after the count
+    phase of the selection.  components.clean is the host statement, bit for bit."""
+    from . import components
+    V, T, C_, m, dev = _mesh_on_gpu("mesh_clean", mesh)
+    mt, ma, largest = components.check_decision("mesh_clean", min_triangles, min_area, largest)
+    _, component, _, total = _components_label(m, V, T, dev)
+    tri, nv, aq = _components_stats(m, V, T, component, V, dev)
+    keep, vertex_keep = _components_decide(tri, aq, total, mt, ma, largest, component, dev)
+    voff, foff, totals = _select_count(m, V, T, vertex_keep, dev)
+    K, V2, T2 = torch.cat([total, totals]).tolist()                     # the read-back: synchronises with the stream
+    out = _select_emit(m, V, T, C_, component, vertex_keep, voff, foff, V2, T2, dev)
+    out["components"] = dict(_components_dict(tri, nv, aq, K), keep=keep[:K])
+    return out
+
+
+def mesh_decide(stats, K, min_triangles=None, min_area=None, largest=False):
+    """keep [K] bool of mesh_components' result (its triangles and area_q) under components.decide's rule, on the GPU."""
+    from . import components
+    mt, ma, largest = components.check_decision("mesh_decide", min_triangles, min_area, largest)
+    tri, aq = stats["triangles"], stats["area_q"]
+    if not (isinstance(tri, torch.Tensor) and isinstance(aq, torch.Tensor) and tri.is_cuda and aq.is_cuda and tri.dtype == torch.int32
+            and aq.dtype == torch.int64 and tri.shape == aq.shape == (K,)):
+        raise ValueError(f"mesh_decide: triangles int32 [{K}] and area_q int64 [{K}] on the GPU, as mesh_components returned them")
+    total = torch.full((1,), K, dtype=torch.int64, device=tri.device)
+    return _components_decide(tri.contiguous(), aq.contiguous(), total, mt, ma, largest, None, tri.device)[0]
 
 
 def depth_normals(depth, cam, step=3, max_jump=0.05, scale=1, window_origin=(0, 0)):

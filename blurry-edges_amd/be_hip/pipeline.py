@@ -592,6 +592,33 @@ class DepthPipeline:
         res.update(normal=out["normal"], normal_valid=out["normal_valid"])
         return res
 
+    @torch.no_grad()
+    def clean_mesh(self, mesh, min_triangles=None, min_area=None, largest=False):
+        """mesh: what extract_mesh returned (or any dict of vertices [V,3], faces [T,3] int32 and per-vertex maps on the GPU) -> the
+        mesh without its small connected components (native.mesh_clean): a component - the vertices a chain of faces joins -
+        stays when it holds at least min_triangles triangles and min_area square metres (None: not asked), and with largest=True
+        only the one with the most triangles does.  The islands of triangles that depth outliers leave in front of a surface are
+        such components; the surfaces themselves are the large ones.  The result holds the keys of `mesh` - vertices, faces
+        (re-indexed), weight, normal, normal_valid and every [.., V] map such as shpd [3,V'] - and adds component [V'] int32 = the
+        id each vertex's component had and components = dict(triangles, vertices, area_q, area, keep), one entry per component of
+        the mesh that came in.  It goes straight into render_mesh, save_mesh and clean_mesh again.  One read-back."""
+        if not isinstance(mesh, dict) or "vertices" not in mesh or "faces" not in mesh:
+            raise ValueError("clean_mesh: mesh must be the dict extract_mesh returned (vertices, faces, ...)")
+        V = mesh["vertices"].shape[0]
+        fixed = ("vertices", "faces", "weight", "normal", "normal_valid", "edge", "component", "components", "vertex_index", "face_index")
+        maps = [k for k, t in mesh.items() if k not in fixed and isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[-1] == V]
+        for k in maps:
+            if mesh[k].dtype != torch.float32:
+                raise ValueError(f"clean_mesh: the map {k!r} must be float32, got {mesh[k].dtype}")
+        feat, channels = pack_channels(mesh, maps, V, tail=1)
+        m = dict(vertices=mesh["vertices"], faces=mesh["faces"], feat=feat, **{k: mesh.get(k) for k in ("weight", "normal", "normal_valid", "edge")})
+        out = native.mesh_clean(m, min_triangles=min_triangles, min_area=min_area, largest=largest)
+        res = {k: v for k, v in mesh.items() if k not in fixed and k not in maps}
+        res.update({k: out[k] for k in ("vertices", "faces", "weight", "normal", "normal_valid", "edge") if k in mesh})
+        res.update(unpack_channels(out["feat"], channels, out["vertices"].shape[:1]))
+        res.update(component=out["component"], components=out["components"])
+        return res
+
     @staticmethod
     def save_mesh(path, mesh):
         """mesh: what extract_mesh returned -> a binary PLY file at `path` (mesh.write_ply): positions, normals when the mesh holds

@@ -17,6 +17,7 @@ formats (argument names and defaults = utils/args.py of the reference):
                                                            (with tsdf_dims / tsdf_origin / tsdf_voxel in FILE: also in a TSDF volume)
                                                            (with tsdf_mesh > 0 beside them: also that volume's triangle mesh)
                                                            (with mesh_render > 0 beside them: also that mesh seen by view 0's camera)
+                                                           (with mesh_min_triangles > 0 beside them: the mesh without its small components)
     ... eval --normals [--out_path DIR]                    also write every pair's surface normals (of its completed depth)
     ... eval --complete [--out_path DIR]                   also write and score every pair's depth map completed to a dense one
     ... eval --complete --complete_method diffuse          ... by edge-aware diffusion instead of the nearest sample's depth
@@ -392,6 +393,15 @@ def load_fusion(path):
                 raise ValueError(f"--fuse: mesh_render renders the mesh of the TSDF volume; {path} lacks the keys that describe one: "
                                  "tsdf_dims, tsdf_origin, tsdf_voxel (tsdf_trunc is optional)")
             cfg["mesh_render"] = int(n)
+        if "mesh_min_triangles" in f:                                       # absent: the dict holds what it held before
+            n = np.asarray(f["mesh_min_triangles"]).reshape(-1)[0]
+            if int(n) != n or not 0 <= n < 1 << 31:
+                raise ValueError("--fuse: mesh_min_triangles must be an integer >= 0 (> 0: drop the mesh's components of fewer triangles), "
+                                 f"got {f['mesh_min_triangles']!r}")
+            if n > 0 and not (cfg.get("tsdf_mesh", 0) > 0 or cfg.get("mesh_render", 0) > 0):
+                raise ValueError(f"--fuse: mesh_min_triangles cleans the mesh of the TSDF volume; {path} asks for no mesh: "
+                                 "tsdf_mesh > 0 or mesh_render > 0 (beside tsdf_dims, tsdf_origin, tsdf_voxel)")
+            cfg["mesh_min_triangles"] = int(n)
         return cfg
 
 
@@ -448,7 +458,9 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     poses: {args.out_path}/mesh_{g:04d}.ply (positions, normals, shpd as colours) and mesh_{g:04d}.npz (vertices, faces, weight, shpd,
     normal, normal_valid), outside the timed region.  With an integer mesh_render > 0 beside them that mesh is also rasterised into
     view 0's camera, DepthPipeline.render_mesh: {args.out_path}/mesh_render_{g:04d}.npz (depth, valid, face, normal, shpd), outside
-    the timed region; without the key nothing changes.
+    the timed region; without the key nothing changes.  With an integer mesh_min_triangles > 0 beside them the mesh is first cleaned,
+    DepthPipeline.clean_mesh: its connected components of fewer triangles - the islands depth outliers leave - are dropped before
+    either file is written, and mesh_{g:04d}.npz also holds component [V'] and components_triangles (every component's size).
     args.normals (not in the reference): every pair's surface normals, DepthPipeline.normals(source="complete"), go to
     {args.out_path}/normals_{j:04d}.npz (normal [3,H,W], valid), outside the timed region."""
     import data, models, utils
@@ -555,9 +567,14 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
                     np.savez(os.path.join(args.out_path, f"tsdf_{j // len(group):04d}.npz"),
                              **{k: cast[k].cpu().numpy() for k in ("depth", "valid", "weight", "normal", "shpd")})
                     tri = pipe.extract_mesh(vol) if fcfg.get("tsdf_mesh", 0) > 0 or fcfg.get("mesh_render", 0) > 0 else None
+                    cleaned = {}
+                    if tri is not None and fcfg.get("mesh_min_triangles", 0) > 0:
+                        tri = pipe.clean_mesh(tri, min_triangles=fcfg["mesh_min_triangles"])
+                        cleaned = dict(components_triangles=tri.pop("components")["triangles"].cpu().numpy())
                     if fcfg.get("tsdf_mesh", 0) > 0:
                         pipe.save_mesh(os.path.join(args.out_path, f"mesh_{j // len(group):04d}.ply"), tri)
-                        np.savez(os.path.join(args.out_path, f"mesh_{j // len(group):04d}.npz"), **{k: v.cpu().numpy() for k, v in tri.items()})
+                        np.savez(os.path.join(args.out_path, f"mesh_{j // len(group):04d}.npz"), **{k: v.cpu().numpy() for k, v in tri.items()},
+                                 **cleaned)
                     if fcfg.get("mesh_render", 0) > 0:                               # view 0's camera, where view 0 stands
                         seen = pipe.render_mesh(tri, cam_dst=vol.meta["camera"], pose=gposes[0], size=vol.meta["size"])
                         np.savez(os.path.join(args.out_path, f"mesh_render_{j // len(group):04d}.npz"),

@@ -870,6 +870,123 @@ std::vector<Tensor> mesh_raster(const Tensor& vertices, const Tensor& faces, con
     return {depth, face, wout, fout, nout, nvout, bary};
 }
 
+// ---- mesh cleaning: the five steps of be_mesh_components_* / be_mesh_select_*, none of which synchronises with the host; the
+// read-backs between them are native.py's, the same for both bindings
+static void mesh_faces(const char* who, const Tensor& faces, int64_t V) {
+    TORCH_CHECK(faces.is_cuda() && faces.dim() == 2 && faces.size(1) == 3 && faces.scalar_type() == at::kInt && faces.is_contiguous(), who,
+                ": faces must be a contiguous int32 tensor [T,3] on the GPU");
+    TORCH_CHECK(V >= 0 && V <= 0x7fffffff && faces.size(0) <= 0x7fffffff, who, ": at most 2^31 - 1 vertices and triangles");
+}
+
+template <typename T>
+static T* on_device(const char* who, const char* name, const Tensor& t, at::ScalarType dtype, const Tensor& like, int64_t numel = -1) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == dtype && t.is_contiguous() && t.device() == like.device() && (numel < 0 || t.numel() == numel), who,
+                ": ", name, " must be a contiguous ", c10::toString(dtype), " tensor", numel < 0 ? "" : " of the mesh's size", " on the mesh's device");
+    return reinterpret_cast<T*>(t.data_ptr());
+}
+
+// faces [T,3] int32 over V vertices -> [label [V], component [V], face_component [T] int32, total [1] int64 on the device = K]
+std::vector<Tensor> mesh_components(const Tensor& faces, int64_t V) {
+    mesh_faces("mesh_components", faces, V);
+    const int64_t T = faces.size(0);
+    auto oi = faces.options();
+    Tensor label = at::empty({V}, oi), component = at::empty({V}, oi), face_component = at::empty({T}, oi), total = at::empty({1}, oi.dtype(at::kLong));
+    const size_t bytes = be_mesh_components_workspace_bytes(V);
+    Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, oi.dtype(at::kLong));
+    check(be_mesh_components_i32(faces.data_ptr<int32_t>(), V, T, label.data_ptr<int32_t>(), component.data_ptr<int32_t>(),
+                                 face_component.data_ptr<int32_t>(), total.data_ptr<int64_t>(), ws.data_ptr<int64_t>(), bytes, stream_of(faces)),
+          "be_mesh_components_i32");
+    return {label, component, face_component, total};
+}
+
+// -> [triangles [Kcap] int32, vertices [Kcap] int32, area_q [Kcap] int64]
+std::vector<Tensor> mesh_components_stats(const Tensor& vertices, const Tensor& faces, const Tensor& component, int64_t Kcap) {
+    fp(vertices, "mesh_components_stats(vertices)");
+    TORCH_CHECK(vertices.dim() == 2 && vertices.size(1) == 3, "mesh_components_stats: vertices [V,3]");
+    const int64_t V = vertices.size(0), T = faces.size(0);
+    mesh_faces("mesh_components_stats", faces, V);
+    const int32_t* comp = on_device<int32_t>("mesh_components_stats", "component", component, at::kInt, vertices, V);
+    TORCH_CHECK(faces.device() == vertices.device() && Kcap >= 0 && Kcap <= V, "mesh_components_stats: faces on vertices' device, Kcap in [0, V]");
+    auto oi = faces.options();
+    Tensor triangles = at::empty({Kcap}, oi), nvertices = at::empty({Kcap}, oi), area_q = at::empty({Kcap}, oi.dtype(at::kLong));
+    check(be_mesh_components_stats(vertices.data_ptr<float>(), faces.data_ptr<int32_t>(), V, T, comp, Kcap, triangles.data_ptr<int32_t>(),
+                                   nvertices.data_ptr<int32_t>(), area_q.data_ptr<int64_t>(), stream_of(vertices)), "be_mesh_components_stats");
+    return {triangles, nvertices, area_q};
+}
+
+// -> [keep [Kcap] bool (0 from K on), vertex_keep [V] bool (empty without component)]
+std::vector<Tensor> mesh_components_decide(const Tensor& triangles, const Tensor& area_q, const Tensor& total, int64_t min_triangles, double min_area,
+                                           bool largest, const c10::optional<Tensor>& component) {
+    const int64_t Kcap = triangles.numel();
+    TORCH_CHECK(triangles.is_cuda() && triangles.scalar_type() == at::kInt && triangles.is_contiguous(),
+                "mesh_components_decide: triangles must be a contiguous int32 tensor on the GPU");
+    const int64_t* aq = on_device<int64_t>("mesh_components_decide", "area_q", area_q, at::kLong, triangles, Kcap);
+    const int64_t* tot = on_device<int64_t>("mesh_components_decide", "total", total, at::kLong, triangles, 1);
+    const bool has_c = given(component);
+    const int64_t V = has_c ? component->numel() : 0;
+    const int32_t* comp = has_c ? on_device<int32_t>("mesh_components_decide", "component", *component, at::kInt, triangles) : nullptr;
+    auto ob = triangles.options().dtype(at::kBool);
+    Tensor keep = at::zeros({Kcap}, ob), vertex_keep = at::empty({V}, ob);
+    Tensor ws = at::empty({BE_COMPONENTS_DECIDE_WORKSPACE_BYTES / 8}, triangles.options().dtype(at::kLong));
+    check(be_mesh_components_decide(triangles.data_ptr<int32_t>(), aq, tot, Kcap, min_triangles, (float)min_area, largest ? 1 : 0,
+                                    reinterpret_cast<uint8_t*>(keep.data_ptr<bool>()), comp, V,
+                                    has_c ? reinterpret_cast<uint8_t*>(vertex_keep.data_ptr<bool>()) : nullptr, ws.data_ptr<int64_t>(),
+                                    BE_COMPONENTS_DECIDE_WORKSPACE_BYTES, stream_of(triangles)), "be_mesh_components_decide");
+    return {keep, vertex_keep};
+}
+
+// faces [T,3], vertex_keep [V] bool -> [voff [V], foff [T] int32, totals [2] int64 on the device = (V', T')]
+std::vector<Tensor> mesh_select_count(const Tensor& faces, const Tensor& vertex_keep) {
+    const int64_t V = vertex_keep.numel(), T = faces.size(0);
+    mesh_faces("mesh_select_count", faces, V);
+    const uint8_t* vk = on_device<uint8_t>("mesh_select_count", "vertex_keep", vertex_keep, at::kBool, faces);
+    auto oi = faces.options();
+    Tensor voff = at::empty({V}, oi), foff = at::empty({T}, oi), totals = at::empty({2}, oi.dtype(at::kLong));
+    const size_t bytes = be_mesh_select_workspace_bytes(V, T);
+    Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, oi.dtype(at::kLong));
+    check(be_mesh_select_count(faces.data_ptr<int32_t>(), V, T, vk, voff.data_ptr<int32_t>(), foff.data_ptr<int32_t>(), totals.data_ptr<int64_t>(),
+                               ws.data_ptr<int64_t>(), bytes, stream_of(faces)), "be_mesh_select_count");
+    return {voff, foff, totals};
+}
+
+// the emit phase -> [vertices [V2,3], faces [T2,3], weight [V2], feat [C,V2], normal [V2,3], normal_valid [V2] bool, edge [V2] int64,
+// component [V2] int32, vertex_index [V2], face_index [T2] int32]; an output whose input is absent is an empty tensor
+std::vector<Tensor> mesh_select(const Tensor& vertices, const Tensor& faces, const c10::optional<Tensor>& weight, const c10::optional<Tensor>& feat,
+                                const c10::optional<Tensor>& normal, const c10::optional<Tensor>& normal_valid, const c10::optional<Tensor>& edge,
+                                const c10::optional<Tensor>& component, const Tensor& vertex_keep, const Tensor& voff, const Tensor& foff, int64_t V2,
+                                int64_t T2) {
+    const char* who = "mesh_select";
+    fp(vertices, "mesh_select(vertices)");
+    TORCH_CHECK(vertices.dim() == 2 && vertices.size(1) == 3, "mesh_select: vertices [V,3]");
+    const int64_t V = vertices.size(0), T = faces.size(0);
+    mesh_faces(who, faces, V);
+    TORCH_CHECK(V2 >= 0 && V2 <= V && T2 >= 0 && T2 <= T, "mesh_select: V2 in [0, V] and T2 in [0, T]");
+    const bool has_w = given(weight), has_f = given(feat), has_n = given(normal), has_nv = given(normal_valid), has_e = given(edge), has_c = given(component);
+    if (has_f) TORCH_CHECK(feat->dim() == 2 && feat->size(1) == V, "mesh_select: feat [C,V]");
+    const int64_t C = has_f ? feat->size(0) : 0;
+    const float* pw = has_w ? on_device<float>(who, "weight", *weight, at::kFloat, vertices, V) : nullptr;
+    const float* pf = has_f && C > 0 ? on_device<float>(who, "feat", *feat, at::kFloat, vertices, C * V) : nullptr;
+    const float* pn = has_n ? on_device<float>(who, "normal", *normal, at::kFloat, vertices, 3 * V) : nullptr;
+    const uint8_t* pnv = has_nv ? on_device<uint8_t>(who, "normal_valid", *normal_valid, at::kBool, vertices, V) : nullptr;
+    const int64_t* pe = has_e ? on_device<int64_t>(who, "edge", *edge, at::kLong, vertices, V) : nullptr;
+    const int32_t* pc = has_c ? on_device<int32_t>(who, "component", *component, at::kInt, vertices, V) : nullptr;
+    const uint8_t* vk = on_device<uint8_t>(who, "vertex_keep", vertex_keep, at::kBool, vertices, V);
+    const int32_t* pvo = on_device<int32_t>(who, "voff", voff, at::kInt, vertices, V);
+    const int32_t* pfo = on_device<int32_t>(who, "foff", foff, at::kInt, vertices, T);
+    auto of = vertices.options(), oi = faces.options();
+    Tensor vout = at::empty({V2, 3}, of), fout = at::empty({T2, 3}, oi), wout = at::empty({has_w ? V2 : 0}, of), ftout = at::empty({C, has_f ? V2 : 0}, of);
+    Tensor nout = at::empty({has_n ? V2 : 0, 3}, of), nvout = at::empty({has_nv ? V2 : 0}, of.dtype(at::kBool));
+    Tensor eout = at::empty({has_e ? V2 : 0}, of.dtype(at::kLong)), cout = at::empty({has_c ? V2 : 0}, oi);
+    Tensor vindex = at::empty({V2}, oi), findex = at::empty({T2}, oi);
+    check(be_mesh_select_emit(vertices.data_ptr<float>(), faces.data_ptr<int32_t>(), V, T, pw, pf, (int)C, pn, pnv, pe, pc, vk, pvo, pfo, V2, T2,
+                              vout.data_ptr<float>(), fout.data_ptr<int32_t>(), has_w ? wout.data_ptr<float>() : nullptr,
+                              pf ? ftout.data_ptr<float>() : nullptr, has_n ? nout.data_ptr<float>() : nullptr,
+                              has_nv ? reinterpret_cast<uint8_t*>(nvout.data_ptr<bool>()) : nullptr, has_e ? eout.data_ptr<int64_t>() : nullptr,
+                              has_c ? cout.data_ptr<int32_t>() : nullptr, vindex.data_ptr<int32_t>(), findex.data_ptr<int32_t>(), stream_of(vertices)),
+          "be_mesh_select_emit");
+    return {vout, fout, wout, ftout, nout, nvout, eout, cout, vindex, findex};
+}
+
 // depth registration: normal [3,H,W] of depth [H,W]; cam [4] a CPU float32 tensor as for unproject
 Tensor depth_normals(const Tensor& depth, const Tensor& cam, int64_t step, double max_jump, int64_t scale, int64_t top, int64_t left) {
     depth_map("depth_normals", depth, "depth", "[H,W]");
@@ -1086,6 +1203,13 @@ TORCH_LIBRARY(be, m) {
     m.def("tsdf_mesh(Tensor D, Tensor W, Tensor Fm, Tensor origin, Tensor voxel, float min_weight, bool normals) -> Tensor[]");
     m.def("mesh_raster(Tensor vertices, Tensor faces, Tensor? weight, Tensor? feat, Tensor? normal, Tensor? normal_valid, Tensor cam_dst, "
           "Tensor pose, float near, int cull, int Ho, int Wo, bool want_bary) -> Tensor[]");
+    m.def("mesh_components(Tensor faces, int V) -> Tensor[]");
+    m.def("mesh_components_stats(Tensor vertices, Tensor faces, Tensor component, int Kcap) -> Tensor[]");
+    m.def("mesh_components_decide(Tensor triangles, Tensor area_q, Tensor total, int min_triangles, float min_area, bool largest, "
+          "Tensor? component) -> Tensor[]");
+    m.def("mesh_select_count(Tensor faces, Tensor vertex_keep) -> Tensor[]");
+    m.def("mesh_select(Tensor vertices, Tensor faces, Tensor? weight, Tensor? feat, Tensor? normal, Tensor? normal_valid, Tensor? edge, "
+          "Tensor? component, Tensor vertex_keep, Tensor voff, Tensor foff, int V2, int T2) -> Tensor[]");
     m.def("tsdf_raycast(Tensor D, Tensor W, Tensor Fm, Tensor origin, Tensor voxel, Tensor cam_dst, Tensor pose, int Ho, int Wo, float z_near, "
           "float step, int n) -> (Tensor, Tensor, Tensor)");
     m.def("depth_normals(Tensor depth, Tensor cam, int step, float max_jump, int scale, int top, int left) -> Tensor");
@@ -1160,6 +1284,11 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("exclusive_scan", exclusive_scan);
     m.impl("tsdf_mesh", tsdf_mesh);
     m.impl("mesh_raster", mesh_raster);
+    m.impl("mesh_components", mesh_components);
+    m.impl("mesh_components_stats", mesh_components_stats);
+    m.impl("mesh_components_decide", mesh_components_decide);
+    m.impl("mesh_select_count", mesh_select_count);
+    m.impl("mesh_select", mesh_select);
     m.impl("depth_normals", depth_normals);
     m.impl("icp_linearize", icp_linearize);
     m.impl("fill_nearest", fill_nearest);

@@ -395,6 +395,57 @@ int be_mesh_raster_f32(const float* vertices, int64_t V, const int32_t* faces, i
                        int Ho, int Wo, float* depth_out, int32_t* face_out, float* weight_out, float* feat_out, float* normal_out,
                        uint8_t* normal_valid_out, float* bary_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The connected components of a mesh (vertices [V,3], faces [T,3] int32), their sizes, a decision per component, and the compaction
+ * of a mesh to the vertices and faces that stay.  be_hip/components.py is the statement and the kernels equal it bit for bit: every
+ * output is a function of the mesh alone.  Two vertices are connected when a chain of faces joins them (one shared vertex is
+ * enough).  A face with an index outside [0, V) is ignored: it links nothing, counts nowhere, has face_component -1 and is never
+ * kept.  0 <= V, T < 2^31 everywhere; nothing synchronises with the host; a repeated run gives the same bits.
+ *
+ * be_mesh_components_i32: label [V] = the least vertex index of the vertex's component, component [V] = the component's dense id
+ * 0..K-1 in increasing order of label, face_component [T] = component[faces[3 t]], *total (int64, on the device) = K.  A lock-free
+ * union-find: parent[v] = v; one thread per face unites (i0, i1) and (i1, i2), a union being atomicMin(&parent[hi], lo) on the two
+ * roots, retried with the value it lost to, which is strictly smaller - no thread waits for another -; one thread per vertex walks
+ * to its root; be_exclusive_scan_u8_i32 over the root flags numbers the components.  workspace: 8-byte aligned,
+ * be_mesh_components_workspace_bytes(V) bytes (0: bad V).
+ *
+ * be_mesh_components_stats: triangles, nvertices [Kcap] int32 and area_q [Kcap] int64 per dense id, Kcap >= K (the elements from K
+ * on are left 0).  The area of a face in float32, one rounding per operation, no fused multiply-add: u = b - a, v = c - a,
+ * n = u x v (each component x y - z w), A = 0.5f * sqrtf((nx nx + ny ny) + nz nz), 0 when not finite, at most 2^(62 - BE_COMPONENTS_AREA_BITS) = 2^22;
+ * q = (int64)(A * 2^BE_COMPONENTS_AREA_BITS); area_q = the integer sum of q.  Integer atomics, the lanes of a wave that share a
+ * component combined first.
+ *
+ * be_mesh_components_decide: keep [Kcap] uint8, written for k < min(*total, Kcap): triangles >= min_triangles and area_q >=
+ * (int64)((double) min_area * 2^BE_COMPONENTS_AREA_BITS) (clamped to 2^63 - 1); largest != 0: of those only the one with the most
+ * triangles, the lowest id on a tie (a 64-bit atomicMax of (triangles << 32) | (0xffffffff - k)).  K is read on the device, so a
+ * caller that sized the arrays by V needs no read-back.  vertex_keep [V] (NULL: not wanted) = keep[component[v]].  workspace:
+ * 8-byte aligned, BE_COMPONENTS_DECIDE_WORKSPACE_BYTES.
+ *
+ * be_mesh_select_count: voff [V] / foff [T] int32 = the exclusive prefix sums of vertex_keep != 0 and of "the face's three indices
+ * are in range and kept", totals [2] int64 on the device = (V', T').  workspace: 8-byte aligned, be_mesh_select_workspace_bytes(V,
+ * T).  The caller reads totals (the one synchronisation a result of variable length costs), allocates and calls
+ * be_mesh_select_emit with the same mesh, vertex_keep, voff, foff and V2 = V', T2 = T': the kept vertices in their order with every
+ * per-vertex array given (weight [V], feat [C,V] -> [C,V2], normal [V,3], normal_valid [V] uint8, edge [V] int64, component [V]
+ * int32; an input and its output are both NULL or both given), the kept faces in their order with their indices renumbered,
+ * vertex_index [V2] and face_index [T2] int32 = the old positions.  Every output element is written exactly once. */
+#define BE_COMPONENTS_AREA_BITS 40
+#define BE_COMPONENTS_DECIDE_WORKSPACE_BYTES 8
+size_t be_mesh_components_workspace_bytes(int64_t V);
+int be_mesh_components_i32(const int32_t* faces, int64_t V, int64_t T, int32_t* label, int32_t* component, int32_t* face_component,
+                           int64_t* total, void* workspace, size_t workspace_bytes, void* stream);
+int be_mesh_components_stats(const float* vertices, const int32_t* faces, int64_t V, int64_t T, const int32_t* component, int64_t Kcap,
+                             int32_t* triangles, int32_t* nvertices, int64_t* area_q, void* stream);
+int be_mesh_components_decide(const int32_t* triangles, const int64_t* area_q, const int64_t* total, int64_t Kcap, int64_t min_triangles,
+                              float min_area, int largest, uint8_t* keep, const int32_t* component, int64_t V, uint8_t* vertex_keep,
+                              void* workspace, size_t workspace_bytes, void* stream);
+size_t be_mesh_select_workspace_bytes(int64_t V, int64_t T);
+int be_mesh_select_count(const int32_t* faces, int64_t V, int64_t T, const uint8_t* vertex_keep, int32_t* voff, int32_t* foff,
+                         int64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
+int be_mesh_select_emit(const float* vertices, const int32_t* faces, int64_t V, int64_t T, const float* weight, const float* feat, int C,
+                        const float* normal, const uint8_t* normal_valid, const int64_t* edge, const int32_t* component,
+                        const uint8_t* vertex_keep, const int32_t* voff, const int32_t* foff, int64_t V2, int64_t T2, float* vertices_out,
+                        int32_t* faces_out, float* weight_out, float* feat_out, float* normal_out, uint8_t* normal_valid_out,
+                        int64_t* edge_out, int32_t* component_out, int32_t* vertex_index, int32_t* face_index, void* stream);
+
 /* Depth registration: the two kernels of a point-to-plane ICP on depth maps; the loop around them is be_hip/registration.py.
  * Lattice, camera and pose arguments are be_reproject_f32's; all per-sample arithmetic is fp32, one rounding per operation.
  *
