@@ -705,10 +705,42 @@ void k_wino_gemm(GemmArgs a) {
 // additions are scalar (5 s_bcnt1_i32_b64, the table look-ups) in the DMA block and the boundary block.
 //   <0, 0, 1>  180 VGPRs, 0 AGPRs, scratch 0, no VGPR spills, 94 SGPR spills, 21.5 KB of code, two workgroups per CU
 //              (with the segment chosen by selects per piece instead of one branch: 181 VGPRs and 12 B of scratch - not kept)
-template <int EPI, int ROWS = 0, int EXT = 0>
+// Round 16, WN: the wave grid as a template parameter.  WN = 2 is the 2x2 grid above (wave tile 64 x 64: waves (wm, 0) and (wm, 1)
+// read and split the same 64 A rows, so every A value is split twice per workgroup); WN = 1 stacks the four waves in M (wave w owns
+// rows 32 w .. 32 w + 31 and all 128 columns: ONE A fragment and one split8 per chunk, 3 x 4 B fragment reads, four 32x32
+// accumulators).  No result bit moves: product p = g / 4 still goes into accumulator g % 4 in the order lo.hi hi.lo mid.mid mid.hi
+// hi.mid hi.hi from the same pieces, K ascending from a zero accumulator with the second segment behind the first - only WHICH wave
+// holds an element changes (tests/test_wino_wave_grid.py: both grids against float64 and against each other).  The ring, the 5 DMA
+// pieces per wave and chunk (wave w's A pieces 2 w, 2 w + 1 are now its own rows), vmcnt(5), the barrier per chunk, the two register
+// sets, the boundary block behind both bodies, the block map, GemmArgs and the host's group search are the ones above.  The default
+// path (<0, 0, 0>, <0, 0, 1>) and the raw-store row GEMM <0, 1, 0> run WN = 1; BE_WINO_WAVES22=1 (read once per process) puts them
+// back on WN = 2, round 12's loop (hipcc -S against the parent build: the same instruction sequence from the first MFMA to the
+// last, both bodies and the boundary block between them; the prologue is 3-5 instructions shorter, register numbers differ).  <1, 1> (fc.1, the one-set loop) stays on WN = 2: its WN = 1
+// form was not measured.  The emitted loop of WN = 1 (hipcc -S, gfx950, read by hand; both bodies alike, the three instantiations alike):
+//   [vmcnt(5)] s_barrier, 5 global_load_lds_dwordx4 + their scalar address arithmetic
+//   gap 0       MFMA, the 2 ds_read_b128 of A (and the 3 v_add_u32 of the slot's addresses)
+//   gaps 1-6    MFMA, 2 ds_read_b128 of B each (plane (g - 1) / 2, column blocks 2 ((g - 1) % 2) and the next)
+//   gaps 7-9    MFMA alone
+//   gap 10      MFMA, s_waitcnt lgkmcnt(0) (the youngest read is three MFMAs old), half A of pair unit 0: 6 VALU + 1 s_nop
+//   gaps 11-17  MFMA, half B (5 VALU + s_nop) and half A (6 VALU + s_nop) in turn
+//   gaps 18-23  MFMA alone
+//   per chunk and wave 24 MFMAs, 14 ds_read_b128 (2x2: 10), 44 VALU + 8 s_nop of split (2x2: 88 + 16), 5 DMA pieces; consecutive MFMAs
+//   write different accumulators (v[48:63] v[32:47] v[16:31] v[0:15] in turn); no v_pk_* f32 instruction, no v_mov of a piece, no
+//   scratch access in the loop; 64 stores per wave in either boundary form, as on the 2x2 grid.
+// Compiler report, WN = 1 [WN = 2 of this build], LDS 80 KB, two workgroups per CU in every case:
+//   <0, 0, 0>  202 VGPRs [179], 0 AGPRs, scratch 0, no VGPR spills, 18 SGPR spills [76], 14.1 KB of code [18.3]
+//   <0, 0, 1>  203 VGPRs [180], 0 AGPRs, scratch 0, no VGPR spills, 32 SGPR spills [94], 17.2 KB [21.0]
+//   <0, 1, 0>  218 VGPRs [210], 0 AGPRs, scratch 0, no VGPR spills,  0 SGPR spills [15], 12.5 KB [14.9]
+//   <1, 1, 0>  WN = 2 only: 180 VGPRs, scratch 0, no VGPR spills, 25 SGPR spills, 41.0 KB
+// What it bought, and what it did not (DESIGN 3.1 "Round 16", profiles/r21_wave_grid_*): half the split instructions, and the GEMM
+// family 4.24 -> 4.16 ms per 8192-patch step (-1.9 %, the second-segment kernel -2.6 %, the plain one -0.6 %) - a quarter of what
+// the vector-issue budget promised.
+template <int EPI, int ROWS = 0, int EXT = 0, int WN = 2>
 __global__ __launch_bounds__(256, 2)
 void k_wino_gemm_ps(GemmArgs a) {
+    static_assert(WN == 1 || WN == 2, "the four waves form a 4x1 (WN = 1) or a 2x2 (WN = 2) grid");
     constexpr int BM = 128, BKT = 16;
+    constexpr int NI = WN == 1 ? 1 : 2, NJ = 4 / NI;    // a wave's 32-row A fragments and 32-column accumulators: NI x NJ = 4
     constexpr int ABYTES = BM * BKT * 4, BBYTES = PS_BLOCK * 2, STAGE = ABYTES + BBYTES;   // 8 KB + 12 KB
     constexpr int NS = PS_STAGES;
     extern __shared__ __attribute__((aligned(16))) float smem_w[];
@@ -738,7 +770,8 @@ void k_wino_gemm_ps(GemmArgs a) {
     const int n0 = n_tile * 128, row_base = m_tile * (ROWS ? a.mrows : BM);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int wm = wave >> 1, wn = wave & 1;
+    // the wave's tile: rows row0 .. row0 + 32 NI - 1, columns col0 .. col0 + 32 NJ - 1 of the 128 x 128 workgroup tile
+    const int row0 = WN == 1 ? wave * 32 : (wave >> 1) * 64, col0 = WN == 1 ? 0 : (wave & 1) * 64;
     const int li = lane & 31, lh = lane >> 5;
     // A staging as in k_wino_gemm: wave w fills pieces 2w, 2w+1 of the A tile, lane -> (row lane >> 2, swizzled quad)
     const int srow = lane >> 2, sq = (lane & 3) ^ ((lane >> 4) & 3);
@@ -765,16 +798,17 @@ void k_wino_gemm_ps(GemmArgs a) {
         x2t = reinterpret_cast<const char*>(a.x2 + (int64_t)row_base * a.lda2);
         w2t = reinterpret_cast<const char*>(a.w2) + (int64_t)n_tile * a.kext * BBYTES + lane * 16;
     }
-    // fragment reads: A row 64 wm + 32 i + li, quads 2 lh, 2 lh + 1 (swizzled as stored); B plane p, row 64 wn + 32 j + li, half lh
+    // fragment reads: A row row0 + 32 i + li, quads 2 lh, 2 lh + 1 (swizzled as stored); B plane p, row col0 + 32 j + li, half lh
+    // (row0, col0 and 32 j are multiples of 32: the same address function of li and lh on either wave grid, conflict-free)
     const int fsw = (li >> 2) & 3;
-    const int a_fr0 = ((wm * 64 + li) * BKT + 4 * ((2 * lh) ^ fsw)) * 4;
-    const int a_fr1 = ((wm * 64 + li) * BKT + 4 * ((2 * lh + 1) ^ fsw)) * 4;
-    const int b_fr = ABYTES + (wn * 64 + li) * 32 + ps_slot(li, lh) * 16;
-    f32x16 acc[2][2];
+    const int a_fr0 = ((row0 + li) * BKT + 4 * ((2 * lh) ^ fsw)) * 4;
+    const int a_fr1 = ((row0 + li) * BKT + 4 * ((2 * lh + 1) ^ fsw)) * 4;
+    const int b_fr = ABYTES + (col0 + li) * 32 + ps_slot(li, lh) * 16;
+    f32x16 acc[NI][NJ];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < NI; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
     int lz = 0, lk = 0, l_buf = 0;                     // (problem, chunk) of the next DMA and its ring slot
@@ -819,48 +853,58 @@ void k_wino_gemm_ps(GemmArgs a) {
         }                                                                                                       \
         l_buf = (l_buf + 1) % NS;                                                                               \
     } while (0)
-    const unsigned y_off = (unsigned)((wm * 64 + 4 * lh) * a.ldy + wn * 64 + li) * 4u;
-    float bias_v[2] = {0.f, 0.f};
+    const unsigned y_off = (unsigned)((row0 + 4 * lh) * a.ldy + col0 + li) * 4u;
+    float bias_v[NJ] = {};
     if (EPI) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int c = n0 + wn * 64 + j * 32 + li;
+        for (int j = 0; j < NJ; ++j) {
+            const int c = n0 + col0 + j * 32 + li;
             bias_v[j] = (a.bias && c < a.N) ? a.bias[c] : 0.0f;
         }
     }
     // two sets of pieces: chunk c's MFMAs read set c & 1 while chunk c + 1's fragments are read and split into the other set, one
     // piece of that work in every gap between two MFMAs (PS_CHUNK).  The set is a compile-time parameter of the body (a run-time
     // index would send the pieces to scratch), so the body is compiled once per set.
-    u32x4 ap[2][3][2];                                 // [set][hi, mid, lo][i], one dword per pair unit
-    bf16x8 bp[2][3][2];                                // [set][hi, mid, lo][j]
+    u32x4 ap[2][3][NI];                                // [set][hi, mid, lo][i], one dword per pair unit
+    bf16x8 bp[2][3][NJ];                               // [set][hi, mid, lo][j]
     int r_buf = 0;                                     // ring slot whose fragments are read next
     // One chunk: 24 groups, each closed by a sched_barrier(0) (nothing crosses it, so the order below is the emitted order).
-    // Group g issues MFMA g - product p = g / 4 (lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi), accumulator (i, j) = ((g / 2) % 2, g % 2):
-    // consecutive MFMAs never share an accumulator - and, for chunk + 1 out of ring slot r_buf into set S ^ 1:
+    // Group g issues MFMA g - product p = g / 4 (lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi), accumulator (i, j) = ((g % 4) / NJ, g % NJ):
+    // consecutive MFMAs never share an accumulator - and, for chunk + 1 out of ring slot r_buf into set S ^ 1,
+    // on the 2x2 grid (two A fragments, 3 x 2 B fragments, two split8):
     //   g = 0, 1    the two fp32 A fragment reads (quads 2 lh, 2 lh + 1) of i = g
     //   g = 2..4    the two reads (j = 0, 1) of B plane g - 2
     //   g = 8..23   one half of one of the eight pair units of the two split8 (unit u = (g - 8) / 2: i = u / 4; half A, then half B)
+    // on the 4x1 grid (one A fragment, 3 x 4 B fragments, one split8):
+    //   g = 0       the two fp32 A fragment reads
+    //   g = 1..6    two B reads each: plane (g - 1) / 2, j = 2 ((g - 1) % 2) and the next
+    //   g = 10..17  one half of one of the four pair units of the split8 (unit u = (g - 10) / 2; half A, then half B)
     // The LDS reads are plain loads and the compiler places their wait.  It only ever emits lgkmcnt(0), in front of the first split
     // group: hence the reads two to a gap and early, so that the youngest is three MFMAs old when the wait comes.
+    constexpr int G_SPLIT = WN == 1 ? 10 : 8;          // the first split group
 #define PS_CHUNK(S)                                                                                             \
     do {                                                                                                        \
         constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};                                   \
         const char* sb_ = lds + r_buf * STAGE;                                                                  \
-        f32x4 af_[2][2];                               /* [quad][i] */                                          \
-        float r0_[8], r1_[8];                                                                                   \
+        f32x4 af_[2][NI];                              /* [quad][i] */                                          \
+        float r0_[4 * NI], r1_[4 * NI];                                                                         \
         _Pragma("unroll") for (int g_ = 0; g_ < 24; ++g_) {                                                     \
-            acc[(g_ >> 1) & 1][g_ & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                               \
-                __builtin_bit_cast(bf16x8, ap[S][PA[g_ >> 2]][(g_ >> 1) & 1]), bp[S][PB[g_ >> 2]][g_ & 1],      \
-                acc[(g_ >> 1) & 1][g_ & 1], 0, 0, 0);                                                           \
-            if (g_ < 2) {                                                                                       \
+            acc[(g_ & 3) / NJ][g_ % NJ] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                              \
+                __builtin_bit_cast(bf16x8, ap[S][PA[g_ >> 2]][(g_ & 3) / NJ]), bp[S][PB[g_ >> 2]][g_ % NJ],     \
+                acc[(g_ & 3) / NJ][g_ % NJ], 0, 0, 0);                                                          \
+            if (g_ < NI) {                                                                                      \
                 af_[0][g_] = *reinterpret_cast<const f32x4*>(sb_ + a_fr0 + g_ * 32 * BKT * 4);                  \
                 af_[1][g_] = *reinterpret_cast<const f32x4*>(sb_ + a_fr1 + g_ * 32 * BKT * 4);                  \
             }                                                                                                   \
-            if (g_ >= 2 && g_ < 5)                                                                              \
+            if (WN == 2 && g_ >= 2 && g_ < 5)                                                                   \
                 _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                                \
-                    bp[(S) ^ 1][g_ - 2][j_] = *reinterpret_cast<const bf16x8*>(sb_ + b_fr + (g_ - 2) * 4096 + j_ * 32 * 32); \
-            if (g_ >= 8) {                                                                                      \
-                const int u_ = (g_ - 8) >> 1, i_ = u_ >> 2, e_ = u_ & 3;                                        \
+                    bp[(S) ^ 1][g_ - 2][j_ % NJ] = *reinterpret_cast<const bf16x8*>(sb_ + b_fr + (g_ - 2) * 4096 + j_ * 32 * 32); \
+            if (WN == 1 && g_ >= 1 && g_ < 7)                                                                   \
+                _Pragma("unroll") for (int j_ = 2 * ((g_ - 1) & 1); j_ < 2 * ((g_ - 1) & 1) + 2; ++j_)          \
+                    bp[(S) ^ 1][(g_ - 1) >> 1][j_ % NJ] =                                                       \
+                        *reinterpret_cast<const bf16x8*>(sb_ + b_fr + ((g_ - 1) >> 1) * 4096 + j_ * 32 * 32);   \
+            if (g_ >= G_SPLIT && g_ < G_SPLIT + 8 * NI) {                                                       \
+                const int u_ = (g_ - G_SPLIT) >> 1, i_ = u_ >> 2, e_ = u_ & 3;                                  \
                 if ((g_ & 1) == 0) {                                                                            \
                     unsigned h_, m_;                                                                            \
                     be::bf6::split_pair_a(af_[e_ >> 1][i_][(2 * e_) & 3], af_[e_ >> 1][i_][(2 * e_ + 1) & 3], h_, m_, r0_[u_], r1_[u_]); \
@@ -880,15 +924,15 @@ void k_wino_gemm_ps(GemmArgs a) {
 #define PS_FRAGS0(SLOT)                                                                                         \
     do {                                                                                                        \
         const char* sb_ = lds + (SLOT) * STAGE;                                                                 \
-        f32x4 af_[2][2];                                                                                        \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                      \
+        f32x4 af_[2][NI];                                                                                       \
+        _Pragma("unroll") for (int i_ = 0; i_ < NI; ++i_) {                                                     \
             af_[0][i_] = *reinterpret_cast<const f32x4*>(sb_ + a_fr0 + i_ * 32 * BKT * 4);                      \
             af_[1][i_] = *reinterpret_cast<const f32x4*>(sb_ + a_fr1 + i_ * 32 * BKT * 4);                      \
         }                                                                                                       \
         _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                        \
-            _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                                    \
+            _Pragma("unroll") for (int j_ = 0; j_ < NJ; ++j_)                                                   \
                 bp[0][p_][j_] = *reinterpret_cast<const bf16x8*>(sb_ + b_fr + p_ * 4096 + j_ * 32 * 32);        \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                      \
+        _Pragma("unroll") for (int i_ = 0; i_ < NI; ++i_) {                                                     \
             bf16x8 h_, m_, l_;                                                                                  \
             split8(af_[0][i_], af_[1][i_], h_, m_, l_);                                                         \
             ap[0][0][i_] = __builtin_bit_cast(u32x4, h_);                                                       \
@@ -937,24 +981,24 @@ void k_wino_gemm_ps(GemmArgs a) {
             }
             if (zrow + BM <= a.M && n0 + 128 <= a.N) {
 #pragma unroll
-                for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < NI; ++i)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
                         float* yr = reinterpret_cast<float*>(yt + (size_t)ro * a.ldy * 4 + y_off);
-                        { PS_VALUE(0) yr[0] = v_; }
-                        { PS_VALUE(1) yr[32] = v_; }
+#pragma unroll
+                        for (int j = 0; j < NJ; ++j) { PS_VALUE(j) yr[32 * j] = v_; }
                     }
             } else {
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const bool c_ok = n0 + wn * 64 + j * 32 + li < a.N;
+                for (int j = 0; j < NJ; ++j) {
+                    const bool c_ok = n0 + col0 + j * 32 + li < a.N;
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
+                    for (int i = 0; i < NI; ++i)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
-                            if (c_ok && zrow + wm * 64 + 4 * lh + ro < a.M) {
+                            if (c_ok && zrow + row0 + 4 * lh + ro < a.M) {
                                 PS_VALUE(j)
                                 reinterpret_cast<float*>(yt + (size_t)ro * a.ldy * 4 + y_off)[j * 32] = v_;
                             }
@@ -963,9 +1007,9 @@ void k_wino_gemm_ps(GemmArgs a) {
             }
 #undef PS_VALUE
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < NI; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
+                for (int j = 0; j < NJ; ++j)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
             ck = 0; ++cz;
@@ -984,9 +1028,9 @@ void k_wino_gemm_ps(GemmArgs a) {
 #pragma unroll
                 for (int p = 0; p < 6; ++p)
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
+                    for (int i = 0; i < NI; ++i)
 #pragma unroll
-                        for (int j = 0; j < 2; ++j)
+                        for (int j = 0; j < NJ; ++j)
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ap[0][PA[p]][i]), bp[0][PB[p]][j],
                                                                                 acc[i][j], 0, 0, 0);
                 PS_FRAGS0(r_buf);                      // chunk + 1's pieces, under this chunk's MFMAs
@@ -1285,13 +1329,25 @@ bool wino_large(int64_t n, int cout) {
 // ascending, then Vx's, from a zero accumulator (k_wino_gemm_ps<0, 0, 1>) - a block's downsample inside conv2's GEMMs.  Vx: the
 // transform of the block's input (cin_ext channels) in V's layout; ds_planes: the planes of be_wino_ds_pack_f32.  tm_force >= 0
 // picks the layout (tile-major 1 / plane-major 0) whatever the batch size.
+// A/B knob: BE_WINO_WAVES22=1 puts the two-set loops back on the 2x2 wave grid of rounds 8-15 (the same bits; read once per process)
+bool ps_waves22() {
+    static const bool on = be::knob_on("BE_WINO_WAVES22");
+    return on;
+}
+
+// one instantiation of k_wino_gemm_ps: its dynamic-LDS cap raised once per device, then the launch
+template <int EPI, int ROWS, int EXT, int WN>
+int launch_ps(const GemmArgs& g, hipStream_t s, unsigned grid) {
+    constexpr size_t lds = (size_t)PS_STAGES * (128 * 16 * 4 + PS_BLOCK * 2);    // stages of 8 KB A + 12 KB B
+    static be::DeviceFlags attr_set{};                          // (thread-safe)
+    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm_ps<EPI, ROWS, EXT, WN>), lds, attr_set)) return rc_;
+    hipLaunchKernelGGL((k_wino_gemm_ps<EPI, ROWS, EXT, WN>), dim3(grid), dim3(256), lds, s, g);
+    return BE_OK;
+}
+
 int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, int cin, int cout, hipStream_t s,
                   const float* Vx = nullptr, const float* ds_planes = nullptr, int cin_ext = 0, int tm_force = -1) {
-    constexpr size_t lds = (size_t)PS_STAGES * (128 * 16 * 4 + PS_BLOCK * 2);    // stages of 8 KB A + 12 KB B
-    static be::DeviceFlags attr_set{}, attr_set_ext{};          // dynamic-LDS cap raised once per device (thread-safe)
-    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm_ps<0, 0>), lds, attr_set)) return rc_;
-    if (Vx)
-        if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm_ps<0, 0, 1>), lds, attr_set_ext)) return rc_;
+    const bool w22 = ps_waves22();
     const int64_t rows = (int64_t)TPI * n;
     const bool tm = tm_force >= 0 ? tm_force != 0 : wino_large(n, cout);
     const int m_tiles = (int)((rows + 127) / 128), n_tiles = (cout + 127) / 128, kchunks = cin / 16;
@@ -1344,13 +1400,13 @@ int wino_gemms_ps(const float* V, const float* packed_w, float* M, int64_t n, in
         be::ProfileScope prof(s, BE_KERNEL_WINO_GEMM, 2.0 * rows * cout * ((double)NPOS * cin + ext * cin_ext),
                               4.0 * rows * ((double)NPOS * (cin + cout) + ext * cin_ext) + 6.0 * n_tiles * 128 * ((double)NPOS * cin + ext * cin_ext),
                               2.0 * m_tiles * n_tiles * 128.0 * 128.0 * ((double)NPOS * cin + ext * cin_ext));
-        hipLaunchKernelGGL((k_wino_gemm_ps<0, 0, 1>), dim3(grid), dim3(256), lds, s, g);
+        if (int rc_ = w22 ? launch_ps<0, 0, 1, 2>(g, s, grid) : launch_ps<0, 0, 1, 1>(g, s, grid)) return rc_;
     } else {
         // (FLOPs in fp32-equivalent products: what the layer computes, not the six bf16 products the matrix pipe issues)
         be::ProfileScope prof(s, BE_KERNEL_WINO_GEMM, (double)NPOS * 2.0 * rows * cin * cout,
                               (double)NPOS * 4.0 * ((double)rows * cin + (double)rows * cout) + (double)NPOS * 6.0 * cin * n_tiles * 128,
                               (double)NPOS * 2.0 * m_tiles * n_tiles * 128.0 * 128.0 * cin);
-        hipLaunchKernelGGL((k_wino_gemm_ps<0, 0>), dim3(grid), dim3(256), lds, s, g);
+        if (int rc_ = w22 ? launch_ps<0, 0, 0, 2>(g, s, grid) : launch_ps<0, 0, 0, 1>(g, s, grid)) return rc_;
     }
     return be::check_launch("be_wino_conv3x3_6x6_f32(gemm, split bf16, pre-split weights)");
 }
@@ -1475,19 +1531,6 @@ bool be::rows_bf6_enabled() {
     return !f32;
 }
 
-namespace {
-
-template <int EPI>
-int launch_rows_ps(const GemmArgs& g, hipStream_t s, unsigned grid) {
-    constexpr size_t lds = (size_t)PS_STAGES * (128 * 16 * 4 + PS_BLOCK * 2);
-    static be::DeviceFlags attr_set{};                          // dynamic-LDS cap raised once per device (thread-safe)
-    if (int rc_ = be::ensure_dynamic_lds(reinterpret_cast<const void*>(&k_wino_gemm_ps<EPI, 1>), lds, attr_set)) return rc_;
-    hipLaunchKernelGGL((k_wino_gemm_ps<EPI, 1>), dim3(grid), dim3(256), lds, s, g);
-    return BE_OK;
-}
-
-}  // namespace
-
 int be::gemm_rows_bf6(const float* x, int64_t M, int K, const float* planes, int N, const float* bias, const float* res, int act,
                       float* y, int ldy, void* stream) {
     BE_REQUIRE(x && planes && y, "be_gemm_rows_bf6_f32: null pointer");
@@ -1523,7 +1566,10 @@ int be::gemm_rows_bf6(const float* x, int64_t M, int K, const float* planes, int
         // (FLOPs in fp32-equivalent products, as the Winograd GEMMs)
         be::ProfileScope prof(s, BE_KERNEL_GEMM_ROWS, 2.0 * M * K * N, 4.0 * ((double)M * K + (double)M * N) + 6.0 * K * n_tiles * 128,
                               2.0 * tiles * n_tiles * 128.0 * 128.0 * K);
-        const int rc = (bias || res || act) ? launch_rows_ps<1>(g, s, grid) : launch_rows_ps<0>(g, s, grid);
+        // (<1, 1>, fc.1, keeps its one-set loop on the 2x2 grid; the raw-store GEMM follows the Winograd GEMMs' grid)
+        const int rc = (bias || res || act) ? launch_ps<1, 1, 0, 2>(g, s, grid)
+                       : ps_waves22()       ? launch_ps<0, 1, 0, 2>(g, s, grid)
+                                            : launch_ps<0, 1, 0, 1>(g, s, grid);
         if (rc) return rc;
     }
     return be::check_launch("be_gemm_rows_bf6_f32");
