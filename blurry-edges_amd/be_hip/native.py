@@ -197,6 +197,14 @@ _SIGNATURES = {
     "be_mesh_select_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "be_mesh_select_count": (C.c_int, [_P, C.c_int64, C.c_int64] + [_P] * 5 + [C.c_size_t, _P]),
     "be_mesh_select_emit": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int] + [_P] * 7 + [C.c_int64, C.c_int64] + [_P] * 10 + [_P]),
+    "be_mesh_cluster_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "be_mesh_cluster_f32": (C.c_int, [_P, _P, C.c_int64] + [C.POINTER(C.c_float)] * 2 + [_P] * 5 + [C.c_size_t, _P]),
+    "be_mesh_simplify_sum_rows": (C.c_int, [C.c_int, C.c_int]),
+    "be_mesh_simplify_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "be_mesh_simplify_count": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P] + [C.POINTER(C.c_float)] * 2
+                               + [_P, C.c_int] + [_P] * 5 + [C.c_size_t, _P]),
+    "be_mesh_simplify_emit": (C.c_int, [_P, _P, C.c_int64, C.c_int64] + [C.POINTER(C.c_float)] * 2 + [_P] * 4 + [C.c_int, C.c_int, _P, _P,
+                                                                                                              C.c_int64, C.c_int64] + [_P] * 7 + [_P]),
     "be_depth_normals_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.c_int, C.c_float, _P, _P]),
     "be_icp_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "be_icp_linearize_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [C.POINTER(C.c_float), _P, _P, _P, C.c_int, C.c_int]
@@ -2019,6 +2027,104 @@ def mesh_decide(stats, K, min_triangles=None, min_area=None, largest=False):
         raise ValueError(f"mesh_decide: triangles int32 [{K}] and area_q int64 [{K}] on the GPU, as mesh_components returned them")
     total = torch.full((1,), K, dtype=torch.int64, device=tri.device)
     return _components_decide(tri.contiguous(), aq.contiguous(), total, mt, ma, largest, None, tri.device)[0]
+
+
+def _simplify_grid(who, cell, origin):
+    """simplify.grid's checks -> (cell, origin) as float32 numpy arrays [3], what both bindings hand to the C entry points."""
+    from . import simplify
+    c, _, o = simplify.grid(cell, origin, who)
+    return c, o
+
+
+def _cluster(m, V, cell, origin, dev):
+    """-> (label [V], cluster [V], members [V] int32 (0 from V' on), totals [2] int64 on the device = (V', overflow)); no sync."""
+    o = ops()
+    if o is not None:
+        return tuple(o.mesh_cluster(m["vertices"], m["weight"], torch.from_numpy(cell), torch.from_numpy(origin)))
+    new = _new(dev)
+    label, cluster, members = (new(V, dtype=torch.int32) for _ in range(3))
+    totals = new(2, dtype=torch.int64)
+    nbytes = lib().be_mesh_cluster_workspace_bytes(V)
+    ws = new((nbytes + 7) // 8, dtype=torch.int64)
+    check(lib().be_mesh_cluster_f32(dptr(m["vertices"]), dptr(m["weight"]), V, _fptr(cell), _fptr(origin), dptr(label), dptr(cluster), dptr(members),
+                                    dptr(totals, "totals", _I64), dptr(ws, "workspace", _I64), nbytes, stream_ptr(dev)), "be_mesh_cluster_f32")
+    return label, cluster, members, totals
+
+
+def _table_overflow(who, overflow):
+    if overflow:
+        raise RuntimeError(f"{who}: a hash table was exhausted before every key found a slot (its probe loops are bounded and do not spin); "
+                           "the result is not to be used")
+
+
+def mesh_cluster(mesh, cell, origin=(0, 0, 0)):
+    """The vertex clusters of a mesh on the GPU (a dict as mesh_field / tsdf_mesh / mesh_clean return it) under the grid of cells of
+    `cell` metres - one number or three (cX, cY, cZ) - with a corner of cell (0, 0, 0) at `origin`: the labelling alone of
+    mesh_simplify.  -> dict(label [V] int32 = the least index among the usable vertices of the vertex's cell, cluster [V] int32 =
+    the cell's dense id 0..V'-1 in increasing order of label, members [V'] int32, V (a python int: V', the one read-back)); -1 for
+    an unusable vertex (a position that is not finite or lies 2^20 cells or more from the origin, a weight whose quantised
+    value is 0).  A hash table of vertex indices (atomicCAS on an empty slot, atomicMin on an equal cell; every probe loop is
+    bounded), the scan for the dense ids: the same bits on every run.  simplify.cluster is the host statement, bit for bit."""
+    V, _, _, m, dev = _mesh_on_gpu("mesh_cluster", mesh)
+    cell, origin = _simplify_grid("mesh_cluster", cell, origin)
+    label, cluster, members, totals = _cluster(m, V, cell, origin, dev)
+    V2, overflow = totals.tolist()                                      # the read-back: synchronises with the stream
+    _table_overflow("mesh_cluster", overflow)
+    return dict(label=label, cluster=cluster, members=members[:V2], V=V2)
+
+
+def mesh_simplify(mesh, cell, origin=(0, 0, 0), flaps=False):
+    """The mesh made coarser by vertex clustering: every vertex falls into a cell of the grid mesh_cluster describes, every occupied
+    cell becomes ONE vertex at the weighted mean of its members (weights quantised as fuse_views quantises them, positions as 2^-24
+    of a cell, every sum an integer), and every face is re-indexed; a face with two corners in one cell, or with an unusable
+    corner, is dropped, of the faces that name the same three cells in the same winding the least index stays, and with
+    flaps=False three cells named in BOTH windings lose all their faces (back-to-back flaps of zero volume; flaps=True keeps the
+    least face of each winding).  -> the mesh with components.select's keys but vertex_index (vertices [V',3], faces [T',3] int32 in
+    their old order and corner order, weight [V'] = the mean weight, feat [C,V'], normal [V',3] = the normalised mean over the
+    members with a valid normal, normal_valid [V'], each None where the mesh holds none; edge = None: an edge id does not survive),
+    and cluster [V] int32 (the new id of every old vertex, -1: unusable), members [V'] int32, face_index [T'] int32 (the old
+    positions).  V' == 0 and T' == 0 are legal.  Two hash tables (bounded probe loops, no thread waits for another), integer
+    atomics, a count phase, ONE read-back of (V', T') and an emit phase: the same bits on every run.  simplify.simplify is the
+    host statement, bit for bit; a face index outside [0, V), which it refuses, is ignored here (finding it would cost a read-back)."""
+    V, T, C_, m, dev = _mesh_on_gpu("mesh_simplify", mesh)
+    cell, origin = _simplify_grid("mesh_simplify", cell, origin)
+    flaps = bool(flaps)
+    has = lambda k: m[k] is not None
+    normals = has("normal")
+    label, cluster, members, totals_v = _cluster(m, V, cell, origin, dev)
+    o = ops()
+    new = _new(dev)
+    if o is not None:
+        tc, to = torch.from_numpy(cell), torch.from_numpy(origin)
+        sums, fflag, foff, totals_f = o.mesh_simplify_count(m["vertices"], m["faces"], m["weight"], m["feat"], m["normal"], m["normal_valid"], tc, to,
+                                                            cluster, flaps)
+    else:
+        rows = lib().be_mesh_simplify_sum_rows(C_, int(normals))
+        sums, fflag, foff = new(rows, V, dtype=torch.int64), new(T, dtype=torch.uint8), new(T, dtype=torch.int32)
+        totals_f = new(2, dtype=torch.int64)
+        nbytes = lib().be_mesh_simplify_workspace_bytes(T)
+        ws = new((nbytes + 7) // 8, dtype=torch.int64)
+        check(lib().be_mesh_simplify_count(dptr(m["vertices"]), dptr(m["faces"]), V, T, dptr(m["weight"]), dptr(m["feat"] if C_ else None), C_,
+                                           dptr(m["normal"]), dptr(m["normal_valid"], "normal_valid", _BOOL), _fptr(cell), _fptr(origin), dptr(cluster),
+                                           int(flaps), dptr(sums, "sums", _I64), dptr(fflag, "fflag", (torch.uint8,)), dptr(foff),
+                                           dptr(totals_f, "totals", _I64), dptr(ws, "workspace", _I64), nbytes, stream_ptr(dev)),
+              "be_mesh_simplify_count")
+    V2, over_v, T2, over_f = torch.cat([totals_v, totals_f]).tolist()   # the read-back: synchronises with the stream
+    _table_overflow("mesh_simplify", over_v or over_f)
+    if o is not None:
+        v, f, w, ft, n, nv, fi = o.mesh_simplify(m["vertices"], m["faces"], tc, to, label, cluster, members, sums, C_, normals, has("weight"), fflag,
+                                                 foff, V2, T2)
+    else:
+        v, f, fi = new(V2, 3), new(T2, 3, dtype=torch.int32), new(T2, dtype=torch.int32)
+        w = new(V2) if has("weight") else None
+        ft = new(C_, V2)
+        n, nv = (new(V2, 3), new(V2, dtype=torch.bool)) if normals else (None, None)
+        check(lib().be_mesh_simplify_emit(dptr(m["vertices"]), dptr(m["faces"]), V, T, _fptr(cell), _fptr(origin), dptr(label), dptr(cluster),
+                                          dptr(members), dptr(sums, "sums", _I64), C_, int(normals), dptr(fflag, "fflag", (torch.uint8,)), dptr(foff),
+                                          V2, T2, dptr(v), dptr(f), dptr(w), dptr(ft if C_ else None), dptr(n), dptr(nv, "normal_valid", _BOOL),
+                                          dptr(fi), stream_ptr(dev)), "be_mesh_simplify_emit")
+    return dict(vertices=v, faces=f, weight=w if has("weight") else None, feat=ft if has("feat") else None, normal=n if normals else None,
+                normal_valid=nv if normals else None, edge=None, cluster=cluster, members=members[:V2], face_index=fi)
 
 
 def depth_normals(depth, cam, step=3, max_jump=0.05, scale=1, window_origin=(0, 0)):

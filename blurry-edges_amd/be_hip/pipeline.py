@@ -605,7 +605,8 @@ class DepthPipeline:
         if not isinstance(mesh, dict) or "vertices" not in mesh or "faces" not in mesh:
             raise ValueError("clean_mesh: mesh must be the dict extract_mesh returned (vertices, faces, ...)")
         V = mesh["vertices"].shape[0]
-        fixed = ("vertices", "faces", "weight", "normal", "normal_valid", "edge", "component", "components", "vertex_index", "face_index")
+        fixed = ("vertices", "faces", "weight", "normal", "normal_valid", "edge", "component", "components", "vertex_index", "face_index", "cluster",
+                 "members")                                                  # the last two: what simplify_mesh adds; they name another mesh
         maps = [k for k, t in mesh.items() if k not in fixed and isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[-1] == V]
         for k in maps:
             if mesh[k].dtype != torch.float32:
@@ -617,6 +618,37 @@ class DepthPipeline:
         res.update({k: out[k] for k in ("vertices", "faces", "weight", "normal", "normal_valid", "edge") if k in mesh})
         res.update(unpack_channels(out["feat"], channels, out["vertices"].shape[:1]))
         res.update(component=out["component"], components=out["components"])
+        return res
+
+    @torch.no_grad()
+    def simplify_mesh(self, mesh, cell, origin=(0, 0, 0), flaps=False):
+        """mesh: what extract_mesh or clean_mesh returned (or any dict of vertices [V,3], faces [T,3] int32 and per-vertex maps on
+        the GPU) -> the mesh made coarser by vertex clustering (native.mesh_simplify): every vertex falls into a cell of a regular
+        grid - `cell` metres, one number or three (cX, cY, cZ), because the voxels are per axis too; `origin` a corner of cell
+        (0, 0, 0) - and every occupied cell becomes one vertex at the weighted mean of its members, which also averages depth
+        noise.  Faces are re-indexed; those that collapse or repeat are dropped, and with flaps=False so are the back-to-back
+        pairs that name the same three cells in both windings.  The result holds the keys of `mesh` - vertices, faces, weight
+        (the mean), normal (the normalised mean), normal_valid and every [.., V] map such as shpd [3,V'] (the weighted mean) - but
+        edge, component, components, vertex_index, which do not survive, and adds cluster [V] int32 = the new id of every old
+        vertex (-1: it took no part), members [V'] int32 and face_index [T'] int32 = the old position of every face that stayed.
+        It goes straight into render_mesh, save_mesh, clean_mesh and simplify_mesh again.  Clean first: simplification keeps
+        a floater's vertex while it thins the surface around it.  One read-back."""
+        if not isinstance(mesh, dict) or "vertices" not in mesh or "faces" not in mesh:
+            raise ValueError("simplify_mesh: mesh must be the dict extract_mesh returned (vertices, faces, ...)")
+        V = mesh["vertices"].shape[0]
+        fixed = ("vertices", "faces", "weight", "normal", "normal_valid", "edge", "component", "components", "vertex_index", "face_index", "cluster",
+                 "members")
+        maps = [k for k, t in mesh.items() if k not in fixed and isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[-1] == V]
+        for k in maps:
+            if mesh[k].dtype != torch.float32:
+                raise ValueError(f"simplify_mesh: the map {k!r} must be float32, got {mesh[k].dtype}")
+        feat, channels = pack_channels(mesh, maps, V, tail=1)
+        m = dict(vertices=mesh["vertices"], faces=mesh["faces"], feat=feat, **{k: mesh.get(k) for k in ("weight", "normal", "normal_valid")})
+        out = native.mesh_simplify(m, cell, origin=origin, flaps=flaps)
+        res = {k: v for k, v in mesh.items() if k not in fixed and k not in maps}
+        res.update({k: out[k] for k in ("vertices", "faces", "weight", "normal", "normal_valid") if k in mesh})
+        res.update(unpack_channels(out["feat"], channels, out["vertices"].shape[:1]))
+        res.update(cluster=out["cluster"], members=out["members"], face_index=out["face_index"])
         return res
 
     @staticmethod

@@ -18,6 +18,7 @@ formats (argument names and defaults = utils/args.py of the reference):
                                                            (with tsdf_mesh > 0 beside them: also that volume's triangle mesh)
                                                            (with mesh_render > 0 beside them: also that mesh seen by view 0's camera)
                                                            (with mesh_min_triangles > 0 beside them: the mesh without its small components)
+                                                           (with mesh_cell beside them: the mesh simplified on cells of that size)
     ... eval --normals [--out_path DIR]                    also write every pair's surface normals (of its completed depth)
     ... eval --complete [--out_path DIR]                   also write and score every pair's depth map completed to a dense one
     ... eval --complete --complete_method diffuse          ... by edge-aware diffusion instead of the nearest sample's depth
@@ -346,7 +347,8 @@ def load_fusion(path):
     DepthPipeline.register, starting from the pose given, before the group is merged.  tsdf_dims, tsdf_origin, tsdf_voxel (and
     optionally tsdf_trunc) describe a TSDF volume (-> cfg["tsdf"]); an integer tsdf_mesh > 0 beside them (-> cfg["tsdf_mesh"]) asks
     for that volume's mesh as well, and an integer mesh_render > 0 (-> cfg["mesh_render"]) for that mesh rendered into view 0's
-    camera."""
+    camera.  mesh_cell = one number or three (cX, cY, cZ) > 0, in metres (-> cfg["mesh_cell"], three numbers), asks for that mesh
+    simplified on cells of that size."""
     from . import camera
     with np.load(path) as f:
         if "poses" not in f:
@@ -402,6 +404,17 @@ def load_fusion(path):
                 raise ValueError(f"--fuse: mesh_min_triangles cleans the mesh of the TSDF volume; {path} asks for no mesh: "
                                  "tsdf_mesh > 0 or mesh_render > 0 (beside tsdf_dims, tsdf_origin, tsdf_voxel)")
             cfg["mesh_min_triangles"] = int(n)
+        if "mesh_cell" in f:                                                # absent: the dict holds what it held before
+            from . import simplify
+            try:
+                cell = simplify.grid(np.asarray(f["mesh_cell"]).reshape(-1).tolist(), who="--fuse(mesh_cell)")[0]
+            except ValueError:
+                raise ValueError("--fuse: mesh_cell must be one number or three (cX, cY, cZ) > 0, in metres (the cells the mesh's vertices are "
+                                 f"clustered in), got {f['mesh_cell']!r}") from None
+            if not (cfg.get("tsdf_mesh", 0) > 0 or cfg.get("mesh_render", 0) > 0):
+                raise ValueError(f"--fuse: mesh_cell simplifies the mesh of the TSDF volume; {path} asks for no mesh: "
+                                 "tsdf_mesh > 0 or mesh_render > 0 (beside tsdf_dims, tsdf_origin, tsdf_voxel)")
+            cfg["mesh_cell"] = tuple(float(c) for c in cell)
         return cfg
 
 
@@ -461,6 +474,10 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     the timed region; without the key nothing changes.  With an integer mesh_min_triangles > 0 beside them the mesh is first cleaned,
     DepthPipeline.clean_mesh: its connected components of fewer triangles - the islands depth outliers leave - are dropped before
     either file is written, and mesh_{g:04d}.npz also holds component [V'] and components_triangles (every component's size).
+    With mesh_cell = one number or three (cX, cY, cZ) > 0, in metres, beside them the mesh is then simplified,
+    DepthPipeline.simplify_mesh on the grid of such cells from the volume's origin - after the cleaning, because clustering keeps a
+    floater's vertex while it thins the surface around it - before either file is written, and mesh_{g:04d}.npz holds the coarser
+    mesh with cluster, members and face_index (and no component: its ids name the mesh before).
     args.normals (not in the reference): every pair's surface normals, DepthPipeline.normals(source="complete"), go to
     {args.out_path}/normals_{j:04d}.npz (normal [3,H,W], valid), outside the timed region."""
     import data, models, utils
@@ -571,6 +588,8 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
                     if tri is not None and fcfg.get("mesh_min_triangles", 0) > 0:
                         tri = pipe.clean_mesh(tri, min_triangles=fcfg["mesh_min_triangles"])
                         cleaned = dict(components_triangles=tri.pop("components")["triangles"].cpu().numpy())
+                    if tri is not None and "mesh_cell" in fcfg:                      # after the cleaning: a floater's vertex would stay
+                        tri = pipe.simplify_mesh(tri, fcfg["mesh_cell"], origin=fcfg["tsdf"]["origin"])
                     if fcfg.get("tsdf_mesh", 0) > 0:
                         pipe.save_mesh(os.path.join(args.out_path, f"mesh_{j // len(group):04d}.ply"), tri)
                         np.savez(os.path.join(args.out_path, f"mesh_{j // len(group):04d}.npz"), **{k: v.cpu().numpy() for k, v in tri.items()},

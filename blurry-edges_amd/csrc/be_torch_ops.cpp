@@ -987,6 +987,89 @@ std::vector<Tensor> mesh_select(const Tensor& vertices, const Tensor& faces, con
     return {vout, fout, wout, ftout, nout, nvout, eout, cout, vindex, findex};
 }
 
+// ---- mesh simplification: the three steps of be_mesh_cluster_f32 / be_mesh_simplify_*, none of which synchronises with the host; the
+// one read-back between count and emit is native.py's, the same for both bindings.  cell, origin: CPU float32 tensors [3].
+static int64_t mesh_vertices(const char* who, const Tensor& vertices) {
+    fp(vertices, who);
+    TORCH_CHECK(vertices.dim() == 2 && vertices.size(1) == 3, who, ": vertices [V,3]");
+    return vertices.size(0);
+}
+
+// -> [label [V], cluster [V], members [V] int32 (0 from V' on), totals [2] int64 on the device = (V', overflow)]
+std::vector<Tensor> mesh_cluster(const Tensor& vertices, const c10::optional<Tensor>& weight, const Tensor& cell, const Tensor& origin) {
+    const char* who = "mesh_cluster";
+    const int64_t V = mesh_vertices(who, vertices);
+    const float* pw = given(weight) ? on_device<float>(who, "weight", *weight, at::kFloat, vertices, V) : nullptr;
+    auto oi = vertices.options().dtype(at::kInt), ol = vertices.options().dtype(at::kLong);
+    Tensor label = at::empty({V}, oi), cluster = at::empty({V}, oi), members = at::empty({V}, oi), totals = at::empty({2}, ol);
+    const size_t bytes = be_mesh_cluster_workspace_bytes(V);
+    TORCH_CHECK(bytes > 0, "mesh_cluster: at most 2^29 vertices");
+    Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, ol);
+    check(be_mesh_cluster_f32(vertices.data_ptr<float>(), pw, V, host_floats(cell, 3, "mesh_cluster(cell)"), host_floats(origin, 3, "mesh_cluster(origin)"),
+                              label.data_ptr<int32_t>(), cluster.data_ptr<int32_t>(), members.data_ptr<int32_t>(), totals.data_ptr<int64_t>(),
+                              ws.data_ptr<int64_t>(), bytes, stream_of(vertices)), "be_mesh_cluster_f32");
+    return {label, cluster, members, totals};
+}
+
+// -> [sums [rows,V] int64, fflag [T] uint8, foff [T] int32, totals [2] int64 on the device = (T', overflow)]
+std::vector<Tensor> mesh_simplify_count(const Tensor& vertices, const Tensor& faces, const c10::optional<Tensor>& weight, const c10::optional<Tensor>& feat,
+                                        const c10::optional<Tensor>& normal, const c10::optional<Tensor>& normal_valid, const Tensor& cell,
+                                        const Tensor& origin, const Tensor& cluster, bool flaps) {
+    const char* who = "mesh_simplify_count";
+    const int64_t V = mesh_vertices(who, vertices), T = faces.size(0);
+    mesh_faces(who, faces, V);
+    const bool has_w = given(weight), has_f = given(feat), has_n = given(normal), has_nv = given(normal_valid);
+    if (has_f) TORCH_CHECK(feat->dim() == 2 && feat->size(1) == V, "mesh_simplify_count: feat [C,V]");
+    TORCH_CHECK(!has_nv || has_n, "mesh_simplify_count: normal_valid needs normal");
+    const int64_t C = has_f ? feat->size(0) : 0;
+    const int rows = be_mesh_simplify_sum_rows((int)C, has_n ? 1 : 0);
+    TORCH_CHECK(rows > 0, "mesh_simplify_count: too many channels");
+    const float* pw = has_w ? on_device<float>(who, "weight", *weight, at::kFloat, vertices, V) : nullptr;
+    const float* pf = has_f && C > 0 ? on_device<float>(who, "feat", *feat, at::kFloat, vertices, C * V) : nullptr;
+    const float* pn = has_n ? on_device<float>(who, "normal", *normal, at::kFloat, vertices, 3 * V) : nullptr;
+    const uint8_t* pnv = has_nv ? on_device<uint8_t>(who, "normal_valid", *normal_valid, at::kBool, vertices, V) : nullptr;
+    const int32_t* pc = on_device<int32_t>(who, "cluster", cluster, at::kInt, vertices, V);
+    auto oi = faces.options(), ol = oi.dtype(at::kLong);
+    Tensor sums = at::empty({rows, V}, ol), fflag = at::empty({T}, oi.dtype(at::kByte)), foff = at::empty({T}, oi), totals = at::empty({2}, ol);
+    const size_t bytes = be_mesh_simplify_workspace_bytes(T);
+    TORCH_CHECK(bytes > 0, "mesh_simplify_count: at most 2^29 triangles");
+    Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, ol);
+    check(be_mesh_simplify_count(vertices.data_ptr<float>(), faces.data_ptr<int32_t>(), V, T, pw, pf, (int)C, pn, pnv,
+                                 host_floats(cell, 3, "mesh_simplify_count(cell)"), host_floats(origin, 3, "mesh_simplify_count(origin)"), pc,
+                                 flaps ? 1 : 0, sums.data_ptr<int64_t>(), fflag.data_ptr<uint8_t>(), foff.data_ptr<int32_t>(),
+                                 totals.data_ptr<int64_t>(), ws.data_ptr<int64_t>(), bytes, stream_of(vertices)), "be_mesh_simplify_count");
+    return {sums, fflag, foff, totals};
+}
+
+// the emit phase -> [vertices [V2,3], faces [T2,3] int32, weight [V2], feat [C,V2], normal [V2,3], normal_valid [V2] bool, face_index
+// [T2] int32]; weight without want_weight and the normals without normal rows in sums are empty tensors
+std::vector<Tensor> mesh_simplify(const Tensor& vertices, const Tensor& faces, const Tensor& cell, const Tensor& origin, const Tensor& label,
+                                  const Tensor& cluster, const Tensor& members, const Tensor& sums, int64_t C, bool normals, bool want_weight,
+                                  const Tensor& fflag, const Tensor& foff, int64_t V2, int64_t T2) {
+    const char* who = "mesh_simplify";
+    const int64_t V = mesh_vertices(who, vertices), T = faces.size(0);
+    mesh_faces(who, faces, V);
+    TORCH_CHECK(V2 >= 0 && V2 <= V && T2 >= 0 && T2 <= T, "mesh_simplify: V2 in [0, V] and T2 in [0, T]");
+    const int rows = be_mesh_simplify_sum_rows((int)C, normals ? 1 : 0);
+    TORCH_CHECK(C >= 0 && rows > 0, "mesh_simplify: too many channels");
+    const int32_t* pl = on_device<int32_t>(who, "label", label, at::kInt, vertices, V);
+    const int32_t* pc = on_device<int32_t>(who, "cluster", cluster, at::kInt, vertices, V);
+    const int32_t* pm = on_device<int32_t>(who, "members", members, at::kInt, vertices, V);
+    const int64_t* ps = on_device<int64_t>(who, "sums", sums, at::kLong, vertices, rows * V);
+    const uint8_t* pff = on_device<uint8_t>(who, "fflag", fflag, at::kByte, vertices, T);
+    const int32_t* pfo = on_device<int32_t>(who, "foff", foff, at::kInt, vertices, T);
+    auto of = vertices.options(), oi = faces.options();
+    Tensor vout = at::empty({V2, 3}, of), fout = at::empty({T2, 3}, oi), wout = at::empty({want_weight ? V2 : 0}, of), ftout = at::empty({C, V2}, of);
+    Tensor nout = at::empty({normals ? V2 : 0, 3}, of), nvout = at::empty({normals ? V2 : 0}, of.dtype(at::kBool)), findex = at::empty({T2}, oi);
+    check(be_mesh_simplify_emit(vertices.data_ptr<float>(), faces.data_ptr<int32_t>(), V, T, host_floats(cell, 3, "mesh_simplify(cell)"),
+                                host_floats(origin, 3, "mesh_simplify(origin)"), pl, pc, pm, ps, (int)C, normals ? 1 : 0, pff, pfo, V2, T2,
+                                vout.data_ptr<float>(), fout.data_ptr<int32_t>(), want_weight ? wout.data_ptr<float>() : nullptr,
+                                C > 0 ? ftout.data_ptr<float>() : nullptr, normals ? nout.data_ptr<float>() : nullptr,
+                                normals ? reinterpret_cast<uint8_t*>(nvout.data_ptr<bool>()) : nullptr, findex.data_ptr<int32_t>(),
+                                stream_of(vertices)), "be_mesh_simplify_emit");
+    return {vout, fout, wout, ftout, nout, nvout, findex};
+}
+
 // depth registration: normal [3,H,W] of depth [H,W]; cam [4] a CPU float32 tensor as for unproject
 Tensor depth_normals(const Tensor& depth, const Tensor& cam, int64_t step, double max_jump, int64_t scale, int64_t top, int64_t left) {
     depth_map("depth_normals", depth, "depth", "[H,W]");
@@ -1210,6 +1293,11 @@ TORCH_LIBRARY(be, m) {
     m.def("mesh_select_count(Tensor faces, Tensor vertex_keep) -> Tensor[]");
     m.def("mesh_select(Tensor vertices, Tensor faces, Tensor? weight, Tensor? feat, Tensor? normal, Tensor? normal_valid, Tensor? edge, "
           "Tensor? component, Tensor vertex_keep, Tensor voff, Tensor foff, int V2, int T2) -> Tensor[]");
+    m.def("mesh_cluster(Tensor vertices, Tensor? weight, Tensor cell, Tensor origin) -> Tensor[]");
+    m.def("mesh_simplify_count(Tensor vertices, Tensor faces, Tensor? weight, Tensor? feat, Tensor? normal, Tensor? normal_valid, Tensor cell, "
+          "Tensor origin, Tensor cluster, bool flaps) -> Tensor[]");
+    m.def("mesh_simplify(Tensor vertices, Tensor faces, Tensor cell, Tensor origin, Tensor label, Tensor cluster, Tensor members, Tensor sums, int C, "
+          "bool normals, bool want_weight, Tensor fflag, Tensor foff, int V2, int T2) -> Tensor[]");
     m.def("tsdf_raycast(Tensor D, Tensor W, Tensor Fm, Tensor origin, Tensor voxel, Tensor cam_dst, Tensor pose, int Ho, int Wo, float z_near, "
           "float step, int n) -> (Tensor, Tensor, Tensor)");
     m.def("depth_normals(Tensor depth, Tensor cam, int step, float max_jump, int scale, int top, int left) -> Tensor");
@@ -1289,6 +1377,9 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("mesh_components_decide", mesh_components_decide);
     m.impl("mesh_select_count", mesh_select_count);
     m.impl("mesh_select", mesh_select);
+    m.impl("mesh_cluster", mesh_cluster);
+    m.impl("mesh_simplify_count", mesh_simplify_count);
+    m.impl("mesh_simplify", mesh_simplify);
     m.impl("depth_normals", depth_normals);
     m.impl("icp_linearize", icp_linearize);
     m.impl("fill_nearest", fill_nearest);

@@ -446,6 +446,52 @@ int be_mesh_select_emit(const float* vertices, const int32_t* faces, int64_t V, 
                         int32_t* faces_out, float* weight_out, float* feat_out, float* normal_out, uint8_t* normal_valid_out,
                         int64_t* edge_out, int32_t* component_out, int32_t* vertex_index, int32_t* face_index, void* stream);
 
+/* Mesh simplification by vertex clustering on a cell grid.  be_hip/simplify.py is the statement and the kernels equal it bit for bit:
+ * every output is a function of the mesh and the grid alone.  cell [3] and origin [3] are host floats (metres per axis; a corner of
+ * cell (0, 0, 0)); cell must be a finite number > 0 whose reciprocal inv = (float)(1.0 / (double) cell) is finite, origin finite.
+ * Per vertex and axis in float32, one rounding per operation: t = (x - o) * inv, i = floorf(t), r = t - i, q = (int64)(r *
+ * 2^BE_SIMPLIFY_FRAC_BITS).  A vertex is unusable when |i| < 2^BE_SIMPLIFY_INDEX_BITS fails on an axis (NaN, inf) or its quantised
+ * weight wq (be_fuse_views_f32's; 65536 with weight NULL) is 0.  0 <= V, T <= 2^29; nothing synchronises with the host; a repeated
+ * run gives the same bits.  No thread waits for another: the two hash tables are open addressing over a power of two >= twice the
+ * keys, a probe loop ends after that many slots at the latest and then sets the overflow word, and nothing spins.
+ *
+ * be_mesh_cluster_f32: label [V] = the least index among the usable vertices of the vertex's cell (-1: unusable), cluster [V] = the
+ * cell's dense id 0..V'-1 in increasing order of label (-1), members [V] int32 = the vertices per dense id (0 from V' on), totals [2]
+ * int64 on the device = (V', overflow != 0: the table was exhausted and the outputs are not to be used).  A slot of the table takes
+ * a vertex index by a 32-bit atomicCAS when empty and atomicMin when its occupant has the same cell; be_exclusive_scan_u8_i32 over
+ * the root flags numbers the clusters.  workspace: 8-byte aligned, be_mesh_cluster_workspace_bytes(V) bytes (0: bad V).
+ *
+ * be_mesh_simplify_count with cluster as be_mesh_cluster_f32 gave it: sums = be_mesh_simplify_sum_rows(C, normal != NULL) rows of V
+ * int64 each, per dense id (64-bit integer atomics): sum wq, sum wq q (3 rows), sum wq fq_c (C rows; fq of be_fuse_views_f32) and,
+ * with normals, sum wq and sum wq fq(normal) (3 rows) over the members whose normal_valid is set (NULL: all).  fflag [T] uint8 = the
+ * face stays: its indices are in range, its corners lie in three different clusters, and, with (a, b, c) its clusters rotated so
+ * that a is the least, it is the LEAST face index among the faces with the same (a, min(b, c), max(b, c)) and the same winding
+ * (b < c) - and, with flaps == 0, no face has that triple in the other winding.  foff [T] int32 = the exclusive prefix sums of
+ * fflag, totals [2] int64 on the device = (T', overflow).  workspace: 8-byte aligned, be_mesh_simplify_workspace_bytes(T).
+ *
+ * The caller reads both totals (the one synchronisation a result of variable length costs), allocates and calls
+ * be_mesh_simplify_emit with V2 = V', T2 = T' (normals != 0: the sums hold the normal rows): per cluster in float64, one rounding per
+ * operation, vertices_out = (float)(o + (i + (double) sum wq q / (double) sum wq * 2^-24) * c), weight_out (NULL: not wanted) =
+ * (float)((double) sum wq / members * 2^-16), feat_out [C,V2] = (float)((double) sum wq fq / (double) sum wq * 2^-16), normal_out =
+ * that mean over the valid members, normalised in float32 (l = sqrtf((x x + y y) + z z), m / l) with normal_valid_out = a valid
+ * member and 0 < l < inf, else +0 and 0; the kept faces in their order with their corners renumbered, face_index [T2] = their old
+ * positions.  Every output element is written exactly once. */
+#define BE_SIMPLIFY_INDEX_BITS 20
+#define BE_SIMPLIFY_FRAC_BITS 24
+size_t be_mesh_cluster_workspace_bytes(int64_t V);
+int be_mesh_cluster_f32(const float* vertices, const float* weight, int64_t V, const float* cell, const float* origin, int32_t* label,
+                        int32_t* cluster, int32_t* members, int64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
+int be_mesh_simplify_sum_rows(int C, int normals);
+size_t be_mesh_simplify_workspace_bytes(int64_t T);
+int be_mesh_simplify_count(const float* vertices, const int32_t* faces, int64_t V, int64_t T, const float* weight, const float* feat, int C,
+                           const float* normal, const uint8_t* normal_valid, const float* cell, const float* origin, const int32_t* cluster,
+                           int flaps, int64_t* sums, uint8_t* fflag, int32_t* foff, int64_t* totals, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int be_mesh_simplify_emit(const float* vertices, const int32_t* faces, int64_t V, int64_t T, const float* cell, const float* origin,
+                          const int32_t* label, const int32_t* cluster, const int32_t* members, const int64_t* sums, int C, int normals,
+                          const uint8_t* fflag, const int32_t* foff, int64_t V2, int64_t T2, float* vertices_out, int32_t* faces_out,
+                          float* weight_out, float* feat_out, float* normal_out, uint8_t* normal_valid_out, int32_t* face_index, void* stream);
+
 /* Depth registration: the two kernels of a point-to-plane ICP on depth maps; the loop around them is be_hip/registration.py.
  * Lattice, camera and pose arguments are be_reproject_f32's; all per-sample arithmetic is fp32, one rounding per operation.
  *
