@@ -636,17 +636,40 @@ def conv_pack(weight, bias, bn=None, eps=1e-5, chw_hw=0):
     return pw, pb
 
 
+def _residual_ptr(residual, rows, cout, ld):
+    """The kernels read the residual with y's row stride (residual[m * ld + c], every route): a dense [.., ld] tensor of `rows`
+    rows, or its [.., :cout] view.  Anything else - a contiguous [N,H,W,cout] residual beside a wider out - would be read at the
+    wrong stride and past its end, so it is refused here, on shapes alone, before any pointer is taken or kernel launched."""
+    if residual is None:
+        return None
+    if not isinstance(residual, torch.Tensor) or residual.dim() < 2:
+        raise RuntimeError("conv_nhwc: residual: expected a tensor of at least two dimensions")
+    c = residual.shape[-1]
+    want, run = [], ld                                     # the strides of a dense [.., ld] tensor under this shape
+    for size in reversed(residual.shape[:-1]):
+        want.append(run)
+        run *= size
+    dense = residual.stride(-1) == 1 and all(s == w_ or size == 1 for s, w_, size in
+                                             zip(reversed(residual.stride()[:-1]), want, reversed(residual.shape[:-1])))
+    if c not in (cout, ld) or not dense or residual.numel() != rows * c:
+        raise RuntimeError(f"conv_nhwc: the residual is read with y's row stride ({ld} floats, {rows} rows of {cout} channels): got "
+                           f"shape {tuple(residual.shape)} with strides {tuple(residual.stride())}")
+    return dptr(residual if c == ld else residual.as_strided((rows, ld), (ld, 1)), "residual")
+
+
 def conv_nhwc(x, pw, pb, cout, ksize, act, residual=None, out=None, scratch=None):
-    """x [N,H,W,Cin] NHWC -> [N,H,W,cout]; out = a [N,H,W,ld] tensor whose first cout channels receive the result;
-    scratch = a float32 buffer the library may use to split the K loop of small launches (training)."""
+    """x [N,H,W,Cin] NHWC -> [N,H,W,cout]; out = a [N,H,W,ld] tensor whose first cout channels receive the result (the other
+    columns are left as they are); residual = a tensor with out's row stride: [N,H,W,ld], or its [..., :cout] view - with no out,
+    [N,H,W,cout]; scratch = a float32 buffer the library may use to split the K loop of small launches (training)."""
     n, h, w, cin = x.shape
     y = torch.empty(n, h, w, cout, dtype=torch.float32, device=x.device) if out is None else out
+    res = _residual_ptr(residual, n * h * w, cout, y.shape[-1])
     d = ConvDesc(n, h, w, cin, cout, ksize, int(act))
     if scratch is not None:
-        check(lib().be_conv_nhwc_splitk_f32(C.byref(d), dptr(x, "x"), dptr(pw), dptr(pb), dptr(residual), dptr(y), y.shape[-1],
+        check(lib().be_conv_nhwc_splitk_f32(C.byref(d), dptr(x, "x"), dptr(pw), dptr(pb), res, dptr(y), y.shape[-1],
                                             dptr(scratch), scratch.numel() * 4, stream_ptr(x.device)), "be_conv_nhwc_splitk_f32")
         return y
-    check(lib().be_conv_nhwc_f32(C.byref(d), dptr(x, "x"), dptr(pw), dptr(pb), dptr(residual), dptr(y), y.shape[-1],
+    check(lib().be_conv_nhwc_f32(C.byref(d), dptr(x, "x"), dptr(pw), dptr(pb), res, dptr(y), y.shape[-1],
                                  stream_ptr(x.device)), "be_conv_nhwc_f32")
     return y
 
@@ -2451,13 +2474,14 @@ def conv_pack_fused2(w, b, bn, w2, b2, bn2, eps=1e-5):
     return pw, pb
 
 
-def conv_nhwc_fused2(x, x2, pw, pb, cout, ksize, act):
-    """y = act(conv_kxk(x) + conv_1x1(x2) + bias): x [N,H,W,Cin], x2 [N,H,W,Cin2]."""
+def conv_nhwc_fused2(x, x2, pw, pb, cout, ksize, act, out=None):
+    """y = act(conv_kxk(x) + conv_1x1(x2) + bias): x [N,H,W,Cin], x2 [N,H,W,Cin2]; out = a [N,H,W,ld] tensor whose first cout
+    channels receive the result, as in conv_nhwc."""
     n, h, w, cin = x.shape
-    y = torch.empty(n, h, w, cout, dtype=torch.float32, device=x.device)
+    y = torch.empty(n, h, w, cout, dtype=torch.float32, device=x.device) if out is None else out
     d = ConvDesc(n, h, w, cin, cout, ksize, int(act))
     check(lib().be_conv_nhwc_fused2_f32(C.byref(d), dptr(x, "x"), dptr(x2, "x2"), x2.shape[-1], dptr(pw), dptr(pb), dptr(y),
-                                        cout, stream_ptr(x.device)), "be_conv_nhwc_fused2_f32")
+                                        y.shape[-1], stream_ptr(x.device)), "be_conv_nhwc_fused2_f32")
     return y
 
 

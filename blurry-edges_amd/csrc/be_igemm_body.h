@@ -84,7 +84,8 @@ __device__ __forceinline__ void conv_igemm_body(ConvArgs a, float* smem, const i
     // the short tiles fill the tail of the launch
     int pix_u = 0;
     if (a.pixmaj) {
-        const int idx = m_tile % a.HW, ni = (a.H - 2) * (a.W - 2);
+        // (no interior when a side is <= 2 pixels: on a 1 x 1 image (H - 2)(W - 2) = 1 named the pixel (1, 1), outside the image)
+        const int idx = m_tile % a.HW, ni = a.H > 2 && a.W > 2 ? (a.H - 2) * (a.W - 2) : 0;
         int py, px;
         if (idx < ni) { py = 1 + idx / (a.W - 2); px = 1 + idx % (a.W - 2); }
         else {
@@ -210,7 +211,10 @@ __device__ __forceinline__ void conv_igemm_body(ConvArgs a, float* smem, const i
         a_ok = 0;                                                                                               \
         _Pragma("unroll") for (int i_ = 0; i_ < NA; ++i_) {                                                     \
             const int yy_ = (a_yx[i_] >> 16) + dy_, xx_ = (a_yx[i_] & 0xffff) + dx_;                            \
-            const bool ok_ = a_yx[i_] >= 0 && (unsigned)yy_ < (unsigned)a.H && (unsigned)xx_ < (unsigned)a.W;   \
+            /* conv1's row mode stages 8 pixels for 7 taps: the eighth (dx = 4) meets zero weights, and is zeroed  \
+             * here as well - 0 * inf = NaN: a non-finite pixel reached the output four columns to its left */    \
+            const bool ok_ = a_yx[i_] >= 0 && (unsigned)yy_ < (unsigned)a.H && (unsigned)xx_ < (unsigned)a.W &&  \
+                             (MODE != MODE_ROW8 || dx_ < 4);                                                     \
             /* branch-free: out-of-image taps read the (valid) first 16 B of the tensor and are zeroed */      \
             int64_t off_ = ok_ ? (int64_t)a_off[i_] * (second_ ? a.Cin2 : a.Cin) + coff_ : 0;                   \
             asm volatile("" : "+v"(off_));  /* opaque: keeps the load unconditional (no exec-mask branch) */    \

@@ -742,13 +742,17 @@ typedef struct be_pack_job {
     int cout, cin, ksize, layout_chw_hw, dgrad;
 } be_pack_job;
 int be_conv_pack_jobs_f32(const be_pack_job* jobs_device, int njobs, void* stream);
-/* y[n,h,w,cout] = act(conv(x) + bias (+ residual)); residual may be NULL; ldy = row stride of y in floats. */
+/* y[n,h,w,cout] = act(conv(x) + bias (+ residual)); residual may be NULL; ldy = row stride of y in floats.
+ * The residual is read with y's row stride: element (m, c) at residual[m * ldy + c], on every route (implicit GEMM, pixel-major,
+ * row GEMM).  With ldy > cout a contiguous [n,h,w,cout] residual would be read at the wrong stride and past its end: lay it out
+ * like y.  Nothing outside y's first cout columns is written. */
 int be_conv_nhwc_f32(const be_conv_desc* desc_host, const float* x, const float* packed_w,
                      const float* packed_bias, const float* residual, float* y, int ldy, void* stream);
 /* The same convolution with scratch lent by the caller: launches with few output tiles (batch-64 training: M = 2304
  * rows) split their K loop over up to 8 slices (partial sums in scratch, summed in a fixed order with the bias /
  * residual / activation applied by a second small kernel); large launches behave exactly as be_conv_nhwc_f32.
- * scratch: 8 * M * cout_pad32 * 4 bytes is always enough (fewer slices are used when it is smaller). */
+ * scratch: 8 * M * cout_pad32 * 4 bytes is always enough (fewer slices are used when it is smaller).
+ * The residual has y's row stride here too (residual[m * ldy + c]): the kernel that sums the slices reads it that way. */
 int be_conv_nhwc_splitk_f32(const be_conv_desc* d, const float* x, const float* packed_w, const float* packed_bias,
                             const float* residual, float* y, int ldy, void* scratch, size_t scratch_bytes, void* stream);
 /* HOST-ONLY inspection hook of the fp32 convolution's planner (no GPU, no launch): the plan that be_conv_nhwc_f32 and its fused2
