@@ -205,6 +205,10 @@ _SIGNATURES = {
                                + [_P, C.c_int] + [_P] * 5 + [C.c_size_t, _P]),
     "be_mesh_simplify_emit": (C.c_int, [_P, _P, C.c_int64, C.c_int64] + [C.POINTER(C.c_float)] * 2 + [_P] * 4 + [C.c_int, C.c_int, _P, _P,
                                                                                                               C.c_int64, C.c_int64] + [_P] * 7 + [_P]),
+    "be_mesh_smooth_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "be_mesh_adjacency_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
+    "be_mesh_smooth_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_int] + [_P] * 5 + [C.c_size_t, _P]),
+    "be_mesh_normals_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
     "be_depth_normals_f32": (C.c_int, [_P] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.c_int, C.c_float, _P, _P]),
     "be_icp_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "be_icp_linearize_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [C.POINTER(C.c_float), _P, _P, _P, C.c_int, C.c_int]
@@ -2148,6 +2152,90 @@ def mesh_simplify(mesh, cell, origin=(0, 0, 0), flaps=False):
                                           dptr(fi), stream_ptr(dev)), "be_mesh_simplify_emit")
     return dict(vertices=v, faces=f, weight=w if has("weight") else None, feat=ft if has("feat") else None, normal=n if normals else None,
                 normal_valid=nv if normals else None, edge=None, cluster=cluster, members=members[:V2], face_index=fi)
+
+
+def _smooth_workspace(V, T, dev):
+    nbytes = lib().be_mesh_smooth_workspace_bytes(V, T)
+    return _new(dev)((nbytes + 7) // 8, dtype=torch.int64), nbytes
+
+
+def _adjacency(m, V, T, dev):
+    """-> (valence [V] int32, boundary [V] bool); no synchronisation."""
+    o = ops()
+    if o is not None:
+        return tuple(o.mesh_adjacency(m["vertices"], m["faces"]))
+    new = _new(dev)
+    valence, boundary = new(V, dtype=torch.int32), new(V, dtype=torch.bool)
+    ws, nbytes = _smooth_workspace(V, T, dev)
+    check(lib().be_mesh_adjacency_f32(dptr(m["vertices"]), dptr(m["faces"]), V, T, dptr(valence), dptr(boundary, "boundary", _BOOL),
+                                      dptr(ws, "workspace", _I64), nbytes, stream_ptr(dev)), "be_mesh_adjacency_f32")
+    return valence, boundary
+
+
+def _normals(vertices, faces, V, T, dev):
+    """-> (normal [V,3], normal_valid [V] bool); no synchronisation."""
+    o = ops()
+    if o is not None:
+        return tuple(o.mesh_normals(vertices, faces))
+    new = _new(dev)
+    normal, valid = new(V, 3), new(V, dtype=torch.bool)
+    ws, nbytes = _smooth_workspace(V, T, dev)
+    check(lib().be_mesh_normals_f32(dptr(vertices), dptr(faces), V, T, dptr(normal), dptr(valid, "normal_valid", _BOOL), dptr(ws, "workspace", _I64),
+                                    nbytes, stream_ptr(dev)), "be_mesh_normals_f32")
+    return normal, valid
+
+
+def mesh_adjacency(mesh):
+    """What mesh_smooth knows of a mesh on the GPU (a dict as mesh_field / tsdf_mesh / mesh_clean / mesh_simplify return it) before
+    it moves a vertex -> dict(valence [V] int32 = the usable faces at the vertex, boundary [V] bool = the vertex touches an edge
+    that exactly one usable face holds).  A vertex is usable when its coordinates are finite and below 2^16 m in size, a face when
+    its indices are in range, pairwise distinct and name usable vertices; a face given twice counts twice.  An edge table of
+    64-bit keys that cannot overflow; no read-back.  smooth.adjacency is the host statement, bit for bit; a face index outside
+    [0, V), which it refuses, is ignored here."""
+    V, T, _, m, dev = _mesh_on_gpu("mesh_adjacency", mesh)
+    valence, boundary = _adjacency(m, V, T, dev)
+    return dict(valence=valence, boundary=boundary)
+
+
+def mesh_normals(mesh):
+    """Area-weighted vertex normals of a mesh on the GPU from its faces alone -> dict(normal [V,3], normal_valid [V] bool): per
+    usable face cross(b - a, c - a) in float32, quantised to 2^-40 m^2, summed per vertex in int64, normalised in float32; +0 and
+    False where the sum has no direction.  The winding normal points to free space, as extract_mesh winds its faces.
+    smooth.vertex_normals is the host statement, bit for bit; no read-back."""
+    V, T, _, m, dev = _mesh_on_gpu("mesh_normals", mesh)
+    normal, valid = _normals(m["vertices"], m["faces"], V, T, dev)
+    return dict(normal=normal, normal_valid=valid)
+
+
+def mesh_smooth(mesh, iters=10, lam=0.5, mu=-0.53, boundary="fixed", normals="keep"):
+    """The mesh denoised at its own resolution by Taubin's lambda | mu smoothing: per iteration every movable vertex steps towards the
+    mean of its neighbours by lam, then away from the new mean by mu (mu = 0: a plain Laplacian, which shrinks).  boundary="fixed"
+    holds the vertices mesh_adjacency calls boundary, "free" moves them too.  Positions are integers of 2^-30 m and a neighbour sum
+    is an integer sum, so the result has the same bits on every run.  -> the mesh's keys (faces, weight, feat the tensors given;
+    edge = None: a moved vertex has left its lattice edge; normals="keep" passes normal / normal_valid through, "recompute"
+    replaces them by mesh_normals of the result, "drop" gives None) and valence [V] int32, boundary [V] bool, displacement [V] =
+    how far each vertex moved.  No vertex or face is lost; iters=0 returns the positions bit for bit.  One launch per step, no
+    atomics in it, no read-back.  smooth.smooth is the host statement, bit for bit; a face index outside [0, V), which it refuses,
+    is ignored here."""
+    from . import smooth
+    V, T, _, m, dev = _mesh_on_gpu("mesh_smooth", mesh)
+    iters, lam, mu, free, normals = smooth.check_args("mesh_smooth", iters, lam, mu, boundary, normals)
+    o = ops()
+    if o is not None:
+        v, disp, valence, bnd = o.mesh_smooth(m["vertices"], m["faces"], iters, lam, mu, free)
+    else:
+        new = _new(dev)
+        v, disp, valence, bnd = new(V, 3), new(V), new(V, dtype=torch.int32), new(V, dtype=torch.bool)
+        ws, nbytes = _smooth_workspace(V, T, dev)
+        check(lib().be_mesh_smooth_f32(dptr(m["vertices"]), dptr(m["faces"]), V, T, iters, lam, mu, int(free), dptr(v), dptr(disp), dptr(valence),
+                                       dptr(bnd, "boundary", _BOOL), dptr(ws, "workspace", _I64), nbytes, stream_ptr(dev)), "be_mesh_smooth_f32")
+    out = dict(vertices=v, faces=m["faces"], weight=m["weight"], feat=m["feat"], normal=None, normal_valid=None, edge=None, valence=valence,
+               boundary=bnd, displacement=disp)
+    if normals == "keep":
+        out.update(normal=m["normal"], normal_valid=m["normal_valid"])
+    elif normals == "recompute":
+        out["normal"], out["normal_valid"] = _normals(v, m["faces"], V, T, dev)
+    return out
 
 
 def depth_normals(depth, cam, step=3, max_jump=0.05, scale=1, window_origin=(0, 0)):

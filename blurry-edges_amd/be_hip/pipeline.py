@@ -606,7 +606,7 @@ class DepthPipeline:
             raise ValueError("clean_mesh: mesh must be the dict extract_mesh returned (vertices, faces, ...)")
         V = mesh["vertices"].shape[0]
         fixed = ("vertices", "faces", "weight", "normal", "normal_valid", "edge", "component", "components", "vertex_index", "face_index", "cluster",
-                 "members")                                                  # the last two: what simplify_mesh adds; they name another mesh
+                 "members", "valence", "boundary", "displacement")           # what simplify_mesh and smooth_mesh add: they describe another mesh
         maps = [k for k, t in mesh.items() if k not in fixed and isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[-1] == V]
         for k in maps:
             if mesh[k].dtype != torch.float32:
@@ -637,7 +637,7 @@ class DepthPipeline:
             raise ValueError("simplify_mesh: mesh must be the dict extract_mesh returned (vertices, faces, ...)")
         V = mesh["vertices"].shape[0]
         fixed = ("vertices", "faces", "weight", "normal", "normal_valid", "edge", "component", "components", "vertex_index", "face_index", "cluster",
-                 "members")
+                 "members", "valence", "boundary", "displacement")
         maps = [k for k, t in mesh.items() if k not in fixed and isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[-1] == V]
         for k in maps:
             if mesh[k].dtype != torch.float32:
@@ -649,6 +649,30 @@ class DepthPipeline:
         res.update({k: out[k] for k in ("vertices", "faces", "weight", "normal", "normal_valid") if k in mesh})
         res.update(unpack_channels(out["feat"], channels, out["vertices"].shape[:1]))
         res.update(cluster=out["cluster"], members=out["members"], face_index=out["face_index"])
+        return res
+
+    @torch.no_grad()
+    def smooth_mesh(self, mesh, iters=10, lam=0.5, mu=-0.53, boundary="fixed", normals="keep"):
+        """mesh: what extract_mesh, clean_mesh or simplify_mesh returned (or any dict of vertices [V,3], faces [T,3] int32 and
+        per-vertex maps on the GPU) -> the mesh denoised at its own resolution by Taubin smoothing (native.mesh_smooth): `iters`
+        times every vertex steps towards the mean of its neighbours by `lam` and away from the new mean by `mu` (mu = 0: a plain
+        Laplacian, which shrinks what it smooths).  No vertex or face is lost.  boundary="fixed" holds the vertices on the rim of
+        the mesh - those that touch an edge only one face holds -, "free" moves them too.  normals="keep" leaves normal /
+        normal_valid as they are - the volume's gradient is the better normal of a depth-noise mesh -, "recompute" replaces them
+        by the area-weighted normals of the new faces (native.mesh_normals), "drop" sets both to None.  The result holds the keys
+        of `mesh` with new vertices, but edge (a moved vertex has left its lattice edge), and adds valence [V] int32, boundary [V]
+        bool and displacement [V] = how far each vertex moved, in metres.  It goes straight into render_mesh, save_mesh,
+        clean_mesh, simplify_mesh and smooth_mesh again.  Clean first: smoothing drags a surface toward a floater that touches
+        it.  The same bits on every run; no read-back."""
+        if not isinstance(mesh, dict) or "vertices" not in mesh or "faces" not in mesh:
+            raise ValueError("smooth_mesh: mesh must be the dict extract_mesh returned (vertices, faces, ...)")
+        m = dict(vertices=mesh["vertices"], faces=mesh["faces"], normal=mesh.get("normal"), normal_valid=mesh.get("normal_valid"))
+        out = native.mesh_smooth(m, iters=iters, lam=lam, mu=mu, boundary=boundary, normals=normals)
+        res = {k: v for k, v in mesh.items() if k != "edge"}
+        res["vertices"] = out["vertices"]
+        if normals != "keep":
+            res.update(normal=out["normal"], normal_valid=out["normal_valid"])
+        res.update(valence=out["valence"], boundary=out["boundary"], displacement=out["displacement"])
         return res
 
     @staticmethod

@@ -18,6 +18,7 @@ formats (argument names and defaults = utils/args.py of the reference):
                                                            (with tsdf_mesh > 0 beside them: also that volume's triangle mesh)
                                                            (with mesh_render > 0 beside them: also that mesh seen by view 0's camera)
                                                            (with mesh_min_triangles > 0 beside them: the mesh without its small components)
+                                                           (with mesh_smooth > 0 beside them: the mesh smoothed by that many Taubin iterations)
                                                            (with mesh_cell beside them: the mesh simplified on cells of that size)
     ... eval --normals [--out_path DIR]                    also write every pair's surface normals (of its completed depth)
     ... eval --complete [--out_path DIR]                   also write and score every pair's depth map completed to a dense one
@@ -348,7 +349,8 @@ def load_fusion(path):
     optionally tsdf_trunc) describe a TSDF volume (-> cfg["tsdf"]); an integer tsdf_mesh > 0 beside them (-> cfg["tsdf_mesh"]) asks
     for that volume's mesh as well, and an integer mesh_render > 0 (-> cfg["mesh_render"]) for that mesh rendered into view 0's
     camera.  mesh_cell = one number or three (cX, cY, cZ) > 0, in metres (-> cfg["mesh_cell"], three numbers), asks for that mesh
-    simplified on cells of that size."""
+    simplified on cells of that size.  An integer mesh_smooth > 0 (-> cfg["mesh_smooth"]) asks for that mesh smoothed by that many
+    iterations of DepthPipeline.smooth_mesh at its defaults, after the cleaning and before the simplification."""
     from . import camera
     with np.load(path) as f:
         if "poses" not in f:
@@ -415,6 +417,15 @@ def load_fusion(path):
                 raise ValueError(f"--fuse: mesh_cell simplifies the mesh of the TSDF volume; {path} asks for no mesh: "
                                  "tsdf_mesh > 0 or mesh_render > 0 (beside tsdf_dims, tsdf_origin, tsdf_voxel)")
             cfg["mesh_cell"] = tuple(float(c) for c in cell)
+        if "mesh_smooth" in f:                                              # absent: the dict holds what it held before
+            n = np.asarray(f["mesh_smooth"]).reshape(-1)[0]
+            if int(n) != n or not 0 <= n <= 10000:
+                raise ValueError("--fuse: mesh_smooth must be an integer in [0, 10000] (> 0: that many iterations of Taubin smoothing on the "
+                                 f"mesh's vertices), got {f['mesh_smooth']!r}")
+            if n > 0 and not (cfg.get("tsdf_mesh", 0) > 0 or cfg.get("mesh_render", 0) > 0):
+                raise ValueError(f"--fuse: mesh_smooth smooths the mesh of the TSDF volume; {path} asks for no mesh: "
+                                 "tsdf_mesh > 0 or mesh_render > 0 (beside tsdf_dims, tsdf_origin, tsdf_voxel)")
+            cfg["mesh_smooth"] = int(n)
         return cfg
 
 
@@ -474,6 +485,9 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
     the timed region; without the key nothing changes.  With an integer mesh_min_triangles > 0 beside them the mesh is first cleaned,
     DepthPipeline.clean_mesh: its connected components of fewer triangles - the islands depth outliers leave - are dropped before
     either file is written, and mesh_{g:04d}.npz also holds component [V'] and components_triangles (every component's size).
+    With an integer mesh_smooth > 0 beside them the mesh is then smoothed, DepthPipeline.smooth_mesh with that many iterations at its
+    defaults - after the cleaning, because smoothing drags a surface toward a floater that touches it, and before the
+    simplification -, and mesh_{g:04d}.npz also holds valence, boundary and displacement (unless mesh_cell follows).
     With mesh_cell = one number or three (cX, cY, cZ) > 0, in metres, beside them the mesh is then simplified,
     DepthPipeline.simplify_mesh on the grid of such cells from the volume's origin - after the cleaning, because clustering keeps a
     floater's vertex while it thins the surface around it - before either file is written, and mesh_{g:04d}.npz holds the coarser
@@ -588,6 +602,8 @@ def evaluate(args, big=False, local_weights=None, global_weights=None, pp_weight
                     if tri is not None and fcfg.get("mesh_min_triangles", 0) > 0:
                         tri = pipe.clean_mesh(tri, min_triangles=fcfg["mesh_min_triangles"])
                         cleaned = dict(components_triangles=tri.pop("components")["triangles"].cpu().numpy())
+                    if tri is not None and fcfg.get("mesh_smooth", 0) > 0:           # after the cleaning: a floater that touches a surface drags it
+                        tri = pipe.smooth_mesh(tri, iters=fcfg["mesh_smooth"])
                     if tri is not None and "mesh_cell" in fcfg:                      # after the cleaning: a floater's vertex would stay
                         tri = pipe.simplify_mesh(tri, fcfg["mesh_cell"], origin=fcfg["tsdf"]["origin"])
                     if fcfg.get("tsdf_mesh", 0) > 0:

@@ -1070,6 +1070,58 @@ std::vector<Tensor> mesh_simplify(const Tensor& vertices, const Tensor& faces, c
     return {vout, fout, wout, ftout, nout, nvout, findex};
 }
 
+// ---- mesh smoothing: be_mesh_adjacency_f32 / be_mesh_smooth_f32 / be_mesh_normals_f32; nothing synchronises with the host
+static Tensor smooth_workspace(const char* who, const Tensor& vertices, int64_t V, int64_t T, size_t* bytes) {
+    *bytes = be_mesh_smooth_workspace_bytes(V, T);
+    TORCH_CHECK(*bytes > 0 || (V == 0 && T == 0), who, ": at most 2^29 vertices and triangles");
+    return at::empty({(int64_t)((*bytes + 7) / 8)}, vertices.options().dtype(at::kLong));
+}
+
+// -> [valence [V] int32, boundary [V] bool]
+std::vector<Tensor> mesh_adjacency(const Tensor& vertices, const Tensor& faces) {
+    const char* who = "mesh_adjacency";
+    const int64_t V = mesh_vertices(who, vertices), T = faces.size(0);
+    mesh_faces(who, faces, V);
+    Tensor valence = at::empty({V}, faces.options()), boundary = at::empty({V}, faces.options().dtype(at::kBool));
+    size_t bytes;
+    Tensor ws = smooth_workspace(who, vertices, V, T, &bytes);
+    check(be_mesh_adjacency_f32(vertices.data_ptr<float>(), faces.data_ptr<int32_t>(), V, T, valence.data_ptr<int32_t>(),
+                                reinterpret_cast<uint8_t*>(boundary.data_ptr<bool>()), ws.data_ptr<int64_t>(), bytes, stream_of(vertices)),
+          "be_mesh_adjacency_f32");
+    return {valence, boundary};
+}
+
+// -> [vertices [V,3], displacement [V], valence [V] int32, boundary [V] bool]
+std::vector<Tensor> mesh_smooth(const Tensor& vertices, const Tensor& faces, int64_t iters, double lam, double mu, bool free_boundary) {
+    const char* who = "mesh_smooth";
+    const int64_t V = mesh_vertices(who, vertices), T = faces.size(0);
+    mesh_faces(who, faces, V);
+    TORCH_CHECK(iters >= 0 && iters <= BE_SMOOTH_MAX_ITERS, "mesh_smooth: iters must be in [0, ", BE_SMOOTH_MAX_ITERS, "]");
+    Tensor out = at::empty({V, 3}, vertices.options()), displacement = at::empty({V}, vertices.options());
+    Tensor valence = at::empty({V}, faces.options()), boundary = at::empty({V}, faces.options().dtype(at::kBool));
+    size_t bytes;
+    Tensor ws = smooth_workspace(who, vertices, V, T, &bytes);
+    check(be_mesh_smooth_f32(vertices.data_ptr<float>(), faces.data_ptr<int32_t>(), V, T, (int)iters, lam, mu, free_boundary ? 1 : 0,
+                             out.data_ptr<float>(), displacement.data_ptr<float>(), valence.data_ptr<int32_t>(),
+                             reinterpret_cast<uint8_t*>(boundary.data_ptr<bool>()), ws.data_ptr<int64_t>(), bytes, stream_of(vertices)),
+          "be_mesh_smooth_f32");
+    return {out, displacement, valence, boundary};
+}
+
+// -> [normal [V,3], normal_valid [V] bool]
+std::vector<Tensor> mesh_normals(const Tensor& vertices, const Tensor& faces) {
+    const char* who = "mesh_normals";
+    const int64_t V = mesh_vertices(who, vertices), T = faces.size(0);
+    mesh_faces(who, faces, V);
+    Tensor normal = at::empty({V, 3}, vertices.options()), valid = at::empty({V}, vertices.options().dtype(at::kBool));
+    size_t bytes;
+    Tensor ws = smooth_workspace(who, vertices, V, T, &bytes);
+    check(be_mesh_normals_f32(vertices.data_ptr<float>(), faces.data_ptr<int32_t>(), V, T, normal.data_ptr<float>(),
+                              reinterpret_cast<uint8_t*>(valid.data_ptr<bool>()), ws.data_ptr<int64_t>(), bytes, stream_of(vertices)),
+          "be_mesh_normals_f32");
+    return {normal, valid};
+}
+
 // depth registration: normal [3,H,W] of depth [H,W]; cam [4] a CPU float32 tensor as for unproject
 Tensor depth_normals(const Tensor& depth, const Tensor& cam, int64_t step, double max_jump, int64_t scale, int64_t top, int64_t left) {
     depth_map("depth_normals", depth, "depth", "[H,W]");
@@ -1298,6 +1350,9 @@ TORCH_LIBRARY(be, m) {
           "Tensor origin, Tensor cluster, bool flaps) -> Tensor[]");
     m.def("mesh_simplify(Tensor vertices, Tensor faces, Tensor cell, Tensor origin, Tensor label, Tensor cluster, Tensor members, Tensor sums, int C, "
           "bool normals, bool want_weight, Tensor fflag, Tensor foff, int V2, int T2) -> Tensor[]");
+    m.def("mesh_adjacency(Tensor vertices, Tensor faces) -> Tensor[]");
+    m.def("mesh_smooth(Tensor vertices, Tensor faces, int iters, float lam, float mu, bool free_boundary) -> Tensor[]");
+    m.def("mesh_normals(Tensor vertices, Tensor faces) -> Tensor[]");
     m.def("tsdf_raycast(Tensor D, Tensor W, Tensor Fm, Tensor origin, Tensor voxel, Tensor cam_dst, Tensor pose, int Ho, int Wo, float z_near, "
           "float step, int n) -> (Tensor, Tensor, Tensor)");
     m.def("depth_normals(Tensor depth, Tensor cam, int step, float max_jump, int scale, int top, int left) -> Tensor");
@@ -1380,6 +1435,9 @@ TORCH_LIBRARY_IMPL(be, CompositeExplicitAutograd, m) {
     m.impl("mesh_cluster", mesh_cluster);
     m.impl("mesh_simplify_count", mesh_simplify_count);
     m.impl("mesh_simplify", mesh_simplify);
+    m.impl("mesh_adjacency", mesh_adjacency);
+    m.impl("mesh_smooth", mesh_smooth);
+    m.impl("mesh_normals", mesh_normals);
     m.impl("depth_normals", depth_normals);
     m.impl("icp_linearize", icp_linearize);
     m.impl("fill_nearest", fill_nearest);

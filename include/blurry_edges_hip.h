@@ -492,6 +492,42 @@ int be_mesh_simplify_emit(const float* vertices, const int32_t* faces, int64_t V
                           const uint8_t* fflag, const int32_t* foff, int64_t V2, int64_t T2, float* vertices_out, int32_t* faces_out,
                           float* weight_out, float* feat_out, float* normal_out, uint8_t* normal_valid_out, int32_t* face_index, void* stream);
 
+/* Mesh smoothing (Taubin's lambda | mu) on integer sums.  be_hip/smooth.py is the statement and the kernels equal it bit for bit: every
+ * output is a function of the mesh alone.  A vertex is usable when its coordinates are finite and |x| < 2^BE_SMOOTH_COORD_MAX_LOG2; a
+ * face when its indices are in [0, V), pairwise distinct, and name usable vertices (any other face is ignored).  0 <= V, T <= 2^29;
+ * nothing synchronises with the host and nothing is read back; a repeated run gives the same bits.  One workspace size serves the
+ * three entries: 8-byte aligned, be_mesh_smooth_workspace_bytes(V, T) bytes (0: bad V or T).
+ *
+ * be_mesh_adjacency_f32: valence [V] int32 = the usable faces at the vertex; boundary [V] uint8 = 1 when the vertex touches an
+ * undirected edge that exactly one usable face holds (a face given twice counts twice), else 0.  The edges are counted in an
+ * open-addressing table of 64-bit keys (min << 32 | max) over a power of two >= 2 * 3 T slots, claimed by atomicCAS; it holds at most
+ * 3 T keys, so a probe always ends and the table cannot overflow.  No thread waits for another.
+ *
+ * be_mesh_smooth_f32: that setup, rows of 2 valence neighbour indices per vertex (a scan, an atomic cursor per vertex; the order in
+ * a row is arbitrary), Q0 = (int64) rint((double) x * 2^BE_SMOOTH_FRAC_BITS), then per iteration a step with lam and - unless mu == 0
+ * - a step with mu, one launch each: S = the int64 sum of Q over the row, d = (double) S / (double) n - (double) Q in float64 with
+ * one rounding per operation, Q' = Q + (int64) rint(f * d) for a vertex with n = 2 valence > 0 that is not boundary (or any such
+ * vertex with free_boundary = 1), else Q; no atomics, no LDS, no barrier.  vertices_out = the input's bits where Q == Q0 on all three
+ * axes, else (float)((double) Q * 2^-30); displacement [V] = sqrtf((dx dx + dy dy) + dz dz) in float32, 0 for an unusable vertex.
+ * iters in [0, BE_SMOOTH_MAX_ITERS], lam in (0, 1], mu in [-2, 0].
+ *
+ * be_mesh_normals_f32: per usable face cross(b - a, c - a) in float32 (be_mesh_components_stats' operation order), components that
+ * are not finite 0, clamped to +-2^12, nq = (int64)(n * 2^BE_SMOOTH_NORMAL_BITS) added to the three corners (64-bit integer
+ * atomics); normal [V,3] = that sum as (float)((double) sum * 2^-40), normalised in float32 (l = sqrtf((x x + y y) + z z), m / l),
+ * normal_valid [V] uint8 = 0 < l < inf, else +0 and 0. */
+#define BE_SMOOTH_FRAC_BITS 30
+#define BE_SMOOTH_COORD_MAX_LOG2 16
+#define BE_SMOOTH_NORMAL_BITS 40
+#define BE_SMOOTH_MAX_ITERS 10000
+size_t be_mesh_smooth_workspace_bytes(int64_t V, int64_t T);
+int be_mesh_adjacency_f32(const float* vertices, const int32_t* faces, int64_t V, int64_t T, int32_t* valence, uint8_t* boundary, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int be_mesh_smooth_f32(const float* vertices, const int32_t* faces, int64_t V, int64_t T, int iters, double lam, double mu, int free_boundary,
+                       float* vertices_out, float* displacement, int32_t* valence, uint8_t* boundary, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int be_mesh_normals_f32(const float* vertices, const int32_t* faces, int64_t V, int64_t T, float* normal, uint8_t* normal_valid, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* Depth registration: the two kernels of a point-to-plane ICP on depth maps; the loop around them is be_hip/registration.py.
  * Lattice, camera and pose arguments are be_reproject_f32's; all per-sample arithmetic is fp32, one rounding per operation.
  *
